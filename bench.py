@@ -5,8 +5,13 @@ A "step" is one pass of the full Canny pipeline (Mode R, thresholds 10/40, final
 over one batch of device-resident synthetic 1080p grayscale frames, through the C ABI
 (hc_run_device).  `value` = frames/s of the whole job (all ranks), inputs already in HBM.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds the untimed legs beside it:
+the same-batch leg, the CPU baseline with its check of the GPU output against the oracle, and the host-fed leg.
+--dump-outputs DIR writes what the last timed step returned (a fixed sample of its edge maps, float32) as DIR/*.npy.
 
 Frames shard over ranks with no data-path collective (independent frames): weak
 scaling, one context + one stream per device; torch.distributed only carries the barrier and the
@@ -66,7 +71,14 @@ def parse():
     ap.add_argument("--sweep", action="store_true", help="one JSON line per batch size in {1, 8, 64, 256, 1024} (SURVEY 8d C2) instead of the single headline line")
     ap.add_argument("--sweep-batches", default="1,8,64,256,1024", help="the batch sizes of --sweep")
     ap.add_argument("--no-host-fed", action="store_true", help="skip the bounded host-fed (PCIe-inclusive) end-to-end leg")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the untimed extra legs: same batch every step, CPU baseline + oracle check, host-fed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) as DIR/*.npy: a fixed sample of its edge maps, float32")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.sweep and a.dump_outputs:
+        ap.error("--dump-outputs needs a single configuration (not --sweep)")
+    return a
 
 
 def main():
@@ -244,11 +256,13 @@ def run_config(a, torch, dist, world, rank, local, backend, brief):
     in_staged, out_staged, front_form = ctx.last_run_info()
     front_waves = ctx.front_waves_per_workgroup() if a.mode == "R" else None   # k_front8: 4, or 1 while the hysteresis stream has the slack (HC_OPT_FRONT_WPB)
     slots_used = ctx.pipeline_slots_in_use()   # 2, or 3 once the context saw the hysteresis chain outlast the next front kernel
+    if a.dump_outputs and rank == 0:   # before any extra leg writes into the output buffers again
+        dump_outputs(a.dump_outputs, d_outs[(nstep[0] - 1) % len(d_outs)], torch)
 
-    # Untimed extra leg (rank 0, N = 1, rotation on): rounds 1-2 measured ONE natural batch processed every step; the same
-    # here over a few steps, so that the line carries the figure that compares with theirs.  Never part of `value`.
+    # Untimed extra leg (--full; rank 0, N = 1, rotation on): rounds 1-2 measured ONE natural batch processed every step; the
+    # same here over a few steps, so that the line carries the figure that compares with theirs.  Never part of `value`.
     same_batch = None
-    if rot > 1 and world == 1 and not brief:
+    if a.full and rot > 1 and world == 1 and not brief:
         nsame = max(8, min(24, steps))
         for k in range(3):   # warm: the adaptive estimates settle on this content
             ctx.run_device(d_ins[0].data_ptr(), W * C, W * C * H, d_outs[k % len(d_outs)].data_ptr(), W, W * H, B, api.CannyStage.HYSTER)
@@ -338,7 +352,7 @@ def run_config(a, torch, dist, world, rank, local, backend, brief):
                     out["roofline"]["traffic_frac_of_peak"] = round(out["roofline"]["traffic"] / (front_ms * 1e-3) / HBM_PEAK_GBPS, 4) if front_ms > 0 else None
             except (OSError, KeyError, ValueError):
                 pass
-        if not brief and not a.no_cpu_baseline and C == 1 and world == 1:   # the CPU baseline is an N = 1 figure
+        if a.full and not brief and not a.no_cpu_baseline and C == 1 and world == 1:   # the CPU baseline is an N = 1 figure
             # (untimed) one more run per content into the first output buffer: the oracle checks a sample of EVERY batch of the rotation
             ncheck = min(B, 16)
             samples = []
@@ -352,7 +366,7 @@ def run_config(a, torch, dist, world, rank, local, backend, brief):
                 out["cpu_baseline_cv_canny_restatement"] = {"value": om["value"], "unit": om["unit"], "cores": om["cores"], "kind": "port",
                                                             "sample": out["cpu_baseline"]["sample"],
                                                             "note": "cv::Canny(img, 50, 150, 3, false) as restated in oracle/canny_oracle.c (Mode O): never compared with a real OpenCV (none on this host)"}
-        if not brief and not a.no_host_fed and world == 1:
+        if a.full and not brief and not a.no_host_fed and world == 1:
             out["host_fed"] = host_fed(a, d_in)
         print(json.dumps(out), flush=True)
     ctx.close()
@@ -376,6 +390,28 @@ def _by_content(kinds, first_timed, intervals, front_each, B, alg_bytes_per_laun
                      "kernel_ms": round(fm, 4) if fm else None,
                      "roofline_frac": round(alg_bytes_per_launch / (fm * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if fm else None}
     return out
+
+
+DUMP_BYTES = 48 << 20   # the float32 sample of --dump-outputs (the whole dump stays under 64 MB)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(dirname, out, torch):
+    """--dump-outputs: what the last timed step returned to this rank, `out` = its (n, H, W) u8 edge maps.
+    edges.npy          float32 (k, rows, W): a fixed, seeded sample of k whole maps (0 / 255), or of rows of one map when
+                       a single map exceeds DUMP_BYTES
+    edges_index.npy    float64 (k,): which maps the sample holds
+    edge_pixels.npy    float64 (n,): the edge pixels of EVERY map of the step"""
+    n, h, w = out.shape
+    rng = np.random.default_rng(DUMP_SEED)
+    k = max(1, min(n, DUMP_BYTES // (h * w * 4)))
+    idx = np.sort(rng.choice(n, size=k, replace=False))
+    rows = np.arange(h) if k > 1 or h * w * 4 <= DUMP_BYTES else np.sort(rng.choice(h, size=DUMP_BYTES // (w * 4), replace=False))
+    sample = out[torch.from_numpy(idx).to(out.device)][:, torch.from_numpy(rows).to(out.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "edges.npy"), sample.float().cpu().numpy())
+    np.save(os.path.join(dirname, "edges_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, "edge_pixels.npy"), (out != 0).sum(dim=(1, 2)).double().cpu().numpy())
 
 
 def _percentiles(ms):

@@ -1,9 +1,10 @@
 """Generates tests/golden/ref_kernels_{fma,nofma}.npz: inputs and EVERY stage output of the reference's own device
-kernels (src/cvp/cannyEdgeD.cu compiled in place by oracle/build_ref.sh into oracle/_ref/libref_*.so), run on an MI355X.
+kernels (src/cvp/cannyEdgeD.cu compiled in place by oracle/build_ref.sh into oracle/_ref/libref_*.so), run on an MI355X,
+and tests/golden/ref_kernels_gpu_cases.npz: the same kernels' outputs on the inputs of tests/test_gpu_reference_kernels.py.
 
-Run once on the GPU box (the reference sources never travel; the prebuilt oracle/_ref/*.so do):
-    gpurun -- python tests/golden/make_ref_fixtures.py gpurun_out/fixtures
-and copy the two .npz files into tests/golden/.  The files hold data only (u8 / i16 / f32 arrays).
+Run once on an MI355X with oracle/_ref built (the reference sources themselves are not needed there):
+    python tests/golden/make_ref_fixtures.py OUTDIR
+and copy the .npz files into tests/golden/.  The files hold data only (u8 / i16 / f32 arrays).
 
 What the fixtures pin and what they cannot: the kernels are the reference's source text, but compiled by hipcc for
 gfx950 (no nvcc in this image) and launched by oracle/ref_driver.hip, a restatement of the host launch sequence of
@@ -11,6 +12,7 @@ src/cvp/cannyEdgeH.cu.  hipcc lowers `min((unsigned char)gradVal, 255)` (cannyEd
 the `nms` arrays here follow the oracle's saturate=True variant; everything else is common to both readings.
 `fma` = default contraction forced to fmaf (nvcc's -fmad=true), `nofma` = -ffp-contract=off."""
 import ctypes as C
+import hashlib
 import os
 import sys
 
@@ -103,7 +105,68 @@ def main(outdir):
         path = os.path.join(outdir, f"ref_kernels_{variant}.npz")
         np.savez_compressed(path, **d)
         print(path, os.path.getsize(path), "bytes,", len(names), "cases")
+    main_gpu_cases(outdir)
+
+
+# the inputs of tests/test_gpu_reference_kernels.py (its IMAGES, the BGR case, the hysteresis-cap maps): keep in step with it
+def gpu_cases():
+    rng = np.random.default_rng(3)
+    return [
+        ("natural_640x480", synth.natural(640, 480, 1)),
+        ("noise_333x222", synth.noise(333, 222, 2)),
+        ("flat100", synth.flat(40, 36, 100)),
+        ("step255", synth.steps(96, 64, 255, "vertical")),
+        ("step234d", synth.steps(96, 96, 234, "diagonal")),
+        ("serpentine", synth.serpentine(300, 200)),
+        ("bgr_noise_77x50", rng.integers(0, 256, (50, 77, 3), dtype=np.uint8)),
+    ]
+
+
+def gpu_hyst_cases():
+    return [("hyst_random_97x61", synth.thresh_map_random(97, 61, 1, 0.45, 0.01)),
+            ("hyst_serpentine_200x300", synth.thresh_map_serpentine(200, 300))]
+
+
+def plane_digest(a):
+    """SHA-256 of a plane's dtype, shape and C-order bytes (tests/test_gpu_reference_kernels.py computes the same)."""
+    a = np.ascontiguousarray(a)
+    return np.frombuffer(hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).digest(), np.uint8)
+
+
+def main_gpu_cases(outdir):
+    """tests/golden/ref_kernels_gpu_cases.npz: what tests/test_gpu_reference_kernels.py reads from the reference kernels,
+    for a checkout without oracle/_ref (thresholds 10 / 40).  Keys "<variant>/<case>/<plane>": the planes that test
+    needs element by element (nms, thresh, edges, mono) as arrays; the dense planes it only compares for equality (blur,
+    the Sobel sums as int16, grad_disp) and the input, by which a case is found, as "<plane>.sha256" (plane_digest)."""
+    d = {}
+    for variant in ("fma", "nofma"):
+        L = load(variant)
+        for name, img in gpu_cases():
+            r = ref_run(L, img, 10, 40)
+            p = f"{variant}/{name}/"
+            d[p + "input.sha256"] = plane_digest(img)
+            for k in (("mono", "edges") if img.ndim == 3 else ("nms", "thresh", "edges")):
+                d[p + k] = r[k]
+            d[p + "launches"] = r["launches"]
+            if img.ndim == 2:
+                for k in ("blur", "grad_disp"):
+                    d[p + k + ".sha256"] = plane_digest(r[k])
+                for k in ("sobelX", "sobelY"):
+                    v = r[k] * 8
+                    assert np.array_equal(v, np.round(v)) and np.abs(v).max() <= 1020
+                    d[p + k + "8.sha256"] = plane_digest(v.astype(np.int16))
+        for name, t in gpu_hyst_cases():
+            out = np.zeros_like(t)
+            n = C.c_int()
+            assert L.ref_hysteresis(t.ctypes.data_as(u8p), t.shape[1], t.shape[0], out.ctypes.data_as(u8p), C.byref(n)) == 0
+            p = f"{variant}/{name}/"
+            d[p + "input.sha256"] = plane_digest(t)
+            d[p + "edges"] = out
+            d[p + "launches"] = np.int32(n.value)
+    path = os.path.join(outdir, "ref_kernels_gpu_cases.npz")
+    np.savez_compressed(path, **d)
+    print(path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "fixtures"))
+    main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "build", "fixtures"))
