@@ -51,6 +51,7 @@ OPT_COPY_STREAMS = 9
 OPT_PIPELINE_SLOTS = 10
 OPT_FRONT_WPB = 11
 OPT_FRONT_MX = 12
+OPT_APERTURE = 13   # mode O: cv::Canny's apertureSize, 3 (default) or 5
 OPT_TEST_HYST_LATE_GRID, OPT_TEST_HYST_LOOP, OPT_TEST_HYST_DIAG, OPT_TEST_HYST_GEOM, OPT_TEST_DENSE_ENTER, OPT_TEST_DENSE_LEAVE = 100, 101, 102, 103, 104, 105   # test / diagnostic hooks
 TAP_BLUR, TAP_THRESH = 1, 2
 
@@ -60,7 +61,7 @@ ABI_SYMBOLS = [
     "hc_hysteresis_device", "hc_download", "hc_sync", "hc_set_stream", "hc_enable_profiling", "hc_stage_time_ms", "hc_profile_get",
     "hc_device_ptrs", "hc_last_hysteresis_info", "hc_hysteresis_stats", "hc_set_tuning", "hc_set_option", "hc_selftest", "hc_last_error", "hc_version",
     "hc_host_alloc", "hc_host_free", "hc_profile_get_front", "hc_debug_tap", "hc_use_own_stream", "hc_profile_get_intervals", "hc_last_run_info", "hc_pipeline_depth", "hc_pipeline_slots_in_use", "hc_front_waves_per_workgroup",
-    "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_download_begin", "hc_download_end",
+    "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
 ]
 
 _lib = None
@@ -113,6 +114,7 @@ def load_library(legacy=False):
     L.hc_run.argtypes = [vp, i, i]
     L.hc_run_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i]
     L.hc_hysteresis_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i]
+    L.hc_run_gradients_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, i]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -175,6 +177,7 @@ class Context:
         such a context is created in libhipcanny_legacy.so (parity tests, bench.py --front split / fused4)."""
         self.lib = load_library(legacy=front_split in (0, 1) and int(mode) == MODE_R)
         self.w, self.h, self.c, self.max_batch = int(width), int(height), int(channels), int(max_batch)
+        self.device = int(device)
         self.handle = self.lib.hc_create(int(device), self.w, self.h, self.c, self.max_batch, int(mode))
         if not self.handle:
             raise HipCannyError(f"hc_create failed: {last_error()}")
@@ -288,6 +291,34 @@ class Context:
     def run_device(self, d_in, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes, final_stage=CannyStage.HYSTER):
         _ck(self.lib.hc_run_device(self.handle, C.c_void_p(d_in), in_pitch, in_fs, C.c_void_p(d_out), out_pitch, out_fs,
                                    int(nframes), int(final_stage)))
+
+    def run_gradients_device(self, d_dx, d_dy, pitch, fs, d_out, out_pitch, out_fs, nframes):
+        """cv::Canny(dx, dy, edges, low, high, L2gradient) on device memory (mode O): int16 dx / dy planes with the same
+        pitch / frame stride in bytes -> u8 edge maps (hc_run_gradients_device).  Asynchronous, as run_device."""
+        _ck(self.lib.hc_run_gradients_device(self.handle, C.c_void_p(d_dx), C.c_void_p(d_dy), pitch, fs, C.c_void_p(d_out),
+                                             out_pitch, out_fs, int(nframes)))
+
+    def process_gradients(self, dx, dy):
+        """cv::Canny(dx, dy, ...) convenience (mode O): numpy int16 (n,H,W) / (n,H,W,3) -- or one frame -- in, uint8
+        (n,H,W) edge maps out, through device tensors."""
+        import torch
+        shape = (self.h, self.w) if self.c == 1 else (self.h, self.w, 3)
+        a, b = (np.ascontiguousarray(v) for v in (dx, dy))
+        if a.dtype != np.int16 or b.dtype != np.int16:
+            raise HipCannyError("process_gradients: dx and dy must be int16 (CV_16SC1 / CV_16SC3)")
+        if a.ndim == len(shape):
+            a, b = a[None], b[None]
+        if a.shape != b.shape or a.shape[1:] != shape:
+            raise HipCannyError(f"process_gradients: dx {a.shape} / dy {b.shape} do not match the context's {shape}")
+        n = a.shape[0]
+        dev = torch.device("cuda", self.device)
+        tx, ty = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
+        pitch = 2 * self.c * self.w
+        self.run_gradients_device(tx.data_ptr(), ty.data_ptr(), pitch, pitch * self.h, out.data_ptr(), self.w, self.w * self.h, n)
+        self.sync()
+        return out.cpu().numpy()
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

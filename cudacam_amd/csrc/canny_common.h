@@ -64,6 +64,17 @@ struct FrontParams {
   u32 wrap_limit;  // S >= wrap_limit: gradient >= 256, the wrap bands apply (0xFFFFFFFF: saturating variant)
 };
 
+// Mode O beyond k_front_o (front_o_ext.hip): the 5x5 Sobel of u8 frames (aperture 5), or caller-given int16 derivatives
+// (cv::Canny's (dx, dy) overload).  f as for k_front_o (thresholds in a_lo[0] / a_hi[0], chunk_rows, l2gradient); with
+// gradients != 0, f.in is dx and dy the dy planes, both with f.in_pitch / f.in_frame_stride (bytes, even), `channels`
+// interleaved int16 per pixel.
+struct FrontExtParams {
+  FrontParams f;
+  int gradients;
+  int channels;
+  const uint8_t *dy;
+};
+
 struct HystParams {
   u32 *sbits;
   const u32 *cbits;
@@ -104,6 +115,7 @@ struct PackParams {  // tri-state u8 map (0/128/255) -> bit planes
 hipError_t launch_selftest(u32 *d_result, hipStream_t s);
 hipError_t check_gauss_coeffs(const float gk[25]);
 hipError_t launch_front_o(const FrontParams &p, hipStream_t s);
+hipError_t launch_front_o_ext(const FrontExtParams &p, hipStream_t s);  // front_o_ext.hip
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

@@ -114,6 +114,7 @@ struct hc_ctx {
   bool split_set = false;  // HC_OPT_FRONT_SPLIT was set by the caller
   int split = 2;        // Mode R front path: 2 = k_front8 (one kernel, 8 px per lane; default), 1 = k_blur + k_nms, 0 = the 4-px fused k_front
   int l2gradient = 0;   // Mode O: cv::Canny's L2gradient flag
+  int aperture = 3;     // Mode O: cv::Canny's apertureSize (HC_OPT_APERTURE: 3 = k_front8o / k_front_o, 5 = k_front_o_ext)
   int half_mode = -1;   // HC_OPT_FRONT_HALF: -1 automatic, 0 never, 1 whenever the buffers allow it
   int dense_mode = -1;  // HC_OPT_FRONT_DENSE: -1 automatic, 0 never, 1 every window
   int mx_mode = 0;      // HC_OPT_FRONT_MX: 1 = k_front_mx whenever the run allows it (opt-in: include/hipcanny.h)
@@ -596,7 +597,10 @@ int queue_hyst_expand(hc_ctx *c, Slot &s, hipStream_t st, uint8_t *out, size_t o
   return HC_OK;
 }
 
-int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_t *out, size_t out_pitch, size_t out_fs, int n, int stage)
+// in_dy != null: `in` and `in_dy` are the int16 dx / dy planes of cv::Canny's (dx, dy) overload (Mode O, HC_STAGE_HYSTER,
+// even addresses / pitch / frame stride: k_front_o_ext reads them as they are, nothing is staged)
+int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_t *out, size_t out_pitch, size_t out_fs, int n, int stage,
+             const uint8_t *in_dy = nullptr)
 {
   if (c->mode == HC_MODE_O && stage != HC_STAGE_HYSTER)
     return fail(HC_E_ARG, "mode O (cv::Canny) produces the final edge map only (cv::Canny has no intermediate outputs)");
@@ -604,6 +608,9 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
   if (c->per_channel && stage != HC_STAGE_HYSTER) return fail(HC_E_ARG, "per-channel mode only produces the final edge maps (HC_STAGE_HYSTER)");
   const int W = c->W, H = c->H;
   const int n_out = c->per_channel ? 3 * n : n;  // output frames (= bit-plane frames)
+  // Mode O forms of k_front_o_ext: caller-given gradients (form 7), or aperture 5 on u8 frames (form 6)
+  const bool grad_in = in_dy != nullptr;
+  const bool ext = c->mode == HC_MODE_O && (grad_in || c->aperture == 5);
   const bool piped = c->pipeline && stage == HC_STAGE_HYSTER;
   if (piped) {
     // big batches rotate through two slots, small ones (fewer than 0.5 G pixels per run: the step is the latency of the
@@ -636,9 +643,10 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
   // 24 bytes per lane and row: tight rows of a width that is not a multiple of 8.  Round 2 fell back to the 4-px kernels
   // for those; one copy through the internal pitched buffer keeps every frame on the one-kernel path)
   c->last_in_staged = 0;
-  const bool wants8 = stage == HC_STAGE_HYSTER && c->split == 2 && (c->mode == HC_MODE_R || c->C == 1);
-  if (!aligned4(in, in_pitch, in_fs) || (c->mode == HC_MODE_O && c->C == 3 && in_pitch < round_up((size_t)c->W, 4) * 3)
-      || (wants8 && in_pitch < round_up((size_t)c->W, 8) * (size_t)c->C)) {
+  // (k_front_o_ext on u8 frames reads whole 4-pixel groups, in every channel count)
+  const bool wants8 = stage == HC_STAGE_HYSTER && c->split == 2 && (c->mode == HC_MODE_R || c->C == 1) && !ext;
+  if (!grad_in && (!aligned4(in, in_pitch, in_fs) || (c->mode == HC_MODE_O && (c->C == 3 || ext) && in_pitch < round_up((size_t)c->W, 4) * c->C)
+                   || (wants8 && in_pitch < round_up((size_t)c->W, 8) * (size_t)c->C))) {
     c->last_in_staged = 1;
     if (int rc = copy_frames_d2d(c, sf, c->d_in, c->in_pitch, c->in_fs, in, in_pitch, in_fs, (size_t)W * c->C, n)) return rc;
     src = c->d_in; sp = c->in_pitch; sfs = c->in_fs;
@@ -682,7 +690,7 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
   const bool whole_groups = sp >= round_up((size_t)W, 4) * 3;
   if (c->per_channel && !whole_groups) return fail(HC_E_ARG, "per-channel mode needs an input pitch of at least 3 * round_up(width, 4) bytes");
   const bool fuse_bgr = c->C == 3 && stage == HC_STAGE_HYSTER && whole_groups;
-  if (c->C == 3 && !fuse_bgr) {
+  if (c->C == 3 && !fuse_bgr && !grad_in) {
     if (stage == HC_STAGE_MONO) {
       HIPCK(launch_gray(src, sp, sfs, dst, dp, dfs, W, H, n, sf));
     } else {
@@ -716,7 +724,8 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
     // Mode O: k_front8o (form 3) for one-channel sources, the 4-px k_front_o (form -1) for 3-channel ones, for rows that
     // do not hold whole 8-pixel groups, or when HC_OPT_FRONT_SPLIT asks for a 4-px form
     // (Narrow frames: k_front8's HALF form, below.  Round 2 sent 640-column batches to k_blur + k_nms instead.)
-    const int form = c->mode != HC_MODE_R ? ((c->C == 1 && c->split == 2 && can8) ? 3 : -1) : (c->split == 2 && !can8) ? 1 : c->split;  // (!can8 cannot happen any more: such rows were staged above)
+    const int form = ext ? (grad_in ? 7 : 6)
+                     : c->mode != HC_MODE_R ? ((c->C == 1 && c->split == 2 && can8) ? 3 : -1) : (c->split == 2 && !can8) ? 1 : c->split;  // (!can8 cannot happen any more: such rows were staged above)
     const bool split = form == 1, f8 = form == 2 || form == 3;
     c->last_front_form = form;  // (4 when k_front8 runs in its half-strip form, below)
     // Pipelined mode: k_nms / k_front_o also write the strong pixels as 255 into the output (4 px per lane: whole
@@ -739,7 +748,8 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
         if (int rc = finish_slot(c, o)) return rc;
       }
     }
-    s.prov = piped && !out_overlap && (f8 ? W % 8 == 0 : (W % 4 == 0 && (split || c->mode == HC_MODE_O)));
+    // (k_front_o_ext writes no provisional map: its runs give the hysteresis the whole map to write)
+    s.prov = piped && !out_overlap && !ext && (f8 ? W % 8 == 0 : (W % 4 == 0 && (split || c->mode == HC_MODE_O)));
     if (piped) { s.out0 = o0; s.out1 = o1; }
     if (s.prov) { fp.prov_out = dst; fp.prov_pitch = (u32)dp; fp.prov_fs = dfs; }
     if (c->debug_taps) {
@@ -846,7 +856,19 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
         fp.a_lo[0] = (u32)c->low * (u32)c->low;
         fp.a_hi[0] = (u32)c->high * (u32)c->high;
       }
-      if (f8) {
+      if (ext) {  // k_front_o_ext: k_front_o's strips and work split (a 6-row warm-up for aperture 5, 2 rows for gradients)
+        const long units = (long)n_out * c->nstrips;
+        const int per_strip = (int)std::max<long>(1, std::min<long>((12288 + units - 1) / units, (H + 15) / 16));
+        fp.chunk_rows = (H + per_strip - 1) / per_strip;
+        fp.nchunks = (H + fp.chunk_rows - 1) / fp.chunk_rows;
+        fp.total_items = n_out * fp.nstrips * fp.nchunks;
+        FrontExtParams ep{};
+        ep.f = fp;
+        ep.gradients = grad_in ? 1 : 0;
+        ep.channels = c->C;
+        ep.dy = in_dy;
+        HIPCK(launch_front_o_ext(ep, sf));
+      } else if (f8) {
         HIPCK(launch_front8o(fp, sf));  // strips and runs as set for k_front8 above
       } else {
         const long units = (long)n_out * c->nstrips;
@@ -857,7 +879,8 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
         if (sp < round_up((size_t)W, 4) * (size_t)c->C) return fail(HC_E_ARG, "mode O needs an input pitch of at least round_up(width, 4) * channels");
         HIPCK(launch_front_o(fp, sf));
       }
-      HIPCK(mark(sf, B_GRAD | B_NMS | B_THR, hc_ctx::K_FRONT_B));  // cv::Canny has no blur stage
+      // cv::Canny has no blur stage; given gradients leave NMS + thresholds only (GRADIENT did not run)
+      HIPCK(mark(sf, (grad_in ? 0u : B_GRAD) | B_NMS | B_THR, hc_ctx::K_FRONT_B));
     } else {
       band_thresholds(c->low, c->nms_saturate != 0, fp.a_lo);
       band_thresholds(c->high, c->nms_saturate != 0, fp.a_hi);
@@ -1175,6 +1198,13 @@ int hc_set_option(hc_ctx *c, int option, int value)
   } else if (option == HC_OPT_L2_GRADIENT) {
     if (c->mode != HC_MODE_O) return fail(HC_E_ARG, "HC_OPT_L2_GRADIENT applies to mode O contexts");
     c->l2gradient = value != 0;
+  } else if (option == HC_OPT_APERTURE) {
+    if (c->mode != HC_MODE_O) return fail(HC_E_ARG, "HC_OPT_APERTURE applies to mode O contexts");
+    if (value == 7)
+      return fail(HC_E_ARG, "HC_OPT_APERTURE 7 is not offered: cv::Canny scales the 7x7 Sobel and its thresholds to stay within "
+                            "int16, which this library does not restate; compute the derivatives and use hc_run_gradients_device");
+    if (value != 3 && value != 5) return fail(HC_E_ARG, "HC_OPT_APERTURE: 3 (default) or 5");
+    c->aperture = value;
   } else if (option == HC_OPT_DEBUG_TAPS) {
     c->debug_taps = value != 0;
     c->dbg_frames = 0;
@@ -1234,6 +1264,22 @@ int hc_run_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, vo
   if (n > 1 && (in_fs < in_pitch * (size_t)c->H || out_fs < out_pitch * (size_t)c->H)) return fail(HC_E_ARG, "hc_run_device: frame stride smaller than a frame");
   HIPCK(hipSetDevice(c->device));
   return run_impl(c, (const uint8_t *)d_in, in_pitch, in_fs, (uint8_t *)d_out, out_pitch, out_fs, n, final_stage);
+}
+
+int hc_run_gradients_device(hc_ctx *c, const void *d_dx, const void *d_dy, size_t pitch, size_t frame_stride, void *d_out, size_t out_pitch,
+                            size_t out_frame_stride, int n)
+{
+  if (!c || !d_dx || !d_dy || !d_out) return fail(HC_E_ARG, "hc_run_gradients_device: null argument");
+  if (c->mode != HC_MODE_O) return fail(HC_E_ARG, "hc_run_gradients_device: mode O contexts only (cv::Canny's (dx, dy) overload)");
+  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_run_gradients_device: nframes out of range");
+  if ((((uintptr_t)d_dx | (uintptr_t)d_dy | pitch | frame_stride) & 1u) != 0)
+    return fail(HC_E_ARG, "hc_run_gradients_device: int16 planes need even addresses, pitch and frame stride");
+  if (pitch < (size_t)2 * c->C * c->W || out_pitch < (size_t)c->W) return fail(HC_E_ARG, "hc_run_gradients_device: pitch smaller than a row");
+  if (n > 1 && (frame_stride < pitch * (size_t)c->H || out_frame_stride < out_pitch * (size_t)c->H))
+    return fail(HC_E_ARG, "hc_run_gradients_device: frame stride smaller than a frame");
+  HIPCK(hipSetDevice(c->device));
+  return run_impl(c, (const uint8_t *)d_dx, pitch, frame_stride, (uint8_t *)d_out, out_pitch, out_frame_stride, n, HC_STAGE_HYSTER,
+                  (const uint8_t *)d_dy);
 }
 
 int hc_hysteresis_device(hc_ctx *c, const void *d_thresh, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n)

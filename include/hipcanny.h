@@ -29,8 +29,10 @@ typedef struct hc_ctx hc_ctx;
 enum { HC_STAGE_MONO = 0, HC_STAGE_GAUSSIAN = 1, HC_STAGE_GRADIENT = 2, HC_STAGE_NMS = 3, HC_STAGE_THRESH = 4, HC_STAGE_HYSTER = 5 };
 
 /* Parity modes.  R: bit-exact with the reference kernels (src/cvp/cannyEdgeD.cu).
- * O: bit-exact with OpenCV cv::Canny(img, low, high, 3, L2gradient) (no blur, replicate border; L2gradient
- *    false unless HC_OPT_L2_GRADIENT is set). */
+ * O: cv::Canny(img, low, high, apertureSize, L2gradient) semantics (no blur, replicate border; apertureSize 3 unless
+ *    HC_OPT_APERTURE is 5; L2gradient false unless HC_OPT_L2_GRADIENT is set), and cv::Canny(dx, dy, edges, low, high,
+ *    L2gradient) through hc_run_gradients_device.  Restated from the published algorithm (tests/ and oracle/); not
+ *    pinned against a build of OpenCV itself. */
 enum { HC_MODE_R = 0, HC_MODE_O = 1 };
 
 enum {
@@ -77,6 +79,20 @@ int hc_run(hc_ctx *ctx, int final_stage, int nframes);
 int hc_run_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
                   size_t out_frame_stride, int nframes, int final_stage);
 
+/* Mode O: cv::Canny's second overload, cv::Canny(dx, dy, edges, low, high, L2gradient) (cv::cuda::CannyEdgeDetector::
+ * detect(dx, dy, edges)): `d_dx` / `d_dy` hold nframes frames of caller-computed int16 derivatives (CV_16SC1, or CV_16SC3:
+ * 3 interleaved channels as the context's `channels`), both with the same `pitch` and `frame_stride` in BYTES; `d_out`
+ * receives the u8 edge maps as for hc_run_device.  The rest of the mode O pipeline after its Sobel runs (magnitude, the
+ * 3-channel select, NMS, thresholds, hysteresis) in 32-bit two's-complement arithmetic with wrap-around, as canny.cpp's
+ * `int`: for full-range input the tangent test's x * (TG22 + 2^16) wraps once |dx| >= 27146, and the L2 magnitude wraps
+ * to INT_MIN for dx = dy = -32768.  Always runs to HC_STAGE_HYSTER; honours HC_OPT_L2_GRADIENT, ignores HC_OPT_APERTURE;
+ * stream semantics as hc_run_device (hc_set_stream, HC_OPT_PIPELINE).  Addresses, pitch and frame stride need only be
+ * even (odd widths with tight rows are fine); no byte outside [row start, row start + 2 * channels * width) of a row is
+ * read.  HC_E_ARG for a mode R context, null or odd pointers / pitches, pitch < 2 * channels * width, nframes outside
+ * 1..max_batch. */
+int hc_run_gradients_device(hc_ctx *ctx, const void *d_dx, const void *d_dy, size_t pitch, size_t frame_stride, void *d_out,
+                            size_t out_pitch, size_t out_frame_stride, int nframes);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
@@ -114,7 +130,8 @@ int hc_use_own_stream(hc_ctx *ctx);
  * books a stage only when it ran.  Attribution: the plain per-stage kernels behind final_stage < HYSTER each have their
  * own interval.  On the HYSTER fast path one kernel covers several reference stages and has no internal boundary to
  * time: k_blur covers MONO (3-channel input) + GAUSSIAN, k_nms covers GRADIENT + NMS + THRESH, a fused front kernel
- * covers all of them, k_front_o (mode O) GRADIENT + NMS + THRESH; a kernel's time is divided EQUALLY among the stages
+ * covers all of them, k_front_o (mode O) GRADIENT + NMS + THRESH, as does k_front_o_ext at aperture 5 (front form 6);
+ * on given gradients (hc_run_gradients_device, form 7) it covers NMS + THRESH and GRADIENT reads -1; a kernel's time is divided EQUALLY among the stages
  * it covers, so every stage that ran shows a non-zero share and the sum over stages -- what the reference's UI totals
  * up to the selected stage (src/imgui/imguiApp.cpp:364-376) -- is the measured time.  Off by default on the batch path. */
 int hc_enable_profiling(hc_ctx *ctx, int on);
@@ -153,7 +170,8 @@ int hc_hysteresis_totals(hc_ctx *ctx, unsigned long long totals[4], int reset);
  * 1 when the frames went through the context's internal pitched buffers (an extra device-to-device copy each: pointer,
  * pitch or frame stride not a multiple of 4, or 3-channel mode O rows without whole 12-byte groups), and *front_form is
  * the front path that ran (Mode R: the HC_OPT_FRONT_SPLIT value 2 / 1 / 0, 4 = k_front8 in its half-strip form, or 5 = k_front_mx; Mode O:
- * 3 = k_front8o, -1 = k_front_o; -1 also for final stages below HYSTER).  Rows that do not hold whole 8-pixel groups
+ * 3 = k_front8o, -1 = k_front_o, 6 = k_front_o_ext at HC_OPT_APERTURE 5, 7 = k_front_o_ext on given gradients
+ * (hc_run_gradients_device); -1 also for final stages below HYSTER).  Rows that do not hold whole 8-pixel groups
  * (tight rows of a width that is not a multiple of 8) are staged (*input_staged = 1) so that the 8-px kernels can run. */
 int hc_last_run_info(hc_ctx *ctx, int *input_staged, int *output_staged, int *front_form);
 
@@ -210,7 +228,17 @@ int hc_set_tuning(hc_ctx *ctx, int chunk_rows, int hyst_launches);
  * 3-channel sources and rows without whole 8-pixel groups use k_front_o), 0 or 1 = k_front_o, the 4-pixel kernel.
  *
  * HC_OPT_L2_GRADIENT (default 0, Mode O contexts): cv::Canny's `L2gradient` argument: magnitude dx^2 + dy^2
- * compared with the squared thresholds instead of |dx| + |dy|. */
+ * compared with the squared thresholds instead of |dx| + |dy|.
+ *
+ * HC_OPT_APERTURE (default 3, Mode O contexts): cv::Canny's `apertureSize`.  5 = Sobel(src, CV_16S, ksize 5, scale 1,
+ * BORDER_REPLICATE): |dx|, |dy| <= 12240, the L1 magnitude up to 24480; thresholds, the 3-channel select, the tangent test
+ * and NMS as at 3.  Runs k_front_o_ext (front form 6; 1 or 3 channels; rows without whole 4-pixel groups are staged).
+ * Any other value, and any mode R context, is HC_E_ARG; 7 is not offered (cv::Canny scales that Sobel and its thresholds
+ * to stay within int16, which is not restated here): such callers compute the derivatives and use
+ * hc_run_gradients_device.  Mode O thresholds stay clamped to 0..32767 at every aperture (L1 thresholds above 32767
+ * cannot be expressed).
+ * Pipelined mode (HC_OPT_PIPELINE) gives exact maps on both k_front_o_ext forms (6 and 7); they write no provisional map,
+ * so the hysteresis writes the whole output map of their runs. */
 /*
  * HC_OPT_DEBUG_TAPS (default 0): parity-test diagnostics.  1 = every HC_STAGE_HYSTER run keeps a copy of what the
  * FAST path's front kernels produced -- the STRONG and CANDIDATE bit planes as they are handed to the hysteresis,
@@ -254,7 +282,7 @@ int hc_set_tuning(hc_ctx *ctx, int chunk_rows, int hyst_launches);
  * before (2.37-2.43 against 2.50 ms), and half as much again on frames full of candidates (iid noise: 7.7 against 5.1 ms),
  * for which it has no dense path. */
 enum { HC_OPT_NMS_SATURATE = 1, HC_OPT_PIPELINE = 2, HC_OPT_PER_CHANNEL = 3, HC_OPT_FRONT_SPLIT = 4, HC_OPT_L2_GRADIENT = 5, HC_OPT_DEBUG_TAPS = 6, HC_OPT_FRONT_HALF = 7,
-       HC_OPT_FRONT_DENSE = 8, HC_OPT_COPY_STREAMS = 9, HC_OPT_PIPELINE_SLOTS = 10, HC_OPT_FRONT_WPB = 11, HC_OPT_FRONT_MX = 12,
+       HC_OPT_FRONT_DENSE = 8, HC_OPT_COPY_STREAMS = 9, HC_OPT_PIPELINE_SLOTS = 10, HC_OPT_FRONT_WPB = 11, HC_OPT_FRONT_MX = 12, HC_OPT_APERTURE = 13,
        /* test and diagnostic hooks (the library reads no environment variables): hysteresis launches >= 1 on a fixed grid with
         * worklists (-1: lists, default grid); the looping hysteresis launch of small runs off (0) / on; per-launch statistics for
         * tools/hyst_diag.py; hysteresis workgroup shape (rows x 100 + waves, 0 = by the rule); k_front8's dense-path thresholds */
