@@ -54,6 +54,8 @@ OPT_FRONT_MX = 12
 OPT_APERTURE = 13   # mode O: cv::Canny's apertureSize, 3 (default) or 5
 OPT_TEST_HYST_LATE_GRID, OPT_TEST_HYST_LOOP, OPT_TEST_HYST_DIAG, OPT_TEST_HYST_GEOM, OPT_TEST_DENSE_ENTER, OPT_TEST_DENSE_LEAVE = 100, 101, 102, 103, 104, 105   # test / diagnostic hooks
 TAP_BLUR, TAP_THRESH = 1, 2
+# words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
+SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
 # every symbol include/hipcanny.h declares
 ABI_SYMBOLS = [
@@ -61,7 +63,7 @@ ABI_SYMBOLS = [
     "hc_hysteresis_device", "hc_download", "hc_sync", "hc_set_stream", "hc_enable_profiling", "hc_stage_time_ms", "hc_profile_get",
     "hc_device_ptrs", "hc_last_hysteresis_info", "hc_hysteresis_stats", "hc_set_tuning", "hc_set_option", "hc_selftest", "hc_last_error", "hc_version",
     "hc_host_alloc", "hc_host_free", "hc_profile_get_front", "hc_debug_tap", "hc_use_own_stream", "hc_profile_get_intervals", "hc_last_run_info", "hc_pipeline_depth", "hc_pipeline_slots_in_use", "hc_front_waves_per_workgroup",
-    "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
+    "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
 ]
 
 _lib = None
@@ -139,6 +141,7 @@ def load_library(legacy=False):
     L.hc_profile_get_intervals.argtypes = [vp, C.POINTER(C.c_float), i, C.POINTER(i)]
     L.hc_profile_get_front_each.argtypes = [vp, C.POINTER(C.c_float), i, C.POINTER(i)]
     L.hc_hysteresis_totals.argtypes = [vp, C.POINTER(C.c_ulonglong), i]
+    L.hc_last_hysteresis_schedule.argtypes = [vp, C.POINTER(i), i]
     L.hc_host_alloc.restype = vp
     L.hc_host_alloc.argtypes = [sz]
     L.hc_host_free.restype = None
@@ -254,6 +257,15 @@ class Context:
         t = (C.c_ulonglong * 4)()
         _ck(self.lib.hc_hysteresis_totals(self.handle, t, int(bool(reset))))
         return tuple(int(v) for v in t)
+
+    def hysteresis_schedule(self):
+        """The schedule the most recent completed run got (hc_last_hysteresis_schedule), as a dict: launches queued,
+        lists (0 none / 1 from launch 1 / 2 mixed), loop, hist_grid (smallest grid sized from the previous run's lists, 0 if
+        none), longest (list a launch had to serve), overflows (launches whose list was longer than such a grid), tiles,
+        tile_rows, waves, panels, frames."""
+        v = (C.c_int * len(SCHEDULE_FIELDS))()
+        _ck(self.lib.hc_last_hysteresis_schedule(self.handle, v, len(SCHEDULE_FIELDS)))
+        return dict(zip(SCHEDULE_FIELDS, (int(x) for x in v)))
 
     def profile_get_front(self):
         """([k_blur_ms_sum, k_nms_ms_sum], nruns) of the profiled runs that took the split front path; call before

@@ -66,6 +66,12 @@ struct Slot {
   hipStream_t s_hyst = nullptr;  // this slot's hysteresis stream (pipelined mode)
   int hyst_level = 0;            // tile height level of this run's hysteresis (hc_ctx::hyst_obs index)
   int mixed_from = 0;            // > 0: launches below it ran a workgroup per tile, launch `mixed_from` wrote the first list, the rest took lists
+  // diagnostics (hc_last_hysteresis_schedule): the list scheme the run started with, whether k_hyst_loop ran its rounds, and
+  // per launch the grid that was sized from the last run's list (0: not a list launch, or sized by the tile count)
+  int sched_lists = 0;
+  bool sched_loop = false;
+  bool served_list[MAX_HYST_LAUNCHES] = { false };
+  int hist_grid[MAX_HYST_LAUNCHES] = { 0 };
   uintptr_t out0 = 0, out1 = 0;  // output range of this (pipelined, still pending) run: a later run into the same memory waits for it
   unsigned long long seq = 0;    // number of the pipelined run that uses the slot (hc_ctx::run_seq)
 };
@@ -136,6 +142,7 @@ struct hc_ctx {
   int hyst_geom = 0;
   bool hyst_launches_set = false;  // hc_set_tuning called: queue exactly that many launches
   int last_work_launches = 0, last_continued = 0;
+  int last_sched[HC_SCHED_WORDS] = { 0 };  // hc_last_hysteresis_schedule: the schedule of the last completed run
   int last_in_staged = 0, last_out_staged = 0, last_front_form = -1;  // what the last run did with the caller's buffers / which front kernels it used
   int hyst_need_rows = 0;  // launches that found work in recent runs (continuation rounds included) x rows per tile: how far changes travelled
   u32 h_stats[3 * MAX_HYST_LAUNCHES] = { 0 };
@@ -201,9 +208,14 @@ int alloc_slot_parts(hc_ctx *c, Slot &s)
   const size_t plane_bytes = sizeof(u32) * (size_t)c->RD * c->H * out_frames;
   HIPCK(hipMalloc((void **)&s.d_sbits, plane_bytes));
   HIPCK(hipMalloc((void **)&s.d_cbits, plane_bytes));
-  // row padding beyond the strips' bytes is never written by the kernels and must read as 0
-  HIPCK(hipMemset(s.d_sbits, 0, plane_bytes));
-  HIPCK(hipMemset(s.d_cbits, 0, plane_bytes));
+  // row padding beyond the strips' bytes is never written by the kernels and must read as 0.
+  // Cleared ON THE CONTEXT STREAM and waited for: slots 1..3 are allocated inside a run, with other runs in flight, and the
+  // front kernel that fills these planes is queued on c->stream a few microseconds later.  A plain hipMemset goes to the
+  // null stream, which the context's non-blocking streams do not wait for, and a device memset need not be complete when
+  // the call returns: a clear that lands after the front kernel wipes the candidate bits of the slot's first run.
+  HIPCK(hipMemsetAsync(s.d_sbits, 0, plane_bytes, c->stream));
+  HIPCK(hipMemsetAsync(s.d_cbits, 0, plane_bytes, c->stream));
+  HIPCK(hipStreamSynchronize(c->stream));
   // tiles of a run: at most out_frames x row tiles (16 rows or more each) x column panels
   s.wl_cap = out_frames * ((size_t)(c->H + 15) / 16 + 1) * ((c->RD + 63) / 64);
   HIPCK(hipMalloc((void **)&s.d_wl_list, sizeof(u32) * 2 * s.wl_cap));
@@ -422,6 +434,21 @@ int finish_slot(hc_ctx *c, Slot &s)
   // worklist lengths of this run's launches (wide frames): the next run of the same shape sizes its grids by them
   c->wl_prev_tiles = (s.ph.npanels > 1 || s.ph.lists) ? s.ph.wl_stride : 0;
   for (int k = 0; k <= MAX_HYST_LAUNCHES; ++k) c->wl_prev[k] = s.h_flags[FLAG_WORDS + k];
+  {  // diagnostics: the schedule this run got (read by hc_last_hysteresis_schedule; decides nothing)
+    int *d = c->last_sched;
+    d[HC_SCHED_LAUNCHES] = K; d[HC_SCHED_LISTS] = s.mixed_from > 0 ? 2 : s.sched_lists; d[HC_SCHED_LOOP] = s.sched_loop ? 1 : 0;
+    d[HC_SCHED_HIST_GRID] = d[HC_SCHED_LONGEST] = d[HC_SCHED_OVERFLOWS] = 0;
+    for (int k = 1; k < K && !s.sched_loop; ++k) {
+      if (!s.served_list[k]) continue;
+      const u32 len = s.h_flags[FLAG_WORDS + k];
+      d[HC_SCHED_LONGEST] = std::max(d[HC_SCHED_LONGEST], (int)std::min<u32>(len, 0x7FFFFFFFu));
+      if (s.hist_grid[k] <= 0) continue;
+      d[HC_SCHED_HIST_GRID] = d[HC_SCHED_HIST_GRID] ? std::min(d[HC_SCHED_HIST_GRID], s.hist_grid[k]) : s.hist_grid[k];
+      if (len > (u32)s.hist_grid[k]) d[HC_SCHED_OVERFLOWS] += 1;
+    }
+    d[HC_SCHED_TILES] = (int)std::min<size_t>(s.ph.wl_stride, 0x7FFFFFFF); d[HC_SCHED_TILE_ROWS] = s.ph.tile_rows; d[HC_SCHED_WAVES] = s.ph.waves;
+    d[HC_SCHED_PANELS] = s.ph.npanels; d[HC_SCHED_FRAMES] = s.ph.nframes;
+  }
   const int tile = s.ph.tile_rows * s.ph.waves;
   c->hyst_need_rows = std::max(c->last_work_launches * tile, c->hyst_need_rows - 32);  // follows the content up at once, down slowly
   // launches this run needed at its tile height (queue_hyst_expand picks the next runs' height from these)
@@ -552,6 +579,7 @@ int queue_hyst_expand(hc_ctx *c, Slot &s, hipStream_t st, uint8_t *out, size_t o
   else if (hp.npanels > 1) hp.lists = !(c->wl_prev_tiles == hp.wl_stride && (size_t)c->wl_prev[1] * 5 > hp.wl_stride * 3);
   else hp.lists = c->last_work_launches >= 20 || (c->hyst_lists_last && c->last_work_launches >= 14);
   c->hyst_lists_last = hp.lists != 0;
+  s.sched_lists = hp.lists != 0 ? 1 : 0;
   hp.first_pass = 1;
   hp.prov = s.prov ? 1 : 0;
   // The other streams: a workgroup per tile for launches 0 and 1 -- which do most of the work, and whose idle workgroups
@@ -568,6 +596,7 @@ int queue_hyst_expand(hc_ctx *c, Slot &s, hipStream_t st, uint8_t *out, size_t o
   // call, the reference's pattern: 0.150 against 0.168 ms)
   const bool loop = c->hyst_loop && !small_tiles && !hp.lists && !c->hyst_late_grid && !c->hyst_diag && hp.npanels == 1 && c->RD == 64 && hp.wl_stride <= (size_t)HYST_LOOP_MAX_TILES
                     && ((hp.tile_rows == 16 && hp.waves == 8) || (hp.tile_rows == 32 && hp.waves == 2));
+  s.sched_loop = loop;
   if (loop) {
     mixed_from = 0;
     hp.iter = 0; hp.late_grid = 0; hp.stats = nullptr;
@@ -581,7 +610,9 @@ int queue_hyst_expand(hc_ctx *c, Slot &s, hipStream_t st, uint8_t *out, size_t o
     // a run, launch_hyst's schedule by the tile count
     hp.late_grid = c->hyst_late_grid > 0 ? c->hyst_late_grid : 0;
     if (mixed_from > 0) hp.lists = k < mixed_from ? 0 : k == mixed_from ? 2 : 1;
-    if (hp.lists == 1 && !hp.late_grid && k > 0 && c->wl_prev_tiles == hp.wl_stride) hp.late_grid = (int)std::min<size_t>(hp.wl_stride, std::max<size_t>((size_t)2048, 2 * (size_t)c->wl_prev[k] + 256));
+    s.served_list[k] = hp.lists == 1 && k > 0;
+    s.hist_grid[k] = 0;
+    if (hp.lists == 1 && !hp.late_grid && k > 0 && c->wl_prev_tiles == hp.wl_stride) s.hist_grid[k] = hp.late_grid = (int)std::min<size_t>(hp.wl_stride, std::max<size_t>((size_t)2048, 2 * (size_t)c->wl_prev[k] + 256));
     // diagnostics cost ~3 same-address atomics per wave (hundreds of microseconds per launch): opt-in only
     hp.stats = c->hyst_diag ? s.d_flags + MAX_HYST_LAUNCHES + 3 * k : nullptr;
     HIPCK(launch_hyst(hp, st));
@@ -1574,6 +1605,14 @@ int hc_last_hysteresis_info(hc_ctx *c, int *launches_with_work, int *continued)
   if (int rc = finish_all(c)) return rc;
   if (launches_with_work) *launches_with_work = c->last_work_launches;
   if (continued) *continued = c->last_continued;
+  return HC_OK;
+}
+
+int hc_last_hysteresis_schedule(hc_ctx *c, int *info, int nwords)
+{
+  if (!c || !info) return fail(HC_E_ARG, "null argument");
+  if (int rc = finish_all(c)) return rc;
+  for (int i = 0; i < nwords && i < HC_SCHED_WORDS; ++i) info[i] = c->last_sched[i];
   return HC_OK;
 }
 

@@ -166,6 +166,27 @@ int hc_last_hysteresis_info(hc_ctx *ctx, int *launches_with_work, int *continued
  * totals[2] = hysteresis launches that found work, totals[3] = hysteresis launches queued.  Completes pending runs. */
 int hc_hysteresis_totals(hc_ctx *ctx, unsigned long long totals[4], int reset);
 
+/* The schedule the most recent completed run got (diagnostics; read-only, changes nothing).  How a run's hysteresis is
+ * queued follows what the earlier runs of the context observed; a prediction that is wrong costs time, never a pixel,
+ * and this entry lets a test see which schedule it exercised.  Completes pending runs, then writes up to `nwords` of:
+ *   info[HC_SCHED_LAUNCHES]    hysteresis launches queued (rounds, when the looping launch ran them)
+ *   info[HC_SCHED_LISTS]       0 = a workgroup per tile in every launch, 1 = worklists from launch 1 on,
+ *                              2 = mixed: a workgroup per tile first, lists from launch 3 on (launch 2 writes the first)
+ *   info[HC_SCHED_LOOP]        1 = all rounds ran inside one looping launch (k_hyst_loop)
+ *   info[HC_SCHED_HIST_GRID]   smallest grid of a list launch that was sized from the previous run's list lengths
+ *                              (max(2048, 2 * previous length + 256), at most the tile count); 0 = no launch was
+ *   info[HC_SCHED_LONGEST]     longest worklist a launch of the run had to serve (entries handed on included)
+ *   info[HC_SCHED_OVERFLOWS]   list launches whose history-sized grid was smaller than their list (entries handed on)
+ *   info[HC_SCHED_TILES]       workgroup tiles of the run (frames x row tiles x column panels)
+ *   info[HC_SCHED_TILE_ROWS], info[HC_SCHED_WAVES]   rows per wave and waves per workgroup: a tile has rows x waves rows
+ *   info[HC_SCHED_PANELS]      column panels (2048 columns each)
+ *   info[HC_SCHED_FRAMES]      output frames of the run
+ * LONGEST and OVERFLOWS describe the launches the run queued: they are taken before a host-side continuation, whose
+ * later lists they do not show.  All zero before the first completed HYSTER run. */
+enum { HC_SCHED_LAUNCHES = 0, HC_SCHED_LISTS, HC_SCHED_LOOP, HC_SCHED_HIST_GRID, HC_SCHED_LONGEST, HC_SCHED_OVERFLOWS, HC_SCHED_TILES,
+       HC_SCHED_TILE_ROWS, HC_SCHED_WAVES, HC_SCHED_PANELS, HC_SCHED_FRAMES, HC_SCHED_WORDS };
+int hc_last_hysteresis_schedule(hc_ctx *ctx, int *info, int nwords);
+
 /* What the last hc_run / hc_run_device did with the caller's buffers -- no silent cliffs: *input_staged / *output_staged are
  * 1 when the frames went through the context's internal pitched buffers (an extra device-to-device copy each: pointer,
  * pitch or frame stride not a multiple of 4, or 3-channel mode O rows without whole 12-byte groups), and *front_form is

@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads, exports every symbol that
 include/hipcanny.h declares, and refuses to run without a GPU (no CPU fallback)."""
+import ctypes as C
 import os
 import re
 
@@ -35,6 +36,20 @@ def test_bad_arguments_rejected(lib):
     assert "bad" in api.last_error()
     assert not lib.hc_create(0, 10, 10, 2, 1, 0)       # only 1 or 3 channels (CV_8UC1 / CV_8UC3)
     assert lib.hc_set_thresholds(None, 1, 2) != 0
+    info = (C.c_int * len(api.SCHEDULE_FIELDS))(*([7] * len(api.SCHEDULE_FIELDS)))
+    assert lib.hc_last_hysteresis_schedule(None, info, len(info)) == -1 and "null" in api.last_error()   # HC_E_ARG, nothing written
+    assert list(info) == [7] * len(info)
+
+
+def test_schedule_words_match_the_header():
+    """api.SCHEDULE_FIELDS names the words of hc_last_hysteresis_schedule in the order of the header's HC_SCHED_* indices."""
+    hdr = open(os.path.join(ROOT, "include", "hipcanny.h")).read()
+    body = re.search(r"enum\s*\{\s*(HC_SCHED_LAUNCHES[^}]*)\}", hdr).group(1)
+    names = [n.strip().split("=")[0].strip() for n in body.split(",") if n.strip()]
+    assert names[-1] == "HC_SCHED_WORDS"
+    assert tuple(n[len("HC_SCHED_"):].lower() for n in names[:-1]) == api.SCHEDULE_FIELDS
+    for n in names[:-1]:
+        assert f"info[{n}]" in hdr, f"{n} is not documented"
 
 
 def test_no_cpu_fallback(lib):

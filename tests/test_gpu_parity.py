@@ -764,10 +764,12 @@ def test_download_begin_end(oracle):
                     api._ck(lib.hc_download_begin(ctx.handle, C.c_void_p(hout), w, w * h, 2))
                     assert lib.hc_download_begin(ctx.handle, C.c_void_p(hout), w, w * h, 2) != 0   # one download at a time
                     api._ck(lib.hc_download_end(ctx.handle))
-                    got = np.ctypeslib.as_array((C.c_uint8 * (2 * w * h)).from_address(hout)).reshape(2, h, w)
+                    view = np.ctypeslib.as_array((C.c_uint8 * (2 * w * h)).from_address(hout)).reshape(2, h, w)
+                    got = view.copy()   # (not the pinned buffer itself: it is freed below, and a failure report would print freed memory)
+                    view[:] = 7
+                    del view
                     for f in range(2):
                         _diff(got[f], want[f], f"download_begin/end, {launches} launches queued, frame {f}")
-                    got[:] = 7
                 assert lib.hc_download_end(ctx.handle) != 0   # nothing in flight
                 if launches == 1:
                     assert ctx.hysteresis_totals()[1] == 2, "the one-launch runs were not continued from the host"
@@ -803,7 +805,7 @@ def test_download_end_after_a_continuation_elsewhere(oracle, between):
             else:
                 ctx.upload(frames)
             api._ck(lib.hc_download_end(ctx.handle))
-            got = np.ctypeslib.as_array((C.c_uint8 * (2 * w * h)).from_address(hout)).reshape(2, h, w)
+            got = np.ctypeslib.as_array((C.c_uint8 * (2 * w * h)).from_address(hout)).reshape(2, h, w).copy()   # (see test_download_begin_end)
             for f in range(2):
                 _diff(got[f], want[f], f"download_begin, hc_{between}, download_end: frame {f}")
     finally:
