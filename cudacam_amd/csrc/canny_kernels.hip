@@ -326,6 +326,7 @@ __global__ __launch_bounds__(256) void k_front_o(const FrontParams p)
 hipError_t launch_front_o(const FrontParams &p, hipStream_t s)
 {
   if (p.chunk_rows < 1 || (unsigned long long)p.H * p.in_pitch >= (1ull << 32)) return hipErrorInvalidValue;
+  if (p.prov_out && (unsigned long long)p.H * p.prov_pitch >= (1ull << 32)) return hipErrorInvalidValue;  // (32-bit row offsets into the provisional map)
   if (p.in_pitch < (size_t)(p.bgr ? 3 : 1) * (((size_t)p.W + 3) / 4 * 4)) return hipErrorInvalidValue;
   const dim3 grid((p.total_items + 3) / 4), block(256);
   if (p.bgr) {

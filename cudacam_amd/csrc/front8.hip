@@ -1070,7 +1070,7 @@ hipError_t launch_front8(const FrontParams &p, hipStream_t s)
   if (windows < 1 || p.run_rows != front8_run_rows(windows) || p.nchunks * p.run_rows < p.H) return hipErrorInvalidValue;
   const size_t w8 = ((size_t)p.W + 7) / 8 * 8;
   if ((unsigned long long)p.H * p.in_pitch >= (1ull << 32) || p.in_pitch < (p.bgr ? 3 : 1) * w8) return hipErrorInvalidValue;
-  if (p.prov_out && (p.W % 8 != 0)) return hipErrorInvalidValue;
+  if (p.prov_out && (p.W % 8 != 0 || (unsigned long long)p.H * p.prov_pitch >= (1ull << 32))) return hipErrorInvalidValue;  // (32-bit row offsets into the provisional map)
   if (p.dbg_blur && p.dbg_pitch < w8) return hipErrorInvalidValue;
   if (!p.dump || !p.dump_c || !p.dump_p || !p.zeros) return hipErrorInvalidValue;
   const int in_frames = p.bgr == 2 ? p.nframes / 3 : p.nframes, per = p.bgr == 2 ? 3 : 1;
@@ -1091,7 +1091,7 @@ hipError_t launch_front8o(const FrontParams &p, hipStream_t s)
   if (windows < 1 || p.run_rows != front8_run_rows(windows) || p.nchunks * p.run_rows < p.H || p.nstrips != front8_strips(p.W) || p.bgr) return hipErrorInvalidValue;
   const size_t w8 = ((size_t)p.W + 7) / 8 * 8;
   if ((unsigned long long)p.H * p.in_pitch >= (1ull << 32) || p.in_pitch < w8) return hipErrorInvalidValue;
-  if (p.prov_out && (p.W % 8 != 0)) return hipErrorInvalidValue;
+  if (p.prov_out && (p.W % 8 != 0 || (unsigned long long)p.H * p.prov_pitch >= (1ull << 32))) return hipErrorInvalidValue;  // (32-bit row offsets into the provisional map)
   if (!p.dump) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((p.total_items + 3) / 4)), block(256);
   const size_t lds = (size_t)4 * F8O_WAVE_BYTES;

@@ -581,7 +581,7 @@ hipError_t launch_front_mx(const FrontParams &p, hipStream_t s)
   if (p.nstrips != front_mx_strips(p.W) || (long)p.total_items != (long)p.nframes * p.nstrips * p.nchunks) return hipErrorInvalidValue;
   const size_t w4 = ((size_t)p.W + 3) / 4 * 4;
   if ((unsigned long long)p.H * p.in_pitch >= (1ull << 32) || p.in_pitch < w4) return hipErrorInvalidValue;
-  if (p.prov_out && (p.W % 8 != 0)) return hipErrorInvalidValue;
+  if (p.prov_out && (p.W % 8 != 0 || (unsigned long long)p.H * p.prov_pitch >= (1ull << 32))) return hipErrorInvalidValue;  // (32-bit row offsets into the provisional map)
   if (p.dbg_blur && p.dbg_pitch < (u32)p.W) return hipErrorInvalidValue;
   const int wpb = p.one_wave ? 1 : 4;
   const dim3 grid((unsigned)((p.total_items + wpb - 1) / wpb)), block(64 * wpb);

@@ -676,7 +676,10 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
   c->last_in_staged = 0;
   // (k_front_o_ext on u8 frames reads whole 4-pixel groups, in every channel count)
   const bool wants8 = stage == HC_STAGE_HYSTER && c->split == 2 && (c->mode == HC_MODE_R || c->C == 1) && !ext;
-  if (!grad_in && (!aligned4(in, in_pitch, in_fs) || (c->mode == HC_MODE_O && (c->C == 3 || ext) && in_pitch < round_up((size_t)c->W, 4) * c->C)
+  // (the front kernels address the rows of a frame with 32-bit offsets: a view whose height x pitch reaches 4 GiB -- a few
+  // columns of a huge parent -- is staged as well instead of being refused by their launchers)
+  const bool far_rows = (unsigned long long)H * in_pitch >= (1ull << 32);
+  if (!grad_in && (!aligned4(in, in_pitch, in_fs) || far_rows || (c->mode == HC_MODE_O && (c->C == 3 || ext) && in_pitch < round_up((size_t)c->W, 4) * c->C)
                    || (wants8 && in_pitch < round_up((size_t)c->W, 8) * (size_t)c->C))) {
     c->last_in_staged = 1;
     if (int rc = copy_frames_d2d(c, sf, c->d_in, c->in_pitch, c->in_fs, in, in_pitch, in_fs, (size_t)W * c->C, n)) return rc;
@@ -780,7 +783,10 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
       }
     }
     // (k_front_o_ext writes no provisional map: its runs give the hysteresis the whole map to write)
-    s.prov = piped && !out_overlap && !ext && (f8 ? W % 8 == 0 : (W % 4 == 0 && (split || c->mode == HC_MODE_O)));
+    // (nor into an output view whose height x pitch reaches 4 GiB: the front kernels place the provisional rows with 32-bit
+    // offsets, which would wrap -- row 1024 of a 4 MiB pitch onto row 0; the hysteresis, with 64-bit offsets, writes that map)
+    const bool far_out = (unsigned long long)H * dp >= (1ull << 32);
+    s.prov = piped && !out_overlap && !ext && !far_out && (f8 ? W % 8 == 0 : (W % 4 == 0 && (split || c->mode == HC_MODE_O)));
     if (piped) { s.out0 = o0; s.out1 = o1; }
     if (s.prov) { fp.prov_out = dst; fp.prov_pitch = (u32)dp; fp.prov_fs = dfs; }
     if (c->debug_taps) {

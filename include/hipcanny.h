@@ -75,7 +75,20 @@ int hc_run(hc_ctx *ctx, int final_stage, int nframes);
  * included -- must be readable for min(in_pitch, round_up(width, 8) * channels) bytes from its first byte: a
  * caller whose rows are padded to whole 8-pixel groups (in_pitch >= round_up(width, 8) * channels) must own that
  * padding after the last row too, i.e. allocate height * in_pitch bytes per frame.  No row is ever read beyond
- * its pitch. */
+ * its pitch.  What those bytes hold never changes a result: they may be row padding, the next frame, or -- for an ROI of
+ * a larger image -- the neighbouring pixels of the parent.
+ * Output views (this entry, hc_run_gradients_device and hc_hysteresis_device alike): only the bytes [row, row + width)
+ * of each of the height rows of each frame are written -- never the rest of a pitch, the gap between frames, or anything
+ * before or after the view -- in plain and in pipelined mode, in place and staged, so `d_out` may be an ROI of a larger
+ * image.  The input is never written.
+ * What keeps a view in place: base pointer, pitch and frame stride that are multiples of 4 (no 8- or 16-byte
+ * alignment is needed, on either side; 16-byte aligned outputs merely get wider stores), and for the input of a
+ * HC_STAGE_HYSTER run rows that hold whole pixel groups (above).  Anything else is staged -- one extra device-to-device
+ * copy of width (x channels) bytes per row, reported by hc_last_run_info -- and gives the same bytes.
+ * Views of 4 GiB and more: the front kernels address the rows of a frame with 32-bit offsets.  An input view with
+ * height * in_pitch >= 2^32 is therefore staged (reported as such); an output view with height * out_pitch >= 2^32 stays
+ * in place, but a pipelined run writes no provisional map into it (HC_OPT_PIPELINE below: the hysteresis then writes the
+ * whole map, as it does in plain mode).  Results are the same. */
 int hc_run_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
                   size_t out_frame_stride, int nframes, int final_stage);
 
@@ -189,7 +202,8 @@ int hc_last_hysteresis_schedule(hc_ctx *ctx, int *info, int nwords);
 
 /* What the last hc_run / hc_run_device did with the caller's buffers -- no silent cliffs: *input_staged / *output_staged are
  * 1 when the frames went through the context's internal pitched buffers (an extra device-to-device copy each: pointer,
- * pitch or frame stride not a multiple of 4, or 3-channel mode O rows without whole 12-byte groups), and *front_form is
+ * pitch or frame stride not a multiple of 4, 3-channel mode O rows without whole 12-byte groups, or an input view with
+ * height * pitch >= 2^32), and *front_form is
  * the front path that ran (Mode R: the HC_OPT_FRONT_SPLIT value 2 / 1 / 0, 4 = k_front8 in its half-strip form, or 5 = k_front_mx; Mode O:
  * 3 = k_front8o, -1 = k_front_o, 6 = k_front_o_ext at HC_OPT_APERTURE 5, 7 = k_front_o_ext on given gradients
  * (hc_run_gradients_device); -1 also for final stages below HYSTER).  Rows that do not hold whole 8-pixel groups
@@ -296,8 +310,9 @@ int hc_set_tuning(hc_ctx *ctx, int chunk_rows, int hyst_launches);
  *
  * HC_OPT_FRONT_MX (default 0, Mode R, one-channel frames): 1 = k_front_mx, the front path whose two integer
  * contractions (the 5x5 Gaussian sum, the 3x3 Sobel sums) run on the matrix pipe as v_mfma_i32_32x32x32_i8 (strips of 216
- * columns, blocks of 16 rows), for every run that allows it (input pitch >= round_up(width, 4), height x pitch < 2^32;
- * pipelined mode: width % 8 == 0).  Same results bit for bit; hc_last_run_info reports form 5; HC_OPT_FRONT_WPB 1 / 4
+ * columns, blocks of 16 rows), for every run that allows it (input pitch >= round_up(width, 4), height x pitch < 2^32
+ * -- other input views are staged first, so every one-channel run does; pipelined mode: the provisional map needs
+ * width % 8 == 0 and height x output pitch < 2^32, other runs go without it).  Same results bit for bit; hc_last_run_info reports form 5; HC_OPT_FRONT_WPB 1 / 4
  * picks its workgroup size.  Opt-in: measured on the MI355X (profiles/r04/mx_experiments.md) it takes 14 % less time than
  * k_front8 alone (1.83 against 2.14 ms per 1024 camera-like 1080p frames), 3-5 % less beside the hysteresis of the batch
  * before (2.37-2.43 against 2.50 ms), and half as much again on frames full of candidates (iid noise: 7.7 against 5.1 ms),

@@ -1,7 +1,10 @@
 // Host-side check of the C++ drop-in surface: drives cvp::cvPipeline exactly as CudaCam's UI does
 // (src/imgui/imguiApp.cpp:102, 328-348, 515) on a PGM-less synthetic frame read from stdin-free args:
-//   test_cvpipeline <w> <h> <channels> <in.raw> <stage> <out.raw>
+//   test_cvpipeline <w> <h> <channels> <in.raw> <stage> <out.raw> [<step> <x0> <y0>]
 // pytest generates the input, runs this binary on the GPU box and compares <out.raw> with the oracle.
+// With the three trailing arguments <in.raw> holds a parent image of <step> bytes per row (every whole row the file has)
+// and the frame is the w x h ROI at column x0, row y0 of it: cv::Mat(rows, cols, type, data, step), a Mat that is not
+// continuous and whose neighbours are the parent's pixels.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -11,11 +14,23 @@
 
 int main(int argc, char **argv)
 {
-  if (argc != 7) return 2;
+  if (argc != 7 && argc != 10) return 2;
   const int w = std::atoi(argv[1]), h = std::atoi(argv[2]), ch = std::atoi(argv[3]), stage = std::atoi(argv[5]);
-  std::vector<unsigned char> in(static_cast<size_t>(w) * h * ch);
+  const bool roi = argc == 10;
+  const size_t step = roi ? static_cast<size_t>(std::atoll(argv[7])) : static_cast<size_t>(w) * ch;
+  const size_t x0 = roi ? static_cast<size_t>(std::atoll(argv[8])) : 0, y0 = roi ? static_cast<size_t>(std::atoll(argv[9])) : 0;
+  if (w <= 0 || h <= 0 || (ch != 1 && ch != 3) || step < (x0 + static_cast<size_t>(w)) * ch) return 2;
   FILE *f = std::fopen(argv[4], "rb");
-  if (!f || std::fread(in.data(), 1, in.size(), f) != in.size()) return 3;
+  if (!f) return 3;
+  std::vector<unsigned char> in(static_cast<size_t>(w) * h * ch);
+  if (roi) {  // the whole parent: the ROI's rows must lie inside it
+    if (std::fseek(f, 0, SEEK_END) != 0) return 3;
+    const long bytes = std::ftell(f);
+    std::rewind(f);
+    if (bytes < 0 || static_cast<size_t>(bytes) < (y0 + static_cast<size_t>(h)) * step) return 3;
+    in.resize(static_cast<size_t>(bytes));
+  }
+  if (std::fread(in.data(), 1, in.size(), f) != in.size()) return 3;
   std::fclose(f);
 
   cvp::cvPipeline pipeline(0, static_cast<unsigned>(w), static_cast<unsigned>(h), ch);
@@ -25,7 +40,7 @@ int main(int argc, char **argv)
   pipeline.setLowThreshold(10);
   if (pipeline.process(cv::Mat(), static_cast<cvp::CannyStage>(stage))) return 6;                  // blank frame -> false
   if (pipeline.process(cv::Mat(h, w, CV_32FC1), static_cast<cvp::CannyStage>(stage))) return 7;   // wrong type -> false
-  cv::Mat frame(h, w, ch == 3 ? CV_8UC3 : CV_8UC1, in.data());
+  cv::Mat frame(h, w, ch == 3 ? CV_8UC3 : CV_8UC1, in.data() + y0 * step + x0 * ch, step);
   if (!pipeline.process(frame, static_cast<cvp::CannyStage>(stage))) return 8;
   const auto &out = pipeline.output();
   f = std::fopen(argv[6], "wb");

@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 from cudacam_amd import api, synth
 api.preload_hip_runtime()
 from oracle import oracle as O
+import view_arena as VA   # (tests/ is the script's directory)
 
 O.build()
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
@@ -84,13 +85,23 @@ for i in range(cases):
         # the same case once more through the pipelined device path: three runs in a row (the frames rolled
         # differently each time) into two output buffers used in turn; the last two maps are checked
         import torch
-        pitch = (w + 3) // 4 * 4
-        def dev(fr):
-            buf = np.zeros((nb, h, pitch), np.uint8); buf[:, :, :w] = fr
-            return torch.from_numpy(buf).cuda()
+        # caller views: pitch padding, base offset, frame gap and fill of the input and of the output are drawn from a second
+        # generator seeded from the case seed (the main stream stays as it was: the cases of a seed do not change); multiples
+        # of 4 only, so that the views stay in place; the output guards are checked with view_arena
+        vr = np.random.default_rng([seed, 0x71E75])
+        def draw_view(width):
+            pitch = (width + 3) // 4 * 4 + 4 * int(vr.choice([0, 0, 1, 2, 3, 16, 129]))
+            return pitch, pitch * h + 4 * int(vr.choice([0, 0, 1, 5, 64])), 4 * int(vr.choice([0, 0, 1, 3, 4, 9]))
+        ip, ifs, ioff = draw_view(w)
+        op, ofs, ooff = draw_view(w)
+        fill = str(vr.choice(["random", "ff", "parent"]))
+        lead_i, lead_o = VA.round_up(ip + 64, 512), VA.round_up(op + 64, 512)   # (whole allocator blocks: base alignment = that of the offset)
         seq = [np.stack([np.roll(f, 7 * (r + 1), axis=0) for f in frames]) for r in range(3)]
-        d_in = [dev(fr) for fr in seq]
-        d_o = [torch.full((nb, h, pitch), 3, dtype=torch.uint8, device="cuda") for _ in range(2)]
+        d_in = [torch.from_numpy(VA.make_input(fr, ip, ifs, ioff, fill, lead=lead_i, seed=seed % 1000 + r)[0]).cuda() for r, fr in enumerate(seq)]
+        o_before = [VA.make_output(nb, h, w, op, ofs, ooff, lead=lead_o, seed=seed % 1000 + j) for j in range(2)]
+        g_out = o_before[0][1]
+        d_o = [torch.from_numpy(b[0]).cuda() for b in o_before]
+        torch.cuda.synchronize()
         with api.Context(w, h, 1, nb, api.MODE_R if mode == "R" else api.MODE_O, front_split=opts["split"]) as ctx:
             ctx.set_thresholds(low, high)
             if mode == "R":
@@ -100,14 +111,21 @@ for i in range(cases):
                 ctx.set_option(api.OPT_L2_GRADIENT, opts["l2"])
             ctx.set_option(api.OPT_PIPELINE, 1)
             for r in range(3):
-                ctx.run_device(d_in[r].data_ptr(), pitch, pitch * h, d_o[r % 2].data_ptr(), pitch, pitch * h, nb)
+                ctx.run_device(d_in[r].data_ptr() + lead_i + ioff, ip, ifs, d_o[r % 2].data_ptr() + g_out.offset, op, ofs, nb)
             ctx.sync()
         for r in (1, 2):
-            g = d_o[r % 2].cpu().numpy()[:, :, :w]
+            arena = d_o[r % 2].cpu().numpy()
+            g = VA.read_view(arena, g_out)
             wnt = np.stack([O.canny_r(f, low, high, saturate=bool(opts["sat"])) if mode == "R" else O.canny_o(f, low, high, l2gradient=bool(opts["l2"])) for f in seq[r]])
             if not np.array_equal(g, wnt):
                 bad += 1
-                print(f"MISMATCH (pipelined run {r}) case {i}: {w}x{h} {kind} seed {seed} mode {mode} thr {low}/{high} nb {nb} {opts}", flush=True)
+                print(f"MISMATCH (pipelined run {r}) case {i}: {w}x{h} {kind} seed {seed} mode {mode} thr {low}/{high} nb {nb} {opts} view in {ip}/{ifs}/+{ioff} {fill} out {op}/{ofs}/+{ooff}", flush=True)
+                break
+            try:
+                VA.check_output(arena, o_before[r % 2][0], g_out, wnt, f"pipelined run {r}")
+            except AssertionError as e:
+                bad += 1
+                print(f"MISMATCH (output guards) case {i}: {w}x{h} {kind} seed {seed} mode {mode} thr {low}/{high} nb {nb} {opts} view in {ip}/{ifs}/+{ioff} {fill} out {op}/{ofs}/+{ooff}: {e}", flush=True)
                 break
     if not np.array_equal(got, want):
         bad += 1

@@ -52,3 +52,30 @@ def test_cpp_pipeline_matches_oracle(oracle, tmp_path, channels, stage, binary):
     if stage == 5 and channels == 3:  # all six timers hold a sample
         assert r.stdout.count("samples 2") == 6, r.stdout
     assert np.array_equal(got, oracle.canny_r(img, 10, 40, stages=True)[key])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("binary", ["test_cvpipeline", "test_cvpipeline_othermat"])
+@pytest.mark.parametrize("channels", [1, 3])
+@pytest.mark.parametrize("w,h,x0,y0,pad", [(321, 200, 20, 3, 23), (640, 83, 4, 1, 0), (29, 5, 7, 2, 5)])
+def test_cpp_pipeline_on_a_roi_of_a_parent(oracle, tmp_path, channels, binary, w, h, x0, y0, pad):
+    """The driver wraps an ROI of a parent image in cv::Mat(rows, cols, type, data, step) -- a Mat that is not continuous,
+    whose row padding is the parent's pixels: stage 5 of the ROI's pixels alone, against the oracle."""
+    BIN = os.path.join(ROOT, "tests", "cpp", binary)
+    if not os.path.exists(BIN):
+        _build()
+    pw, ph = x0 + w + pad, y0 + h + 4
+    parent = synth.natural(pw, ph, 31) if channels == 1 else np.stack([synth.natural(pw, ph, 31 + c) for c in range(3)], -1)
+    parent[y0:y0 + h, x0 + w - 1] = 255          # a maximal gradient in the ROI's last column ...
+    if pad:
+        parent[y0:y0 + h, x0 + w] = 0            # ... against the parent's pixel beside it, which is not part of the frame
+    roi = np.ascontiguousarray(parent[y0:y0 + h, x0:x0 + w])
+    fin, fout = tmp_path / "parent.raw", tmp_path / "out.raw"
+    parent.tofile(fin)
+    r = subprocess.run([BIN, str(w), str(h), str(channels), str(fin), "5", str(fout), str(pw * channels), str(x0), str(y0)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    got = np.fromfile(fout, np.uint8).reshape(h, w)
+    want = oracle.canny_r(roi, 10, 40)
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, f"{len(bad)} pixels differ, first (row, col) {bad[:5].tolist()}"
