@@ -519,32 +519,7 @@ static __device__ __forceinline__ RowBits<NW> row_dilate(const RowBits<NW> &p)
 // (lane l holds dwords l*NW.. of each row; rows are picked with a wave-uniform index, which the
 // compiler turns into VGPR-indexed moves); LDS only carries the rows neighbours look at.
 struct HystGeom { int nw, tr, waves; };
-// 8 waves x 32 rows (256-row tiles) when the hysteresis has the chip to itself: fewer tile boundaries, fewer
-// launches.  4 waves x 32 rows (one wave per SIMD) when it runs beside the next run's front kernels (pipelined mode):
-// a 4-wave workgroup finds a place as soon as one wave slot per SIMD frees up, an 8-wave one has to wait for two --
-// measured 1.7 ms against 4.2 ms for the hysteresis of 1024 frames under overlap.
-// (beside k_front8, whose three workgroups fill a CU's LDS and registers, a hysteresis workgroup only finds room when a
-// front workgroup retires: 2-wave workgroups fit the freed wave slots best -- 376 k frames/s against 368 k with 4 waves,
-// 350 k with 8; one-wave workgroups need more launches than are queued for a 1080-row frame)
-static inline HystGeom hyst_geom(bool beside_front) { return beside_front ? HystGeom{ 1, 32, 2 } : HystGeom{ 1, 32, 8 }; }
-// frames_x_rows: frames x rows of the run.  geom: 0 = by the rules here; otherwise a shape picked by the caller for tuning experiments (encoded rows * 100 + waves:
-// 3208, 3204, 3202, 1608, 3216 -- hc_create reads HC_HYST_GEOM once)
-void hyst_tile_geometry(int geom, bool beside_front, long frames_x_rows, int H, int *tile_rows, int *waves)
-{
-  HystGeom g = hyst_geom(beside_front);
-  // (Taller frames had taller tiles here -- 4 waves above 1200 rows, 8 above 2400 -- from the time when 16 launches were
-  // queued per run.  With up to 48 launches queued and the tile height following the content (queue_hyst_expand), the small
-  // 2-wave workgroups are as good at 4K (101 k frames/s either way) and better at 8K x 3 channels: 7.5 k against 6.6 k
-  // frames/s -- an 8-wave workgroup needs two free wave slots on every SIMD of a CU at once, and launch 0 ran starved
-  // beside the front kernel for as long as that took.)
-  // a few frames only (the reference's one-frame-per-call pattern): the chip is nearly empty and the launches are pure
-  // latency -- 8 waves x 16 rows per workgroup halve the rows a wave walks one after the other (measured on one 1080p
-  // frame: hysteresis 0.122 ms against 0.139 ms with 8 x 32 and 0.130 ms with 4 x 32)
-  if (frames_x_rows < 128 * 1024) g = HystGeom{ 1, 16, 8 };
-  if (geom == 3208 || geom == 3204 || geom == 3202 || geom == 1608 || geom == 3216 || geom == 3201 || geom == 1604 || geom == 1602) g = HystGeom{ 1, geom / 100, geom % 100 };
-  *tile_rows = g.tr;
-  *waves = g.waves;
-}
+// (which shape a run gets: hyst_tile_geometry, canny_params.h)
 
 // PANELS: the frame is wider than one 2048-column panel (tiles then also have left / right neighbours); the common
 // narrower case is compiled without that code.

@@ -1,0 +1,162 @@
+// canny_params.h -- the parameter blocks the host hands to the kernels and the geometry facts it plans with.
+// Plain C++ (no HIP): shared by the kernel files, the launcher (hipcanny.hip), the planner (host_plan.h) and the CPU test
+// of the planner.  Every kernel constant the host also needs is defined here, once.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace hc {
+
+typedef uint32_t u32;
+typedef uint64_t u64;
+
+// ---- geometry of the fused path ---------------------------------------------------------------
+// A wave owns a vertical STRIP of the frame: lane l holds the 4 adjacent pixels at columns
+// strip*STRIP_W - 4 + 4*l .. +3 of the current row, packed in one dword.  Lanes 0 and 63 are halo
+// lanes (4 px each side = 2 blur + 1 Sobel + 1 NMS), lanes 1..62 produce STRIP_W = 248 outputs.
+constexpr int LANES = 64;
+constexpr int PX_PER_LANE = 4;
+constexpr int STRIP_W = (LANES - 2) * PX_PER_LANE;  // 248
+constexpr int STRIP_HALO = PX_PER_LANE;             // 4 columns = one lane
+
+// Bit planes: two plain bitmaps per frame, STRONG and CANDIDATE (candidate includes strong):
+// bit c of a row <-> column c, rows padded to RD dwords.  A strip's 248 valid columns are 31 whole
+// bytes, so each wave-row of k_front stores its 31 bytes at byte offset strip*31 of the row.
+struct FrontParams {
+  const uint8_t *in;       // u8 frames, pitched: mono, or interleaved BGR when bgr != 0 (stage 0 fused into the load)
+  int bgr;
+  size_t in_pitch;         // bytes per row   (multiple of 4)
+  size_t in_frame_stride;  // bytes per frame (multiple of 4)
+  u32 *sbits, *cbits;      // bit planes [frame][H][RD]
+  int RD;                  // dwords per bit-plane row
+  int W, H;
+  int nstrips, nchunks, nframes;
+  int subchunks;   // Mode R kernel: sub-chunks of 24 blur rows a wave marches through per work item
+  int run_rows;    // = 24 * subchunks - 4 output rows per work item; nchunks = ceil(H / run_rows)
+  int chunk_rows;          // Mode O kernel: output rows per work item (any value >= 1)
+  int l2gradient;          // Mode O kernel: magnitude dx^2 + dy^2 instead of |dx| + |dy| (cv::Canny's L2gradient)
+  int total_items;         // nframes * nstrips * nchunks
+  // thresholds on S = sumX^2 + sumY^2 for "u8-wrapped gradient > T" (band test)
+  u32 a_lo[3], a_hi[3];
+  // split mode (k_blur + k_nms): the u8 blur plane between the two kernels and k_nms's own work split
+  uint8_t *blur;             // [frame][strip][H][256]: one aligned 256-byte row per wave-row (bytes 4..251 = the strip's columns)
+  size_t blur_frame_stride;  // >= nstrips * H * 256
+  int nchunks_b, run_rows_b, total_items_b;
+  // k_nms: when set, the strong pixels are also written as 255 (others 0) into this u8 map -- the provisional edge
+  // map the hysteresis then only patches (W % 4 == 0: a lane stores its 4 pixels as one dword)
+  uint8_t *prov_out; u32 prov_pitch; size_t prov_fs;
+  // diagnostics (HC_OPT_DEBUG_TAPS): the fused kernel also stores its (fixed-up) blur rows here, plain [frame][H][pitch]
+  uint8_t *dbg_blur; u32 dbg_pitch; size_t dbg_fs;
+  const uint8_t *zeros;  // k_front8: >= 3 * 8192 + 32 bytes of zeros (what rows above / below the image read as); HALF form: + in_frame_stride
+  // k_front8: memory that may be overwritten with anything -- where the branch-free row code stores rows that are not its
+  // own: STRONG plane bytes (dump), CANDIDATE plane bytes (dump_c), provisional map (dump_p).  Plain form: 2 KiB, 2 KiB,
+  // W + 8 bytes.  HALF form: each + the byte offset of half-wave B's frame (3 * H * RD * 4 / 3 * prov_fs at most).
+  uint8_t *dump, *dump_c, *dump_p;
+  // k_front8 / k_front8o: words the kernel zeroes before anything else (the run's hysteresis flags, worklist counts and
+  // reason words: one memset kernel and one host call fewer per run); null: nothing
+  u32 *zero_words; u32 zero_count;
+  int half;        // k_front8: HALF form (two 240-column half-strips per wave, narrow frames); nstrips is unused then
+  int one_wave;    // k_front8, mono / BGR with a provisional map: one-wave workgroups instead of four-wave ones
+  int nhalf;       // HALF form: half-strips per frame = ceil(W / 240); total_items = ceil(in_frames * nhalf / 2) * nchunks (* 3 per-channel)
+  // k_front8: a window that follows one with more than dense_enter half-lanes above the low threshold takes the dense path
+  // (wave-wide NMS in registers), and the windows after it while they count more than dense_leave (0x7FFFFFFF: never)
+  int dense_enter, dense_leave;
+  u32 wrap_limit;  // S >= wrap_limit: gradient >= 256, the wrap bands apply (0xFFFFFFFF: saturating variant)
+};
+
+// Mode O beyond k_front_o (front_o_ext.hip): the 5x5 Sobel of u8 frames (aperture 5), or caller-given int16 derivatives
+// (cv::Canny's (dx, dy) overload).  f as for k_front_o (thresholds in a_lo[0] / a_hi[0], chunk_rows, l2gradient); with
+// gradients != 0, f.in is dx and dy the dy planes, both with f.in_pitch / f.in_frame_stride (bytes, even), `channels`
+// interleaved int16 per pixel.
+struct FrontExtParams {
+  FrontParams f;
+  int gradients;
+  int channels;
+  const uint8_t *dy;
+};
+
+struct HystParams {
+  u32 *sbits;
+  const u32 *cbits;
+  int RD, H, nframes;
+  int tile_rows;   // rows per wave
+  int waves;       // waves per workgroup; a workgroup tile is waves * tile_rows rows
+  int nrtiles;     // row tiles per frame = ceil(H / (waves * tile_rows))
+  int npanels;     // column panels per row tile = RD / 64 (a panel = 64 dwords = 2048 columns)
+  u32 *flags;      // flags[k] != 0: launch k changed a tile-boundary row (another launch is needed)
+  // How launches >= 1 find the tiles with work: a tile that changes a boundary row / column leaves a reason word with the
+  // neighbours that look at it; wide frames also append them to the next launch's worklist.  [2] = launch parity;
+  // wl_stride >= nframes * nrtiles * npanels words.
+  u32 *wl_count;   // [launches + 1] wide frames: tiles on the list of (visited by) launch k; zero at the start of a run
+  u32 *wl_reason;  // [2][wl_stride] per tile: 1 a tile above changed (its `top`), 2 below, 4 beside; zero at the start of a run
+  u32 *wl_list;    // [2][wl_stride] wide frames: tile ids (frame * tiles per frame + tile)
+  size_t wl_stride;
+  int lists;       // this launch: 1 takes its tiles from the worklist (k_hyst MODE 1 / 2); 0 a workgroup per tile (MODE 0); 2 a workgroup per tile that also writes the next launch's list (MODE 3)
+  int late_grid;   // worklist scheme: workgroups of launches >= 1 (0 = by the tile count, launch_hyst)
+  int iter;        // index of this launch
+  u32 *stats;      // optional diagnostics (3 words per launch) or null
+  // fused expand: every launch also writes the 0/255 u8 rows it owns (launch 0: all rows of the tile,
+  // later launches: the rows they changed), so no separate bit-plane -> u8 pass is needed
+  uint8_t *out;
+  size_t out_pitch, out_frame_stride;
+  int W;
+  int prov;        // the output already holds 255 for every strong pixel of the input planes (written by k_nms): launch 0 only rewrites rows it changes
+  int first_pass;  // the planes come straight from k_front / k_pack: rows are not yet closed under the in-row fill
+};
+
+struct PackParams {  // tri-state u8 map (0/128/255) -> bit planes
+  const uint8_t *in;
+  size_t in_pitch, in_frame_stride;
+  u32 *sbits, *cbits;
+  int RD, W, H, nframes;
+};
+
+// ---- work split of the front kernels ----------------------------------------------------------
+// front8.hip: 8 px per lane
+constexpr int F8_STRIP_W = 62 * 8;   // 496 output columns per wave
+constexpr int F8_HSTRIP_W = 30 * 8;  // HALF form: 240 output columns per half-wave (lanes 0 / 31 and 32 / 63 are its halo lanes)
+constexpr int F8_SUB = 6;            // rows per window = lcm(2, 3) rows: the d / s register ring has period 2
+inline int front8_run_rows(int windows) { return F8_SUB * windows - 4; }
+inline int front8_strips(int W) { return (W + F8_STRIP_W - 1) / F8_STRIP_W; }
+inline int front8_half_strips(int W) { return (W + F8_HSTRIP_W - 1) / F8_HSTRIP_W; }
+// front_mx.hip
+constexpr int MX_STRIP_W = 216;  // output columns per strip: 7 tiles of 28 + 20 columns of the eighth
+constexpr int MX_ROWS = 16;      // rows per block
+constexpr int MX_LAG = 4;        // the Sobel stage's rows trail the blur stage's by 4
+inline int front_mx_strips(int W) { return (W + MX_STRIP_W - 1) / MX_STRIP_W; }
+inline int front_mx_run_rows(int blocks) { return MX_ROWS * blocks - MX_LAG; }
+// legacy_front.hip (the round-1 fused kernel)
+constexpr int FSUB = 24;  // blur rows per sub-chunk: multiple of the prefetch group (4) and of the ring period (6)
+inline int front_run_rows(int subchunks) { return FSUB * subchunks - 4; }
+
+// ---- hysteresis workgroup shape ---------------------------------------------------------------
+// k_hyst_loop (all rounds of a small run in one launch): at most this many tiles
+constexpr int HYST_LOOP_MAX_TILES = 128;
+// Workgroup tile = waves x tile_rows rows (canny_kernels.hip).
+// 8 waves x 32 rows (256-row tiles) when the hysteresis has the chip to itself: fewer tile boundaries, fewer
+// launches.  4 waves x 32 rows (one wave per SIMD) when it runs beside the next run's front kernels (pipelined mode):
+// a 4-wave workgroup finds a place as soon as one wave slot per SIMD frees up, an 8-wave one has to wait for two --
+// measured 1.7 ms against 4.2 ms for the hysteresis of 1024 frames under overlap.
+// (beside k_front8, whose three workgroups fill a CU's LDS and registers, a hysteresis workgroup only finds room when a
+// front workgroup retires: 2-wave workgroups fit the freed wave slots best -- 376 k frames/s against 368 k with 4 waves,
+// 350 k with 8; one-wave workgroups need more launches than are queued for a 1080-row frame)
+// frames_x_rows: frames x rows of the run.  geom: 0 = by the rules here; otherwise a shape picked by the caller for tuning experiments (encoded rows * 100 + waves:
+// 3208, 3204, 3202, 1608, 3216 -- hc_create reads HC_HYST_GEOM once)
+inline void hyst_tile_geometry(int geom, bool beside_front, long frames_x_rows, int H, int *tile_rows, int *waves)
+{
+  (void)H;
+  *tile_rows = 32;
+  *waves = beside_front ? 2 : 8;
+  // (Taller frames had taller tiles here -- 4 waves above 1200 rows, 8 above 2400 -- from the time when 16 launches were
+  // queued per run.  With up to 48 launches queued and the tile height following the content (plan_hyst), the small
+  // 2-wave workgroups are as good at 4K (101 k frames/s either way) and better at 8K x 3 channels: 7.5 k against 6.6 k
+  // frames/s -- an 8-wave workgroup needs two free wave slots on every SIMD of a CU at once, and launch 0 ran starved
+  // beside the front kernel for as long as that took.)
+  // a few frames only (the reference's one-frame-per-call pattern): the chip is nearly empty and the launches are pure
+  // latency -- 8 waves x 16 rows per workgroup halve the rows a wave walks one after the other (measured on one 1080p
+  // frame: hysteresis 0.122 ms against 0.139 ms with 8 x 32 and 0.130 ms with 4 x 32)
+  if (frames_x_rows < 128 * 1024) { *tile_rows = 16; *waves = 8; }
+  if (geom == 3208 || geom == 3204 || geom == 3202 || geom == 1608 || geom == 3216 || geom == 3201 || geom == 1604 || geom == 1602) { *tile_rows = geom / 100; *waves = geom % 100; }
+}
+
+}  // namespace hc

@@ -43,10 +43,8 @@
 
 namespace hc {
 
-constexpr int F8_STRIP_W = 62 * 8;                 // 496 output columns per wave
-constexpr int F8_HSTRIP_W = 30 * 8;                // HALF form: 240 output columns per half-wave (lanes 0 / 31 and 32 / 63 are its halo lanes)
+// (F8_STRIP_W, F8_HSTRIP_W, F8_SUB and the strip / run arithmetic: canny_params.h, shared with the host planner)
 constexpr int F8_HALO = 8;                         // one lane each side
-constexpr int F8_SUB = 6;                          // rows per window = lcm(2, 3) rows: the d / s register ring has period 2
 constexpr int F8_RING = F8_SUB + 4;                // rows kept in each LDS ring (masked input rows; blur rows)
 constexpr int F8_FQ = 128;                         // flagged-pixel queue entries per window (expected fill ~20); [F8_FQ] is a dump slot
 constexpr int F8_NQ = 512;                         // NMS queue (ids), circular; [F8_NQ] is a dump slot
@@ -54,9 +52,6 @@ constexpr int F8_ROW_BYTES = 64 * 8;
 constexpr int F8_WPB = 4;                          // waves per workgroup of k_front8 (mono / BGR; one-wave form: 1; per-channel mode: 3, one per channel).  The waves are independent.
 constexpr int F8_WAVE_BYTES = 2 * F8_RING * F8_ROW_BYTES + (F8_FQ + 4) * 4 + (F8_NQ + 4) * 4;  // 12,832 B: 3 workgroups of 4 waves per CU
 
-int front8_run_rows(int windows) { return F8_SUB * windows - 4; }
-int front8_strips(int W) { return (W + F8_STRIP_W - 1) / F8_STRIP_W; }
-int front8_half_strips(int W) { return (W + F8_HSTRIP_W - 1) / F8_HSTRIP_W; }
 size_t front8_lds_bytes() { return (size_t)4 * F8_WAVE_BYTES; }
 
 typedef __attribute__((address_space(3))) u32 lds_u32;

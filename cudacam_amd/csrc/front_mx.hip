@@ -57,9 +57,7 @@
 
 namespace hc {
 
-constexpr int MX_STRIP_W = 216;                      // output columns per strip: 7 tiles of 28 + 20 columns of the eighth
-constexpr int MX_ROWS = 16;                          // rows per block
-constexpr int MX_LAG = 4;                            // the Sobel stage's rows trail the blur stage's by 4
+// (MX_STRIP_W, MX_ROWS, MX_LAG and the strip / run arithmetic: canny_params.h, shared with the host planner)
 constexpr int MX_RING = 20;                          // rows per LDS ring
 constexpr int MX_SEG0 = 16;                          // a ring row: 16 bytes of padding, then 8 segments of 32 bytes
 constexpr int MX_PITCH = 272;
@@ -71,8 +69,6 @@ constexpr u32 MX_PAD = 0x80808080u;                  // four zero pixels, biased
 constexpr u32 MX_MAGIC = 105518u;                    // ceil(2^24 / 159)
 constexpr u32 MX_C0 = (u32)(20352ull * 105518ull + 0x80000000ull);  // (S - 128 * 159) * M + C0 = S * M + 2^31 (mod 2^32)
 
-int front_mx_strips(int W) { return (W + MX_STRIP_W - 1) / MX_STRIP_W; }
-int front_mx_run_rows(int blocks) { return MX_ROWS * blocks - MX_LAG; }
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));

@@ -1,0 +1,567 @@
+// host_plan.h -- every scheduling decision of the library as plain functions: which front kernel form a run gets and
+// how its work is cut (plan_front), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
+// (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch).  No HIP, no hc_ctx: hipcanny.hip fills
+// the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
+#pragma once
+#include "../../include/hipcanny.h"
+#include "canny_params.h"
+
+#include <algorithm>
+
+namespace hc {
+
+inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline bool aligned4(uintptr_t p, size_t a, size_t b) { return ((p | a | b) & 3u) == 0; }
+inline bool reaches_4g(int H, size_t pitch) { return (unsigned long long)H * pitch >= (1ull << 32); }
+
+constexpr int MAX_HYST_LAUNCHES = 96;  // (48 until a weak edge wobbling along a tile boundary needed 52: one launch per crossing)
+constexpr int FLAG_WORDS = MAX_HYST_LAUNCHES * 4;  // [0 .. MAX) launch flags, then 3 diagnostic words per launch
+// d_flags continues with what must also be zero when a run starts (one memset): the worklist counts of the hysteresis
+// launches, then the per-tile reason words of both launch parities (HystParams::wl_count / wl_reason)
+constexpr int WL_COUNT_WORDS = 128;
+static_assert(WL_COUNT_WORDS >= MAX_HYST_LAUNCHES + 1 + 2, "a count per launch, one beyond the last, and the two words of k_hyst_loop's barrier");
+// tiles a run can have: at most out_frames x row tiles (16 rows or more each) x column panels
+inline size_t slot_wl_cap(size_t out_frames, int H, int RD) { return out_frames * ((size_t)(H + 15) / 16 + 1) * (size_t)((RD + 63) / 64); }
+// words of a slot's d_flags / words of them a run of wl_stride tiles needs zero when it starts
+inline size_t run_flag_words(size_t wl_stride) { return FLAG_WORDS + WL_COUNT_WORDS + 2 * wl_stride; }
+
+// ---- what hc_create derives from the frame size -------------------------------------------------
+// internal frame buffers: rows of whole 16-byte groups are stored tight, others padded to 256 bytes (alloc_frames)
+inline size_t frame_pitch(size_t row_bytes, size_t tight_row_bytes) { return (tight_row_bytes && tight_row_bytes % 16 == 0) ? tight_row_bytes : round_up(row_bytes, 256); }
+// bit-plane row: covers every strip's 31 bytes, padded to a multiple of 64 dwords (one LDS row per wave); 0: too wide
+inline int plane_row_dwords(int W)
+{
+  const size_t need = std::max<size_t>((size_t)(W + 31) / 32, ((size_t)((W + STRIP_W - 1) / STRIP_W) * 31 + 3) / 4);
+  return need > 256 ? 0 : need <= 64 ? 64 : need <= 128 ? 128 : 256;  // 64 * NW dwords, NW in {1, 2, 4}
+}
+// narrow frames take k_front8's HALF form when that needs fewer waves: an odd number of half-strips (pairs across frames)
+inline bool half_pays(int W) { return front8_half_strips(W) % 2 == 1 || (front8_half_strips(W) + 1) / 2 < front8_strips(W); }
+// size of each of the four dump regions the HALF form needs: half-wave B reaches its frame through lane offsets of up to
+// one frame stride (three bit-plane / output frames in per-channel mode)
+inline size_t half_dump_region(size_t in_fs, size_t out_fs, int RD, int H) { return round_up(std::max(std::max(in_fs, 3 * out_fs), 3 * sizeof(u32) * (size_t)RD * H) + 32768, 4096); }
+
+// Slots a pipelined context rotates through.  Two slots let run i+1's front kernel overlap run i's hysteresis.  Big batches
+// rotate through two -- or three, while the hysteresis chain of a run is seen to outlast the front kernel of the next
+// (ChainWatch; 8K x 3: 6.9 -> 7.8 k frames/s, 8K grey 25.3 -> 27.5 k; where the front kernel bounds the step a third slot
+// costs 1 %, a fourth 4 %: profiles/r03/experiments.md).  SMALL batches use four slots, each with a hysteresis stream of
+// its own: there a step is the latency of the hysteresis' chain of dependent launches (8 frames: 0.33 ms for a 0.04 ms
+// front kernel), and chains of different runs share the device without noticing each other.
+constexpr int NSLOT = 4;
+// slots the pipelined runs of n_out output frames rotate through: by pixels (16 8K x 3 frames are a big batch; fewer than
+// 0.5 G pixels per run: the step is the latency of the hysteresis chain)
+// (measured at 1080p: 128 frames per run 237 against 218 k frames/s with four, 256 frames 301 against 310 k)
+inline int pipeline_slots(int pipe_slots, int big_slots, int n_out, int W, int H) { return pipe_slots ? pipe_slots : (long long)n_out * H * W < 500ll * 1000 * 1000 ? NSLOT : big_slots; }
+// hc_pipeline_depth.  big batches: two slots, three while the hysteresis chain bounds the step (ChainWatch)
+inline int pipeline_depth(bool pipeline, int pipe_slots, int big_slots, int n_out, int W, int H)
+{
+  if (!pipeline) return 1;
+  const int n = pipeline_slots(pipe_slots, big_slots, n_out, W, H);
+  return (n < NSLOT && !pipe_slots) ? 3 : n;
+}
+
+// What the hysteresis chain of a run did to the front kernel it ran beside, from timestamps of the runs themselves
+// (recorded behind every pipelined run's front kernel and behind its last hysteresis launch).  update() is called
+// when run i is complete: the chain of run i-1 ran beside the front kernel of run i, and all three events involved --
+// end of front i-1, end of chain i-1, end of front i -- are complete.
+//  * Two or three slots for big batches?  With two, the front kernel of run i+2 waits for the hysteresis of run i: while
+//    that chain is the shorter of the two nothing waits, and a third slot only lets a second chain compete for the same
+//    wave slots (-1 % at 1080p).  Where the chain outlasts the front kernel (8K: 30 dependent launches over 68 row tiles
+//    and 4 column panels) the front kernels sit idle for the difference, and a third slot lets the next run start on
+//    time.  Three runs in a row whose chain ended after the front kernel beside it -> a third slot ON TRIAL: kept if
+//    the mean step of runs 7-10 with it is 3 % shorter than the last four steps without (8K x 3: -11 %, 8K grey -8 %,
+//    256 frames of 1080p -5 %), otherwise given back, next trial after 64 runs, doubling; from three back to two after
+//    16 runs in a row (doubling, up to 1024) whose chain ended first.
+//  * One-wave or four-wave workgroups for k_front8?  One-wave workgroups take every slot a retiring wave leaves at once:
+//    the front kernel gains 2-3 %, the hysteresis stream needs 40 % longer -- good while that stream has the time
+//    (1080p grey: it ends 40 % of a front kernel early; +1.5 % frames/s), bad where it has none (BGR -> grey: -5 %).
+//    By the smoothed share of the front kernel's time that the chain left unused: above 25 % -> one wave (1080p grey 41 %,
+//    640 x 480 32 %, 4K 27 %; BGR -> grey 5 %), and back to four below 3 % (with one-wave workgroups the same streams
+//    leave 17 %, 7 %, 15 %; BGR -> grey would fall 90 % behind).
+struct ChainWatch {
+  int pipe_slots = 0;  // HC_OPT_PIPELINE_SLOTS 2 / 3: that many slots whatever the batch size (0: by the rule)
+  int chain_told = 0;  // diagnostics (HC_OPT_PIPELINE_SLOTS 20 / 21): +1 / -1 = every chain counts as ending after / before the next front kernel
+  int big_slots = 2;   // slots of big pipelined batches: 2, or 3 while the hysteresis chain bounds the step
+  bool front_one = false;  // the automatic choice: one-wave workgroups for k_front8 (mono / BGR, pipelined big batches)
+  float slack_ema = 0.0f;  // share of a front kernel's time by which the previous run's hysteresis chain ended before it (smoothed)
+  int chain_bound_runs = 0, chain_light_runs = 0, chain_light_needed = 16;
+  float period_ms[4] = { 0, 0, 0, 0 }, period_two = 0.0f;  // the last four steps (front kernel end to front kernel end); their mean before the trial of a third slot
+  int trial_runs = -1;                                      // >= 0: runs since the third slot was taken on trial
+  int retry_wait = 0, retry_backoff = 64;                   // runs until the next trial after one that did not pay (doubling)
+
+  // run i of a ring of nslot_use (2 or 3) slots is complete.  front_ms: front kernel i, end of the previous one to its end
+  // (the step); lead_ms: end of chain i-1 -> end of front kernel i
+  void update(unsigned long long i, int nslot_use, float front_ms, float lead_ms)
+  {
+    if (front_ms <= 0.0f) return;
+    const bool outlasts = chain_told ? chain_told > 0 : lead_ms < 0.0f;
+    period_ms[i & 3] = front_ms;
+    const float period4 = 0.25f * (period_ms[0] + period_ms[1] + period_ms[2] + period_ms[3]);
+    if (retry_wait > 0) --retry_wait;
+    if (!pipe_slots) {
+      if (nslot_use == 2 && big_slots == 2) {
+        chain_bound_runs = outlasts ? chain_bound_runs + 1 : 0;
+        if (chain_bound_runs >= 3 && i >= 5 && (retry_wait == 0 || chain_told)) {  // try a third slot
+          period_two = period4;
+          big_slots = 3;
+          trial_runs = 0;
+          chain_bound_runs = chain_light_runs = 0;
+        }
+      } else if (nslot_use == 3 && trial_runs >= 0) {  // the trial: ten runs, the last four measured
+        if (++trial_runs >= 10) {
+          trial_runs = -1;
+          const bool better = chain_told ? chain_told > 0 : period4 < 0.97f * period_two;
+          if (!better) {
+            big_slots = 2;
+            retry_wait = retry_backoff;
+            retry_backoff = std::min(4096, 2 * retry_backoff);
+          }
+        }
+      } else if (nslot_use == 3) {
+        chain_light_runs = outlasts ? 0 : chain_light_runs + 1;
+        if (chain_light_runs >= chain_light_needed) {
+          big_slots = 2;
+          chain_light_needed = std::min(1024, 2 * chain_light_needed);
+          chain_bound_runs = chain_light_runs = 0;
+        }
+      }
+    }
+    const float slack = std::max(-1.0f, std::min(1.0f, lead_ms / front_ms));
+    slack_ema = 0.75f * slack_ema + 0.25f * slack;
+    if (!front_one && slack_ema > 0.25f) front_one = true;
+    else if (front_one && slack_ema < 0.03f) front_one = false;
+  }
+};
+
+// ---- the front path -----------------------------------------------------------------------------
+// bits of the reference's stages a profiled interval covers (ProfRing::mark)
+constexpr unsigned B_MONO = 1u << HC_STAGE_MONO, B_GAUSS = 1u << HC_STAGE_GAUSSIAN, B_GRAD = 1u << HC_STAGE_GRADIENT,
+                   B_NMS = 1u << HC_STAGE_NMS, B_THR = 1u << HC_STAGE_THRESH, B_HYST = 1u << HC_STAGE_HYSTER;
+
+// the caller's choices that shape the front path (hc_set_option, hc_set_tuning, hc_set_thresholds)
+struct FrontOpts {
+  int low = 10, high = 40;
+  int nms_saturate = 0;
+  int split = 2;        // Mode R front path: 2 = k_front8 (one kernel, 8 px per lane; default), 1 = k_blur + k_nms, 0 = the 4-px fused k_front
+  int l2gradient = 0;   // Mode O: cv::Canny's L2gradient flag
+  int aperture = 3;     // Mode O: cv::Canny's apertureSize (HC_OPT_APERTURE: 3 = k_front8o / k_front_o, 5 = k_front_o_ext)
+  int half_mode = -1;   // HC_OPT_FRONT_HALF: -1 automatic, 0 never, 1 whenever the buffers allow it
+  int dense_mode = -1;  // HC_OPT_FRONT_DENSE: -1 automatic, 0 never, 1 every window
+  int mx_mode = 0;      // HC_OPT_FRONT_MX: 1 = k_front_mx whenever the run allows it (opt-in: include/hipcanny.h)
+  int wpb_mode = -1;    // HC_OPT_FRONT_WPB: -1 = by the slack of the hysteresis stream, 1 / 4 = fixed
+  int dense_enter = 512, dense_leave = 384;  // HC_OPT_TEST_DENSE_ENTER / LEAVE (experiments)
+  int chunk = 0;        // hc_set_tuning: rows per work item (0: by the rules)
+  bool debug_taps = false;
+};
+
+struct View { uintptr_t p; size_t pitch, fs; };  // a pitched batch of frames: address, bytes per row, bytes per frame
+
+struct FrontIn {
+  int mode, C, W, H, RD, nstrips, per_channel, stage, n;
+  View in, out;                      // the caller's views
+  uintptr_t in_dy;                   // != 0: `in` / in_dy are the int16 dx / dy planes of cv::Canny's (dx, dy) overload
+  View own_in, own_mono, own_out;    // the context's internal buffers (pitch and frame stride only)
+  FrontOpts o;
+  size_t dump_region;  // 0: the plain dump layout; otherwise four regions of this size (alloc_dump)
+  bool piped;          // pipelined run (its hysteresis goes to the slot's own stream)
+  int nslot_use;       // slots the pipelined runs rotate through
+  bool front_one;      // ChainWatch's hint
+  bool out_overlap;    // the output overlaps that of the previous, still pending run
+  size_t wl_cap;       // tiles the slot's worklists and reason words hold (slot_wl_cap)
+};
+
+struct FrontPlan {
+  const char *error = nullptr;  // HC_E_ARG with this text: nothing may be launched
+  bool in_staged = false, out_staged = false;  // the caller's view goes through the internal buffer
+  bool gray = false;    // 3-channel frames the front kernel cannot convert while loading: launch_gray first (stage MONO: into the output)
+  View src{}, mono{}, dst{};  // what the kernels read / the one-channel frames / what they write (p: 0 = the internal buffer)
+  int form = -1;        // hc_last_run_info: 2 k_front8, 4 its HALF form, 5 k_front_mx, 3 k_front8o, -1 k_front_o, 6 / 7 k_front_o_ext, 1 k_blur + k_nms, 0 k_front
+  bool prov = false;    // the front kernel writes the provisional map
+  FrontParams fp{};     // complete but for the device pointers (in, planes, prov_out, dbg_blur, blur, dump areas, zero_words)
+  size_t zeroed_words = 0;  // words of the slot's d_flags the front kernel zeroes (0: the host clears them)
+  int waves = 0;        // waves per workgroup of k_front8 / k_front_mx (0: another kernel runs)
+  unsigned mask = 0, mask_a = 0;  // reference stages the front launch covers; mask_a: k_blur's, when k_blur + k_nms run
+};
+
+// "stored u8 gradient > T" as thresholds on S = sumX^2+sumY^2 (gradient g = isqrt(S>>2)):
+// wrapping variant: g in [256k+T+1, 256k+255] for k = 0,1,2  ->  S >= a[k] (and below 4*(256(k+1))^2);
+// saturating variant: min(g,255) > T  ->  S >= a[0], never for T = 255.
+inline void band_thresholds(int T, bool saturate, u32 a[3])
+{
+  for (int k = 0; k < 3; ++k) {
+    const u64 g = 256ull * k + (u64)T + 1;
+    a[k] = (u32)std::min<u64>(4ull * g * g, 0xFFFFFFFFull);
+  }
+  if (saturate && T >= 255) a[0] = 0xFFFFFFFFu;
+}
+
+#ifdef HC_LEGACY_FRONT
+// rows per work item: about 16 rounds of the whole chip (8192 resident waves) when the batch allows it -- the tail of a
+// launch is one work item long, measured optimum 68-135 rows at 1024 frames -- but never runs shorter than 64 rows
+// (each run repeats a 4-row warm-up)
+inline int pick_run_rows(long units, int H, int want_rows)
+{
+  if (want_rows > 0) return std::min(std::max(want_rows, 2), H);
+  const long nch = std::min<long>(std::max<long>((16 * 8192 + units - 1) / units, 1), std::max(1, H / 64));
+  return (int)((H + nch - 1) / nch);
+}
+#endif
+
+// does the caller's output view go through the internal buffer?  (the kernels store dwords)
+inline bool out_view_staged(const View &out) { return !aligned4(out.p, out.pitch, out.fs); }
+
+inline FrontPlan plan_front(const FrontIn &in)
+{
+  FrontPlan P;
+  const FrontOpts &o = in.o;
+  const int W = in.W, H = in.H, C = in.C;
+  const int n_out = in.per_channel ? 3 * in.n : in.n;  // output frames (= bit-plane frames)
+  const bool hyster = in.stage == HC_STAGE_HYSTER;
+  // Mode O forms of k_front_o_ext: caller-given gradients (form 7), or aperture 5 on u8 frames (form 6)
+  const bool grad_in = in.in_dy != 0;
+  const bool ext = in.mode == HC_MODE_O && (grad_in || o.aperture == 5);
+  // unaligned caller buffers go through the internal pitched ones
+  // (mode O on 3-channel data reads whole 12-byte groups of 4 pixels: a tighter caller pitch is staged as well; so are
+  // rows that do not hold whole 8-pixel groups when the 8-px front kernels are to run -- k_front8 / k_front8o load 8 or
+  // 24 bytes per lane and row: tight rows of a width that is not a multiple of 8.  Round 2 fell back to the 4-px kernels
+  // for those; one copy through the internal pitched buffer keeps every frame on the one-kernel path)
+  // (k_front_o_ext on u8 frames reads whole 4-pixel groups, in every channel count)
+  const bool wants8 = hyster && o.split == 2 && (in.mode == HC_MODE_R || C == 1) && !ext;
+  // (the front kernels address the rows of a frame with 32-bit offsets: a view whose height x pitch reaches 4 GiB -- a few
+  // columns of a huge parent -- is staged as well instead of being refused by their launchers)
+  P.in_staged = !grad_in && (!aligned4(in.in.p, in.in.pitch, in.in.fs) || reaches_4g(H, in.in.pitch)
+                             || (in.mode == HC_MODE_O && (C == 3 || ext) && in.in.pitch < round_up((size_t)W, 4) * C)
+                             || (wants8 && in.in.pitch < round_up((size_t)W, 8) * (size_t)C));
+  P.src = P.in_staged ? View{ 0, in.own_in.pitch, in.own_in.fs } : in.in;
+  P.out_staged = out_view_staged(in.out);
+  P.dst = P.out_staged ? View{ 0, in.own_out.pitch, in.own_out.fs } : in.out;
+  const size_t sp = P.src.pitch, sfs = P.src.fs, dp = P.dst.pitch, dfs = P.dst.fs;
+  // stage 0 (cannyEdgeH.cu:214-227); 1-channel input skips it (the reference's mono path is broken, SURVEY §3 ii)
+  // the fused kernel converts BGR while loading (needs whole 12-byte pixel groups inside each row)
+  const bool whole_groups = sp >= round_up((size_t)W, 4) * 3;
+  if (in.per_channel && !whole_groups) { P.error = "per-channel mode needs an input pitch of at least 3 * round_up(width, 4) bytes"; return P; }
+  const bool fuse_bgr = C == 3 && hyster && whole_groups;
+  P.gray = C == 3 && !fuse_bgr && !grad_in;
+  P.mono = (P.gray && in.stage != HC_STAGE_MONO) ? View{ 0, in.own_mono.pitch, in.own_mono.fs } : P.src;
+  if (!hyster) return P;
+
+  FrontParams &fp = P.fp;
+  fp.bgr = in.per_channel ? 2 : fuse_bgr ? 1 : 0; fp.in_pitch = P.mono.pitch; fp.in_frame_stride = P.mono.fs; fp.RD = in.RD; fp.W = W; fp.H = H;
+  fp.nstrips = in.nstrips; fp.nframes = n_out;
+#ifdef HC_LEGACY_FRONT
+  {
+    // Mode R, fused kernel: a wave marches through `subchunks` sub-chunks of 24 blur rows (run of 24*m - 4
+    // output rows).  Longer runs amortise the 8-row warm-up; shorter runs give more work items (small batches).
+    int m = o.chunk ? (o.chunk + 4 + 23) / 24 : 0;
+    if (m == 0) {
+      m = 3;
+      while (m > 1 && (long)n_out * in.nstrips * ((H + front_run_rows(m) - 1) / front_run_rows(m)) < 24576) --m;
+    }
+    fp.subchunks = m; fp.run_rows = front_run_rows(m);
+    fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
+    fp.total_items = n_out * fp.nstrips * fp.nchunks;
+  }
+#endif
+  // Mode R front path: k_front8 reads whole 8-pixel groups (8 or 24 bytes per lane and row), the 4-px kernels 4-pixel
+  // groups.  (Rows too tight for the 8-px kernels were staged above -- wants8 covers every case that picks form 2 or 3 --
+  // so no run falls back to another form for its pitch; tests/cpp/plan_driver.cpp checks it.)
+  // Mode O: k_front8o (form 3) for one-channel sources, the 4-px k_front_o (form -1) for 3-channel ones or when
+  // HC_OPT_FRONT_SPLIT asks for a 4-px form
+  // (Narrow frames: k_front8's HALF form, below.  Round 2 sent 640-column batches to k_blur + k_nms instead.)
+  P.form = ext ? (grad_in ? 7 : 6) : in.mode != HC_MODE_R ? ((C == 1 && o.split == 2) ? 3 : -1) : o.split;
+  const bool split = P.form == 1, f8 = P.form == 2 || P.form == 3;
+  // Pipelined mode: k_nms / k_front_o also write the strong pixels as 255 into the output (4 px per lane: whole
+  // dwords need W % 4 == 0), so that the hysteresis, which runs beside the next run's bandwidth-hungry k_blur, only
+  // rewrites the 16-pixel groups it changes instead of streaming out the whole map (+8 % end to end; without the
+  // overlap the extra stores of the VALU-bound kernel cost more than the hysteresis saves).
+  // Not when this run's output overlaps the previous run's (a caller that keeps one output buffer): that run's
+  // hysteresis may still be patching it, and a late patch would survive into this run's map.
+  // (k_front_o_ext writes no provisional map: its runs give the hysteresis the whole map to write)
+  // (nor into an output view whose height x pitch reaches 4 GiB: the front kernels place the provisional rows with 32-bit
+  // offsets, which would wrap -- row 1024 of a 4 MiB pitch onto row 0; the hysteresis, with 64-bit offsets, writes that map)
+  P.prov = in.piped && !in.out_overlap && !ext && !reaches_4g(H, dp) && (f8 ? W % 8 == 0 : (W % 4 == 0 && (split || in.mode == HC_MODE_O)));
+  if (P.prov) { fp.prov_pitch = (u32)dp; fp.prov_fs = dfs; }
+  if (o.debug_taps && !split) { fp.dbg_pitch = (u32)in.own_out.pitch; fp.dbg_fs = in.own_out.fs; }  // own_out.pitch: the width if that is a multiple of 16, else padded to 256
+#ifdef HC_LEGACY_FRONT
+  if (split) {  // k_blur + k_nms through the blur plane
+    const int rows = pick_run_rows((long)n_out * in.nstrips, H, o.chunk);
+    fp.run_rows = (rows + 1) & ~1;  // k_blur walks rows in pairs
+    fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
+    fp.total_items = n_out * fp.nstrips * fp.nchunks;
+    fp.run_rows_b = rows;
+    fp.nchunks_b = (H + rows - 1) / rows;
+    fp.total_items_b = n_out * fp.nstrips * fp.nchunks_b;
+  }
+#else
+  if (!f8 && in.mode == HC_MODE_R) { P.error = "this library is built without the round-1 front kernels (HC_OPT_FRONT_SPLIT 1 / 0: libhipcanny_legacy.so)"; return P; }
+#endif
+  bool use_mx = false;
+  if (f8) {  // strips of 496 columns, runs of 6 * windows - 4 rows
+    // the 8-px kernels zero the run's hysteresis flag words on their way in: every tile shape has at least 16 rows per tile
+    P.zeroed_words = run_flag_words(std::min(in.wl_cap, slot_wl_cap((size_t)n_out, H, in.RD)));
+    fp.zero_count = (u32)P.zeroed_words;
+    fp.nstrips = front8_strips(W);
+    // dense path of k_front8 (wave-wide NMS): enter above 512 half-lanes per window of 768, leave below 384.  (The batch
+    // scheme costs 27 + 41 + 3.6 e instructions per row for e queued half-lanes, the dense path ~260: break-even near
+    // 320 per window -- but the zero padding makes the first two rows of every frame candidates across the whole
+    // width, and with 320 the window after them went dense on every natural frame: +1.2 % on the benchmark's frames.)
+    fp.dense_enter = o.dense_mode == 0 ? 0x7FFFFFFF : o.dense_mode == 1 ? -1 : o.dense_enter;
+    fp.dense_leave = o.dense_mode == 0 ? 0x7FFFFFFF : o.dense_mode == 1 ? -1 : o.dense_leave;
+    long waves_per_chunk = (long)n_out * fp.nstrips;
+    if (in.mode == HC_MODE_R && in.dump_region && o.half_mode != 0 && !(o.mx_mode == 1 && fp.bgr == 0 && !in.per_channel)) {  // (HC_OPT_FRONT_MX 1 goes first)
+      // HALF form (narrow frames): the (frame, 240-column half-strip) units of a run of rows are dealt to half-waves in
+      // pairs -- 640 columns: 1.5 waves instead of 2 -- when that needs fewer waves and the lane offsets fit
+      const long per = in.per_channel ? 3 : 1, nh = front8_half_strips(W), pairs = ((long)in.n * nh + 1) / 2;
+      const size_t R = in.dump_region;
+      const bool fits = sfs + 32768 <= R && per * sizeof(u32) * (size_t)in.RD * H + 4096 <= R && (!P.prov || per * dfs + 16384 <= R)
+                        && (unsigned long long)sfs + (unsigned long long)H * sp < (1ull << 32) && (!P.prov || (unsigned long long)per * dfs + (unsigned long long)H * dp < (1ull << 32));
+      if ((pairs * per < waves_per_chunk || o.half_mode == 1) && fits) {
+        fp.half = 1; fp.nhalf = (int)nh;
+        waves_per_chunk = pairs * per;
+        P.form = 4;
+      }
+    }
+    // Run length.  Every run repeats an 8-row warm-up, so long runs are cheaper -- measured optimum 110-180 rows at 1024
+    // frames, provided the runs tile the frame evenly (a last run of a few rows pays the warm-up for nothing): the frame
+    // is cut into round(H / 120) equal runs.  A small batch is cut into shorter runs instead, down to 8 rows, where the
+    // warm-up doubles the work but one frame still spreads over 540 waves (3072 waves of this kernel are resident).
+    int rows;
+    if (o.chunk) rows = std::min(std::max(o.chunk, 2), H);
+    else {
+      const long units = waves_per_chunk;
+      long nch = std::max<long>(1, (H + 60) / 120);
+      if (units * nch < 3072) nch = std::min<long>((3072 + units - 1) / units, std::max(1, H / 8));  // (spread over 2048 / 1536 / 1024 waves instead: no better, profiles/r03/experiments.md)
+      rows = (int)((H + nch - 1) / nch);
+    }
+    const int windows = std::max(1, (rows + 4 + 5) / 6);
+    fp.run_rows = front8_run_rows(windows);
+    fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
+    fp.total_items = (int)(waves_per_chunk * fp.nchunks);
+    // k_front_mx (blur and Sobel on the matrix pipe): one-channel frames of Mode R, on request (HC_OPT_FRONT_MX)
+    use_mx = in.mode == HC_MODE_R && P.form == 2 && fp.bgr == 0 && o.mx_mode == 1 && !reaches_4g(H, sp) && sp >= round_up((size_t)W, 4) && (!P.prov || W % 8 == 0);
+    if (use_mx) {
+      fp.nstrips = front_mx_strips(W);
+      const long units = (long)n_out * fp.nstrips;
+      // a run of n blocks covers 16 n - 4 rows and costs about one block more to start (workgroup launch, prologue: 0.2 ms
+      // of a 1024-frame launch in runs of 124 rows, profiles/r04/mx_ablation.txt): the run count that needs the fewest
+      // blocks in all, among those that give every wave slot of the chip (3072) six runs or more where the frame allows
+      long nch;
+      if (o.chunk) nch = std::max<long>(1, (H + o.chunk - 1) / o.chunk);
+      else {
+        const long hi = std::max<long>(1, (H + 11) / 12);
+        const long lo = std::min<long>(hi, std::max<long>(1, (6 * 3072 + units - 1) / units));
+        long best = -1, best_cost = 0;
+        for (long k = lo; k <= std::min<long>(hi, lo + 24); ++k) {
+          const long rows = (H + k - 1) / k, runs = (H + rows - 1) / rows, last = H - rows * (runs - 1);
+          const long cost = ((rows + 4 + 15) / 16 + 1) * (runs - 1) + (last + 4 + 15) / 16 + 1;
+          if (best < 0 || cost < best_cost) { best = k; best_cost = cost; }
+        }
+        nch = best;
+      }
+      fp.run_rows = (int)((H + nch - 1) / nch);
+      fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
+      fp.total_items = (int)(units * fp.nchunks);
+      P.form = 5;
+    }
+  }
+  if (in.mode == HC_MODE_O) {
+    // cv::Canny: plain thresholds on the L1 magnitude; long chunks (no LDS slab, 4-row warm-up)
+    fp.a_lo[0] = (u32)o.low; fp.a_hi[0] = (u32)o.high;
+    fp.l2gradient = o.l2gradient;
+    if (o.l2gradient) {  // canny.cpp: thresholds capped at 32767 (hc_set_thresholds) and squared; the magnitude is dx^2 + dy^2
+      fp.a_lo[0] = (u32)o.low * (u32)o.low;
+      fp.a_hi[0] = (u32)o.high * (u32)o.high;
+    }
+    if (!f8) {  // k_front_o, and k_front_o_ext with its strips and work split (a 6-row warm-up for aperture 5, 2 rows for gradients); k_front8o: strips and runs as set for k_front8 above
+      const long units = (long)n_out * in.nstrips;
+      const int per_strip = (int)std::max<long>(1, std::min<long>((12288 + units - 1) / units, (H + 15) / 16));
+      fp.chunk_rows = (H + per_strip - 1) / per_strip;
+      fp.nchunks = (H + fp.chunk_rows - 1) / fp.chunk_rows;
+      fp.total_items = n_out * fp.nstrips * fp.nchunks;
+      if (!ext && sp < round_up((size_t)W, 4) * (size_t)C) { P.error = "mode O needs an input pitch of at least round_up(width, 4) * channels"; return P; }
+    }
+    // cv::Canny has no blur stage; given gradients leave NMS + thresholds only (GRADIENT did not run)
+    P.mask = (grad_in ? 0u : B_GRAD) | B_NMS | B_THR;
+    return P;
+  }
+  band_thresholds(o.low, o.nms_saturate != 0, fp.a_lo);
+  band_thresholds(o.high, o.nms_saturate != 0, fp.a_hi);
+  fp.wrap_limit = o.nms_saturate ? 0xFFFFFFFFu : 262144u;
+  const unsigned b_mono = fuse_bgr ? B_MONO : 0u;  // stage 0 fused into the blur's load (per-channel mode has no grey stage)
+  P.mask = split ? B_GRAD | B_NMS | B_THR : b_mono | B_GAUSS | B_GRAD | B_NMS | B_THR;
+  P.mask_a = split ? b_mono | B_GAUSS : 0u;
+  if (!f8) return P;
+  // one-wave workgroups: pipelined big batches with the provisional map, mono / BGR (the per-channel form is three waves, one per channel)
+  // (small batches, whose four chains overlap anyway: from 0.12 G pixels per run -- 64 frames of 1080p +3.5 %, 128 frames
+  //  +4.5 %; 4 to 32 frames -3 to -6 %: tools/experiments/exp_small_wpb.sh)
+  const bool auto_one = in.nslot_use < NSLOT ? in.front_one : (long long)n_out * W * H >= 120ll * 1000 * 1000;
+  fp.one_wave = (P.prov && !in.per_channel && (o.wpb_mode == 1 || (o.wpb_mode < 0 && auto_one))) ? 1 : 0;
+  P.waves = in.per_channel ? 3 : fp.one_wave ? 1 : 4;
+  if (use_mx) {  // (its waves are independent too: one-wave workgroups beside the hysteresis, -3.5 % there, four-wave ones alone; HC_OPT_FRONT_WPB 1 / 4 fixes it)
+    fp.one_wave = (o.wpb_mode == 1 || (o.wpb_mode < 0 && P.prov)) ? 1 : 0;
+    P.waves = fp.one_wave ? 1 : 4;
+  }
+  return P;
+}
+
+// ---- the hysteresis schedule ----------------------------------------------------------------------
+// hc_set_tuning and the HC_OPT_TEST_HYST_* hooks
+struct HystOpts {
+  int launches = 6;           // launches queued per run at least (hc_set_tuning)
+  bool launches_set = false;  // hc_set_tuning called: queue exactly that many launches
+  int late_grid = 0;          // tests (HC_OPT_TEST_HYST_LATE_GRID): workgroups of the hysteresis launches >= 1
+  bool loop = true;           // small runs: one looping hysteresis launch (HC_OPT_TEST_HYST_LOOP 0 turns it off)
+  // HC_HYST_DIAG (per-launch counters for hc_hysteresis_stats; slows the launches), HC_HYST_GEOM (hysteresis workgroup shape, e.g. "32x8")
+  bool diag = false;
+  int geom = 0;
+};
+
+struct HystPlan {
+  int level = 0;                    // tile height level: waves = base shape's waves << level (HystHistory::obs index)
+  int tile_rows = 0, waves = 0;     // rows per wave, waves per workgroup
+  int nrtiles = 0, npanels = 0;     // row tiles per frame, column panels
+  int K = 0;                        // launches queued (rounds of the looping launch)
+  size_t wl_stride = 0;             // tiles of the run
+  bool fits = true;                 // wl_stride <= the slot's wl_cap
+  bool clear = true;                // the host must zero run_flag_words(wl_stride) words first (the front kernel zeroed too few)
+  bool loop = false;                // all K rounds in one launch (k_hyst_loop)
+  int lists0 = 0;                   // the list scheme the run started with (diagnostics)
+  bool mixed = false;               // per-tile launches, then lists (lists[] = 0 .. 0, 2, 1 .. 1)
+  int test_grid = 0;                // HC_OPT_TEST_HYST_LATE_GRID > 0: the grid of every launch, continuation rounds included
+  uint8_t lists[MAX_HYST_LAUNCHES] = { 0 };  // per launch: HystParams::lists
+  int late_grid[MAX_HYST_LAUNCHES] = { 0 };  // per launch: HystParams::late_grid (sized from the last run's list unless test_grid)
+  bool served_list(int k) const { return lists[k] == 1 && k > 0; }
+  int hist_grid(int k) const { return test_grid ? 0 : late_grid[k]; }  // the grid that was sized from the last run's list (0: none)
+};
+
+// what finished runs teach the next plan
+struct HystHistory {
+  int obs[3] = { 0, 0, 0 };       // hysteresis launches the last runs needed with base_waves << i waves per workgroup (0: not seen)
+  int obs_base = 0, obs_rows = 0;  // the base shape those observations belong to
+  int need_rows = 0;  // launches that found work in recent runs (continuation rounds included) x rows per tile: how far changes travelled
+  u32 wl_prev[MAX_HYST_LAUNCHES + 1] = { 0 };  // worklist lengths of the last finished run's launches
+  size_t wl_prev_tiles = 0;                    // ... and its tile count (0: none / not a wide-frame run)
+  int last_work_launches = 0;
+  bool lists_last = false;  // the last run used the worklist scheme
+
+  // a run has reached its fixpoint.  work: launches that found work, continuation rounds included (+ 1 when the queued
+  // launches sufficed); wl_counts: MAX_HYST_LAUNCHES + 1 list lengths as the QUEUED launches left them
+  void finished(const HystPlan &p, int work, const u32 *wl_counts)
+  {
+    last_work_launches = work;
+    // worklist lengths of this run's launches (wide frames): the next run of the same shape sizes its grids by them
+    wl_prev_tiles = (p.npanels > 1 || p.lists[p.K - 1]) ? p.wl_stride : 0;
+    for (int k = 0; k <= MAX_HYST_LAUNCHES; ++k) wl_prev[k] = wl_counts[k];
+    need_rows = std::max(work * p.tile_rows * p.waves, need_rows - 32);  // follows the content up at once, down slowly
+    // launches this run needed at its tile height (plan_hyst picks the next runs' height from these)
+    if ((p.waves >> p.level) != obs_base || p.tile_rows != obs_rows) return;
+    const int o = obs[p.level];
+    // the content changed: what was seen at the other heights no longer holds
+    if (o && (work * 10 > o * 13 + 20 || work * 10 < o * 7 - 20)) obs[0] = obs[1] = obs[2] = 0;
+    obs[p.level] = work;
+  }
+};
+
+// n: output frames; small_tiles: the run is pipelined (its hysteresis runs beside the next front kernel);
+// zeroed_words: what the front kernel zeroes of the slot's d_flags (FrontPlan::zeroed_words)
+inline HystPlan plan_hyst(int RD, int H, int n, bool small_tiles, const HystOpts &o, HystHistory &h, size_t wl_cap, size_t zeroed_words)
+{
+  HystPlan p;
+  // one workgroup per (frame, tile of waves x tile_rows rows); the geometry follows the row width
+  hyst_tile_geometry(o.geom, small_tiles, (long)n * H, H, &p.tile_rows, &p.waves);
+  // Adaptive tile height: a launch carries a change across one tile boundary, so frames whose weak edges wind through
+  // many tiles need many launches.  The library remembers how many launches the runs needed with the base shape and
+  // with twice / four times its waves (HystHistory::obs, forgotten when the content changes): above 20
+  // launches the next taller shape is tried -- and kept only if it needs fewer than 60 % of the launches.  Mode O frames:
+  // 24 launches with 64-row tiles, 5 with 128 rows: taller (501 against 480 k frames/s).  BGR frames blended into grey:
+  // 25 either way, their chains wind around the tile boundaries whatever the height: the small workgroups, which find
+  // room beside the front kernel more easily, and the worklists (255 against 224 k frames/s with 4-wave tiles).
+  // (Round 2's first rule went by rows -- launches x tile height -- alone: it kept the BGR stream on tall tiles, and
+  // made the Mode O stream flip between the two shapes every few runs, each flip a host-side continuation.)
+  const int base_waves = p.waves;
+  if (base_waves != h.obs_base || p.tile_rows != h.obs_rows) {  // another base shape (batch size, plain / pipelined): start over
+    h.obs_base = base_waves; h.obs_rows = p.tile_rows;
+    h.obs[0] = h.obs[1] = h.obs[2] = 0;
+  }
+  int lvl = 0;
+  while (lvl < 2 && (base_waves << (lvl + 1)) <= 8) {
+    const int cur = h.obs[lvl], nxt = h.obs[lvl + 1];
+    if (cur <= 20) break;                  // unknown (0) or few enough
+    if (nxt != 0 && nxt * 5 > cur * 3) {  // the taller tiles did not pay
+      // (frames of several panels: the tallest then -- an 8K grey stream whose weak edge wobbles along a tile boundary
+      // needs 53 launches at every height, and runs them faster on a quarter of the tiles: 21.1 against 16.5 k frames/s)
+      if (RD > 64) while (lvl < 2 && (base_waves << (lvl + 1)) <= 8) ++lvl;
+      break;
+    }
+    ++lvl;
+  }
+  p.waves = base_waves << lvl;
+  p.level = lvl;
+  const int tile = p.tile_rows * p.waves;
+  p.nrtiles = (H + tile - 1) / tile;
+  p.npanels = (RD + 63) / 64;
+  // launches queued per run: the user's number, or by default enough for an edge that crosses every row tile of a
+  // tall frame (later launches exit at once after convergence; beyond the queue, hc_sync continues from the host)
+  // (one more than the tiles an edge can cross monotonically: the last queued launch must find nothing to do, or the host
+  // continues in hc_sync -- which stalls a pipelined stream of runs)
+  const int need = (h.need_rows + tile - 1) / tile;
+  int K = std::min(MAX_HYST_LAUNCHES, std::max(std::max(o.launches, p.nrtiles + p.npanels + 1), need + 2));
+  // One or a few frames per call, not pipelined (the reference's pattern): every queued launch that finds nothing to do
+  // still costs ~5 us of pure latency, so only what the last runs needed is queued, + 2; frames that need more are
+  // finished by the host-side continuation (cheap here: nothing else is in flight).
+  if (!small_tiles && (long)n * H < 128 * 1024 && h.need_rows > 0) K = std::min(K, std::max(4, need + 2));
+  // ... and in a pipelined stream whose needs are known, not the worst case of an edge down the whole frame (68 row tiles
+  // at 8K: 70 launches queued, 50 of them idle at ~5 us each on the hysteresis stream) but what the last runs needed, + 4;
+  // a frame that needs more is finished by the continuation, and the estimate follows it at once
+  if (small_tiles && h.need_rows > 0) K = std::min(K, std::max(6, need + 4));
+  // (a few frames per run, pipelined: the step is the host's time to queue the run -- 75 us for ~25 API calls -- so every
+  // launch that is not needed counts)
+  if (small_tiles && h.need_rows > 0 && (long)n * H < 128 * 1024) K = std::min(K, std::max(4, need + 2));
+  if (o.launches_set) K = o.launches;
+  p.K = K;
+  // worklists of launches >= 1: counts and reason words live behind the launch flags and are zeroed with them
+  p.wl_stride = (size_t)n * p.nrtiles * p.npanels;
+  p.fits = p.wl_stride <= wl_cap;
+  if (!p.fits) return p;
+  p.clear = zeroed_words < run_flag_words(p.wl_stride);
+  // Worklists or a workgroup per tile in every launch (k_hyst)?  Lists where the step follows the hysteresis chain:
+  // frames wider than one panel -- unless they are dense (the last run visited more than 60 % of the tiles in launch 1:
+  // noise; camera-like frames: a third; the front kernel, which bounds such streams, loses less to a hysteresis that is
+  // spread over it: 33.6 against 30.8 k frames/s on 4K noise) -- and one-panel streams whose runs need 20 launches or more
+  // (BGR frames blended into grey: 25 launches, 205 -> 222 k frames/s; the 16 launches of 1080p grey frames fit inside
+  // the front kernel's time, and there the lists cost 2 %).
+  bool lists;
+  if (o.late_grid) lists = o.late_grid > 0;
+  else if (p.npanels > 1) lists = !(h.wl_prev_tiles == p.wl_stride && (size_t)h.wl_prev[1] * 5 > p.wl_stride * 3);
+  else lists = h.last_work_launches >= 20 || (h.lists_last && h.last_work_launches >= 14);
+  h.lists_last = lists;
+  p.lists0 = lists ? 1 : 0;
+  p.test_grid = std::max(o.late_grid, 0);
+  // The other streams: a workgroup per tile for launches 0 and 1 -- which do most of the work, and whose idle workgroups
+  // keep the hysteresis spread over the front kernel it runs beside -- then lists for the tail of launches that follow a
+  // few long edges through the frame (launch 2 still starts every tile, and writes the first list): 1080p grey 394 -> 405 k
+  // frames/s, 256 frames per run 307 -> 317 k; with the lists from launch 1 on: 400 k, from launch 4: 404 k.  (The list
+  // streams above keep their lists from launch 1: BGR 259 against 252 k, 8K x 3 8.76 against 8.64 k; 4K would gain 2 %.)
+  constexpr int MIXED_FROM = 2;  // first launch of a mixed-schedule run that works from lists
+  p.mixed = !lists && !o.late_grid && small_tiles;
+  // A small run (a few frames): all K rounds in one launch, device-wide barriers between them (k_hyst_loop) -- K host
+  // calls and K trips through the command processor fewer per run; a run it cannot finish (its workgroups not resident
+  // together, or more rounds needed than queued) is continued by finish_slot like any other.
+  // (not beside other runs: in the pipelined small batches the rounds' barriers -- ~10 us each, with the waiting workgroups
+  // resident -- cost more than the launches they replace: 8 frames per run 0.147 against 0.117 ms per call; one frame per
+  // call, the reference's pattern: 0.150 against 0.168 ms)
+  p.loop = o.loop && !small_tiles && !lists && !o.late_grid && !o.diag && p.npanels == 1 && RD == 64 && p.wl_stride <= (size_t)HYST_LOOP_MAX_TILES
+           && ((p.tile_rows == 16 && p.waves == 8) || (p.tile_rows == 32 && p.waves == 2));
+  if (p.loop) p.mixed = false;
+  for (int k = 0; k < K; ++k) {
+    p.lists[k] = (uint8_t)(p.mixed ? (k < MIXED_FROM ? 0 : k == MIXED_FROM ? 2 : 1) : lists ? 1 : 0);
+    // worklist scheme, launches >= 1: a workgroup per list entry.  Grid: twice what the last run of this shape listed for
+    // the launch (entries beyond the grid wait a launch: a dense frame would need several launches more); without such
+    // a run, launch_hyst's schedule by the tile count
+    p.late_grid[k] = p.test_grid;
+    if (!p.loop && p.lists[k] == 1 && !p.test_grid && k > 0 && h.wl_prev_tiles == p.wl_stride)
+      p.late_grid[k] = (int)std::min<size_t>(p.wl_stride, std::max<size_t>((size_t)2048, 2 * (size_t)h.wl_prev[k] + 256));
+  }
+  return p;
+}
+
+}  // namespace hc

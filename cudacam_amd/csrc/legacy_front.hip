@@ -22,12 +22,11 @@ namespace hc {
 // The vertical accumulators of phase 1 and the row rings of phase 2 are carried across sub-chunks, so
 // the only redundant work per run is the 4-row blur warm-up and the 4 extra blur rows (RUN+8 input
 // rows and RUN+4 blur rows per RUN output rows), while LDS stays at 6.5 KiB per wave.
-constexpr int FSUB = 24;    // blur rows per sub-chunk: multiple of the prefetch group (4) and of the ring period (6)
+// (FSUB, blur rows per sub-chunk, and front_run_rows: canny_params.h, shared with the host planner)
 constexpr int QCAP = 128;   // fix-up queue entries per wave and sub-chunk (one lane-dword each; expected fill ~37)
 constexpr int FRONT_WAVE_BYTES = FSUB * 256 + QCAP * 4;
 
 size_t front_lds_bytes() { return (size_t)4 * FRONT_WAVE_BYTES; }  // 26,624 B: 6 workgroups per CU
-int front_run_rows(int subchunks) { return FSUB * subchunks - 4; }
 
 #ifndef HC_FRONT_WAVES
 #define HC_FRONT_WAVES 4

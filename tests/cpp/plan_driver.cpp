@@ -1,0 +1,313 @@
+// plan_driver.cpp -- the planner of cudacam_amd/csrc/host_plan.h, checked without a GPU (tests/test_plan_cpu.py builds this
+// with g++ under ASan + UBSan).  A context is modelled with the same helpers hc_create uses (frame_pitch,
+// plane_row_dwords, half_pays, half_dump_region, slot_wl_cap); every plan of the sweep must keep the capacity claims the
+// launchers and kernels rest on.  Prints "ok <plans checked>" or the first violations.
+#include "../../cudacam_amd/csrc/host_plan.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+using namespace hc;
+
+static long g_plans = 0, g_fail = 0;
+static void bad(const char *what, const FrontIn &in, const FrontPlan &P)
+{
+  if (++g_fail <= 20)
+    std::printf("FAIL %s: mode %d C %d W %d H %d n %d pc %d piped %d form %d half %d chunk %d mx %d halfmode %d in.pitch %zu\n", what, in.mode, in.C, in.W, in.H, in.n,
+                in.per_channel, (int)in.piped, P.form, P.fp.half, in.o.chunk, in.o.mx_mode, in.o.half_mode, in.in.pitch);
+}
+#define CHECK(cond, what) do { if (!(cond)) bad(what, in, P); } while (0)
+
+struct Ctx {  // what hc_create / hc_set_option derive
+  int mode, C, W, H, per_channel, max_batch, RD, nstrips;
+  View own_in, own_mono, own_out;
+  size_t dump_region, wl_cap;
+};
+static Ctx make_ctx(int mode, int C, int W, int H, int per_channel, int max_batch, bool force_half)
+{
+  Ctx c{ mode, C, W, H, per_channel, max_batch, plane_row_dwords(W), (W + STRIP_W - 1) / STRIP_W };
+  c.own_in.pitch = frame_pitch(round_up((size_t)W, 8) * C, (size_t)W * C);
+  c.own_out.pitch = frame_pitch((size_t)W, (size_t)W);
+  c.own_mono.pitch = frame_pitch((size_t)W, 0);
+  c.own_in.fs = c.own_in.pitch * H; c.own_out.fs = c.own_out.pitch * H; c.own_mono.fs = c.own_mono.pitch * H;
+  c.own_in.p = c.own_mono.p = c.own_out.p = 0;
+  c.dump_region = (half_pays(W) || force_half) ? half_dump_region(c.own_in.fs, c.own_out.fs, c.RD, H) : 0;
+  c.wl_cap = slot_wl_cap((size_t)max_batch * (per_channel ? 3 : 1), H, c.RD);
+  return c;
+}
+static FrontIn make_in(const Ctx &c, int n, bool piped, const FrontOpts &o, const View &in, const View &out, bool grads = false)
+{
+  FrontIn fi{ c.mode, c.C, c.W, c.H, c.RD, c.nstrips, c.per_channel, HC_STAGE_HYSTER, n };
+  fi.in = in; fi.out = out; fi.in_dy = grads ? 0x30000000u : 0;
+  fi.own_in = c.own_in; fi.own_mono = c.own_mono; fi.own_out = c.own_out;
+  fi.o = o; fi.dump_region = c.dump_region; fi.piped = piped;
+  fi.nslot_use = piped ? pipeline_slots(0, 2, c.per_channel ? 3 * n : n, c.W, c.H) : 2;
+  fi.front_one = false; fi.out_overlap = false; fi.wl_cap = c.wl_cap;
+  return fi;
+}
+
+// the claims of the issue, for one front plan and the hysteresis plans that can follow it
+static void check(const Ctx &c, const FrontIn &in, const HystOpts &ho, bool full = true)
+{
+  const FrontPlan P = plan_front(in);
+  ++g_plans;
+  if (P.error) {  // only the product build's refusal of the round-1 forms may appear in this sweep
+    CHECK(in.mode == HC_MODE_R && in.o.split != 2, "unexpected plan error");
+    return;
+  }
+  const FrontParams &f = P.fp;
+  const int H = in.H, W = in.W, n_out = in.per_channel ? 3 * in.n : in.n;
+  const long per = in.per_channel ? 3 : 1;
+  const int rows = (P.form == -1 || P.form == 6 || P.form == 7) ? f.chunk_rows : f.run_rows;
+  CHECK(rows >= 1 && (long)f.nchunks * rows >= H, "nchunks * run_rows >= H");
+  long units = (long)n_out * f.nstrips;
+  if (P.form == 4) units = (((long)in.n * front8_half_strips(W) + 1) / 2) * per;
+  if (P.form == 5) CHECK(f.nstrips == front_mx_strips(W), "mx strips");
+  if (P.form == 2 || P.form == 3 || P.form == 4) CHECK(f.nstrips == front8_strips(W) && (f.run_rows + 4) % F8_SUB == 0, "f8 strips / windows");
+  CHECK(f.total_items > 0 && (long)f.total_items == units * f.nchunks, "total_items = units x chunks");
+  if (P.form == 2 || P.form == 3 || P.form == 4)  // the dead `!can8` branch: rows always hold whole 8-pixel groups
+    CHECK(f.in_pitch >= round_up((size_t)W, 8) * (size_t)(f.bgr ? 3 : 1), "8-px kernels read whole groups");
+  CHECK((f.in_pitch | f.in_frame_stride) % (P.form == 7 ? 2 : 4) == 0 && !reaches_4g(H, f.in_pitch), "input rows within 32-bit offsets, aligned");
+  if (P.form == 4) {  // the `fits` inequalities, from the buffers the kernel really gets
+    const size_t R = in.dump_region;
+    CHECK(f.half == 1 && f.nhalf == front8_half_strips(W) && R != 0, "HALF parameters");
+    CHECK(f.in_frame_stride + 32768 <= R && per * sizeof(u32) * (size_t)in.RD * H + 4096 <= R, "HALF: lane offsets fit the dump region");
+    CHECK((unsigned long long)f.in_frame_stride + (unsigned long long)H * f.in_pitch < (1ull << 32), "HALF: input offsets below 4 GiB");
+    if (P.prov) CHECK(per * f.prov_fs + 16384 <= R && (unsigned long long)per * f.prov_fs + (unsigned long long)H * f.prov_pitch < (1ull << 32), "HALF: provisional map offsets");
+  } else CHECK(f.half == 0, "half only in form 4");
+  if (P.prov) CHECK(in.piped && (unsigned long long)H * P.dst.pitch < (1ull << 32) && f.prov_pitch == P.dst.pitch, "prov never with H * pitch >= 2^32");
+  CHECK(P.zeroed_words <= run_flag_words(c.wl_cap) && f.zero_count == P.zeroed_words, "zeroed_words within d_flags");
+  CHECK(P.waves == 0 || P.waves == 1 || P.waves == 3 || P.waves == 4, "waves per workgroup");
+  // the hysteresis plans: fresh history, and histories that push every rule
+  for (int hist = 0; hist < 4; hist += full ? 1 : 2) {
+    HystHistory h;
+    if (hist == 1) { h.need_rows = 64; h.last_work_launches = 3; }
+    if (hist == 2) { h.need_rows = 40000; h.last_work_launches = 60; h.lists_last = true; h.obs[0] = 60; h.obs[1] = 50; }
+    for (int rep = 0; rep < 2; ++rep) {
+      const HystPlan p = plan_hyst(in.RD, H, n_out, in.piped, ho, h, c.wl_cap, P.zeroed_words);
+      CHECK(p.fits && p.wl_stride <= c.wl_cap, "wl_stride <= wl_cap");
+      CHECK(run_flag_words(p.wl_stride) <= run_flag_words(c.wl_cap), "flag words within d_flags");
+      CHECK(p.K >= 1 && p.K <= MAX_HYST_LAUNCHES && WL_COUNT_WORDS >= p.K + 3, "1 <= K <= MAX_HYST_LAUNCHES");
+      CHECK(p.nrtiles * p.tile_rows * p.waves >= H && p.wl_stride == (size_t)n_out * p.nrtiles * p.npanels, "tiles cover the frame");
+      if (p.loop) CHECK(p.wl_stride <= (size_t)HYST_LOOP_MAX_TILES && !in.piped && p.npanels == 1 && ((p.tile_rows == 16 && p.waves == 8) || (p.tile_rows == 32 && p.waves == 2)), "loop form: small, whitelisted shape");
+      for (int k = 0; k < p.K; ++k) {
+        const int want = p.mixed ? (k < 2 ? 0 : k == 2 ? 2 : 1) : p.lists0;
+        CHECK(p.lists[k] == want && (!p.loop || p.lists[k] == 0), "list modes 0..0, 2, 1..1");
+        CHECK(p.late_grid[k] >= 0 && (size_t)p.late_grid[k] <= std::max<size_t>(p.wl_stride, (size_t)p.test_grid), "late grid");
+      }
+      if (p.mixed) CHECK(in.piped && !p.lists0 && !p.loop, "mixed only beside a front kernel");
+      // the run finishes: the last launches found work (hist 3: every launch did, as a continued run reports)
+      std::vector<u32> counts(MAX_HYST_LAUNCHES + 1, (u32)std::min<size_t>(p.wl_stride, 0xFFFFFFFFu));
+      h.finished(p, hist == 3 ? 3 * p.K : std::min(p.K, 2 + hist), counts.data());
+    }
+  }
+}
+
+static void sweep_geometry(int W, int H, bool full)
+{
+  const HystOpts ho0;
+  std::vector<int> batches = { 1, 8 };
+  if (full) { batches.push_back(2); batches.push_back(64); }
+  const long cross = (500l * 1000 * 1000 + (long)W * H - 1) / ((long)W * H);  // the first batch the slot rule calls big
+  if (cross <= (1 << 20)) { batches.push_back((int)cross); if (cross > 1 && full) batches.push_back((int)cross - 1); }
+  for (int mode : { HC_MODE_R, HC_MODE_O })
+    for (int C : { 1, 3 })
+      for (int pc = 0; pc <= (mode == HC_MODE_R && C == 3 ? 1 : 0); ++pc)
+        for (int n : batches) {
+          const int max_batch = n;
+          for (int piped = 0; piped <= 1; ++piped) {
+            std::vector<FrontOpts> opts(1);
+            if (!full) {  // every geometry: the forms that cut the work their own way
+              FrontOpts o;
+              o.mx_mode = 1; opts.push_back(o);
+              o = FrontOpts{}; o.half_mode = 1; opts.push_back(o);
+              o = FrontOpts{}; o.chunk = 8; o.aperture = 5; opts.push_back(o);
+            } else {
+              FrontOpts o;
+              for (int v : { 0, 1 }) { o = FrontOpts{}; o.half_mode = v; opts.push_back(o); }
+              o = FrontOpts{}; o.mx_mode = 1; opts.push_back(o);
+              o.half_mode = 0; opts.push_back(o);
+              for (int v : { 0, 1 }) { o = FrontOpts{}; o.dense_mode = v; opts.push_back(o); }
+              for (int v : { 1, 4 }) { o = FrontOpts{}; o.wpb_mode = v; o.mx_mode = v == 1; opts.push_back(o); }
+              for (int v : { 8, 50, 300, 16384 }) { o = FrontOpts{}; o.chunk = v; o.half_mode = v == 50; o.mx_mode = v == 300; opts.push_back(o); }
+              o = FrontOpts{}; o.nms_saturate = 1; o.debug_taps = true; opts.push_back(o);
+              o = FrontOpts{}; o.split = 1; opts.push_back(o);
+              o.split = 0; opts.push_back(o);
+              if (mode == HC_MODE_O) { o = FrontOpts{}; o.aperture = 5; opts.push_back(o); o.l2gradient = 1; opts.push_back(o); o.aperture = 3; opts.push_back(o); }
+            }
+            for (const FrontOpts &o : opts) {
+              const Ctx c = make_ctx(mode, C, W, H, pc, max_batch, o.half_mode == 1);
+              const size_t tight = (size_t)W * C;
+              const View out{ 0x20000000u, (size_t)W, (size_t)W * H };
+              std::vector<View> ins = { View{ 0x10000000u, tight, tight * H }, View{ 0x10000000u, c.own_in.pitch, c.own_in.fs } };
+              if (full) { ins.push_back(View{ 0x10000001u, tight + 3, (tight + 3) * H }); ins.push_back(View{ 0x10000000u, round_up(tight, 4) + 4096, (round_up(tight, 4) + 4096) * H }); }
+              if (!full) { check(c, make_in(c, n, piped != 0, o, ins[(W + H + n) & 1], out), ho0, false); continue; }
+              for (const View &v : ins) check(c, make_in(c, n, piped != 0, o, v, out), ho0);
+              if (full) {
+                check(c, make_in(c, n, piped != 0, o, ins[0], View{ 0x20000002u, (size_t)W + 1, ((size_t)W + 1) * H }), ho0);  // staged output
+                HystOpts ho;
+                for (int g : { -1, 1, 7 }) { ho = HystOpts{}; ho.late_grid = g; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho); }
+                ho = HystOpts{}; ho.loop = false; ho.diag = true; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho);
+                for (int g : { 3208, 3204, 3202, 1608, 3216, 3201, 1604, 1602 }) { ho = HystOpts{}; ho.geom = g; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho); }
+                for (int k : { 1, 6, 96 }) { ho = HystOpts{}; ho.launches = k; ho.launches_set = true; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho); }
+                if (mode == HC_MODE_O) check(c, make_in(c, n, piped != 0, o, View{ 0x10000000u, 2 * tight + 2, (2 * tight + 2) * H }, out, true), ho0);
+              }
+            }
+          }
+        }
+}
+
+// forms the GPU tests pin (tests/test_gpu_half_strips.py, test_gpu_front_mx.py, test_gpu_canny_o_ext.py, test_gpu_views.py,
+// __graft_entry__.py): (input staged, output staged, form)
+static void expect(const char *what, const Ctx &c, int n, bool piped, const FrontOpts &o, const View &in, const View &out, int staged_in, int staged_out, int form, bool grads = false)
+{
+  const FrontPlan P = plan_front(make_in(c, n, piped, o, in, out, grads));
+  if (P.error || P.form != form || (staged_in >= 0 && P.in_staged != (staged_in != 0)) || (staged_out >= 0 && P.out_staged != (staged_out != 0))) {
+    ++g_fail;
+    std::printf("FAIL pinned %s: got (%d, %d, %d)%s\n", what, (int)P.in_staged, (int)P.out_staged, P.form, P.error ? P.error : "");
+  }
+}
+static void pinned()
+{
+  FrontOpts d, o;
+  auto tight = [](const Ctx &c) { return View{ 0x10000000u, (size_t)c.W * c.C, (size_t)c.W * c.C * c.H }; };
+  auto tout = [](const Ctx &c) { return View{ 0x20000000u, (size_t)c.W, (size_t)c.W * c.H }; };
+  {  // test_half_form_pipelined_device_buffers: 640 x 480, 5 frames, pipelined
+    const Ctx c = make_ctx(HC_MODE_R, 1, 640, 480, 0, 5, false);
+    o = d; expect("half auto", c, 5, true, o, tight(c), tout(c), 0, 0, 4);
+    o.half_mode = 0; expect("half 0", c, 5, true, o, tight(c), tout(c), 0, 0, 2);
+    o.half_mode = 1; expect("half 1", c, 5, true, o, tight(c), tout(c), 0, 0, 4);
+  }
+  for (int chunk : { 8, 20, 50, 300 }) {  // test_half_form_run_lengths_and_thresholds (hc_run: the internal buffers)
+    const Ctx c = make_ctx(HC_MODE_R, 1, 640, 230, 0, 3, true);
+    o = d; o.half_mode = 1; o.chunk = chunk; expect("half chunk", c, 3, false, o, c.own_in, c.own_out, -1, -1, 4);
+  }
+  for (int w : { 96, 500, 640, 1000 })  // test_half_form_three_channel
+    for (int pc : { 0, 1 }) {
+      const Ctx c = make_ctx(HC_MODE_R, 3, w, 70, pc, 3, true);
+      o = d; o.half_mode = 1; o.debug_taps = true; expect("half 3ch", c, 3, false, o, c.own_in, c.own_out, -1, -1, 4);
+    }
+  {  // __graft_entry__.py smoke: 640 x 480 x 2 with HC_OPT_FRONT_MX
+    const Ctx c = make_ctx(HC_MODE_R, 1, 640, 480, 0, 2, false);
+    o = d; o.mx_mode = 1; expect("smoke mx", c, 2, false, o, c.own_in, c.own_out, -1, -1, 5);
+  }
+  for (int ap5 = 0; ap5 <= 1; ++ap5)  // test_gpu_canny_o_ext: aperture 5 -> 6, gradients -> 7
+    for (int C : { 1, 3 }) {
+      const Ctx c = make_ctx(HC_MODE_O, C, 322, 97, 0, 2, false);
+      o = d; o.aperture = ap5 ? 5 : 3;
+      if (ap5) expect("aperture 5", c, 2, false, o, c.own_in, c.own_out, -1, -1, 6);
+      expect("gradients", c, 2, true, o, View{ 0x10000000u, (size_t)2 * C * 322 + 4, ((size_t)2 * C * 322 + 4) * 97 }, tout(c), 0, -1, 7, true);
+    }
+  for (int mx = 0; mx <= 1; ++mx) {  // test_gpu_views: a 4 GiB-reaching view of a wide parent, w x h = 64 x 1024 rows of a 4 MiB pitch
+    const int w = 64, h = 1024;
+    const size_t pitch = (size_t)4 << 20;
+    const Ctx c = make_ctx(HC_MODE_R, 1, w, h, 0, 1, false);
+    o = d; o.half_mode = 0; o.mx_mode = mx;
+    const View far{ 0x40000000u, pitch, pitch * h };
+    FrontIn fi = make_in(c, 1, true, o, tight(c), far);
+    const FrontPlan P = plan_front(fi);
+    if (P.prov || P.in_staged || P.out_staged || P.form != (mx ? 5 : 2)) { ++g_fail; std::printf("FAIL pinned far output view\n"); }
+    expect("far input view", c, 1, true, o, far, tout(c), 1, 0, mx ? 5 : 2);
+  }
+  {  // non-final stages plan no front kernel
+    const Ctx c = make_ctx(HC_MODE_R, 3, 100, 50, 0, 2, false);
+    FrontIn fi = make_in(c, 2, false, d, tight(c), tout(c));
+    fi.stage = HC_STAGE_NMS;
+    const FrontPlan P = plan_front(fi);
+    if (P.form != -1 || P.in_staged || P.out_staged || !P.gray) { ++g_fail; std::printf("FAIL pinned stage tap\n"); }
+  }
+}
+
+// ChainWatch against the rules stated above it
+#define WCHECK(cond, what) do { if (!(cond)) { ++g_fail; std::printf("FAIL ChainWatch: %s (line %d)\n", what, __LINE__); } } while (0)
+static void chain_watch()
+{
+  auto step = [](ChainWatch &w, unsigned long long &i, float front, float lead) { ++i; w.update(i, pipeline_slots(w.pipe_slots, w.big_slots, 1 << 20, 1920, 1080), front, lead); };
+  {  // three outlasting runs, but never before run 5
+    ChainWatch w; unsigned long long i = 1;
+    step(w, i, 1.0f, -0.1f); step(w, i, 1.0f, -0.1f); step(w, i, 1.0f, -0.1f);  // runs 2, 3, 4
+    WCHECK(w.big_slots == 2 && w.chain_bound_runs == 3, "no trial before run 5");
+    step(w, i, 1.0f, -0.1f);  // run 5
+    WCHECK(w.big_slots == 3 && w.trial_runs == 0, "trial at run 5 after three outlasting runs");
+    // the trial: ten runs; 0.98 of the old step is not enough -> back, wait 64, back-off doubles
+    for (int k = 0; k < 9; ++k) { step(w, i, 0.98f, -0.1f); WCHECK(w.big_slots == 3, "trial lasts ten runs"); }
+    step(w, i, 0.98f, -0.1f);
+    WCHECK(w.big_slots == 2 && w.retry_wait == 64 && w.retry_backoff == 128, "trial that did not pay: back-off 64, doubling");
+    int waited = 0;
+    while (w.big_slots == 2 && waited < 200) { step(w, i, 1.0f, -0.1f); ++waited; }
+    WCHECK(waited == 64, "next trial after 64 runs");
+    for (int k = 0; k < 10; ++k) step(w, i, 0.96f, -0.1f);
+    WCHECK(w.big_slots == 3 && w.trial_runs == -1, "kept below 0.97 x the pre-trial mean");
+    // 16 light runs -> two slots, the next time 32
+    for (int k = 0; k < 15; ++k) step(w, i, 0.96f, 0.01f);
+    WCHECK(w.big_slots == 3, "15 light runs keep the slot");
+    step(w, i, 0.96f, 0.01f);
+    WCHECK(w.big_slots == 2 && w.chain_light_needed == 32, "two slots after 16 light runs, doubling");
+  }
+  {  // the caps: 4096 and 1024
+    ChainWatch w; unsigned long long i = 10;
+    for (int t = 0; t < 12; ++t) {
+      while (w.big_slots == 2) step(w, i, 1.0f, -0.1f);
+      for (int k = 0; k < 10; ++k) step(w, i, 1.0f, -0.1f);
+    }
+    WCHECK(w.retry_backoff == 4096, "back-off doubles to 4096");
+    ChainWatch v; i = 10;
+    for (int t = 0; t < 10; ++t) {
+      v.retry_wait = 0;
+      while (v.big_slots == 2) step(v, i, 1.0f, -0.1f);
+      for (int k = 0; k < 10; ++k) step(v, i, 0.5f, -0.1f);  // kept
+      WCHECK(v.big_slots == 3, "kept");
+      while (v.big_slots == 3) step(v, i, 0.5f, 0.01f);
+      for (int k = 0; k < 4; ++k) step(v, i, 1.0f, 0.01f);  // the old step again
+    }
+    WCHECK(v.chain_light_needed == 1024, "light runs needed double to 1024");
+  }
+  {  // one wave above 0.25, four below 0.03
+    ChainWatch w; unsigned long long i = 1;
+    step(w, i, 1.0f, 0.9f);
+    WCHECK(!w.front_one, "ema 0.225");
+    step(w, i, 1.0f, 0.9f);
+    WCHECK(w.front_one && w.slack_ema > 0.25f, "one wave above 0.25");
+    while (w.slack_ema >= 0.03f) { WCHECK(w.front_one, "stays until below 0.03"); step(w, i, 1.0f, 0.0f); }
+    WCHECK(!w.front_one, "four waves below 0.03");
+    step(w, i, 0.0f, 0.5f);
+    WCHECK(w.slack_ema < 0.03f, "a run without a front time changes nothing");
+  }
+  {  // chain_told: +1 every chain outlasts and the trial is kept; -1 nothing outlasts; fixed slots: no trials
+    ChainWatch w; w.chain_told = 1; unsigned long long i = 1;
+    for (int k = 0; k < 4; ++k) step(w, i, 1.0f, 0.5f);
+    WCHECK(w.big_slots == 3, "told +1: trial although the chains end early");
+    for (int k = 0; k < 10; ++k) step(w, i, 2.0f, 0.5f);
+    WCHECK(w.big_slots == 3, "told +1: kept although slower");
+    for (int k = 0; k < 100; ++k) step(w, i, 2.0f, 0.5f);
+    WCHECK(w.big_slots == 3, "told +1: no light runs");
+    ChainWatch v; v.chain_told = -1; i = 1;
+    for (int k = 0; k < 50; ++k) step(v, i, 1.0f, -0.5f);
+    WCHECK(v.big_slots == 2, "told -1: no trial although the chains outlast");
+    ChainWatch f; f.pipe_slots = 2; i = 1;
+    for (int k = 0; k < 50; ++k) step(f, i, 1.0f, -0.5f);
+    WCHECK(f.big_slots == 2 && pipeline_slots(f.pipe_slots, f.big_slots, 1, 8, 8) == 2 && pipeline_depth(true, 2, 2, 1, 8, 8) == 2, "fixed slots");
+    WCHECK(pipeline_slots(0, 2, 241, 1920, 1080) == 4 && pipeline_slots(0, 2, 242, 1920, 1080) == 2 && pipeline_depth(true, 0, 2, 242, 1920, 1080) == 3 && pipeline_depth(false, 0, 2, 1, 8, 8) == 1, "0.5 G-pixel slot rule");
+  }
+}
+
+int main()
+{
+  const int heights[] = { 1, 8, 480, 1080, 4320 };  // every width at these heights, every height at these widths; the full option product where both are special
+  const int widths[] = { 1, 8, 240, 248, 496, 640, 1920, 3840, 8184 };
+  const int special[] = { 1, 7, 8, 16, 239, 240, 241, 247, 248, 249, 480, 495, 496, 497, 1079, 1080, 2160, 4320 };
+  auto is_special = [&](int v) { for (int s : special) if (s == v) return true; return false; };
+  for (int H : heights)
+    for (int W = 1; W <= 8184; ++W) sweep_geometry(W, H, is_special(W) && is_special(H));
+  for (int W : widths)
+    for (int H = 1; H <= 4400; ++H) sweep_geometry(W, H, is_special(W) && is_special(H));
+  for (int W : special)
+    for (int H : special) sweep_geometry(W, H, true);
+  pinned();
+  chain_watch();
+  if (plane_row_dwords(8184) != 256 || plane_row_dwords(8185) != 0) { ++g_fail; std::printf("FAIL width limit\n"); }
+  if (g_fail) { std::printf("%ld violations in %ld plans\n", g_fail, g_plans); return 1; }
+  std::printf("ok %ld\n", g_plans);
+  return 0;
+}

@@ -1,0 +1,33 @@
+"""The host planner (cudacam_amd/csrc/host_plan.h: plan_front, plan_hyst, HystHistory, ChainWatch, pipeline_slots) without
+a GPU.  tests/cpp/plan_driver.cpp is compiled against the header with g++ under ASan + UBSan and sweeps every width
+1..8184 at heights 1 / 8 / 480 / 1080 / 4320 and every height 1..4400 at widths 1 / 8 / 240 / 248 / 496 / 640 / 1920 /
+3840 / 8184 (both modes, 1 and 3 channels, per-channel, plain and pipelined, batches up to the first one the 0.5 G-pixel
+slot rule calls big), and the whole option product where width and height are both of 1, 7, 8, 16, 240 / 248 / 496 +- 1,
+480, 1079, 1080, 2160, 4320.  Every plan must keep what the launchers and kernels rest on:
+
+* nchunks * run_rows >= H; total_items = units x chunks > 0 for each form; rows of the 8-px forms hold whole groups;
+* a HALF plan satisfies the `fits` inequalities; a plan with the provisional map never has H * pitch >= 2^32;
+* wl_stride <= wl_cap; zeroed_words and FLAG_WORDS + WL_COUNT_WORDS + 2 * wl_stride within the d_flags allocation;
+* 1 <= K <= MAX_HYST_LAUNCHES; the loop form only for <= HYST_LOOP_MAX_TILES tiles of the two whitelisted shapes;
+  per-launch list modes 0 .. 0, 2, 1 .. 1 when mixed;
+* the forms the GPU tests pin (half strips, k_front_mx, k_front_o_ext, the 4 GiB views, the smoke run);
+* ChainWatch on synthetic traces: trial after three outlasting runs and run >= 5, kept only below 0.97 x the pre-trial
+  mean, back-off 64 doubling to 4096, back to two slots after 16 light runs doubling to 1024, one wave above 0.25 and
+  back below 0.03, the chain_told overrides."""
+import os
+import subprocess
+
+from test_sanitizers import ENV, ROOT, SAN, _cc
+
+
+def test_planner_under_asan_ubsan(tmp_path):
+    exe = str(tmp_path / "plan_driver")
+    _cc(["g++", "-std=c++17", "-Wall", "-Werror", *SAN, "-o", exe, os.path.join(ROOT, "tests", "cpp", "plan_driver.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=1500, env=ENV)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-4000:] + out.stderr[-4000:]
+    assert int(out.stdout.split()[1]) > 10 * 1000 * 1000
+
+
+def test_planner_builds_for_the_legacy_library(tmp_path):
+    """The round-1 arithmetic (HC_LEGACY_FRONT) stays behind its macro and compiles without HIP as well."""
+    _cc(["g++", "-std=c++17", "-Wall", "-Werror", "-DHC_LEGACY_FRONT", "-fsyntax-only", os.path.join(ROOT, "tests", "cpp", "plan_driver.cpp")])

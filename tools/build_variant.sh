@@ -14,7 +14,7 @@ for f in canny_kernels.hip front8.hip front_mx.hip front_o_ext.hip hipcanny.hip;
     objs+=("exp/obj/${f%.hip}_${name}.o")
   else
     o="exp/obj/${f%.hip}.o"
-    if [ ! -f "$o" ] || [ "csrc/$f" -nt "$o" ] || [ csrc/canny_common.h -nt "$o" ] || [ csrc/canny_device.h -nt "$o" ] || [ ../include/hipcanny.h -nt "$o" ]; then $CC -c "csrc/$f" -o "$o"; fi
+    if [ ! -f "$o" ] || [ "csrc/$f" -nt "$o" ] || [ csrc/canny_common.h -nt "$o" ] || [ csrc/canny_params.h -nt "$o" ] || [ csrc/host_plan.h -nt "$o" ] || [ csrc/canny_device.h -nt "$o" ] || [ ../include/hipcanny.h -nt "$o" ]; then $CC -c "csrc/$f" -o "$o"; fi
     objs+=("$o")
   fi
 done
