@@ -7,7 +7,7 @@
 
 namespace hc {
 
-// ---- host-callable launchers (defined in canny_kernels.hip) -----------------------------------
+// ---- host-callable launchers (defined in canny_kernels.hip unless noted) ----------------------
 hipError_t launch_selftest(u32 *d_result, hipStream_t s);
 hipError_t check_gauss_coeffs(const float gk[25]);
 hipError_t launch_front_o(const FrontParams &p, hipStream_t s);
@@ -24,7 +24,7 @@ hipError_t launch_front8o(const FrontParams &p, hipStream_t s);  // Mode O on th
 // front_mx.hip: Mode R, one-channel frames, the blur and Sobel contractions as i8 MFMAs (strips of 216 columns, runs of
 // 16 * blocks rows); big batches
 hipError_t launch_front_mx(const FrontParams &p, hipStream_t s);
-hipError_t launch_hyst(const HystParams &p, hipStream_t s);
+hipError_t launch_hyst(const HystParams &p, hipStream_t s);  // hyst.hip, as the next two
 // the first `rounds` launches of the workgroup-per-tile form as ONE launch with device-wide barriers between the rounds
 // (small runs: at most HYST_LOOP_MAX_TILES tiles); bar: two zeroed words (arrival counter, abort flag)
 hipError_t launch_hyst_loop(const HystParams &p, int rounds, u32 *bar, hipStream_t s);

@@ -38,7 +38,7 @@ struct FrontParams {
   int total_items;         // nframes * nstrips * nchunks
   // thresholds on S = sumX^2 + sumY^2 for "u8-wrapped gradient > T" (band test)
   u32 a_lo[3], a_hi[3];
-  // split mode (k_blur + k_nms): the u8 blur plane between the two kernels and k_nms's own work split
+  // split mode (k_blur + k_nms, legacy_front.hip): the u8 blur plane between the two kernels and k_nms's own work split
   uint8_t *blur;             // [frame][strip][H][256]: one aligned 256-byte row per wave-row (bytes 4..251 = the strip's columns)
   size_t blur_frame_stride;  // >= nstrips * H * 256
   int nchunks_b, run_rows_b, total_items_b;
@@ -91,7 +91,7 @@ struct HystParams {
   u32 *wl_reason;  // [2][wl_stride] per tile: 1 a tile above changed (its `top`), 2 below, 4 beside; zero at the start of a run
   u32 *wl_list;    // [2][wl_stride] wide frames: tile ids (frame * tiles per frame + tile)
   size_t wl_stride;
-  int lists;       // this launch: 1 takes its tiles from the worklist (k_hyst MODE 1 / 2); 0 a workgroup per tile (MODE 0); 2 a workgroup per tile that also writes the next launch's list (MODE 3)
+  int lists;       // this launch: 1 takes its tiles from the worklist; 0 a workgroup per tile; 2 a workgroup per tile that also writes the next launch's list (k_hyst's modes: hyst_mode, hyst.hip)
   int late_grid;   // worklist scheme: workgroups of launches >= 1 (0 = by the tile count, launch_hyst)
   int iter;        // index of this launch
   u32 *stats;      // optional diagnostics (3 words per launch) or null
@@ -132,7 +132,20 @@ inline int front_run_rows(int subchunks) { return FSUB * subchunks - 4; }
 // ---- hysteresis workgroup shape ---------------------------------------------------------------
 // k_hyst_loop (all rounds of a small run in one launch): at most this many tiles
 constexpr int HYST_LOOP_MAX_TILES = 128;
-// Workgroup tile = waves x tile_rows rows (canny_kernels.hip).
+// Workgroup tile = waves x tile_rows rows (hyst.hip).  The shapes k_hyst is compiled for, declared here once: the kernel
+// launchers, the planner and its CPU test all go by this table.
+struct HystShape { int tile_rows, waves; };
+constexpr HystShape HYST_SHAPES[] = { { 32, 8 }, { 32, 4 }, { 32, 2 }, { 16, 8 }, { 32, 16 }, { 32, 1 }, { 16, 4 }, { 16, 2 } };
+constexpr int N_HYST_SHAPES = (int)(sizeof(HYST_SHAPES) / sizeof(HYST_SHAPES[0]));
+constexpr bool is_hyst_shape(int tile_rows, int waves)
+{
+  for (const HystShape &s : HYST_SHAPES)
+    if (s.tile_rows == tile_rows && s.waves == waves) return true;
+  return false;
+}
+// ... and the two that also have the looping kernel (k_hyst_loop)
+constexpr bool hyst_shape_loops(int tile_rows, int waves) { return (tile_rows == 16 && waves == 8) || (tile_rows == 32 && waves == 2); }
+static_assert(is_hyst_shape(16, 8) && is_hyst_shape(32, 2), "the looping shapes are shapes");
 // 8 waves x 32 rows (256-row tiles) when the hysteresis has the chip to itself: fewer tile boundaries, fewer
 // launches.  4 waves x 32 rows (one wave per SIMD) when it runs beside the next run's front kernels (pipelined mode):
 // a 4-wave workgroup finds a place as soon as one wave slot per SIMD frees up, an 8-wave one has to wait for two --
@@ -140,8 +153,8 @@ constexpr int HYST_LOOP_MAX_TILES = 128;
 // (beside k_front8, whose three workgroups fill a CU's LDS and registers, a hysteresis workgroup only finds room when a
 // front workgroup retires: 2-wave workgroups fit the freed wave slots best -- 376 k frames/s against 368 k with 4 waves,
 // 350 k with 8; one-wave workgroups need more launches than are queued for a 1080-row frame)
-// frames_x_rows: frames x rows of the run.  geom: 0 = by the rules here; otherwise a shape picked by the caller for tuning experiments (encoded rows * 100 + waves:
-// 3208, 3204, 3202, 1608, 3216 -- hc_create reads HC_HYST_GEOM once)
+// frames_x_rows: frames x rows of the run.  geom: 0 = by the rules here; otherwise a shape of HYST_SHAPES picked by the caller for tuning experiments (encoded
+// rows * 100 + waves, e.g. 3208 -- hc_create reads HC_HYST_GEOM once)
 inline void hyst_tile_geometry(int geom, bool beside_front, long frames_x_rows, int H, int *tile_rows, int *waves)
 {
   (void)H;
@@ -156,7 +169,7 @@ inline void hyst_tile_geometry(int geom, bool beside_front, long frames_x_rows, 
   // latency -- 8 waves x 16 rows per workgroup halve the rows a wave walks one after the other (measured on one 1080p
   // frame: hysteresis 0.122 ms against 0.139 ms with 8 x 32 and 0.130 ms with 4 x 32)
   if (frames_x_rows < 128 * 1024) { *tile_rows = 16; *waves = 8; }
-  if (geom == 3208 || geom == 3204 || geom == 3202 || geom == 1608 || geom == 3216 || geom == 3201 || geom == 1604 || geom == 1602) { *tile_rows = geom / 100; *waves = geom % 100; }
+  if (is_hyst_shape(geom / 100, geom % 100)) { *tile_rows = geom / 100; *waves = geom % 100; }
 }
 
 }  // namespace hc

@@ -6,7 +6,7 @@
 // src/cvp/cannyEdgeH.cu:214-295): input frames in, the STRONG / CANDIDATE bit planes (and, in pipelined mode, the
 // provisional 0/255 edge map) out.  HBM traffic per pixel: 1 B read, 1/4 B of bit planes written, 1 B of provisional
 // map written -- against 25 B/px of intermediates in the reference and 4.4 B/px more in the k_blur + k_nms pair
-// (canny_kernels.hip), whose arithmetic this kernel shares.
+// (legacy_front.hip), whose arithmetic this kernel shares.
 //
 // Work decomposition.  A wave owns a vertical STRIP of 496 output columns and a RUN of rows it marches down.  Lane l
 // holds the 8 adjacent pixels at columns strip*496 - 8 + 8l .. +7 of the current row (two dwords); lanes 0 and 63 are
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     x[0] &= cmask[0]; x[1] &= cmask[1];  // (rows outside the image are read from a page of zeros, see load_raw)
   };
 
-  // ---- phase 1: the exact Gaussian (see k_blur in canny_kernels.hip for the derivation) ------------------------------
+  // ---- phase 1: the exact Gaussian (see k_blur in legacy_front.hip for the derivation) -------------------------------
   // per input row and pixel pair: p = x[-2]+x[+2], q = x[-1]+x[+1], c = x[0];  h0 = 2p+4q+5c, h1 = 4p+9q+12c, h2 = 5p+12q+15c;
   // S(row i) = h0[i-2] + h1[i-1] + h2[i] + h1[i+1] + h0[i+2] by four running accumulators.  Every packed u16 sum stays
   // below 2^16 per half (S <= 40545), so plain 32-bit adds act on both halves at once -- and on gfx950 v_add / v_sub / v_and /
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     *reinterpret_cast<u32x2 *>(bring + bslot * F8_ROW_BYTES + lane * 8) = u32x2{ bl0, bl1 };
   };
 
-  // ---- phase 2: blur -> Sobel -> S2 -> which half-lanes hold a candidate (see k_nms for the arithmetic) ---------------
+  // ---- phase 2: blur -> Sobel -> S2 -> which half-lanes hold a candidate (see k_nms in legacy_front.hip for the arithmetic) ---
   u32 dr[2][4], sr[2][4];  // d = b[+1]-b[-1] and s = b[-1]+2b[0]+b[+1] of the two previous blur rows, [ring][pair]
 #pragma unroll
   for (int a = 0; a < 2; ++a)

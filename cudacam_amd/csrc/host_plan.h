@@ -32,7 +32,7 @@ inline size_t frame_pitch(size_t row_bytes, size_t tight_row_bytes) { return (ti
 inline int plane_row_dwords(int W)
 {
   const size_t need = std::max<size_t>((size_t)(W + 31) / 32, ((size_t)((W + STRIP_W - 1) / STRIP_W) * 31 + 3) / 4);
-  return need > 256 ? 0 : need <= 64 ? 64 : need <= 128 ? 128 : 256;  // 64 * NW dwords, NW in {1, 2, 4}
+  return need > 256 ? 0 : need <= 64 ? 64 : need <= 128 ? 128 : 256;  // 1, 2 or 4 column panels of 64 dwords
 }
 // narrow frames take k_front8's HALF form when that needs fewer waves: an odd number of half-strips (pairs across frames)
 inline bool half_pays(int W) { return front8_half_strips(W) % 2 == 1 || (front8_half_strips(W) + 1) / 2 < front8_strips(W); }
@@ -550,7 +550,7 @@ inline HystPlan plan_hyst(int RD, int H, int n, bool small_tiles, const HystOpts
   // resident -- cost more than the launches they replace: 8 frames per run 0.147 against 0.117 ms per call; one frame per
   // call, the reference's pattern: 0.150 against 0.168 ms)
   p.loop = o.loop && !small_tiles && !lists && !o.late_grid && !o.diag && p.npanels == 1 && RD == 64 && p.wl_stride <= (size_t)HYST_LOOP_MAX_TILES
-           && ((p.tile_rows == 16 && p.waves == 8) || (p.tile_rows == 32 && p.waves == 2));
+           && hyst_shape_loops(p.tile_rows, p.waves);
   if (p.loop) p.mixed = false;
   for (int k = 0; k < K; ++k) {
     p.lists[k] = (uint8_t)(p.mixed ? (k < MIXED_FROM ? 0 : k == MIXED_FROM ? 2 : 1) : lists ? 1 : 0);

@@ -90,7 +90,7 @@ static void check(const Ctx &c, const FrontIn &in, const HystOpts &ho, bool full
       CHECK(run_flag_words(p.wl_stride) <= run_flag_words(c.wl_cap), "flag words within d_flags");
       CHECK(p.K >= 1 && p.K <= MAX_HYST_LAUNCHES && WL_COUNT_WORDS >= p.K + 3, "1 <= K <= MAX_HYST_LAUNCHES");
       CHECK(p.nrtiles * p.tile_rows * p.waves >= H && p.wl_stride == (size_t)n_out * p.nrtiles * p.npanels, "tiles cover the frame");
-      if (p.loop) CHECK(p.wl_stride <= (size_t)HYST_LOOP_MAX_TILES && !in.piped && p.npanels == 1 && ((p.tile_rows == 16 && p.waves == 8) || (p.tile_rows == 32 && p.waves == 2)), "loop form: small, whitelisted shape");
+      if (p.loop) CHECK(p.wl_stride <= (size_t)HYST_LOOP_MAX_TILES && !in.piped && p.npanels == 1 && hyst_shape_loops(p.tile_rows, p.waves), "loop form: small, whitelisted shape");
       for (int k = 0; k < p.K; ++k) {
         const int want = p.mixed ? (k < 2 ? 0 : k == 2 ? 2 : 1) : p.lists0;
         CHECK(p.lists[k] == want && (!p.loop || p.lists[k] == 0), "list modes 0..0, 2, 1..1");
@@ -149,7 +149,7 @@ static void sweep_geometry(int W, int H, bool full)
                 HystOpts ho;
                 for (int g : { -1, 1, 7 }) { ho = HystOpts{}; ho.late_grid = g; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho); }
                 ho = HystOpts{}; ho.loop = false; ho.diag = true; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho);
-                for (int g : { 3208, 3204, 3202, 1608, 3216, 3201, 1604, 1602 }) { ho = HystOpts{}; ho.geom = g; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho); }
+                for (const HystShape &g : HYST_SHAPES) { ho = HystOpts{}; ho.geom = g.tile_rows * 100 + g.waves; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho); }
                 for (int k : { 1, 6, 96 }) { ho = HystOpts{}; ho.launches = k; ho.launches_set = true; check(c, make_in(c, n, piped != 0, o, ins[0], out), ho); }
                 if (mode == HC_MODE_O) check(c, make_in(c, n, piped != 0, o, View{ 0x10000000u, 2 * tight + 2, (2 * tight + 2) * H }, out, true), ho0);
               }

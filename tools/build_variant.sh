@@ -8,7 +8,7 @@ cd "$(dirname "$0")/../cudacam_amd"
 mkdir -p exp/obj
 CC="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function"
 objs=()
-for f in canny_kernels.hip front8.hip front_mx.hip front_o_ext.hip hipcanny.hip; do
+for f in canny_kernels.hip hyst.hip front8.hip front_mx.hip front_o_ext.hip hipcanny.hip; do
   if [ "$f" = "$src" ]; then
     $CC "$@" -c "csrc/$f" -o "exp/obj/${f%.hip}_${name}.o"
     objs+=("exp/obj/${f%.hip}_${name}.o")
