@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "hc_device_ptrs", "hc_last_hysteresis_info", "hc_hysteresis_stats", "hc_set_tuning", "hc_set_option", "hc_selftest", "hc_last_error", "hc_version",
     "hc_host_alloc", "hc_host_free", "hc_profile_get_front", "hc_debug_tap", "hc_use_own_stream", "hc_profile_get_intervals", "hc_last_run_info", "hc_pipeline_depth", "hc_pipeline_slots_in_use", "hc_front_waves_per_workgroup",
     "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
+    "hc_derivatives_device",
 ]
 
 _lib = None
@@ -117,6 +118,7 @@ def load_library(legacy=False):
     L.hc_run_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i]
     L.hc_hysteresis_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i]
     L.hc_run_gradients_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, i]
+    L.hc_derivatives_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, sz, i, i]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -329,6 +331,55 @@ class Context:
         torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
         pitch = 2 * self.c * self.w
         self.run_gradients_device(tx.data_ptr(), ty.data_ptr(), pitch, pitch * self.h, out.data_ptr(), self.w, self.w * self.h, n)
+        self.sync()
+        return out.cpu().numpy()
+
+    def derivatives_device(self, d_in, in_pitch, in_fs, d_dx, d_dy, pitch, fs, nframes, ksize):
+        """The derivatives cv::Canny computes before its NMS (hc_derivatives_device): u8 frames on the device -> int16 dx / dy
+        planes with the same channel interleave; ksize 3, 5, 7 (scaled by 1/16, half to even) or -1 (Scharr).  Pitches and
+        frame strides in bytes.  Asynchronous on the context stream; not a run."""
+        _ck(self.lib.hc_derivatives_device(self.handle, C.c_void_p(d_in), in_pitch, in_fs, C.c_void_p(d_dx), C.c_void_p(d_dy),
+                                           pitch, fs, int(nframes), int(ksize)))
+
+    def _frames_u8(self, frames, who):
+        shape = (self.h, self.w) if self.c == 1 else (self.h, self.w, 3)
+        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        if a.ndim == len(shape):
+            a = a[None]
+        if a.shape[1:] != shape:
+            raise HipCannyError(f"{who}: frames {a.shape} do not match the context's {shape}")
+        return a
+
+    def derivatives(self, frames, ksize):
+        """numpy u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, (dx, dy) numpy int16 of the same shape out, through device
+        tensors (either mode)."""
+        import torch
+        a = self._frames_u8(frames, "derivatives")
+        n = a.shape[0]
+        dev = torch.device("cuda", self.device)
+        src = torch.from_numpy(a).to(dev)
+        dx, dy = torch.empty(a.shape, dtype=torch.int16, device=dev), torch.empty(a.shape, dtype=torch.int16, device=dev)
+        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
+        row = self.c * self.w
+        self.derivatives_device(src.data_ptr(), row, row * self.h, dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * self.h, n, ksize)
+        self.sync()
+        return dx.cpu().numpy(), dy.cpu().numpy()
+
+    def process_aperture(self, frames, ksize):
+        """cv::Canny(img, low, high, ksize, L2gradient) for any of its apertures (mode O): frames -> derivatives ->
+        run_gradients_device -> uint8 (n,H,W) edge maps, with no host round trip in between.  Uses the context's thresholds
+        as they are (at 7 they are in the units of the scaled derivatives: see hc_derivatives_device)."""
+        import torch
+        a = self._frames_u8(frames, "process_aperture")
+        n = a.shape[0]
+        dev = torch.device("cuda", self.device)
+        src = torch.from_numpy(a).to(dev)
+        dx, dy = torch.empty(a.shape, dtype=torch.int16, device=dev), torch.empty(a.shape, dtype=torch.int16, device=dev)
+        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream().synchronize()
+        row = self.c * self.w
+        self.derivatives_device(src.data_ptr(), row, row * self.h, dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * self.h, n, ksize)
+        self.run_gradients_device(dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * self.h, out.data_ptr(), self.w, self.w * self.h, n)
         self.sync()
         return out.cpu().numpy()
 

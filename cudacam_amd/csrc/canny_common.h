@@ -12,6 +12,7 @@ hipError_t launch_selftest(u32 *d_result, hipStream_t s);
 hipError_t check_gauss_coeffs(const float gk[25]);
 hipError_t launch_front_o(const FrontParams &p, hipStream_t s);
 hipError_t launch_front_o_ext(const FrontExtParams &p, hipStream_t s);  // front_o_ext.hip
+hipError_t launch_deriv16(const DerivParams &p, hipStream_t s);  // deriv.hip: Sobel 3 / 5 / 7 and Scharr derivatives, u8 -> int16 dx / dy
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

@@ -75,6 +75,27 @@ struct FrontExtParams {
   const uint8_t *dy;
 };
 
+// k_deriv16 (deriv.hip): the Sobel / Scharr derivatives cv::Canny computes before its NMS, u8 frames -> int16 dx / dy planes
+// with the input's channel interleave.  Strips and lanes as the 4-px front kernels (one halo lane = 4 columns each side; the
+// 7-tap filters need 3); a work item is (frame, strip, DERIV_CHUNK_ROWS output rows) with a warm-up of ksize - 1 rows.
+constexpr int DERIV_STRIP_W = 248;       // output columns per wave
+static_assert(DERIV_STRIP_W == STRIP_W, "k_deriv16 uses the lane layout of the 4-px front kernels");
+constexpr int DERIV_CHUNK_ROWS = 64;     // output rows per work item
+constexpr bool deriv_ksize_ok(int ksize) { return ksize == 3 || ksize == 5 || ksize == 7 || ksize == -1; }
+inline int deriv_strips(int W) { return (W + DERIV_STRIP_W - 1) / DERIV_STRIP_W; }
+inline int deriv_chunks(int H) { return (H + DERIV_CHUNK_ROWS - 1) / DERIV_CHUNK_ROWS; }
+struct DerivParams {
+  const uint8_t *in;       // u8 frames, `channels` interleaved; any alignment (in_aligned: base, pitch and frame stride are multiples of 4)
+  size_t in_pitch, in_frame_stride;
+  uint8_t *dx, *dy;        // int16 planes, even addresses; same pitch / frame stride (bytes, even)
+  size_t pitch, frame_stride;
+  int W, H, nframes, channels;
+  int ksize;               // 3, 5, 7 (scaled by 1/16, rounded half to even) or -1 (Scharr)
+  int in_aligned;          // the input rows may be read as dwords (whole 4-pixel groups inside the row only)
+  int out_align;           // 8, 4 or 2: what base, pitch and frame stride of BOTH outputs are multiples of
+  int nstrips, nchunks, total_items;
+};
+
 struct HystParams {
   u32 *sbits;
   const u32 *cbits;

@@ -889,7 +889,8 @@ int hc_set_option(hc_ctx *c, int option, int value)
     if (c->mode != HC_MODE_O) return fail(HC_E_ARG, "HC_OPT_APERTURE applies to mode O contexts");
     if (value == 7)
       return fail(HC_E_ARG, "HC_OPT_APERTURE 7 is not offered: cv::Canny scales the 7x7 Sobel and its thresholds to stay within "
-                            "int16, which this library does not restate; compute the derivatives and use hc_run_gradients_device");
+                            "int16, which HC_OPT_APERTURE does not restate; hc_derivatives_device computes those derivatives (ksize 7, and -1 for "
+                            "Scharr) for hc_run_gradients_device");
     if (value != 3 && value != 5) return fail(HC_E_ARG, "HC_OPT_APERTURE: 3 (default) or 5");
     c->opt.aperture = value;
   } else if (option == HC_OPT_DEBUG_TAPS) {
@@ -967,6 +968,38 @@ int hc_run_gradients_device(hc_ctx *c, const void *d_dx, const void *d_dy, size_
   HIPCK(hipSetDevice(c->device));
   return run_impl(c, (const uint8_t *)d_dx, pitch, frame_stride, (uint8_t *)d_out, out_pitch, out_frame_stride, n, HC_STAGE_HYSTER,
                   (const uint8_t *)d_dy);
+}
+
+// Not a run: one kernel on the context stream, in order with whatever is queued there (a following hc_run_gradients_device
+// reads the planes through its front kernel on the same stream).  Touches no slot, plan, timer or diagnostic of the runs.
+int hc_derivatives_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, void *d_dx, void *d_dy, size_t pitch, size_t fs, int n,
+                          int ksize)
+{
+  if (!c || !d_in || !d_dx || !d_dy) return fail(HC_E_ARG, "hc_derivatives_device: null argument");
+  if (!deriv_ksize_ok(ksize)) return fail(HC_E_ARG, "hc_derivatives_device: ksize 3, 5, 7 (scaled by 1/16, as in cv::Canny) or -1 (Scharr)");
+  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_derivatives_device: nframes out of range");
+  if ((((uintptr_t)d_dx | (uintptr_t)d_dy | pitch | fs) & 1u) != 0)
+    return fail(HC_E_ARG, "hc_derivatives_device: int16 planes need even addresses, pitch and frame stride");
+  if (in_pitch < (size_t)c->C * c->W) return fail(HC_E_ARG, "hc_derivatives_device: in_pitch smaller than a row");
+  if (pitch < (size_t)2 * c->C * c->W) return fail(HC_E_ARG, "hc_derivatives_device: pitch smaller than a row of int16");
+  if (n > 1 && (in_fs < in_pitch * (size_t)c->H || fs < pitch * (size_t)c->H))
+    return fail(HC_E_ARG, "hc_derivatives_device: frame stride smaller than a frame");
+  if ((u64)c->H * in_pitch >= (1ull << 32) || (u64)c->H * pitch >= (1ull << 32))
+    return fail(HC_E_ARG, "hc_derivatives_device: views of 4 GiB and more (height * pitch >= 2^32) are not supported by this entry");
+  DerivParams dp{};
+  dp.in = (const uint8_t *)d_in; dp.in_pitch = in_pitch; dp.in_frame_stride = in_fs;
+  dp.dx = (uint8_t *)d_dx; dp.dy = (uint8_t *)d_dy; dp.pitch = pitch; dp.frame_stride = fs;
+  dp.W = c->W; dp.H = c->H; dp.nframes = n; dp.channels = c->C; dp.ksize = ksize;
+  dp.in_aligned = (((uintptr_t)d_in | in_pitch | in_fs) & 3u) == 0;
+  const uintptr_t oa = (uintptr_t)d_dx | (uintptr_t)d_dy | pitch | fs;
+  dp.out_align = (oa & 7u) == 0 ? 8 : (oa & 3u) == 0 ? 4 : 2;
+  dp.nstrips = deriv_strips(c->W); dp.nchunks = deriv_chunks(c->H);
+  const long long items = (long long)n * dp.nstrips * dp.nchunks;
+  if (items > 0x7FFFFFF0ll) return fail(HC_E_ARG, "hc_derivatives_device: too many work items (nframes x strips x row chunks)");
+  dp.total_items = (int)items;
+  HIPCK(hipSetDevice(c->device));
+  HIPCK(launch_deriv16(dp, c->stream));
+  return HC_OK;
 }
 
 int hc_hysteresis_device(hc_ctx *c, const void *d_thresh, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n)

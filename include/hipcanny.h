@@ -106,6 +106,42 @@ int hc_run_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_fram
 int hc_run_gradients_device(hc_ctx *ctx, const void *d_dx, const void *d_dy, size_t pitch, size_t frame_stride, void *d_out,
                             size_t out_pitch, size_t out_frame_stride, int nframes);
 
+/* The derivatives cv::Canny(img, low, high, apertureSize, L2gradient) computes before its NMS, on their own (k_deriv16):
+ * `d_in` holds nframes u8 frames of width * channels bytes per row (1 or 3 interleaved channels, as the context's);
+ * `d_dx` / `d_dy` receive int16 planes with the same interleave (CV_16SC1 / CV_16SC3), both with `pitch` and `frame_stride`
+ * in BYTES: the layout hc_run_gradients_device reads.  Chained with that entry, every apertureSize of cv::Canny runs on
+ * the device: 3, 5, 7 and -1 (Scharr).  Contexts of either mode; width, height, channels and max_batch are the context's.
+ * Semantics: those of canny.cpp's Sobel(src, dx, CV_16S, 1, 0, ksize, scale, 0, BORDER_REPLICATE) and Sobel(src, dy, CV_16S,
+ * 0, 1, ...), restated (tests/deriv_ref.py) and, like all of Mode O, not pinned against a build of OpenCV.  Border indices
+ * are clamped, the filter is a correlation; dx = derivative taps along x and smoothing taps along y, dy the other way round:
+ *     ksize   smoothing taps         derivative taps        scale   range
+ *       3     [1 2 1]                [-1 0 1]               1       +-1020
+ *       5     [1 4 6 4 1]            [-1 -2 0 2 1]          1       +-12240
+ *       7     [1 6 15 20 15 6 1]     [-1 -4 -5 0 5 4 1]     1/16    +-10200
+ *      -1     [3 10 3]  (Scharr)     [-1 0 1]               1       +-4080
+ * ksize 7: cv::Canny passes scale = 1/16; OpenCV filters in float (every intermediate is a multiple of 1/16 below 2^19, so
+ * that path is exact) and converts with saturate_cast<short>(cvRound(v)).  The result is the exact integer sum S
+ * (|S| <= 163200) divided by 16 and rounded HALF TO EVEN: (S + 7 + ((S >> 4) & 1)) >> 4 with an arithmetic shift.  The
+ * unscaled 7x7 Sobel (cv::Sobel on its own) saturates int16 and is not offered.
+ * Thresholds at 7: cv::Canny(img, low, high, 7) also divides low and high by 16 before it floors them.  The context
+ * thresholds used with these derivatives are therefore in the SCALED units: a caller porting cv::Canny(img, low, high, 7)
+ * sets floor(low / 16), floor(high / 16).  That mapping is exact for the L1 magnitude; with L2gradient (squared thresholds)
+ * it is exact only for low / high that are multiples of 16.  The library does not rescale thresholds.
+ * Asynchronous on the context stream (hc_set_stream honoured), in order with everything else queued there: a following
+ * hc_run_gradients_device on the same context needs no synchronisation in between, in plain and in pipelined mode.  It is not
+ * a run: hc_last_run_info, the stage timers, the hysteresis schedule / history and the pipeline slots stay as they were, and
+ * runs in flight are neither finished nor waited for.
+ * Memory: no byte outside [row, row + channels * width) of an input row is read and none outside [row, row + 2 * channels *
+ * width) of an output row is written -- never the rest of a pitch or the gap between frames -- so both sides may be ROIs
+ * of larger images.  The input may have any alignment (rows that are not 4-byte aligned are read bytewise: slower, same
+ * result); the outputs need even addresses, pitch and frame stride (8-byte aligned ones get the widest stores).
+ * Rows are addressed with 32-bit offsets: a view with height * in_pitch >= 2^32 or height * pitch >= 2^32 is HC_E_ARG for
+ * this entry (nothing is staged).  HC_E_ARG also for: a null pointer; odd d_dx / d_dy / pitch / frame_stride; in_pitch <
+ * channels * width; pitch < 2 * channels * width; ksize not in {3, 5, 7, -1}; nframes outside 1..max_batch; nframes > 1
+ * with a frame stride smaller than height * pitch on either side. */
+int hc_derivatives_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, void *d_dx, void *d_dy,
+                          size_t pitch, size_t frame_stride, int nframes, int ksize);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
@@ -268,9 +304,9 @@ int hc_set_tuning(hc_ctx *ctx, int chunk_rows, int hyst_launches);
  * HC_OPT_APERTURE (default 3, Mode O contexts): cv::Canny's `apertureSize`.  5 = Sobel(src, CV_16S, ksize 5, scale 1,
  * BORDER_REPLICATE): |dx|, |dy| <= 12240, the L1 magnitude up to 24480; thresholds, the 3-channel select, the tangent test
  * and NMS as at 3.  Runs k_front_o_ext (front form 6; 1 or 3 channels; rows without whole 4-pixel groups are staged).
- * Any other value, and any mode R context, is HC_E_ARG; 7 is not offered (cv::Canny scales that Sobel and its thresholds
- * to stay within int16, which is not restated here): such callers compute the derivatives and use
- * hc_run_gradients_device.  Mode O thresholds stay clamped to 0..32767 at every aperture (L1 thresholds above 32767
+ * Any other value, and any mode R context, is HC_E_ARG; 7 and -1 (Scharr) are not offered as options (cv::Canny scales the
+ * 7x7 Sobel and its thresholds to stay within int16): such callers chain hc_derivatives_device (ksize 7 / -1, which states
+ * the scaling and what it means for the thresholds) with hc_run_gradients_device.  Mode O thresholds stay clamped to 0..32767 at every aperture (L1 thresholds above 32767
  * cannot be expressed).
  * Pipelined mode (HC_OPT_PIPELINE) gives exact maps on both k_front_o_ext forms (6 and 7); they write no provisional map,
  * so the hysteresis writes the whole output map of their runs. */
