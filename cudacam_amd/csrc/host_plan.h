@@ -372,9 +372,11 @@ inline FrontPlan plan_front(const FrontIn &in)
       fp.a_hi[0] = (u32)o.high * (u32)o.high;
     }
     if (!f8) {  // k_front_o, and k_front_o_ext with its strips and work split (a 6-row warm-up for aperture 5, 2 rows for gradients); k_front8o: strips and runs as set for k_front8 above
+      // rows per work item: hc_set_tuning's number (any value >= 1: these kernels have no window to fill, unlike the 8-px
+      // forms, whose runs are 2 rows at least), or about 12288 items per launch in chunks of 16 rows or more
       const long units = (long)n_out * in.nstrips;
       const int per_strip = (int)std::max<long>(1, std::min<long>((12288 + units - 1) / units, (H + 15) / 16));
-      fp.chunk_rows = (H + per_strip - 1) / per_strip;
+      fp.chunk_rows = o.chunk ? std::min(std::max(o.chunk, 1), H) : (H + per_strip - 1) / per_strip;
       fp.nchunks = (H + fp.chunk_rows - 1) / fp.chunk_rows;
       fp.total_items = n_out * fp.nstrips * fp.nchunks;
       if (!ext && sp < round_up((size_t)W, 4) * (size_t)C) { P.error = "mode O needs an input pitch of at least round_up(width, 4) * channels"; return P; }

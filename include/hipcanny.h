@@ -262,7 +262,9 @@ int hc_front_waves_per_workgroup(hc_ctx *ctx);
  * (sweeps summed over tiles, max sweeps of a tile, tiles that did work). */
 int hc_hysteresis_stats(hc_ctx *ctx, unsigned *stats, int nwords);
 
-/* Tuning knobs: rows per front-path work item (0 = auto); hysteresis launches queued per run (0 = auto:
+/* Tuning knobs: rows per front-path work item (0 = auto; k_front8 / k_front8o round it up to whole 6-row windows, 2 rows at
+ * least; the 4-px Mode O kernels -- k_front_o, and k_front_o_ext for aperture 5 and given gradients -- take any number of
+ * rows from 1 to the frame height as it is; larger values mean one item per strip); hysteresis launches queued per run (0 = auto:
  * 6, or one more than the row tiles + column panels of a frame, or what the last runs needed + 4, at most 96; launches
  * after convergence exit at once, and
  * hc_sync continues from the host in the rare case the queue was too short -- non-monotone, serpentine edges). */

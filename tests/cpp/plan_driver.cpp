@@ -61,6 +61,9 @@ static void check(const Ctx &c, const FrontIn &in, const HystOpts &ho, bool full
   const long per = in.per_channel ? 3 : 1;
   const int rows = (P.form == -1 || P.form == 6 || P.form == 7) ? f.chunk_rows : f.run_rows;
   CHECK(rows >= 1 && (long)f.nchunks * rows >= H, "nchunks * run_rows >= H");
+  // the 4-px Mode O forms take hc_set_tuning's rows per work item as they are (any value >= 1, at most the frame)
+  if ((P.form == -1 || P.form == 6 || P.form == 7) && in.o.chunk)
+    CHECK(f.chunk_rows == std::min(std::max(in.o.chunk, 1), H) && f.nchunks == (H + f.chunk_rows - 1) / f.chunk_rows, "4-px Mode O forms: chunk_rows = min(max(chunk, 1), H)");
   long units = (long)n_out * f.nstrips;
   if (P.form == 4) units = (((long)in.n * front8_half_strips(W) + 1) / 2) * per;
   if (P.form == 5) CHECK(f.nstrips == front_mx_strips(W), "mx strips");
@@ -135,6 +138,8 @@ static void sweep_geometry(int W, int H, bool full)
               o = FrontOpts{}; o.split = 1; opts.push_back(o);
               o.split = 0; opts.push_back(o);
               if (mode == HC_MODE_O) { o = FrontOpts{}; o.aperture = 5; opts.push_back(o); o.l2gradient = 1; opts.push_back(o); o.aperture = 3; opts.push_back(o); }
+              if (mode == HC_MODE_O)  // work items of 1, 7 and 17 rows: k_front_o (split 0 / 3 channels), k_front_o_ext (aperture 5; gradients below)
+                for (int v : { 1, 7, 17 }) { o = FrontOpts{}; o.chunk = v; o.split = 0; opts.push_back(o); o.aperture = 5; opts.push_back(o); }
             }
             for (const FrontOpts &o : opts) {
               const Ctx c = make_ctx(mode, C, W, H, pc, max_batch, o.half_mode == 1);
@@ -168,6 +173,16 @@ static void expect(const char *what, const Ctx &c, int n, bool piped, const Fron
     std::printf("FAIL pinned %s: got (%d, %d, %d)%s\n", what, (int)P.in_staged, (int)P.out_staged, P.form, P.error ? P.error : "");
   }
 }
+// the work split of the 4-px Mode O forms: (form, rows per work item, items per strip, items)
+static void expect_cut(const char *what, const Ctx &c, int n, const FrontOpts &o, bool grads, int form, int chunk_rows, int nchunks, int total_items)
+{
+  const View in = grads ? View{ 0x10000000u, (size_t)2 * c.C * c.W, (size_t)2 * c.C * c.W * c.H } : c.own_in;
+  const FrontPlan P = plan_front(make_in(c, n, false, o, in, c.own_out, grads));
+  if (P.error || P.form != form || P.fp.chunk_rows != chunk_rows || P.fp.nchunks != nchunks || P.fp.total_items != total_items) {
+    ++g_fail;
+    std::printf("FAIL pinned cut %s: got form %d, %d rows x %d, %d items%s\n", what, P.form, P.fp.chunk_rows, P.fp.nchunks, P.fp.total_items, P.error ? P.error : "");
+  }
+}
 static void pinned()
 {
   FrontOpts d, o;
@@ -199,6 +214,28 @@ static void pinned()
       if (ap5) expect("aperture 5", c, 2, false, o, c.own_in, c.own_out, -1, -1, 6);
       expect("gradients", c, 2, true, o, View{ 0x10000000u, (size_t)2 * C * 322 + 4, ((size_t)2 * C * 322 + 4) * 97 }, tout(c), 0, -1, 7, true);
     }
+  {  // the automatic work split of the 4-px Mode O forms (hc_set_tuning 0): ceil(12288 / (frames x strips)) items per strip, of 16 rows or more
+    FrontOpts a5 = d; a5.aperture = 5;
+    const Ctx one = make_ctx(HC_MODE_O, 3, 322, 97, 0, 1, false);  // one frame, two strips: 7 items of 14 rows per strip
+    expect_cut("one frame", one, 1, d, false, -1, 14, 7, 14);
+    expect_cut("one frame, aperture 5", one, 1, a5, false, 6, 14, 7, 14);
+    expect_cut("one frame, gradients", one, 1, d, true, 7, 14, 7, 14);
+    const Ctx hd = make_ctx(HC_MODE_O, 1, 1920, 1080, 0, 1024, false);  // 1024 frames of 1080p: 8192 strips, two items of 540 rows each
+    expect_cut("1080p x 1024, aperture 5", hd, 1024, a5, false, 6, 540, 2, 16384);
+    // test_gpu_mode_o_chunks.py: one strip, 6144 frames -> two items per strip, 12288 -> one spans the frame
+    const Ctx s3 = make_ctx(HC_MODE_O, 3, 64, 26, 0, 12288, false), s1 = make_ctx(HC_MODE_O, 1, 64, 26, 0, 12288, false);
+    expect_cut("two per strip", s3, 6144, d, false, -1, 13, 2, 12288);
+    expect_cut("one per strip", s3, 12288, d, false, -1, 26, 1, 12288);
+    expect_cut("two per strip, aperture 5", s1, 6144, a5, false, 6, 13, 2, 12288);
+    expect_cut("one per strip, aperture 5", s1, 12288, a5, false, 6, 26, 1, 12288);
+    expect_cut("two per strip, gradients", s1, 6144, d, true, 7, 13, 2, 12288);
+    expect_cut("one per strip, gradients", s1, 12288, d, true, 7, 26, 1, 12288);
+    for (int chunk : { 1, 7, 17, 300 }) {  // ... and a set length, as it is
+      FrontOpts t = a5; t.chunk = chunk;
+      const int rows = std::min(chunk, 97), items = (97 + rows - 1) / rows;
+      expect_cut("set length", one, 1, t, false, 6, rows, items, 2 * items);
+    }
+  }
   for (int mx = 0; mx <= 1; ++mx) {  // test_gpu_views: a 4 GiB-reaching view of a wide parent, w x h = 64 x 1024 rows of a 4 MiB pitch
     const int w = 64, h = 1024;
     const size_t pitch = (size_t)4 << 20;

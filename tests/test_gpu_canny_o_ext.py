@@ -268,7 +268,8 @@ def test_errors():
 
 
 def test_fuzz():
-    """~300 seeded cases: sizes up to 700 x 300, 1 / 3 channels, L1 / L2, thresholds, aperture 5 and the gradient entry."""
+    """~300 seeded cases: sizes up to 700 x 300, 1 / 3 channels, L1 / L2, thresholds, aperture 5 and the gradient entry, rows
+    per work item (hc_set_tuning) from 1 to more than the frame."""
     rng = np.random.default_rng(20261016)
     bad = []
     for case in range(300):
@@ -283,6 +284,9 @@ def test_fuzz():
         mk = (lambda s: synth.natural(w, h, s)) if kind == 0 else (lambda s: synth.noise(w, h, s)) if kind == 1 else (
             lambda s: synth.serpentine(max(w, 1), max(h, 1), amp=20, seed_amp=200) if w > 40 and h > 40 else synth.natural(w, h, s))
         img = mk(seed) if ch == 1 else np.stack([mk(seed), mk(seed + 1), mk(seed + 2)], -1)
+        # rows per work item: from a second generator seeded from the case seed (the main stream, and with it the sizes and
+        # contents of the cases, stays as it was)
+        chunk = int(np.random.default_rng([seed, 0xC4A2]).choice([0, 0, 1, 2, 3, 5, 7, 8, 13, 17, 50, 300]))
         if grad:
             if rng.integers(0, 2):
                 dx, dy = _rand_grad((1, h, w) if ch == 1 else (1, h, w, 3), seed)
@@ -292,12 +296,14 @@ def test_fuzz():
             low, high = (int(v) for v in rng.integers(0, 32768, size=2))
             want = X.canny_o_from_gradients(dx[0], dy[0], low, high, l2)[None]
             with _ctx(w, h, ch, 1, aperture=3, l2=l2, low=low, high=high) as ctx:
+                ctx.set_tuning(chunk, 0)
                 got = _run_grad(ctx, dx, dy, int(rng.integers(0, 3)))
         else:
             low, high = (int(v) for v in rng.integers(0, 3000, size=2))
             want = _want5([img], low, high, l2)
             with _ctx(w, h, ch, 1, l2=l2, low=low, high=high) as ctx:
+                ctx.set_tuning(chunk, 0)
                 got = ctx.process(img) if rng.integers(0, 2) else _run_device5(ctx, img[None], int(rng.integers(0, 5)))
         if not np.array_equal(got, want):
-            bad.append((case, w, h, ch, l2, grad, int((got != want).sum())))
+            bad.append((case, w, h, ch, l2, grad, chunk, int((got != want).sum())))
     assert not bad, f"{len(bad)} of 300 cases differ: {bad[:10]}"

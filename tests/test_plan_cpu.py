@@ -6,6 +6,8 @@ slot rule calls big), and the whole option product where width and height are bo
 480, 1079, 1080, 2160, 4320.  Every plan must keep what the launchers and kernels rest on:
 
 * nchunks * run_rows >= H; total_items = units x chunks > 0 for each form; rows of the 8-px forms hold whole groups;
+* the 4-px Mode O forms (-1, 6, 7) take hc_set_tuning's rows per work item as they are, chunk_rows = min(max(chunk, 1), H)
+  (1, 7, 17 among the swept values); their automatic split pinned for one frame and for one and two items per strip;
 * a HALF plan satisfies the `fits` inequalities; a plan with the provisional map never has H * pitch >= 2^32;
 * wl_stride <= wl_cap; zeroed_words and FLAG_WORDS + WL_COUNT_WORDS + 2 * wl_stride within the d_flags allocation;
 * 1 <= K <= MAX_HYST_LAUNCHES; the loop form only for <= HYST_LOOP_MAX_TILES tiles of the two whitelisted shapes;
