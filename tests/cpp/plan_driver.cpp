@@ -183,6 +183,94 @@ static void expect_cut(const char *what, const Ctx &c, int n, const FrontOpts &o
     std::printf("FAIL pinned cut %s: got form %d, %d rows x %d, %d items%s\n", what, P.form, P.fp.chunk_rows, P.fp.nchunks, P.fp.total_items, P.error ? P.error : "");
   }
 }
+// the work split of the 8-px forms on the contexts' internal buffers (hc_run): (form, rows per run, runs per strip, items)
+static void expect_runs(const char *what, const Ctx &c, int n, const FrontOpts &o, int form, int run_rows, int nchunks, int total_items)
+{
+  const FrontPlan P = plan_front(make_in(c, n, false, o, c.own_in, c.own_out));
+  if (P.error || P.form != form || P.in_staged || P.out_staged || P.fp.run_rows != run_rows || P.fp.nchunks != nchunks || P.fp.total_items != total_items) {
+    ++g_fail;
+    std::printf("FAIL pinned runs %s (%d x %d, set length %d): got form %d, %d rows x %d, %d items%s\n", what, c.W, c.H, o.chunk, P.form, P.fp.run_rows, P.fp.nchunks, P.fp.total_items, P.error ? P.error : "");
+  }
+}
+// ... and of its pipelined leg: tight device buffers (hc_run_device), nothing staged, and the front kernel writes the provisional map
+static void expect_prov(const char *what, const Ctx &c, int n, const FrontOpts &o, int form, int run_rows, int nchunks, int total_items)
+{
+  const View in{ 0x10000000u, (size_t)c.W * c.C, (size_t)c.W * c.C * c.H }, out{ 0x20000000u, (size_t)c.W, (size_t)c.W * c.H };
+  const FrontPlan P = plan_front(make_in(c, n, true, o, in, out));
+  if (P.error || P.form != form || P.in_staged || P.out_staged || !P.prov || P.fp.prov_pitch != (u32)c.W || P.fp.prov_fs != (size_t)c.W * c.H
+      || P.fp.run_rows != run_rows || P.fp.nchunks != nchunks || P.fp.total_items != total_items) {
+    ++g_fail;
+    std::printf("FAIL pinned pipelined %s (%d x %d, set length %d): got form %d, prov %d, staged %d %d, %d rows x %d, %d items%s\n", what, c.W, c.H, o.chunk, P.form, (int)P.prov,
+                (int)P.in_staged, (int)P.out_staged, P.fp.run_rows, P.fp.nchunks, P.fp.total_items, P.error ? P.error : "");
+  }
+}
+// tests/test_gpu_front8_runs.py (tests/front8_runs_inputs.py): batches of three frames, hc_set_tuning's length -> the runs
+static void pinned_front8_runs()
+{
+  FrontOpts f8; f8.half_mode = 0;
+  FrontOpts half; half.half_mode = 1;
+  FrontOpts mx; mx.half_mode = 0; mx.mx_mode = 1;
+  const FrontOpts fo;  // Mode O: k_front8o by default
+  FrontOpts l2o; l2o.l2gradient = 1;
+  auto with = [](FrontOpts o, int chunk, int dense = -1) { o.chunk = chunk; o.dense_mode = dense; return o; };
+  {  // leg B: 41 rows, every distinct run length 6 k - 4, the frame, beyond it; 504 columns: two strips, six units
+    const Ctx c = make_ctx(HC_MODE_R, 1, 504, 41, 0, 3, false), co = make_ctx(HC_MODE_O, 1, 504, 41, 0, 3, false);
+    const int cut[][3] = { { 2, 2, 21 }, { 8, 8, 6 }, { 14, 14, 3 }, { 20, 20, 3 }, { 26, 26, 2 }, { 32, 32, 2 }, { 38, 38, 2 }, { 41, 44, 1 }, { 100, 44, 1 } };
+    for (const auto &k : cut) {
+      expect_runs("k_front8 mono", c, 3, with(f8, k[0]), 2, k[1], k[2], 6 * k[2]);
+      expect_runs("k_front8o", co, 3, with(fo, k[0]), 3, k[1], k[2], 6 * k[2]);
+    }
+    FrontOpts l2 = with(fo, 26); l2.l2gradient = 1;
+    expect_runs("k_front8o L2, a second strip of one column", make_ctx(HC_MODE_O, 1, 497, 41, 0, 3, false), 3, l2, 3, 26, 2, 12);
+    expect_runs("k_front8, one strip", make_ctx(HC_MODE_R, 1, 496, 41, 0, 3, false), 3, with(f8, 14), 2, 14, 3, 9);
+  }
+  {  // leg A: the last run of every length comes from heights 1 .. 22 under runs of 2, 8 and 14 rows
+    const int cut[][4] = { { 1, 2, 2, 1 }, { 1, 8, 2, 1 }, { 3, 2, 2, 2 }, { 3, 14, 8, 1 }, { 4, 8, 8, 1 }, { 5, 8, 8, 1 }, { 7, 2, 2, 4 }, { 8, 14, 8, 1 },
+                           { 9, 8, 8, 2 }, { 9, 14, 14, 1 }, { 15, 14, 14, 2 }, { 16, 8, 8, 2 }, { 17, 8, 8, 3 }, { 21, 2, 2, 11 }, { 21, 14, 14, 2 }, { 22, 14, 14, 2 }, { 22, 2, 2, 11 },
+                           { 8, 0, 8, 1 }, { 21, 0, 14, 2 }, { 22, 0, 14, 2 } };  // (0: the automatic split of a small batch)
+    for (const auto &k : cut) {
+      expect_runs("k_front8 heights", make_ctx(HC_MODE_R, 1, 504, k[0], 0, 3, false), 3, with(f8, k[1]), 2, k[2], k[3], 6 * k[3]);
+      expect_runs("k_front8o heights", make_ctx(HC_MODE_O, 1, 504, k[0], 0, 3, false), 3, with(fo, k[1]), 3, k[2], k[3], 6 * k[3]);
+    }
+    expect_runs("tiny", make_ctx(HC_MODE_R, 1, 5, 7, 0, 3, false), 3, with(f8, 2), 2, 2, 4, 12);
+    expect_runs("tiny, half", make_ctx(HC_MODE_R, 1, 5, 7, 0, 3, true), 3, with(half, 2), 4, 2, 4, 8);
+  }
+  // each form once: dense forced, BGR -> grey, per-channel (nine output frames)
+  expect_runs("k_front8 dense", make_ctx(HC_MODE_R, 1, 504, 21, 0, 3, false), 3, with(f8, 8, 1), 2, 8, 3, 18);
+  expect_runs("k_front8 BGR", make_ctx(HC_MODE_R, 3, 504, 21, 0, 3, false), 3, with(f8, 14), 2, 14, 2, 12);
+  expect_runs("k_front8 per-channel", make_ctx(HC_MODE_R, 3, 504, 21, 1, 3, false), 3, with(f8, 2), 2, 2, 11, 198);
+  // the half-strip form: 488 columns are three half-strips, nine units, five pairs; 241 columns two, three pairs; 240 one, two pairs
+  expect_runs("half mono", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 8), 4, 8, 6, 30);
+  expect_runs("half mono dense", make_ctx(HC_MODE_R, 1, 488, 21, 0, 3, true), 3, with(half, 14, 1), 4, 14, 2, 10);
+  expect_runs("half BGR", make_ctx(HC_MODE_R, 3, 241, 41, 0, 3, true), 3, with(half, 20), 4, 20, 3, 9);
+  expect_runs("half per-channel", make_ctx(HC_MODE_R, 3, 488, 41, 1, 3, true), 3, with(half, 2), 4, 2, 21, 315);
+  expect_runs("half, one half-strip", make_ctx(HC_MODE_R, 1, 240, 41, 0, 3, true), 3, with(half, 38), 4, 38, 2, 4);
+  {  // k_front_mx: ceil(H / c) runs of ceil(H / runs) rows; 224 columns: two strips, six units.  Both sides of the block
+     // borders front_mx_run_rows(1) = 12 and (2) = 28, a last run of 1 and of 16 rows, runs of one row, the frame
+    if (front_mx_run_rows(1) != 12 || front_mx_run_rows(2) != 28) { ++g_fail; std::printf("FAIL front_mx_run_rows\n"); }
+    const int cut[][4] = { { 24, 12, 12, 2 }, { 25, 13, 13, 2 }, { 26, 13, 13, 2 }, { 36, 12, 12, 3 }, { 39, 13, 13, 3 }, { 56, 28, 28, 2 }, { 57, 29, 29, 2 }, { 58, 29, 29, 2 },
+                           { 84, 28, 28, 3 }, { 87, 29, 29, 3 }, { 3, 2, 2, 2 }, { 33, 17, 17, 2 }, { 21, 8, 7, 3 }, { 21, 14, 11, 2 }, { 41, 1, 1, 41 }, { 41, 6, 6, 7 }, { 41, 14, 14, 3 },
+                           { 41, 21, 21, 2 }, { 41, 41, 41, 1 }, { 41, 100, 41, 1 } };
+    for (const auto &k : cut) expect_runs("k_front_mx", make_ctx(HC_MODE_R, 1, 224, k[0], 0, 3, false), 3, with(mx, k[1]), 5, k[2], k[3], 6 * k[3]);
+    expect_runs("k_front_mx, a second strip of one column", make_ctx(HC_MODE_R, 1, 217, 41, 0, 3, false), 3, with(mx, 9), 5, 9, 5, 30);
+    expect_runs("k_front_mx, one strip", make_ctx(HC_MODE_R, 1, 216, 41, 0, 3, false), 3, with(mx, 11), 5, 11, 4, 12);
+  }
+  // the pipelined leg: 41 rows at the provisional-map width of each kernel; every form keeps its provisional map (the
+  // half-strip form: the `fits` terms with the map, per-channel with three maps per frame)
+  expect_prov("k_front8 mono", make_ctx(HC_MODE_R, 1, 504, 41, 0, 3, false), 3, with(f8, 8), 2, 8, 6, 36);
+  expect_prov("k_front8 dense", make_ctx(HC_MODE_R, 1, 504, 41, 0, 3, false), 3, with(f8, 2, 1), 2, 2, 21, 126);
+  expect_prov("k_front8 BGR", make_ctx(HC_MODE_R, 3, 504, 41, 0, 3, false), 3, with(f8, 14), 2, 14, 3, 18);
+  expect_prov("k_front8 per-channel", make_ctx(HC_MODE_R, 3, 504, 41, 1, 3, false), 3, with(f8, 100), 2, 44, 1, 18);
+  expect_prov("half mono", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 2), 4, 2, 21, 105);
+  expect_prov("half mono dense", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 20, 1), 4, 20, 3, 15);
+  expect_prov("half BGR", make_ctx(HC_MODE_R, 3, 488, 41, 0, 3, true), 3, with(half, 41), 4, 44, 1, 5);
+  expect_prov("half per-channel", make_ctx(HC_MODE_R, 3, 488, 41, 1, 3, true), 3, with(half, 8), 4, 8, 6, 90);
+  expect_prov("k_front8o", make_ctx(HC_MODE_O, 1, 504, 41, 0, 3, false), 3, with(fo, 26), 3, 26, 2, 12);
+  expect_prov("k_front8o L2", make_ctx(HC_MODE_O, 1, 504, 41, 0, 3, false), 3, with(l2o, 38), 3, 38, 2, 12);
+  expect_prov("k_front_mx", make_ctx(HC_MODE_R, 1, 224, 41, 0, 3, false), 3, with(mx, 6), 5, 6, 7, 42);
+  expect_prov("k_front_mx, runs of one row", make_ctx(HC_MODE_R, 1, 224, 41, 0, 3, false), 3, with(mx, 1), 5, 1, 41, 246);
+}
+
 static void pinned()
 {
   FrontOpts d, o;
@@ -342,6 +430,7 @@ int main()
   for (int W : special)
     for (int H : special) sweep_geometry(W, H, true);
   pinned();
+  pinned_front8_runs();
   chain_watch();
   if (plane_row_dwords(8184) != 256 || plane_row_dwords(8185) != 0) { ++g_fail; std::printf("FAIL width limit\n"); }
   if (g_fail) { std::printf("%ld violations in %ld plans\n", g_fail, g_plans); return 1; }

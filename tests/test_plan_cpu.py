@@ -8,6 +8,9 @@ slot rule calls big), and the whole option product where width and height are bo
 * nchunks * run_rows >= H; total_items = units x chunks > 0 for each form; rows of the 8-px forms hold whole groups;
 * the 4-px Mode O forms (-1, 6, 7) take hc_set_tuning's rows per work item as they are, chunk_rows = min(max(chunk, 1), H)
   (1, 7, 17 among the swept values); their automatic split pinned for one frame and for one and two items per strip;
+* the runs hc_set_tuning's length gives the 8-px forms (2, 4, 3, 5) on the shapes of tests/test_gpu_front8_runs.py: rows per
+  run, runs per strip and items pinned for every run length 6 k - 4 of 41 rows, the heights that give each last-run length,
+  each form once, and both sides of k_front_mx's block borders (12 | 13, 28 | 29);
 * a HALF plan satisfies the `fits` inequalities; a plan with the provisional map never has H * pitch >= 2^32;
 * wl_stride <= wl_cap; zeroed_words and FLAG_WORDS + WL_COUNT_WORDS + 2 * wl_stride within the d_flags allocation;
 * 1 <= K <= MAX_HYST_LAUNCHES; the loop form only for <= HYST_LOOP_MAX_TILES tiles of the two whitelisted shapes;
