@@ -31,17 +31,18 @@ struct FrontParams {
   int RD;                  // dwords per bit-plane row
   int W, H;
   int nstrips, nchunks, nframes;
-  int subchunks;   // Mode R kernel: sub-chunks of 24 blur rows a wave marches through per work item
-  int run_rows;    // = 24 * subchunks - 4 output rows per work item; nchunks = ceil(H / run_rows)
+  int subchunks;   // k_front (legacy_front.hip) only: sub-chunks of 24 blur rows a wave marches through per work item
+  int run_rows;    // the run-based kernels (k_front8 / k_front8o, k_front_mx, k_front, k_blur): output rows per work item; nchunks = ceil(H / run_rows).  k_front: = 24 * subchunks - 4
   int chunk_rows;          // Mode O kernel: output rows per work item (any value >= 1)
   int l2gradient;          // Mode O kernel: magnitude dx^2 + dy^2 instead of |dx| + |dy| (cv::Canny's L2gradient)
   int total_items;         // nframes * nstrips * nchunks
   // thresholds on S = sumX^2 + sumY^2 for "u8-wrapped gradient > T" (band test)
   u32 a_lo[3], a_hi[3];
-  // split mode (k_blur + k_nms, legacy_front.hip): the u8 blur plane between the two kernels and k_nms's own work split
-  uint8_t *blur;             // [frame][strip][H][256]: one aligned 256-byte row per wave-row (bytes 4..251 = the strip's columns)
+  // split mode (k_blur + k_nms, legacy_front.hip): the u8 blur plane between the two kernels -- k_blur writes it by
+  // nchunks / run_rows / total_items, k_nms reads it by its own work split
+  uint8_t *blur;             // k_blur, k_nms: [frame][strip][H][256]: one aligned 256-byte row per wave-row (bytes 4..251 = the strip's columns)
   size_t blur_frame_stride;  // >= nstrips * H * 256
-  int nchunks_b, run_rows_b, total_items_b;
+  int nchunks_b, run_rows_b, total_items_b;  // k_nms only
   // k_nms: when set, the strong pixels are also written as 255 (others 0) into this u8 map -- the provisional edge
   // map the hysteresis then only patches (W % 4 == 0: a lane stores its 4 pixels as one dword)
   uint8_t *prov_out; u32 prov_pitch; size_t prov_fs;

@@ -191,7 +191,7 @@ struct hc_ctx {
   } dbg;
   struct {  // diagnostics of the last run(s); decide nothing
     int front_waves = 4;  // waves per workgroup of the most recent k_front8 launch
-    int in_staged = 0, out_staged = 0, front_form = -1;  // what the last run did with the caller's buffers / which front kernels it used
+    int in_staged = 0, out_staged = 0, front_form = HC_FORM_FRONT_O;  // what the last run did with the caller's buffers / which front kernels it used
     int continued = 0;
     int sched[HC_SCHED_WORDS] = { 0 };  // hc_last_hysteresis_schedule: the schedule of the last completed run
     u32 stats[3 * MAX_HYST_LAUNCHES] = { 0 };
@@ -470,6 +470,18 @@ int queue_hyst_expand(hc_ctx *c, Slot &s, hipStream_t st, uint8_t *out, size_t o
   return HC_OK;
 }
 
+// n maps of the internal output buffer to the host: tight rows on both sides are one contiguous block, one DMA; otherwise
+// a 2-D copy per frame
+int copy_out_d2h(hc_ctx *c, uint8_t *host, size_t row_stride, size_t frame_stride, int n, hipStream_t st)
+{
+  if (row_stride == (size_t)c->W && c->out_pitch == (size_t)c->W && frame_stride == c->out_fs)
+    HIPCK(hipMemcpyAsync(host, c->d_out, c->out_fs * (size_t)n, hipMemcpyDeviceToHost, st));
+  else
+    for (int f = 0; f < n; ++f)
+      HIPCK(hipMemcpy2DAsync(host + frame_stride * f, row_stride, c->d_out + c->out_fs * f, c->out_pitch, (size_t)c->W, (size_t)c->H, hipMemcpyDeviceToHost, st));
+  return HC_OK;
+}
+
 // Pipelined runs: the slot of this run, after the run that used it nslot_use steps ago; a ring of another size is drained
 // first.  Plain runs: slot 0, with nothing else in flight.
 int rotate_slots(hc_ctx *c, bool piped, int n_out, Slot **slot)
@@ -505,6 +517,66 @@ int finish_overlapping(hc_ctx *c, uintptr_t o0, uintptr_t o1, bool *with_previou
     if (k == c->nslot_use - 1) *with_previous = true;
     if (int rc = finish_slot(c, o)) return rc;
   }
+  return HC_OK;
+}
+
+// The front kernel of the planned form on stream sf.  fp: P.fp with the device pointers patched in.
+int launch_front_form(hc_ctx *c, const FrontPlan &P, FrontParams &fp, const uint8_t *in_dy, hipStream_t sf)
+{
+  switch (P.form) {
+  case HC_FORM_O_APERTURE5: case HC_FORM_O_GRADIENTS: {
+    FrontExtParams ep{};
+    ep.f = fp;
+    ep.gradients = in_dy ? 1 : 0;
+    ep.channels = c->C;
+    ep.dy = in_dy;
+    HIPCK(launch_front_o_ext(ep, sf));
+    break;
+  }
+  case HC_FORM_FRONT8O: HIPCK(launch_front8o(fp, sf)); break;
+  case HC_FORM_FRONT_O: HIPCK(launch_front_o(fp, sf)); break;
+  case HC_FORM_FRONT_MX: HIPCK(launch_front_mx(fp, sf)); break;
+  case HC_FORM_FRONT8: case HC_FORM_FRONT8_HALF: HIPCK(launch_front8(fp, sf)); break;
+#ifdef HC_LEGACY_FRONT
+  case HC_FORM_SPLIT:  // k_blur + k_nms through the blur plane
+    if (int rc = ensure_blur_plane(c)) return rc;
+    fp.blur = c->d_bplane; fp.blur_frame_stride = c->bplane_fs;
+    HIPCK(launch_blur(fp, sf));
+    HIPCK(c->prof.mark(sf, P.mask_a, ProfRing::K_FRONT_A));
+    HIPCK(launch_nms(fp, sf));
+    break;
+  case HC_FORM_FRONT4: HIPCK(launch_front(fp, sf)); break;
+#endif
+  default: return fail(HC_E_ARG, "internal: front kernel form");
+  }
+  return HC_OK;
+}
+
+// Final stages GAUSSIAN .. THRESH: the plain per-stage kernels up to `stage`, the last of them into dst, the others into
+// the stage scratch planes.  mono: the one-channel frames (pitch mp, frame stride mfs)
+int queue_stage_taps(hc_ctx *c, int stage, const uint8_t *mono, size_t mp, size_t mfs, uint8_t *dst, size_t dp, size_t dfs, int n, hipStream_t sf)
+{
+  const int W = c->W, H = c->H;
+  ProfRing &prof = c->prof;
+  if (int rc = ensure_stage_scratch(c)) return rc;
+  const size_t bp = c->out_pitch, bfs = c->out_fs;  // scratch planes share the output geometry
+  uint8_t *blur = stage == HC_STAGE_GAUSSIAN ? dst : c->d_blur;
+  const size_t blp = stage == HC_STAGE_GAUSSIAN ? dp : bp, blfs = stage == HC_STAGE_GAUSSIAN ? dfs : bfs;
+  // every plain kernel is booked on its own stage, as the reference's _endCudaTimer(stage) does (cannyEdgeH.cu:415-430)
+  HIPCK(launch_gauss(mono, mp, mfs, blur, blp, blfs, W, H, n, sf));
+  HIPCK(prof.mark(sf, B_GAUSS, ProfRing::K_FRONT_B));
+  if (stage == HC_STAGE_GAUSSIAN) return HC_OK;
+  HIPCK(launch_sobel(blur, blp, blfs, c->d_sx, c->d_sy, bp, bfs, W, H, n, sf));
+  if (stage == HC_STAGE_GRADIENT) HIPCK(launch_graddisp(c->d_sx, c->d_sy, bp, bfs, dst, dp, dfs, W, H, n, sf));
+  HIPCK(prof.mark(sf, B_GRAD, ProfRing::K_FRONT_B));
+  if (stage == HC_STAGE_GRADIENT) return HC_OK;
+  uint8_t *nms = stage == HC_STAGE_NMS ? dst : c->d_nms;
+  const size_t np = stage == HC_STAGE_NMS ? dp : bp, nfs = stage == HC_STAGE_NMS ? dfs : bfs;
+  HIPCK(launch_nms(c->d_sx, c->d_sy, bp, bfs, nms, np, nfs, W, H, n, c->opt.nms_saturate, sf));
+  HIPCK(prof.mark(sf, B_NMS, ProfRing::K_FRONT_B));
+  if (stage == HC_STAGE_NMS) return HC_OK;
+  HIPCK(launch_thresh(nms, np, nfs, dst, dp, dfs, W, H, n, c->opt.low, c->opt.high, sf));
+  HIPCK(prof.mark(sf, B_THR, ProfRing::K_FRONT_B));
   return HC_OK;
 }
 
@@ -563,7 +635,6 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
     if (int rc = copy_frames_d2d(c, sf, dst, dp, dfs, src, P.src.pitch, P.src.fs, (size_t)W, n)) return rc;
     HIPCK(prof.mark(sf, B_MONO, ProfRing::K_STAGE0));
   }
-  const size_t mp = P.mono.pitch, mfs = P.mono.fs;
 
   if (stage == HC_STAGE_HYSTER) {
     // 4. the front kernel of the planned form, with the device pointers patched in
@@ -573,41 +644,16 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
     if (P.prov) fp.prov_out = dst;
     if (c->opt.debug_taps) {
       if (int rc = ensure_debug_buffers(c)) return rc;
-      if (P.form != 1) fp.dbg_blur = c->dbg.blur;
+      if (P.form != HC_FORM_SPLIT) fp.dbg_blur = c->dbg.blur;
     }
-    if (P.zeroed_words) {  // the 8-px kernels: flag words they zero, dump areas and page of zeros (alloc_dump)
+    if (form_zeroes_flags(P.form)) {  // the 8-px kernels and k_front_mx: flag words they zero, dump areas and page of zeros (alloc_dump)
       const size_t R = c->dump_region;
       fp.zero_words = s.d_flags;
       fp.dump = c->d_dump; fp.dump_c = c->d_dump + (fp.half ? R : 2048); fp.dump_p = c->d_dump + (fp.half ? 2 * R : 4096);
       fp.zeros = c->d_dump + (fp.half ? 3 * R : 16384);
     }
     if (P.waves) c->last.front_waves = P.waves;
-    switch (P.form) {
-    case 6: case 7: {
-      FrontExtParams ep{};
-      ep.f = fp;
-      ep.gradients = in_dy ? 1 : 0;
-      ep.channels = c->C;
-      ep.dy = in_dy;
-      HIPCK(launch_front_o_ext(ep, sf));
-      break;
-    }
-    case 3: HIPCK(launch_front8o(fp, sf)); break;
-    case -1: HIPCK(launch_front_o(fp, sf)); break;
-    case 5: HIPCK(launch_front_mx(fp, sf)); break;
-    case 2: case 4: HIPCK(launch_front8(fp, sf)); break;
-#ifdef HC_LEGACY_FRONT
-    case 1:  // k_blur + k_nms through the blur plane
-      if (int rc = ensure_blur_plane(c)) return rc;
-      fp.blur = c->d_bplane; fp.blur_frame_stride = c->bplane_fs;
-      HIPCK(launch_blur(fp, sf));
-      HIPCK(prof.mark(sf, P.mask_a, ProfRing::K_FRONT_A));
-      HIPCK(launch_nms(fp, sf));
-      break;
-    case 0: HIPCK(launch_front(fp, sf)); break;
-#endif
-    default: return fail(HC_E_ARG, "internal: front kernel form");
-    }
+    if (int rc = launch_front_form(c, P, fp, in_dy, sf)) return rc;
     HIPCK(prof.mark(sf, P.mask, ProfRing::K_FRONT_B));
     // 5. taps
     if (c->opt.debug_taps) {  // what the front kernels hand to the hysteresis (which updates the STRONG plane in place)
@@ -615,7 +661,7 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
       HIPCK(hipMemcpyAsync(c->dbg.s, s.d_sbits, bytes, hipMemcpyDeviceToDevice, sf));
       HIPCK(hipMemcpyAsync(c->dbg.c, s.d_cbits, bytes, hipMemcpyDeviceToDevice, sf));
       c->dbg.frames = n_out;
-      c->dbg.blur_split = P.form == 1;
+      c->dbg.blur_split = P.form == HC_FORM_SPLIT;
       c->dbg.blur_valid = c->mode == HC_MODE_R;
     }
     // 6. events between the front kernel and the hysteresis
@@ -630,28 +676,7 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
     // 7. the hysteresis
     if (int rc = queue_hyst_expand(c, s, sh, dst, dp, dfs, n_out, piped, P.zeroed_words)) return rc;
   } else if (stage > HC_STAGE_MONO) {
-    if (int rc = ensure_stage_scratch(c)) return rc;
-    const size_t bp = c->out_pitch, bfs = c->out_fs;  // scratch planes share the output geometry
-    uint8_t *blur = stage == HC_STAGE_GAUSSIAN ? dst : c->d_blur;
-    const size_t blp = stage == HC_STAGE_GAUSSIAN ? dp : bp, blfs = stage == HC_STAGE_GAUSSIAN ? dfs : bfs;
-    // every plain kernel is booked on its own stage, as the reference's _endCudaTimer(stage) does (cannyEdgeH.cu:415-430)
-    HIPCK(launch_gauss(mono, mp, mfs, blur, blp, blfs, W, H, n, sf));
-    HIPCK(prof.mark(sf, B_GAUSS, ProfRing::K_FRONT_B));
-    if (stage >= HC_STAGE_GRADIENT) {
-      HIPCK(launch_sobel(blur, blp, blfs, c->d_sx, c->d_sy, bp, bfs, W, H, n, sf));
-      if (stage == HC_STAGE_GRADIENT) HIPCK(launch_graddisp(c->d_sx, c->d_sy, bp, bfs, dst, dp, dfs, W, H, n, sf));
-      HIPCK(prof.mark(sf, B_GRAD, ProfRing::K_FRONT_B));
-      if (stage > HC_STAGE_GRADIENT) {
-        uint8_t *nms = stage == HC_STAGE_NMS ? dst : c->d_nms;
-        const size_t np = stage == HC_STAGE_NMS ? dp : bp, nfs = stage == HC_STAGE_NMS ? dfs : bfs;
-        HIPCK(launch_nms(c->d_sx, c->d_sy, bp, bfs, nms, np, nfs, W, H, n, c->opt.nms_saturate, sf));
-        HIPCK(prof.mark(sf, B_NMS, ProfRing::K_FRONT_B));
-        if (stage == HC_STAGE_THRESH) {
-          HIPCK(launch_thresh(nms, np, nfs, dst, dp, dfs, W, H, n, c->opt.low, c->opt.high, sf));
-          HIPCK(prof.mark(sf, B_THR, ProfRing::K_FRONT_B));
-        }
-      }
-    }
+    if (int rc = queue_stage_taps(c, stage, mono, P.mono.pitch, P.mono.fs, dst, dp, dfs, n, sf)) return rc;
   }
 
   // 8. copy-out, end of the run
@@ -1046,11 +1071,7 @@ int hc_download(hc_ctx *c, uint8_t *host, size_t row_stride, size_t frame_stride
   if (n <= 0 || n > c->last.run_n) return fail(HC_E_STATE, "hc_download: more frames than the last run produced");
   if (row_stride < (size_t)c->W) return fail(HC_E_ARG, "hc_download: row_stride smaller than a row");
   if (int rc = hc_sync(c)) return rc;
-  if (row_stride == (size_t)c->W && c->out_pitch == (size_t)c->W && frame_stride == c->out_fs)
-    HIPCK(hipMemcpyAsync(host, c->d_out, c->out_fs * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  else
-    for (int f = 0; f < n; ++f)
-      HIPCK(hipMemcpy2DAsync(host + frame_stride * f, row_stride, c->d_out + c->out_fs * f, c->out_pitch, (size_t)c->W, (size_t)c->H, hipMemcpyDeviceToHost, c->stream));
+  if (int rc = copy_out_d2h(c, host, row_stride, frame_stride, n, c->stream)) return rc;
   HIPCK(hipStreamSynchronize(c->stream));
   return HC_OK;
 }
@@ -1065,11 +1086,7 @@ int queue_download(hc_ctx *c)
     Slot &s = c->slot[c->last.slot];
     if (s.pending && s.stream != c->stream) HIPCK(hipStreamWaitEvent(cs, s.ev_done, 0));
   }
-  if (c->dl.row == (size_t)c->W && c->out_pitch == (size_t)c->W && c->dl.fs == c->out_fs)
-    HIPCK(hipMemcpyAsync(c->dl.host, c->d_out, c->out_fs * (size_t)c->dl.n, hipMemcpyDeviceToHost, cs));
-  else
-    for (int f = 0; f < c->dl.n; ++f)
-      HIPCK(hipMemcpy2DAsync(c->dl.host + c->dl.fs * f, c->dl.row, c->d_out + c->out_fs * f, c->out_pitch, (size_t)c->W, (size_t)c->H, hipMemcpyDeviceToHost, cs));
+  if (int rc = copy_out_d2h(c, c->dl.host, c->dl.row, c->dl.fs, c->dl.n, cs)) return rc;
   if (c->copy_streams) HIPCK(hipEventRecord(c->ev_down, cs));
   return HC_OK;
 }

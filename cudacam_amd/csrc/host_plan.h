@@ -1,5 +1,5 @@
 // host_plan.h -- every scheduling decision of the library as plain functions: which front kernel form a run gets and
-// how its work is cut (plan_front), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
+// how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
@@ -174,7 +174,7 @@ struct FrontPlan {
   bool in_staged = false, out_staged = false;  // the caller's view goes through the internal buffer
   bool gray = false;    // 3-channel frames the front kernel cannot convert while loading: launch_gray first (stage MONO: into the output)
   View src{}, mono{}, dst{};  // what the kernels read / the one-channel frames / what they write (p: 0 = the internal buffer)
-  int form = -1;        // hc_last_run_info: 2 k_front8, 4 its HALF form, 5 k_front_mx, 3 k_front8o, -1 k_front_o, 6 / 7 k_front_o_ext, 1 k_blur + k_nms, 0 k_front
+  int form = HC_FORM_FRONT_O;  // hc_last_run_info: one of HC_FORM_* (include/hipcanny.h); stays HC_FORM_FRONT_O when no front kernel runs
   bool prov = false;    // the front kernel writes the provisional map
   FrontParams fp{};     // complete but for the device pointers (in, planes, prov_out, dbg_blur, blur, dump areas, zero_words)
   size_t zeroed_words = 0;  // words of the slot's d_flags the front kernel zeroes (0: the host clears them)
@@ -209,16 +209,24 @@ inline int pick_run_rows(long units, int H, int want_rows)
 // does the caller's output view go through the internal buffer?  (the kernels store dwords)
 inline bool out_view_staged(const View &out) { return !aligned4(out.p, out.pitch, out.fs); }
 
-inline FrontPlan plan_front(const FrontIn &in)
+// groups of front forms (HC_FORM_*, include/hipcanny.h) that share a rule
+inline bool form_8px(int f) { return f == HC_FORM_FRONT8 || f == HC_FORM_FRONT8O || f == HC_FORM_FRONT8_HALF; }
+inline bool form_o_4px(int f) { return f == HC_FORM_FRONT_O || f == HC_FORM_O_APERTURE5 || f == HC_FORM_O_GRADIENTS; }
+inline bool form_zeroes_flags(int f) { return form_8px(f) || f == HC_FORM_FRONT_MX; }  // these kernels zero the run's hysteresis flag words on their way in
+
+inline int front_out_frames(const FrontIn &in) { return in.per_channel ? 3 * in.n : in.n; }  // output frames (= bit-plane frames)
+// Mode O forms of k_front_o_ext: caller-given gradients (HC_FORM_O_GRADIENTS), or aperture 5 on u8 frames (HC_FORM_O_APERTURE5)
+inline bool front_o_ext(const FrontIn &in) { return in.mode == HC_MODE_O && (in.in_dy != 0 || in.o.aperture == 5); }
+// the fused kernel converts BGR while loading (needs whole 12-byte pixel groups inside each row)
+inline bool whole_bgr_groups(const View &src, int W) { return src.pitch >= round_up((size_t)W, 4) * 3; }
+inline bool fuses_bgr(const FrontIn &in, const FrontPlan &P) { return in.C == 3 && in.stage == HC_STAGE_HYSTER && whole_bgr_groups(P.src, in.W); }
+
+// Staging: which of the caller's views go through the internal buffers, and where stage 0 (grey) runs.
+inline void stage_views(const FrontIn &in, FrontPlan &P)
 {
-  FrontPlan P;
   const FrontOpts &o = in.o;
   const int W = in.W, H = in.H, C = in.C;
-  const int n_out = in.per_channel ? 3 * in.n : in.n;  // output frames (= bit-plane frames)
-  const bool hyster = in.stage == HC_STAGE_HYSTER;
-  // Mode O forms of k_front_o_ext: caller-given gradients (form 7), or aperture 5 on u8 frames (form 6)
-  const bool grad_in = in.in_dy != 0;
-  const bool ext = in.mode == HC_MODE_O && (grad_in || o.aperture == 5);
+  const bool hyster = in.stage == HC_STAGE_HYSTER, grad_in = in.in_dy != 0, ext = front_o_ext(in);
   // unaligned caller buffers go through the internal pitched ones
   // (mode O on 3-channel data reads whole 12-byte groups of 4 pixels: a tighter caller pitch is staged as well; so are
   // rows that do not hold whole 8-pixel groups when the 8-px front kernels are to run -- k_front8 / k_front8o load 8 or
@@ -234,174 +242,269 @@ inline FrontPlan plan_front(const FrontIn &in)
   P.src = P.in_staged ? View{ 0, in.own_in.pitch, in.own_in.fs } : in.in;
   P.out_staged = out_view_staged(in.out);
   P.dst = P.out_staged ? View{ 0, in.own_out.pitch, in.own_out.fs } : in.out;
-  const size_t sp = P.src.pitch, sfs = P.src.fs, dp = P.dst.pitch, dfs = P.dst.fs;
   // stage 0 (cannyEdgeH.cu:214-227); 1-channel input skips it (the reference's mono path is broken, SURVEY §3 ii)
-  // the fused kernel converts BGR while loading (needs whole 12-byte pixel groups inside each row)
-  const bool whole_groups = sp >= round_up((size_t)W, 4) * 3;
-  if (in.per_channel && !whole_groups) { P.error = "per-channel mode needs an input pitch of at least 3 * round_up(width, 4) bytes"; return P; }
-  const bool fuse_bgr = C == 3 && hyster && whole_groups;
-  P.gray = C == 3 && !fuse_bgr && !grad_in;
+  if (in.per_channel && !whole_bgr_groups(P.src, W)) { P.error = "per-channel mode needs an input pitch of at least 3 * round_up(width, 4) bytes"; return; }
+  P.gray = C == 3 && !fuses_bgr(in, P) && !grad_in;
   P.mono = (P.gray && in.stage != HC_STAGE_MONO) ? View{ 0, in.own_mono.pitch, in.own_mono.fs } : P.src;
-  if (!hyster) return P;
+}
 
+// The form HC_OPT_FRONT_SPLIT, the mode and the source ask for; choose_form looks at a HC_FORM_FRONT8 run more closely.
+// Mode R front path: k_front8 reads whole 8-pixel groups (8 or 24 bytes per lane and row), the 4-px kernels 4-pixel
+// groups.  (Rows too tight for the 8-px kernels were staged above -- wants8 covers every case that asks for HC_FORM_FRONT8
+// or HC_FORM_FRONT8O -- so no run falls back to another form for its pitch; tests/cpp/plan_driver.cpp checks it.)
+// Mode O: k_front8o for one-channel sources, the 4-px k_front_o for 3-channel ones or when HC_OPT_FRONT_SPLIT asks for a
+// 4-px form
+// (Narrow frames: k_front8's HALF form, choose_form.  Round 2 sent 640-column batches to k_blur + k_nms instead.)
+inline int asked_form(const FrontIn &in)
+{
+  if (front_o_ext(in)) return in.in_dy != 0 ? HC_FORM_O_GRADIENTS : HC_FORM_O_APERTURE5;
+  if (in.mode != HC_MODE_R) return (in.C == 1 && in.o.split == 2) ? HC_FORM_FRONT8O : HC_FORM_FRONT_O;
+  return in.o.split;  // HC_FORM_FRONT8 / HC_FORM_SPLIT / HC_FORM_FRONT4 are HC_OPT_FRONT_SPLIT's values
+}
+
+// Does the front kernel write the provisional map?  By the inputs alone, so it is settled before the form is.
+// Pipelined mode: k_nms / k_front_o also write the strong pixels as 255 into the output (4 px per lane: whole
+// dwords need W % 4 == 0), so that the hysteresis, which runs beside the next run's bandwidth-hungry k_blur, only
+// rewrites the 16-pixel groups it changes instead of streaming out the whole map (+8 % end to end; without the
+// overlap the extra stores of the VALU-bound kernel cost more than the hysteresis saves).
+// Not when this run's output overlaps the previous run's (a caller that keeps one output buffer): that run's
+// hysteresis may still be patching it, and a late patch would survive into this run's map.
+// (k_front_o_ext writes no provisional map: its runs give the hysteresis the whole map to write)
+// (nor into an output view whose height x pitch reaches 4 GiB: the front kernels place the provisional rows with 32-bit
+// offsets, which would wrap -- row 1024 of a 4 MiB pitch onto row 0; the hysteresis, with 64-bit offsets, writes that map)
+inline bool front_writes_prov(const FrontIn &in, const View &dst, int asked)
+{
+  const bool f8 = asked == HC_FORM_FRONT8 || asked == HC_FORM_FRONT8O;
+  return in.piped && !in.out_overlap && !front_o_ext(in) && !reaches_4g(in.H, dst.pitch)
+         && (f8 ? in.W % 8 == 0 : (in.W % 4 == 0 && (asked == HC_FORM_SPLIT || in.mode == HC_MODE_O)));
+}
+
+// waves a run of rows of the 8-px kernels takes: one per (output frame, strip of 496 columns); HALF form (narrow frames):
+// the (frame, 240-column half-strip) units of a run of rows are dealt to half-waves in pairs -- 640 columns: 1.5 waves
+// instead of 2 -- three times that in per-channel mode
+inline long front8_waves_per_run(const FrontIn &in, bool half)
+{
+  if (!half) return (long)front_out_frames(in) * front8_strips(in.W);
+  return (((long)in.n * front8_half_strips(in.W) + 1) / 2) * (in.per_channel ? 3 : 1);
+}
+
+// The form that runs (needs P.src, P.dst, P.prov and P.fp.bgr).  Whatever is not HC_FORM_FRONT8 runs as asked.
+inline int choose_form(const FrontIn &in, const FrontPlan &P, int asked)
+{
+  if (asked != HC_FORM_FRONT8) return asked;
+  const FrontOpts &o = in.o;
+  const int W = in.W, H = in.H;
+  const size_t sp = P.src.pitch, sfs = P.src.fs, dp = P.dst.pitch, dfs = P.dst.fs;
+  const bool mx_asked = o.mx_mode == 1 && P.fp.bgr == 0 && !in.per_channel;
+  if (in.dump_region && o.half_mode != 0 && !mx_asked) {  // (HC_OPT_FRONT_MX 1 goes first)
+    // HALF form: when that needs fewer waves and the lane offsets fit
+    const long per = in.per_channel ? 3 : 1;
+    const size_t R = in.dump_region;
+    const bool fits = sfs + 32768 <= R && per * sizeof(u32) * (size_t)in.RD * H + 4096 <= R && (!P.prov || per * dfs + 16384 <= R)
+                      && (unsigned long long)sfs + (unsigned long long)H * sp < (1ull << 32) && (!P.prov || (unsigned long long)per * dfs + (unsigned long long)H * dp < (1ull << 32));
+    if ((front8_waves_per_run(in, true) < front8_waves_per_run(in, false) || o.half_mode == 1) && fits) return HC_FORM_FRONT8_HALF;
+  }
+  // k_front_mx (blur and Sobel on the matrix pipe): one-channel frames of Mode R, on request (HC_OPT_FRONT_MX)
+  if (P.fp.bgr == 0 && o.mx_mode == 1 && !reaches_4g(H, sp) && sp >= round_up((size_t)W, 4) && (!P.prov || W % 8 == 0)) return HC_FORM_FRONT_MX;
+  return HC_FORM_FRONT8;
+}
+
+// what the flag-zeroing forms share: the words of the slot's d_flags the kernel zeroes (every tile shape has at least 16
+// rows per tile), and k_front8's dense path
+inline void plan_zeroing_and_dense(const FrontIn &in, FrontPlan &P)
+{
+  const FrontOpts &o = in.o;
   FrontParams &fp = P.fp;
-  fp.bgr = in.per_channel ? 2 : fuse_bgr ? 1 : 0; fp.in_pitch = P.mono.pitch; fp.in_frame_stride = P.mono.fs; fp.RD = in.RD; fp.W = W; fp.H = H;
-  fp.nstrips = in.nstrips; fp.nframes = n_out;
+  P.zeroed_words = run_flag_words(std::min(in.wl_cap, slot_wl_cap((size_t)front_out_frames(in), in.H, in.RD)));
+  fp.zero_count = (u32)P.zeroed_words;
+  // dense path of k_front8 (wave-wide NMS): enter above 512 half-lanes per window of 768, leave below 384.  (The batch
+  // scheme costs 27 + 41 + 3.6 e instructions per row for e queued half-lanes, the dense path ~260: break-even near
+  // 320 per window -- but the zero padding makes the first two rows of every frame candidates across the whole
+  // width, and with 320 the window after them went dense on every natural frame: +1.2 % on the benchmark's frames.)
+  // (k_front_mx has no dense path and reads neither value; its plans have always carried them and still do)
+  fp.dense_enter = o.dense_mode == 0 ? 0x7FFFFFFF : o.dense_mode == 1 ? -1 : o.dense_enter;
+  fp.dense_leave = o.dense_mode == 0 ? 0x7FFFFFFF : o.dense_mode == 1 ? -1 : o.dense_leave;
+}
+
+// k_front8, its HALF form and k_front8o: strips of 496 columns, runs of 6 * windows - 4 rows
+inline void cut_front8_runs(const FrontIn &in, FrontPlan &P)
+{
+  const FrontOpts &o = in.o;
+  FrontParams &fp = P.fp;
+  const int H = in.H;
+  plan_zeroing_and_dense(in, P);
+  fp.nstrips = front8_strips(in.W);
+  if (P.form == HC_FORM_FRONT8_HALF) { fp.half = 1; fp.nhalf = front8_half_strips(in.W); }
+  const long waves_per_chunk = front8_waves_per_run(in, P.form == HC_FORM_FRONT8_HALF);
+  // Run length.  Every run repeats an 8-row warm-up, so long runs are cheaper -- measured optimum 110-180 rows at 1024
+  // frames, provided the runs tile the frame evenly (a last run of a few rows pays the warm-up for nothing): the frame
+  // is cut into round(H / 120) equal runs.  A small batch is cut into shorter runs instead, down to 8 rows, where the
+  // warm-up doubles the work but one frame still spreads over 540 waves (3072 waves of this kernel are resident).
+  int rows;
+  if (o.chunk) rows = std::min(std::max(o.chunk, 2), H);
+  else {
+    const long units = waves_per_chunk;
+    long nch = std::max<long>(1, (H + 60) / 120);
+    if (units * nch < 3072) nch = std::min<long>((3072 + units - 1) / units, std::max(1, H / 8));  // (spread over 2048 / 1536 / 1024 waves instead: no better, profiles/r03/experiments.md)
+    rows = (int)((H + nch - 1) / nch);
+  }
+  const int windows = std::max(1, (rows + 4 + 5) / 6);
+  fp.run_rows = front8_run_rows(windows);
+  fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
+  fp.total_items = (int)(waves_per_chunk * fp.nchunks);
+}
+
+// k_front_mx: strips of 216 columns, runs of any length (blocks of 16 rows)
+inline void cut_front_mx_runs(const FrontIn &in, FrontPlan &P)
+{
+  const FrontOpts &o = in.o;
+  FrontParams &fp = P.fp;
+  const int H = in.H;
+  plan_zeroing_and_dense(in, P);
+  fp.nstrips = front_mx_strips(in.W);
+  const long units = (long)front_out_frames(in) * fp.nstrips;
+  // a run of n blocks covers 16 n - 4 rows and costs about one block more to start (workgroup launch, prologue: 0.2 ms
+  // of a 1024-frame launch in runs of 124 rows, profiles/r04/mx_ablation.txt): the run count that needs the fewest
+  // blocks in all, among those that give every wave slot of the chip (3072) six runs or more where the frame allows
+  long nch;
+  if (o.chunk) nch = std::max<long>(1, (H + o.chunk - 1) / o.chunk);
+  else {
+    const long hi = std::max<long>(1, (H + 11) / 12);
+    const long lo = std::min<long>(hi, std::max<long>(1, (6 * 3072 + units - 1) / units));
+    long best = -1, best_cost = 0;
+    for (long k = lo; k <= std::min<long>(hi, lo + 24); ++k) {
+      const long rows = (H + k - 1) / k, runs = (H + rows - 1) / rows, last = H - rows * (runs - 1);
+      const long cost = ((rows + 4 + 15) / 16 + 1) * (runs - 1) + (last + 4 + 15) / 16 + 1;
+      if (best < 0 || cost < best_cost) { best = k; best_cost = cost; }
+    }
+    nch = best;
+  }
+  fp.run_rows = (int)((H + nch - 1) / nch);
+  fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
+  fp.total_items = (int)(units * fp.nchunks);
+}
+
+// k_front_o, and k_front_o_ext with its strips and work split (a 6-row warm-up for aperture 5, 2 rows for gradients):
+// strips of 248 columns (FrontIn::nstrips), long chunks (no LDS slab, 4-row warm-up)
+inline void cut_front_o_chunks(const FrontIn &in, FrontPlan &P)
+{
+  FrontParams &fp = P.fp;
+  const int H = in.H;
+  // rows per work item: hc_set_tuning's number (any value >= 1: these kernels have no window to fill, unlike the 8-px
+  // forms, whose runs are 2 rows at least), or about 12288 items per launch in chunks of 16 rows or more
+  const long units = (long)front_out_frames(in) * in.nstrips;
+  const int per_strip = (int)std::max<long>(1, std::min<long>((12288 + units - 1) / units, (H + 15) / 16));
+  fp.chunk_rows = in.o.chunk ? std::min(std::max(in.o.chunk, 1), H) : (H + per_strip - 1) / per_strip;
+  fp.nchunks = (H + fp.chunk_rows - 1) / fp.chunk_rows;
+  fp.total_items = front_out_frames(in) * fp.nstrips * fp.nchunks;
+  if (!front_o_ext(in) && P.src.pitch < round_up((size_t)in.W, 4) * (size_t)in.C) P.error = "mode O needs an input pitch of at least round_up(width, 4) * channels";
+}
+
 #ifdef HC_LEGACY_FRONT
-  {
-    // Mode R, fused kernel: a wave marches through `subchunks` sub-chunks of 24 blur rows (run of 24*m - 4
-    // output rows).  Longer runs amortise the 8-row warm-up; shorter runs give more work items (small batches).
-    int m = o.chunk ? (o.chunk + 4 + 23) / 24 : 0;
-    if (m == 0) {
-      m = 3;
-      while (m > 1 && (long)n_out * in.nstrips * ((H + front_run_rows(m) - 1) / front_run_rows(m)) < 24576) --m;
-    }
-    fp.subchunks = m; fp.run_rows = front_run_rows(m);
-    fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
-    fp.total_items = n_out * fp.nstrips * fp.nchunks;
+// k_front (Mode R, fused, 4 px per lane): a wave marches through `subchunks` sub-chunks of 24 blur rows (run of 24*m - 4
+// output rows).  Longer runs amortise the 8-row warm-up; shorter runs give more work items (small batches).
+inline void cut_front4_runs(const FrontIn &in, FrontPlan &P)
+{
+  FrontParams &fp = P.fp;
+  const int H = in.H, n_out = front_out_frames(in);
+  int m = in.o.chunk ? (in.o.chunk + 4 + 23) / 24 : 0;
+  if (m == 0) {
+    m = 3;
+    while (m > 1 && (long)n_out * in.nstrips * ((H + front_run_rows(m) - 1) / front_run_rows(m)) < 24576) --m;
   }
+  fp.subchunks = m; fp.run_rows = front_run_rows(m);
+  fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
+  fp.total_items = n_out * fp.nstrips * fp.nchunks;
+}
+
+// k_blur + k_nms through the blur plane: each with a work split of its own
+inline void cut_split_runs(const FrontIn &in, FrontPlan &P)
+{
+  FrontParams &fp = P.fp;
+  const int H = in.H, n_out = front_out_frames(in);
+  const int rows = pick_run_rows((long)n_out * in.nstrips, H, in.o.chunk);
+  fp.run_rows = (rows + 1) & ~1;  // k_blur walks rows in pairs
+  fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
+  fp.total_items = n_out * fp.nstrips * fp.nchunks;
+  fp.run_rows_b = rows;
+  fp.nchunks_b = (H + rows - 1) / rows;
+  fp.total_items_b = n_out * fp.nstrips * fp.nchunks_b;
+}
 #endif
-  // Mode R front path: k_front8 reads whole 8-pixel groups (8 or 24 bytes per lane and row), the 4-px kernels 4-pixel
-  // groups.  (Rows too tight for the 8-px kernels were staged above -- wants8 covers every case that picks form 2 or 3 --
-  // so no run falls back to another form for its pitch; tests/cpp/plan_driver.cpp checks it.)
-  // Mode O: k_front8o (form 3) for one-channel sources, the 4-px k_front_o (form -1) for 3-channel ones or when
-  // HC_OPT_FRONT_SPLIT asks for a 4-px form
-  // (Narrow frames: k_front8's HALF form, below.  Round 2 sent 640-column batches to k_blur + k_nms instead.)
-  P.form = ext ? (grad_in ? 7 : 6) : in.mode != HC_MODE_R ? ((C == 1 && o.split == 2) ? 3 : -1) : o.split;
-  const bool split = P.form == 1, f8 = P.form == 2 || P.form == 3;
-  // Pipelined mode: k_nms / k_front_o also write the strong pixels as 255 into the output (4 px per lane: whole
-  // dwords need W % 4 == 0), so that the hysteresis, which runs beside the next run's bandwidth-hungry k_blur, only
-  // rewrites the 16-pixel groups it changes instead of streaming out the whole map (+8 % end to end; without the
-  // overlap the extra stores of the VALU-bound kernel cost more than the hysteresis saves).
-  // Not when this run's output overlaps the previous run's (a caller that keeps one output buffer): that run's
-  // hysteresis may still be patching it, and a late patch would survive into this run's map.
-  // (k_front_o_ext writes no provisional map: its runs give the hysteresis the whole map to write)
-  // (nor into an output view whose height x pitch reaches 4 GiB: the front kernels place the provisional rows with 32-bit
-  // offsets, which would wrap -- row 1024 of a 4 MiB pitch onto row 0; the hysteresis, with 64-bit offsets, writes that map)
-  P.prov = in.piped && !in.out_overlap && !ext && !reaches_4g(H, dp) && (f8 ? W % 8 == 0 : (W % 4 == 0 && (split || in.mode == HC_MODE_O)));
-  if (P.prov) { fp.prov_pitch = (u32)dp; fp.prov_fs = dfs; }
-  if (o.debug_taps && !split) { fp.dbg_pitch = (u32)in.own_out.pitch; fp.dbg_fs = in.own_out.fs; }  // own_out.pitch: the width if that is a multiple of 16, else padded to 256
-#ifdef HC_LEGACY_FRONT
-  if (split) {  // k_blur + k_nms through the blur plane
-    const int rows = pick_run_rows((long)n_out * in.nstrips, H, o.chunk);
-    fp.run_rows = (rows + 1) & ~1;  // k_blur walks rows in pairs
-    fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
-    fp.total_items = n_out * fp.nstrips * fp.nchunks;
-    fp.run_rows_b = rows;
-    fp.nchunks_b = (H + rows - 1) / rows;
-    fp.total_items_b = n_out * fp.nstrips * fp.nchunks_b;
-  }
-#else
-  if (!f8 && in.mode == HC_MODE_R) { P.error = "this library is built without the round-1 front kernels (HC_OPT_FRONT_SPLIT 1 / 0: libhipcanny_legacy.so)"; return P; }
-#endif
-  bool use_mx = false;
-  if (f8) {  // strips of 496 columns, runs of 6 * windows - 4 rows
-    // the 8-px kernels zero the run's hysteresis flag words on their way in: every tile shape has at least 16 rows per tile
-    P.zeroed_words = run_flag_words(std::min(in.wl_cap, slot_wl_cap((size_t)n_out, H, in.RD)));
-    fp.zero_count = (u32)P.zeroed_words;
-    fp.nstrips = front8_strips(W);
-    // dense path of k_front8 (wave-wide NMS): enter above 512 half-lanes per window of 768, leave below 384.  (The batch
-    // scheme costs 27 + 41 + 3.6 e instructions per row for e queued half-lanes, the dense path ~260: break-even near
-    // 320 per window -- but the zero padding makes the first two rows of every frame candidates across the whole
-    // width, and with 320 the window after them went dense on every natural frame: +1.2 % on the benchmark's frames.)
-    fp.dense_enter = o.dense_mode == 0 ? 0x7FFFFFFF : o.dense_mode == 1 ? -1 : o.dense_enter;
-    fp.dense_leave = o.dense_mode == 0 ? 0x7FFFFFFF : o.dense_mode == 1 ? -1 : o.dense_leave;
-    long waves_per_chunk = (long)n_out * fp.nstrips;
-    if (in.mode == HC_MODE_R && in.dump_region && o.half_mode != 0 && !(o.mx_mode == 1 && fp.bgr == 0 && !in.per_channel)) {  // (HC_OPT_FRONT_MX 1 goes first)
-      // HALF form (narrow frames): the (frame, 240-column half-strip) units of a run of rows are dealt to half-waves in
-      // pairs -- 640 columns: 1.5 waves instead of 2 -- when that needs fewer waves and the lane offsets fit
-      const long per = in.per_channel ? 3 : 1, nh = front8_half_strips(W), pairs = ((long)in.n * nh + 1) / 2;
-      const size_t R = in.dump_region;
-      const bool fits = sfs + 32768 <= R && per * sizeof(u32) * (size_t)in.RD * H + 4096 <= R && (!P.prov || per * dfs + 16384 <= R)
-                        && (unsigned long long)sfs + (unsigned long long)H * sp < (1ull << 32) && (!P.prov || (unsigned long long)per * dfs + (unsigned long long)H * dp < (1ull << 32));
-      if ((pairs * per < waves_per_chunk || o.half_mode == 1) && fits) {
-        fp.half = 1; fp.nhalf = (int)nh;
-        waves_per_chunk = pairs * per;
-        P.form = 4;
-      }
-    }
-    // Run length.  Every run repeats an 8-row warm-up, so long runs are cheaper -- measured optimum 110-180 rows at 1024
-    // frames, provided the runs tile the frame evenly (a last run of a few rows pays the warm-up for nothing): the frame
-    // is cut into round(H / 120) equal runs.  A small batch is cut into shorter runs instead, down to 8 rows, where the
-    // warm-up doubles the work but one frame still spreads over 540 waves (3072 waves of this kernel are resident).
-    int rows;
-    if (o.chunk) rows = std::min(std::max(o.chunk, 2), H);
-    else {
-      const long units = waves_per_chunk;
-      long nch = std::max<long>(1, (H + 60) / 120);
-      if (units * nch < 3072) nch = std::min<long>((3072 + units - 1) / units, std::max(1, H / 8));  // (spread over 2048 / 1536 / 1024 waves instead: no better, profiles/r03/experiments.md)
-      rows = (int)((H + nch - 1) / nch);
-    }
-    const int windows = std::max(1, (rows + 4 + 5) / 6);
-    fp.run_rows = front8_run_rows(windows);
-    fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
-    fp.total_items = (int)(waves_per_chunk * fp.nchunks);
-    // k_front_mx (blur and Sobel on the matrix pipe): one-channel frames of Mode R, on request (HC_OPT_FRONT_MX)
-    use_mx = in.mode == HC_MODE_R && P.form == 2 && fp.bgr == 0 && o.mx_mode == 1 && !reaches_4g(H, sp) && sp >= round_up((size_t)W, 4) && (!P.prov || W % 8 == 0);
-    if (use_mx) {
-      fp.nstrips = front_mx_strips(W);
-      const long units = (long)n_out * fp.nstrips;
-      // a run of n blocks covers 16 n - 4 rows and costs about one block more to start (workgroup launch, prologue: 0.2 ms
-      // of a 1024-frame launch in runs of 124 rows, profiles/r04/mx_ablation.txt): the run count that needs the fewest
-      // blocks in all, among those that give every wave slot of the chip (3072) six runs or more where the frame allows
-      long nch;
-      if (o.chunk) nch = std::max<long>(1, (H + o.chunk - 1) / o.chunk);
-      else {
-        const long hi = std::max<long>(1, (H + 11) / 12);
-        const long lo = std::min<long>(hi, std::max<long>(1, (6 * 3072 + units - 1) / units));
-        long best = -1, best_cost = 0;
-        for (long k = lo; k <= std::min<long>(hi, lo + 24); ++k) {
-          const long rows = (H + k - 1) / k, runs = (H + rows - 1) / rows, last = H - rows * (runs - 1);
-          const long cost = ((rows + 4 + 15) / 16 + 1) * (runs - 1) + (last + 4 + 15) / 16 + 1;
-          if (best < 0 || cost < best_cost) { best = k; best_cost = cost; }
-        }
-        nch = best;
-      }
-      fp.run_rows = (int)((H + nch - 1) / nch);
-      fp.nchunks = (H + fp.run_rows - 1) / fp.run_rows;
-      fp.total_items = (int)(units * fp.nchunks);
-      P.form = 5;
-    }
-  }
+
+// thresholds as the form's kernel compares them, and the reference stages its launch covers
+inline void plan_thresholds_and_masks(const FrontIn &in, FrontPlan &P)
+{
+  const FrontOpts &o = in.o;
+  FrontParams &fp = P.fp;
   if (in.mode == HC_MODE_O) {
-    // cv::Canny: plain thresholds on the L1 magnitude; long chunks (no LDS slab, 4-row warm-up)
+    // cv::Canny: plain thresholds on the L1 magnitude
     fp.a_lo[0] = (u32)o.low; fp.a_hi[0] = (u32)o.high;
     fp.l2gradient = o.l2gradient;
     if (o.l2gradient) {  // canny.cpp: thresholds capped at 32767 (hc_set_thresholds) and squared; the magnitude is dx^2 + dy^2
       fp.a_lo[0] = (u32)o.low * (u32)o.low;
       fp.a_hi[0] = (u32)o.high * (u32)o.high;
     }
-    if (!f8) {  // k_front_o, and k_front_o_ext with its strips and work split (a 6-row warm-up for aperture 5, 2 rows for gradients); k_front8o: strips and runs as set for k_front8 above
-      // rows per work item: hc_set_tuning's number (any value >= 1: these kernels have no window to fill, unlike the 8-px
-      // forms, whose runs are 2 rows at least), or about 12288 items per launch in chunks of 16 rows or more
-      const long units = (long)n_out * in.nstrips;
-      const int per_strip = (int)std::max<long>(1, std::min<long>((12288 + units - 1) / units, (H + 15) / 16));
-      fp.chunk_rows = o.chunk ? std::min(std::max(o.chunk, 1), H) : (H + per_strip - 1) / per_strip;
-      fp.nchunks = (H + fp.chunk_rows - 1) / fp.chunk_rows;
-      fp.total_items = n_out * fp.nstrips * fp.nchunks;
-      if (!ext && sp < round_up((size_t)W, 4) * (size_t)C) { P.error = "mode O needs an input pitch of at least round_up(width, 4) * channels"; return P; }
-    }
     // cv::Canny has no blur stage; given gradients leave NMS + thresholds only (GRADIENT did not run)
-    P.mask = (grad_in ? 0u : B_GRAD) | B_NMS | B_THR;
-    return P;
+    P.mask = (in.in_dy != 0 ? 0u : B_GRAD) | B_NMS | B_THR;
+    return;
   }
   band_thresholds(o.low, o.nms_saturate != 0, fp.a_lo);
   band_thresholds(o.high, o.nms_saturate != 0, fp.a_hi);
   fp.wrap_limit = o.nms_saturate ? 0xFFFFFFFFu : 262144u;
-  const unsigned b_mono = fuse_bgr ? B_MONO : 0u;  // stage 0 fused into the blur's load (per-channel mode has no grey stage)
+  const unsigned b_mono = fuses_bgr(in, P) ? B_MONO : 0u;  // stage 0 fused into the blur's load (per-channel mode has no grey stage)
+  const bool split = P.form == HC_FORM_SPLIT;
   P.mask = split ? B_GRAD | B_NMS | B_THR : b_mono | B_GAUSS | B_GRAD | B_NMS | B_THR;
   P.mask_a = split ? b_mono | B_GAUSS : 0u;
-  if (!f8) return P;
-  // one-wave workgroups: pipelined big batches with the provisional map, mono / BGR (the per-channel form is three waves, one per channel)
-  // (small batches, whose four chains overlap anyway: from 0.12 G pixels per run -- 64 frames of 1080p +3.5 %, 128 frames
-  //  +4.5 %; 4 to 32 frames -3 to -6 %: tools/experiments/exp_small_wpb.sh)
-  const bool auto_one = in.nslot_use < NSLOT ? in.front_one : (long long)n_out * W * H >= 120ll * 1000 * 1000;
-  fp.one_wave = (P.prov && !in.per_channel && (o.wpb_mode == 1 || (o.wpb_mode < 0 && auto_one))) ? 1 : 0;
-  P.waves = in.per_channel ? 3 : fp.one_wave ? 1 : 4;
-  if (use_mx) {  // (its waves are independent too: one-wave workgroups beside the hysteresis, -3.5 % there, four-wave ones alone; HC_OPT_FRONT_WPB 1 / 4 fixes it)
+}
+
+// waves per workgroup of k_front8 (both forms) and k_front_mx; every other kernel has one shape (P.waves stays 0)
+inline void plan_front_waves(const FrontIn &in, FrontPlan &P)
+{
+  const FrontOpts &o = in.o;
+  FrontParams &fp = P.fp;
+  if (P.form == HC_FORM_FRONT8 || P.form == HC_FORM_FRONT8_HALF) {
+    // one-wave workgroups: pipelined big batches with the provisional map, mono / BGR (the per-channel form is three waves, one per channel)
+    // (small batches, whose four chains overlap anyway: from 0.12 G pixels per run -- 64 frames of 1080p +3.5 %, 128 frames
+    //  +4.5 %; 4 to 32 frames -3 to -6 %: tools/experiments/exp_small_wpb.sh)
+    const bool auto_one = in.nslot_use < NSLOT ? in.front_one : (long long)front_out_frames(in) * in.W * in.H >= 120ll * 1000 * 1000;
+    fp.one_wave = (P.prov && !in.per_channel && (o.wpb_mode == 1 || (o.wpb_mode < 0 && auto_one))) ? 1 : 0;
+    P.waves = in.per_channel ? 3 : fp.one_wave ? 1 : 4;
+  } else if (P.form == HC_FORM_FRONT_MX) {
+    // (its waves are independent too: one-wave workgroups beside the hysteresis, -3.5 % there, four-wave ones alone; HC_OPT_FRONT_WPB 1 / 4 fixes it)
     fp.one_wave = (o.wpb_mode == 1 || (o.wpb_mode < 0 && P.prov)) ? 1 : 0;
     P.waves = fp.one_wave ? 1 : 4;
   }
+}
+
+// A run's front path: staging, then the form, then the work split, thresholds and workgroup shape of that form.
+inline FrontPlan plan_front(const FrontIn &in)
+{
+  FrontPlan P;
+  stage_views(in, P);
+  if (P.error || in.stage != HC_STAGE_HYSTER) return P;
+
+  FrontParams &fp = P.fp;
+  fp.bgr = in.per_channel ? 2 : fuses_bgr(in, P) ? 1 : 0; fp.in_pitch = P.mono.pitch; fp.in_frame_stride = P.mono.fs; fp.RD = in.RD; fp.W = in.W; fp.H = in.H;
+  fp.nstrips = in.nstrips; fp.nframes = front_out_frames(in);
+  const int asked = asked_form(in);
+  P.prov = front_writes_prov(in, P.dst, asked);
+  P.form = choose_form(in, P, asked);
+  if (P.prov) { fp.prov_pitch = (u32)P.dst.pitch; fp.prov_fs = P.dst.fs; }
+  if (in.o.debug_taps && P.form != HC_FORM_SPLIT) { fp.dbg_pitch = (u32)in.own_out.pitch; fp.dbg_fs = in.own_out.fs; }  // own_out.pitch: the width if that is a multiple of 16, else padded to 256
+  switch (P.form) {
+  case HC_FORM_FRONT8: case HC_FORM_FRONT8_HALF: case HC_FORM_FRONT8O: cut_front8_runs(in, P); break;
+  case HC_FORM_FRONT_MX: cut_front_mx_runs(in, P); break;
+  case HC_FORM_FRONT_O: case HC_FORM_O_APERTURE5: case HC_FORM_O_GRADIENTS: cut_front_o_chunks(in, P); break;
+#ifdef HC_LEGACY_FRONT
+  case HC_FORM_FRONT4: cut_front4_runs(in, P); break;
+  case HC_FORM_SPLIT: cut_split_runs(in, P); break;
+#endif
+  default: P.error = "this library is built without the round-1 front kernels (HC_OPT_FRONT_SPLIT 1 / 0: libhipcanny_legacy.so)"; break;
+  }
+  if (P.error) return P;
+  plan_thresholds_and_masks(in, P);
+  plan_front_waves(in, P);
   return P;
 }
 

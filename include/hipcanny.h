@@ -179,8 +179,8 @@ int hc_use_own_stream(hc_ctx *ctx);
  * books a stage only when it ran.  Attribution: the plain per-stage kernels behind final_stage < HYSTER each have their
  * own interval.  On the HYSTER fast path one kernel covers several reference stages and has no internal boundary to
  * time: k_blur covers MONO (3-channel input) + GAUSSIAN, k_nms covers GRADIENT + NMS + THRESH, a fused front kernel
- * covers all of them, k_front_o (mode O) GRADIENT + NMS + THRESH, as does k_front_o_ext at aperture 5 (front form 6);
- * on given gradients (hc_run_gradients_device, form 7) it covers NMS + THRESH and GRADIENT reads -1; a kernel's time is divided EQUALLY among the stages
+ * covers all of them, k_front_o (mode O) GRADIENT + NMS + THRESH, as does k_front_o_ext at aperture 5 (HC_FORM_O_APERTURE5);
+ * on given gradients (hc_run_gradients_device, HC_FORM_O_GRADIENTS) it covers NMS + THRESH and GRADIENT reads -1; a kernel's time is divided EQUALLY among the stages
  * it covers, so every stage that ran shows a non-zero share and the sum over stages -- what the reference's UI totals
  * up to the selected stage (src/imgui/imguiApp.cpp:364-376) -- is the measured time.  Off by default on the batch path. */
 int hc_enable_profiling(hc_ctx *ctx, int on);
@@ -236,14 +236,27 @@ enum { HC_SCHED_LAUNCHES = 0, HC_SCHED_LISTS, HC_SCHED_LOOP, HC_SCHED_HIST_GRID,
        HC_SCHED_TILE_ROWS, HC_SCHED_WAVES, HC_SCHED_PANELS, HC_SCHED_FRAMES, HC_SCHED_WORDS };
 int hc_last_hysteresis_schedule(hc_ctx *ctx, int *info, int nwords);
 
+/* The front path of a run, as hc_last_run_info reports it: which kernel turned the frames into the STRONG / CANDIDATE bit
+ * planes.  The values are part of the ABI. */
+enum {
+  HC_FORM_FRONT_O = -1,     /* Mode O: k_front_o (4 px per lane); also "no front kernel ran" (final stages below HYSTER) */
+  HC_FORM_FRONT4 = 0,       /* Mode R, HC_OPT_FRONT_SPLIT 0: the 4-px fused k_front (libhipcanny_legacy.so) */
+  HC_FORM_SPLIT = 1,        /* Mode R, HC_OPT_FRONT_SPLIT 1: k_blur + k_nms (libhipcanny_legacy.so) */
+  HC_FORM_FRONT8 = 2,       /* Mode R, HC_OPT_FRONT_SPLIT 2: k_front8 */
+  HC_FORM_FRONT8O = 3,      /* Mode O: k_front8o */
+  HC_FORM_FRONT8_HALF = 4,  /* Mode R: k_front8 in its half-strip form (HC_OPT_FRONT_HALF) */
+  HC_FORM_FRONT_MX = 5,     /* Mode R: k_front_mx (HC_OPT_FRONT_MX) */
+  HC_FORM_O_APERTURE5 = 6,  /* Mode O: k_front_o_ext at HC_OPT_APERTURE 5 */
+  HC_FORM_O_GRADIENTS = 7   /* Mode O: k_front_o_ext on given gradients (hc_run_gradients_device) */
+};
+
 /* What the last hc_run / hc_run_device did with the caller's buffers -- no silent cliffs: *input_staged / *output_staged are
  * 1 when the frames went through the context's internal pitched buffers (an extra device-to-device copy each: pointer,
  * pitch or frame stride not a multiple of 4, 3-channel mode O rows without whole 12-byte groups, or an input view with
- * height * pitch >= 2^32), and *front_form is
- * the front path that ran (Mode R: the HC_OPT_FRONT_SPLIT value 2 / 1 / 0, 4 = k_front8 in its half-strip form, or 5 = k_front_mx; Mode O:
- * 3 = k_front8o, -1 = k_front_o, 6 = k_front_o_ext at HC_OPT_APERTURE 5, 7 = k_front_o_ext on given gradients
- * (hc_run_gradients_device); -1 also for final stages below HYSTER).  Rows that do not hold whole 8-pixel groups
- * (tight rows of a width that is not a multiple of 8) are staged (*input_staged = 1) so that the 8-px kernels can run. */
+ * height * pitch >= 2^32), and *front_form is the front path that ran, one of the HC_FORM_* values above (Mode R:
+ * HC_FORM_FRONT8 / HC_FORM_SPLIT / HC_FORM_FRONT4 are the HC_OPT_FRONT_SPLIT values 2 / 1 / 0; HC_FORM_FRONT_O also for
+ * final stages below HYSTER).  Rows that do not hold whole 8-pixel groups (tight rows of a width that is not a multiple
+ * of 8) are staged (*input_staged = 1) so that the 8-px kernels can run. */
 int hc_last_run_info(hc_ctx *ctx, int *input_staged, int *output_staged, int *front_form);
 
 /* Pipelined mode: how many runs of `nframes` frames the context may keep in flight (4 for small batches -- fewer
@@ -305,12 +318,12 @@ int hc_set_tuning(hc_ctx *ctx, int chunk_rows, int hyst_launches);
  *
  * HC_OPT_APERTURE (default 3, Mode O contexts): cv::Canny's `apertureSize`.  5 = Sobel(src, CV_16S, ksize 5, scale 1,
  * BORDER_REPLICATE): |dx|, |dy| <= 12240, the L1 magnitude up to 24480; thresholds, the 3-channel select, the tangent test
- * and NMS as at 3.  Runs k_front_o_ext (front form 6; 1 or 3 channels; rows without whole 4-pixel groups are staged).
+ * and NMS as at 3.  Runs k_front_o_ext (HC_FORM_O_APERTURE5; 1 or 3 channels; rows without whole 4-pixel groups are staged).
  * Any other value, and any mode R context, is HC_E_ARG; 7 and -1 (Scharr) are not offered as options (cv::Canny scales the
  * 7x7 Sobel and its thresholds to stay within int16): such callers chain hc_derivatives_device (ksize 7 / -1, which states
  * the scaling and what it means for the thresholds) with hc_run_gradients_device.  Mode O thresholds stay clamped to 0..32767 at every aperture (L1 thresholds above 32767
  * cannot be expressed).
- * Pipelined mode (HC_OPT_PIPELINE) gives exact maps on both k_front_o_ext forms (6 and 7); they write no provisional map,
+ * Pipelined mode (HC_OPT_PIPELINE) gives exact maps on both k_front_o_ext forms (HC_FORM_O_APERTURE5 and HC_FORM_O_GRADIENTS); they write no provisional map,
  * so the hysteresis writes the whole output map of their runs. */
 /*
  * HC_OPT_DEBUG_TAPS (default 0): parity-test diagnostics.  1 = every HC_STAGE_HYSTER run keeps a copy of what the
@@ -320,7 +333,7 @@ int hc_set_tuning(hc_ctx *ctx, int chunk_rows, int hyst_launches);
  * HC_OPT_FRONT_HALF (default -1 = automatic, Mode R): the half-strip form of k_front8 for narrow frames -- a wave is two
  * independent half-waves of 240 columns each, and the (frame, half-strip) units of a run of rows are dealt to them in pairs
  * (640 columns: 1.5 waves per frame instead of 2).  -1 = when it needs fewer waves; 0 = never; 1 = whenever the buffers
- * allow it (parity tests).  hc_last_run_info reports it as front form 4.
+ * allow it (parity tests).  hc_last_run_info reports it as HC_FORM_FRONT8_HALF.
  *
  * HC_OPT_FRONT_DENSE (default -1 = automatic, Mode R): k_front8's dense path -- a window of 6 rows that follows one in
  * which more than 512 of the wave's 768 half-lanes passed the low threshold (noise, texture) is processed by wave-wide
@@ -350,7 +363,7 @@ int hc_set_tuning(hc_ctx *ctx, int chunk_rows, int hyst_launches);
  * contractions (the 5x5 Gaussian sum, the 3x3 Sobel sums) run on the matrix pipe as v_mfma_i32_32x32x32_i8 (strips of 216
  * columns, blocks of 16 rows), for every run that allows it (input pitch >= round_up(width, 4), height x pitch < 2^32
  * -- other input views are staged first, so every one-channel run does; pipelined mode: the provisional map needs
- * width % 8 == 0 and height x output pitch < 2^32, other runs go without it).  Same results bit for bit; hc_last_run_info reports form 5; HC_OPT_FRONT_WPB 1 / 4
+ * width % 8 == 0 and height x output pitch < 2^32, other runs go without it).  Same results bit for bit; hc_last_run_info reports HC_FORM_FRONT_MX; HC_OPT_FRONT_WPB 1 / 4
  * picks its workgroup size.  Opt-in: measured on the MI355X (profiles/r04/mx_experiments.md) it takes 14 % less time than
  * k_front8 alone (1.83 against 2.14 ms per 1024 camera-like 1080p frames), 3-5 % less beside the hysteresis of the batch
  * before (2.37-2.43 against 2.50 ms), and half as much again on frames full of candidates (iid noise: 7.7 against 5.1 ms),

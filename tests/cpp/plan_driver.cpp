@@ -1,7 +1,9 @@
 // plan_driver.cpp -- the planner of cudacam_amd/csrc/host_plan.h, checked without a GPU (tests/test_plan_cpu.py builds this
 // with g++ under ASan + UBSan).  A context is modelled with the same helpers hc_create uses (frame_pitch,
 // plane_row_dwords, half_pays, half_dump_region, slot_wl_cap); every plan of the sweep must keep the capacity claims the
-// launchers and kernels rest on.  Prints "ok <plans checked>" or the first violations.
+// launchers and kernels rest on.  Every front plan the driver makes is also folded into a 64-bit FNV-1a digest, field by field:
+// tests/golden/plan_front_digest.json holds the value of the commit named there, so a restructured planner proves that it
+// plans what that one planned.  Prints "ok <plans checked> <digest>" or the first violations.
 #include "../../cudacam_amd/csrc/host_plan.h"
 
 #include <cstdio>
@@ -18,6 +20,49 @@ static void bad(const char *what, const FrontIn &in, const FrontPlan &P)
                 in.per_channel, (int)in.piped, P.form, P.fp.half, in.o.chunk, in.o.mx_mode, in.o.half_mode, in.in.pitch);
 }
 #define CHECK(cond, what) do { if (!(cond)) bad(what, in, P); } while (0)
+
+// ---- the digest: FNV-1a over every field of every FrontPlan, in the order the driver makes them -------------------
+static unsigned long long g_digest = 0xcbf29ce484222325ull;
+static void fold_byte(unsigned b) { g_digest = (g_digest ^ (b & 0xFFu)) * 0x100000001b3ull; }
+template <class T> static void fold(T v)  // an integer of any width, low byte first
+{
+  const unsigned long long u = (unsigned long long)v;
+  for (unsigned k = 0; k < sizeof(T); ++k) fold_byte((unsigned)(u >> (8 * k)));
+}
+template <class T> static void fold(T *p) { fold((uintptr_t)p); }  // (every pointer of a plan is null: hipcanny.hip patches them in)
+static void fold(bool b) { fold_byte(b ? 1 : 0); }
+static void fold(const char *s) { for (; s && *s; ++s) fold_byte((unsigned char)*s); fold_byte(0); }
+static void fold(const View &v) { fold(v.p); fold(v.pitch); fold(v.fs); }
+static void fold(const FrontPlan &P)
+{
+  const FrontParams &f = P.fp;
+  fold(P.error); fold(P.in_staged); fold(P.out_staged); fold(P.gray); fold(P.src); fold(P.mono); fold(P.dst);
+  fold(P.form); fold(P.prov); fold(P.zeroed_words); fold(P.waves); fold(P.mask); fold(P.mask_a);
+  fold(f.in); fold(f.bgr); fold(f.in_pitch); fold(f.in_frame_stride); fold(f.sbits); fold(f.cbits); fold(f.RD); fold(f.W); fold(f.H);
+  fold(f.nstrips); fold(f.nchunks); fold(f.nframes);
+#ifdef HC_LEGACY_FRONT
+  // The legacy build's digest leaves out two values that no kernel reads, and nothing else: `subchunks` in plans of any
+  // form but HC_FORM_FRONT4 (only k_front and launch_front use it) and `run_rows` in plans of the 4-px Mode O forms
+  // (k_front_o and k_front_o_ext go by chunk_rows).  The commit the golden digest comes from filled both for every form
+  // in one block that later code overwrote or left unread; the planner of today fills what the form's kernel reads.
+  if (P.form == HC_FORM_FRONT4) fold(f.subchunks);
+  if (!form_o_4px(P.form)) fold(f.run_rows);
+#else
+  fold(f.subchunks); fold(f.run_rows);
+#endif
+  fold(f.chunk_rows); fold(f.l2gradient); fold(f.total_items);
+  for (int k = 0; k < 3; ++k) { fold(f.a_lo[k]); fold(f.a_hi[k]); }
+  fold(f.blur); fold(f.blur_frame_stride); fold(f.nchunks_b); fold(f.run_rows_b); fold(f.total_items_b);
+  fold(f.prov_out); fold(f.prov_pitch); fold(f.prov_fs); fold(f.dbg_blur); fold(f.dbg_pitch); fold(f.dbg_fs);
+  fold(f.zeros); fold(f.dump); fold(f.dump_c); fold(f.dump_p); fold(f.zero_words); fold(f.zero_count);
+  fold(f.half); fold(f.one_wave); fold(f.nhalf); fold(f.dense_enter); fold(f.dense_leave); fold(f.wrap_limit);
+}
+static FrontPlan plan_folded(const FrontIn &in)
+{
+  const FrontPlan P = plan_front(in);
+  fold(P);
+  return P;
+}
 
 struct Ctx {  // what hc_create / hc_set_option derive
   int mode, C, W, H, per_channel, max_batch, RD, nstrips;
@@ -50,7 +95,7 @@ static FrontIn make_in(const Ctx &c, int n, bool piped, const FrontOpts &o, cons
 // the claims of the issue, for one front plan and the hysteresis plans that can follow it
 static void check(const Ctx &c, const FrontIn &in, const HystOpts &ho, bool full = true)
 {
-  const FrontPlan P = plan_front(in);
+  const FrontPlan P = plan_folded(in);
   ++g_plans;
   if (P.error) {  // only the product build's refusal of the round-1 forms may appear in this sweep
     CHECK(in.mode == HC_MODE_R && in.o.split != 2, "unexpected plan error");
@@ -59,26 +104,26 @@ static void check(const Ctx &c, const FrontIn &in, const HystOpts &ho, bool full
   const FrontParams &f = P.fp;
   const int H = in.H, W = in.W, n_out = in.per_channel ? 3 * in.n : in.n;
   const long per = in.per_channel ? 3 : 1;
-  const int rows = (P.form == -1 || P.form == 6 || P.form == 7) ? f.chunk_rows : f.run_rows;
+  const int rows = form_o_4px(P.form) ? f.chunk_rows : f.run_rows;
   CHECK(rows >= 1 && (long)f.nchunks * rows >= H, "nchunks * run_rows >= H");
   // the 4-px Mode O forms take hc_set_tuning's rows per work item as they are (any value >= 1, at most the frame)
-  if ((P.form == -1 || P.form == 6 || P.form == 7) && in.o.chunk)
+  if (form_o_4px(P.form) && in.o.chunk)
     CHECK(f.chunk_rows == std::min(std::max(in.o.chunk, 1), H) && f.nchunks == (H + f.chunk_rows - 1) / f.chunk_rows, "4-px Mode O forms: chunk_rows = min(max(chunk, 1), H)");
   long units = (long)n_out * f.nstrips;
-  if (P.form == 4) units = (((long)in.n * front8_half_strips(W) + 1) / 2) * per;
-  if (P.form == 5) CHECK(f.nstrips == front_mx_strips(W), "mx strips");
-  if (P.form == 2 || P.form == 3 || P.form == 4) CHECK(f.nstrips == front8_strips(W) && (f.run_rows + 4) % F8_SUB == 0, "f8 strips / windows");
+  if (P.form == HC_FORM_FRONT8_HALF) units = (((long)in.n * front8_half_strips(W) + 1) / 2) * per;
+  if (P.form == HC_FORM_FRONT_MX) CHECK(f.nstrips == front_mx_strips(W), "mx strips");
+  if (form_8px(P.form)) CHECK(f.nstrips == front8_strips(W) && (f.run_rows + 4) % F8_SUB == 0, "f8 strips / windows");
   CHECK(f.total_items > 0 && (long)f.total_items == units * f.nchunks, "total_items = units x chunks");
-  if (P.form == 2 || P.form == 3 || P.form == 4)  // the dead `!can8` branch: rows always hold whole 8-pixel groups
+  if (form_8px(P.form))  // the dead `!can8` branch: rows always hold whole 8-pixel groups
     CHECK(f.in_pitch >= round_up((size_t)W, 8) * (size_t)(f.bgr ? 3 : 1), "8-px kernels read whole groups");
-  CHECK((f.in_pitch | f.in_frame_stride) % (P.form == 7 ? 2 : 4) == 0 && !reaches_4g(H, f.in_pitch), "input rows within 32-bit offsets, aligned");
-  if (P.form == 4) {  // the `fits` inequalities, from the buffers the kernel really gets
+  CHECK((f.in_pitch | f.in_frame_stride) % (P.form == HC_FORM_O_GRADIENTS ? 2 : 4) == 0 && !reaches_4g(H, f.in_pitch), "input rows within 32-bit offsets, aligned");
+  if (P.form == HC_FORM_FRONT8_HALF) {  // the `fits` inequalities, from the buffers the kernel really gets
     const size_t R = in.dump_region;
     CHECK(f.half == 1 && f.nhalf == front8_half_strips(W) && R != 0, "HALF parameters");
     CHECK(f.in_frame_stride + 32768 <= R && per * sizeof(u32) * (size_t)in.RD * H + 4096 <= R, "HALF: lane offsets fit the dump region");
     CHECK((unsigned long long)f.in_frame_stride + (unsigned long long)H * f.in_pitch < (1ull << 32), "HALF: input offsets below 4 GiB");
     if (P.prov) CHECK(per * f.prov_fs + 16384 <= R && (unsigned long long)per * f.prov_fs + (unsigned long long)H * f.prov_pitch < (1ull << 32), "HALF: provisional map offsets");
-  } else CHECK(f.half == 0, "half only in form 4");
+  } else CHECK(f.half == 0, "half only in HC_FORM_FRONT8_HALF");
   if (P.prov) CHECK(in.piped && (unsigned long long)H * P.dst.pitch < (1ull << 32) && f.prov_pitch == P.dst.pitch, "prov never with H * pitch >= 2^32");
   CHECK(P.zeroed_words <= run_flag_words(c.wl_cap) && f.zero_count == P.zeroed_words, "zeroed_words within d_flags");
   CHECK(P.waves == 0 || P.waves == 1 || P.waves == 3 || P.waves == 4, "waves per workgroup");
@@ -167,7 +212,7 @@ static void sweep_geometry(int W, int H, bool full)
 // __graft_entry__.py): (input staged, output staged, form)
 static void expect(const char *what, const Ctx &c, int n, bool piped, const FrontOpts &o, const View &in, const View &out, int staged_in, int staged_out, int form, bool grads = false)
 {
-  const FrontPlan P = plan_front(make_in(c, n, piped, o, in, out, grads));
+  const FrontPlan P = plan_folded(make_in(c, n, piped, o, in, out, grads));
   if (P.error || P.form != form || (staged_in >= 0 && P.in_staged != (staged_in != 0)) || (staged_out >= 0 && P.out_staged != (staged_out != 0))) {
     ++g_fail;
     std::printf("FAIL pinned %s: got (%d, %d, %d)%s\n", what, (int)P.in_staged, (int)P.out_staged, P.form, P.error ? P.error : "");
@@ -177,7 +222,7 @@ static void expect(const char *what, const Ctx &c, int n, bool piped, const Fron
 static void expect_cut(const char *what, const Ctx &c, int n, const FrontOpts &o, bool grads, int form, int chunk_rows, int nchunks, int total_items)
 {
   const View in = grads ? View{ 0x10000000u, (size_t)2 * c.C * c.W, (size_t)2 * c.C * c.W * c.H } : c.own_in;
-  const FrontPlan P = plan_front(make_in(c, n, false, o, in, c.own_out, grads));
+  const FrontPlan P = plan_folded(make_in(c, n, false, o, in, c.own_out, grads));
   if (P.error || P.form != form || P.fp.chunk_rows != chunk_rows || P.fp.nchunks != nchunks || P.fp.total_items != total_items) {
     ++g_fail;
     std::printf("FAIL pinned cut %s: got form %d, %d rows x %d, %d items%s\n", what, P.form, P.fp.chunk_rows, P.fp.nchunks, P.fp.total_items, P.error ? P.error : "");
@@ -186,7 +231,7 @@ static void expect_cut(const char *what, const Ctx &c, int n, const FrontOpts &o
 // the work split of the 8-px forms on the contexts' internal buffers (hc_run): (form, rows per run, runs per strip, items)
 static void expect_runs(const char *what, const Ctx &c, int n, const FrontOpts &o, int form, int run_rows, int nchunks, int total_items)
 {
-  const FrontPlan P = plan_front(make_in(c, n, false, o, c.own_in, c.own_out));
+  const FrontPlan P = plan_folded(make_in(c, n, false, o, c.own_in, c.own_out));
   if (P.error || P.form != form || P.in_staged || P.out_staged || P.fp.run_rows != run_rows || P.fp.nchunks != nchunks || P.fp.total_items != total_items) {
     ++g_fail;
     std::printf("FAIL pinned runs %s (%d x %d, set length %d): got form %d, %d rows x %d, %d items%s\n", what, c.W, c.H, o.chunk, P.form, P.fp.run_rows, P.fp.nchunks, P.fp.total_items, P.error ? P.error : "");
@@ -196,7 +241,7 @@ static void expect_runs(const char *what, const Ctx &c, int n, const FrontOpts &
 static void expect_prov(const char *what, const Ctx &c, int n, const FrontOpts &o, int form, int run_rows, int nchunks, int total_items)
 {
   const View in{ 0x10000000u, (size_t)c.W * c.C, (size_t)c.W * c.C * c.H }, out{ 0x20000000u, (size_t)c.W, (size_t)c.W * c.H };
-  const FrontPlan P = plan_front(make_in(c, n, true, o, in, out));
+  const FrontPlan P = plan_folded(make_in(c, n, true, o, in, out));
   if (P.error || P.form != form || P.in_staged || P.out_staged || !P.prov || P.fp.prov_pitch != (u32)c.W || P.fp.prov_fs != (size_t)c.W * c.H
       || P.fp.run_rows != run_rows || P.fp.nchunks != nchunks || P.fp.total_items != total_items) {
     ++g_fail;
@@ -217,58 +262,58 @@ static void pinned_front8_runs()
     const Ctx c = make_ctx(HC_MODE_R, 1, 504, 41, 0, 3, false), co = make_ctx(HC_MODE_O, 1, 504, 41, 0, 3, false);
     const int cut[][3] = { { 2, 2, 21 }, { 8, 8, 6 }, { 14, 14, 3 }, { 20, 20, 3 }, { 26, 26, 2 }, { 32, 32, 2 }, { 38, 38, 2 }, { 41, 44, 1 }, { 100, 44, 1 } };
     for (const auto &k : cut) {
-      expect_runs("k_front8 mono", c, 3, with(f8, k[0]), 2, k[1], k[2], 6 * k[2]);
-      expect_runs("k_front8o", co, 3, with(fo, k[0]), 3, k[1], k[2], 6 * k[2]);
+      expect_runs("k_front8 mono", c, 3, with(f8, k[0]), HC_FORM_FRONT8, k[1], k[2], 6 * k[2]);
+      expect_runs("k_front8o", co, 3, with(fo, k[0]), HC_FORM_FRONT8O, k[1], k[2], 6 * k[2]);
     }
     FrontOpts l2 = with(fo, 26); l2.l2gradient = 1;
-    expect_runs("k_front8o L2, a second strip of one column", make_ctx(HC_MODE_O, 1, 497, 41, 0, 3, false), 3, l2, 3, 26, 2, 12);
-    expect_runs("k_front8, one strip", make_ctx(HC_MODE_R, 1, 496, 41, 0, 3, false), 3, with(f8, 14), 2, 14, 3, 9);
+    expect_runs("k_front8o L2, a second strip of one column", make_ctx(HC_MODE_O, 1, 497, 41, 0, 3, false), 3, l2, HC_FORM_FRONT8O, 26, 2, 12);
+    expect_runs("k_front8, one strip", make_ctx(HC_MODE_R, 1, 496, 41, 0, 3, false), 3, with(f8, 14), HC_FORM_FRONT8, 14, 3, 9);
   }
   {  // leg A: the last run of every length comes from heights 1 .. 22 under runs of 2, 8 and 14 rows
     const int cut[][4] = { { 1, 2, 2, 1 }, { 1, 8, 2, 1 }, { 3, 2, 2, 2 }, { 3, 14, 8, 1 }, { 4, 8, 8, 1 }, { 5, 8, 8, 1 }, { 7, 2, 2, 4 }, { 8, 14, 8, 1 },
                            { 9, 8, 8, 2 }, { 9, 14, 14, 1 }, { 15, 14, 14, 2 }, { 16, 8, 8, 2 }, { 17, 8, 8, 3 }, { 21, 2, 2, 11 }, { 21, 14, 14, 2 }, { 22, 14, 14, 2 }, { 22, 2, 2, 11 },
                            { 8, 0, 8, 1 }, { 21, 0, 14, 2 }, { 22, 0, 14, 2 } };  // (0: the automatic split of a small batch)
     for (const auto &k : cut) {
-      expect_runs("k_front8 heights", make_ctx(HC_MODE_R, 1, 504, k[0], 0, 3, false), 3, with(f8, k[1]), 2, k[2], k[3], 6 * k[3]);
-      expect_runs("k_front8o heights", make_ctx(HC_MODE_O, 1, 504, k[0], 0, 3, false), 3, with(fo, k[1]), 3, k[2], k[3], 6 * k[3]);
+      expect_runs("k_front8 heights", make_ctx(HC_MODE_R, 1, 504, k[0], 0, 3, false), 3, with(f8, k[1]), HC_FORM_FRONT8, k[2], k[3], 6 * k[3]);
+      expect_runs("k_front8o heights", make_ctx(HC_MODE_O, 1, 504, k[0], 0, 3, false), 3, with(fo, k[1]), HC_FORM_FRONT8O, k[2], k[3], 6 * k[3]);
     }
-    expect_runs("tiny", make_ctx(HC_MODE_R, 1, 5, 7, 0, 3, false), 3, with(f8, 2), 2, 2, 4, 12);
-    expect_runs("tiny, half", make_ctx(HC_MODE_R, 1, 5, 7, 0, 3, true), 3, with(half, 2), 4, 2, 4, 8);
+    expect_runs("tiny", make_ctx(HC_MODE_R, 1, 5, 7, 0, 3, false), 3, with(f8, 2), HC_FORM_FRONT8, 2, 4, 12);
+    expect_runs("tiny, half", make_ctx(HC_MODE_R, 1, 5, 7, 0, 3, true), 3, with(half, 2), HC_FORM_FRONT8_HALF, 2, 4, 8);
   }
   // each form once: dense forced, BGR -> grey, per-channel (nine output frames)
-  expect_runs("k_front8 dense", make_ctx(HC_MODE_R, 1, 504, 21, 0, 3, false), 3, with(f8, 8, 1), 2, 8, 3, 18);
-  expect_runs("k_front8 BGR", make_ctx(HC_MODE_R, 3, 504, 21, 0, 3, false), 3, with(f8, 14), 2, 14, 2, 12);
-  expect_runs("k_front8 per-channel", make_ctx(HC_MODE_R, 3, 504, 21, 1, 3, false), 3, with(f8, 2), 2, 2, 11, 198);
+  expect_runs("k_front8 dense", make_ctx(HC_MODE_R, 1, 504, 21, 0, 3, false), 3, with(f8, 8, 1), HC_FORM_FRONT8, 8, 3, 18);
+  expect_runs("k_front8 BGR", make_ctx(HC_MODE_R, 3, 504, 21, 0, 3, false), 3, with(f8, 14), HC_FORM_FRONT8, 14, 2, 12);
+  expect_runs("k_front8 per-channel", make_ctx(HC_MODE_R, 3, 504, 21, 1, 3, false), 3, with(f8, 2), HC_FORM_FRONT8, 2, 11, 198);
   // the half-strip form: 488 columns are three half-strips, nine units, five pairs; 241 columns two, three pairs; 240 one, two pairs
-  expect_runs("half mono", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 8), 4, 8, 6, 30);
-  expect_runs("half mono dense", make_ctx(HC_MODE_R, 1, 488, 21, 0, 3, true), 3, with(half, 14, 1), 4, 14, 2, 10);
-  expect_runs("half BGR", make_ctx(HC_MODE_R, 3, 241, 41, 0, 3, true), 3, with(half, 20), 4, 20, 3, 9);
-  expect_runs("half per-channel", make_ctx(HC_MODE_R, 3, 488, 41, 1, 3, true), 3, with(half, 2), 4, 2, 21, 315);
-  expect_runs("half, one half-strip", make_ctx(HC_MODE_R, 1, 240, 41, 0, 3, true), 3, with(half, 38), 4, 38, 2, 4);
+  expect_runs("half mono", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 8), HC_FORM_FRONT8_HALF, 8, 6, 30);
+  expect_runs("half mono dense", make_ctx(HC_MODE_R, 1, 488, 21, 0, 3, true), 3, with(half, 14, 1), HC_FORM_FRONT8_HALF, 14, 2, 10);
+  expect_runs("half BGR", make_ctx(HC_MODE_R, 3, 241, 41, 0, 3, true), 3, with(half, 20), HC_FORM_FRONT8_HALF, 20, 3, 9);
+  expect_runs("half per-channel", make_ctx(HC_MODE_R, 3, 488, 41, 1, 3, true), 3, with(half, 2), HC_FORM_FRONT8_HALF, 2, 21, 315);
+  expect_runs("half, one half-strip", make_ctx(HC_MODE_R, 1, 240, 41, 0, 3, true), 3, with(half, 38), HC_FORM_FRONT8_HALF, 38, 2, 4);
   {  // k_front_mx: ceil(H / c) runs of ceil(H / runs) rows; 224 columns: two strips, six units.  Both sides of the block
      // borders front_mx_run_rows(1) = 12 and (2) = 28, a last run of 1 and of 16 rows, runs of one row, the frame
     if (front_mx_run_rows(1) != 12 || front_mx_run_rows(2) != 28) { ++g_fail; std::printf("FAIL front_mx_run_rows\n"); }
     const int cut[][4] = { { 24, 12, 12, 2 }, { 25, 13, 13, 2 }, { 26, 13, 13, 2 }, { 36, 12, 12, 3 }, { 39, 13, 13, 3 }, { 56, 28, 28, 2 }, { 57, 29, 29, 2 }, { 58, 29, 29, 2 },
                            { 84, 28, 28, 3 }, { 87, 29, 29, 3 }, { 3, 2, 2, 2 }, { 33, 17, 17, 2 }, { 21, 8, 7, 3 }, { 21, 14, 11, 2 }, { 41, 1, 1, 41 }, { 41, 6, 6, 7 }, { 41, 14, 14, 3 },
                            { 41, 21, 21, 2 }, { 41, 41, 41, 1 }, { 41, 100, 41, 1 } };
-    for (const auto &k : cut) expect_runs("k_front_mx", make_ctx(HC_MODE_R, 1, 224, k[0], 0, 3, false), 3, with(mx, k[1]), 5, k[2], k[3], 6 * k[3]);
-    expect_runs("k_front_mx, a second strip of one column", make_ctx(HC_MODE_R, 1, 217, 41, 0, 3, false), 3, with(mx, 9), 5, 9, 5, 30);
-    expect_runs("k_front_mx, one strip", make_ctx(HC_MODE_R, 1, 216, 41, 0, 3, false), 3, with(mx, 11), 5, 11, 4, 12);
+    for (const auto &k : cut) expect_runs("k_front_mx", make_ctx(HC_MODE_R, 1, 224, k[0], 0, 3, false), 3, with(mx, k[1]), HC_FORM_FRONT_MX, k[2], k[3], 6 * k[3]);
+    expect_runs("k_front_mx, a second strip of one column", make_ctx(HC_MODE_R, 1, 217, 41, 0, 3, false), 3, with(mx, 9), HC_FORM_FRONT_MX, 9, 5, 30);
+    expect_runs("k_front_mx, one strip", make_ctx(HC_MODE_R, 1, 216, 41, 0, 3, false), 3, with(mx, 11), HC_FORM_FRONT_MX, 11, 4, 12);
   }
   // the pipelined leg: 41 rows at the provisional-map width of each kernel; every form keeps its provisional map (the
   // half-strip form: the `fits` terms with the map, per-channel with three maps per frame)
-  expect_prov("k_front8 mono", make_ctx(HC_MODE_R, 1, 504, 41, 0, 3, false), 3, with(f8, 8), 2, 8, 6, 36);
-  expect_prov("k_front8 dense", make_ctx(HC_MODE_R, 1, 504, 41, 0, 3, false), 3, with(f8, 2, 1), 2, 2, 21, 126);
-  expect_prov("k_front8 BGR", make_ctx(HC_MODE_R, 3, 504, 41, 0, 3, false), 3, with(f8, 14), 2, 14, 3, 18);
-  expect_prov("k_front8 per-channel", make_ctx(HC_MODE_R, 3, 504, 41, 1, 3, false), 3, with(f8, 100), 2, 44, 1, 18);
-  expect_prov("half mono", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 2), 4, 2, 21, 105);
-  expect_prov("half mono dense", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 20, 1), 4, 20, 3, 15);
-  expect_prov("half BGR", make_ctx(HC_MODE_R, 3, 488, 41, 0, 3, true), 3, with(half, 41), 4, 44, 1, 5);
-  expect_prov("half per-channel", make_ctx(HC_MODE_R, 3, 488, 41, 1, 3, true), 3, with(half, 8), 4, 8, 6, 90);
-  expect_prov("k_front8o", make_ctx(HC_MODE_O, 1, 504, 41, 0, 3, false), 3, with(fo, 26), 3, 26, 2, 12);
-  expect_prov("k_front8o L2", make_ctx(HC_MODE_O, 1, 504, 41, 0, 3, false), 3, with(l2o, 38), 3, 38, 2, 12);
-  expect_prov("k_front_mx", make_ctx(HC_MODE_R, 1, 224, 41, 0, 3, false), 3, with(mx, 6), 5, 6, 7, 42);
-  expect_prov("k_front_mx, runs of one row", make_ctx(HC_MODE_R, 1, 224, 41, 0, 3, false), 3, with(mx, 1), 5, 1, 41, 246);
+  expect_prov("k_front8 mono", make_ctx(HC_MODE_R, 1, 504, 41, 0, 3, false), 3, with(f8, 8), HC_FORM_FRONT8, 8, 6, 36);
+  expect_prov("k_front8 dense", make_ctx(HC_MODE_R, 1, 504, 41, 0, 3, false), 3, with(f8, 2, 1), HC_FORM_FRONT8, 2, 21, 126);
+  expect_prov("k_front8 BGR", make_ctx(HC_MODE_R, 3, 504, 41, 0, 3, false), 3, with(f8, 14), HC_FORM_FRONT8, 14, 3, 18);
+  expect_prov("k_front8 per-channel", make_ctx(HC_MODE_R, 3, 504, 41, 1, 3, false), 3, with(f8, 100), HC_FORM_FRONT8, 44, 1, 18);
+  expect_prov("half mono", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 2), HC_FORM_FRONT8_HALF, 2, 21, 105);
+  expect_prov("half mono dense", make_ctx(HC_MODE_R, 1, 488, 41, 0, 3, true), 3, with(half, 20, 1), HC_FORM_FRONT8_HALF, 20, 3, 15);
+  expect_prov("half BGR", make_ctx(HC_MODE_R, 3, 488, 41, 0, 3, true), 3, with(half, 41), HC_FORM_FRONT8_HALF, 44, 1, 5);
+  expect_prov("half per-channel", make_ctx(HC_MODE_R, 3, 488, 41, 1, 3, true), 3, with(half, 8), HC_FORM_FRONT8_HALF, 8, 6, 90);
+  expect_prov("k_front8o", make_ctx(HC_MODE_O, 1, 504, 41, 0, 3, false), 3, with(fo, 26), HC_FORM_FRONT8O, 26, 2, 12);
+  expect_prov("k_front8o L2", make_ctx(HC_MODE_O, 1, 504, 41, 0, 3, false), 3, with(l2o, 38), HC_FORM_FRONT8O, 38, 2, 12);
+  expect_prov("k_front_mx", make_ctx(HC_MODE_R, 1, 224, 41, 0, 3, false), 3, with(mx, 6), HC_FORM_FRONT_MX, 6, 7, 42);
+  expect_prov("k_front_mx, runs of one row", make_ctx(HC_MODE_R, 1, 224, 41, 0, 3, false), 3, with(mx, 1), HC_FORM_FRONT_MX, 1, 41, 246);
 }
 
 static void pinned()
@@ -278,50 +323,50 @@ static void pinned()
   auto tout = [](const Ctx &c) { return View{ 0x20000000u, (size_t)c.W, (size_t)c.W * c.H }; };
   {  // test_half_form_pipelined_device_buffers: 640 x 480, 5 frames, pipelined
     const Ctx c = make_ctx(HC_MODE_R, 1, 640, 480, 0, 5, false);
-    o = d; expect("half auto", c, 5, true, o, tight(c), tout(c), 0, 0, 4);
-    o.half_mode = 0; expect("half 0", c, 5, true, o, tight(c), tout(c), 0, 0, 2);
-    o.half_mode = 1; expect("half 1", c, 5, true, o, tight(c), tout(c), 0, 0, 4);
+    o = d; expect("half auto", c, 5, true, o, tight(c), tout(c), 0, 0, HC_FORM_FRONT8_HALF);
+    o.half_mode = 0; expect("half 0", c, 5, true, o, tight(c), tout(c), 0, 0, HC_FORM_FRONT8);
+    o.half_mode = 1; expect("half 1", c, 5, true, o, tight(c), tout(c), 0, 0, HC_FORM_FRONT8_HALF);
   }
   for (int chunk : { 8, 20, 50, 300 }) {  // test_half_form_run_lengths_and_thresholds (hc_run: the internal buffers)
     const Ctx c = make_ctx(HC_MODE_R, 1, 640, 230, 0, 3, true);
-    o = d; o.half_mode = 1; o.chunk = chunk; expect("half chunk", c, 3, false, o, c.own_in, c.own_out, -1, -1, 4);
+    o = d; o.half_mode = 1; o.chunk = chunk; expect("half chunk", c, 3, false, o, c.own_in, c.own_out, -1, -1, HC_FORM_FRONT8_HALF);
   }
   for (int w : { 96, 500, 640, 1000 })  // test_half_form_three_channel
     for (int pc : { 0, 1 }) {
       const Ctx c = make_ctx(HC_MODE_R, 3, w, 70, pc, 3, true);
-      o = d; o.half_mode = 1; o.debug_taps = true; expect("half 3ch", c, 3, false, o, c.own_in, c.own_out, -1, -1, 4);
+      o = d; o.half_mode = 1; o.debug_taps = true; expect("half 3ch", c, 3, false, o, c.own_in, c.own_out, -1, -1, HC_FORM_FRONT8_HALF);
     }
   {  // __graft_entry__.py smoke: 640 x 480 x 2 with HC_OPT_FRONT_MX
     const Ctx c = make_ctx(HC_MODE_R, 1, 640, 480, 0, 2, false);
-    o = d; o.mx_mode = 1; expect("smoke mx", c, 2, false, o, c.own_in, c.own_out, -1, -1, 5);
+    o = d; o.mx_mode = 1; expect("smoke mx", c, 2, false, o, c.own_in, c.own_out, -1, -1, HC_FORM_FRONT_MX);
   }
   for (int ap5 = 0; ap5 <= 1; ++ap5)  // test_gpu_canny_o_ext: aperture 5 -> 6, gradients -> 7
     for (int C : { 1, 3 }) {
       const Ctx c = make_ctx(HC_MODE_O, C, 322, 97, 0, 2, false);
       o = d; o.aperture = ap5 ? 5 : 3;
-      if (ap5) expect("aperture 5", c, 2, false, o, c.own_in, c.own_out, -1, -1, 6);
-      expect("gradients", c, 2, true, o, View{ 0x10000000u, (size_t)2 * C * 322 + 4, ((size_t)2 * C * 322 + 4) * 97 }, tout(c), 0, -1, 7, true);
+      if (ap5) expect("aperture 5", c, 2, false, o, c.own_in, c.own_out, -1, -1, HC_FORM_O_APERTURE5);
+      expect("gradients", c, 2, true, o, View{ 0x10000000u, (size_t)2 * C * 322 + 4, ((size_t)2 * C * 322 + 4) * 97 }, tout(c), 0, -1, HC_FORM_O_GRADIENTS, true);
     }
   {  // the automatic work split of the 4-px Mode O forms (hc_set_tuning 0): ceil(12288 / (frames x strips)) items per strip, of 16 rows or more
     FrontOpts a5 = d; a5.aperture = 5;
     const Ctx one = make_ctx(HC_MODE_O, 3, 322, 97, 0, 1, false);  // one frame, two strips: 7 items of 14 rows per strip
-    expect_cut("one frame", one, 1, d, false, -1, 14, 7, 14);
-    expect_cut("one frame, aperture 5", one, 1, a5, false, 6, 14, 7, 14);
-    expect_cut("one frame, gradients", one, 1, d, true, 7, 14, 7, 14);
+    expect_cut("one frame", one, 1, d, false, HC_FORM_FRONT_O, 14, 7, 14);
+    expect_cut("one frame, aperture 5", one, 1, a5, false, HC_FORM_O_APERTURE5, 14, 7, 14);
+    expect_cut("one frame, gradients", one, 1, d, true, HC_FORM_O_GRADIENTS, 14, 7, 14);
     const Ctx hd = make_ctx(HC_MODE_O, 1, 1920, 1080, 0, 1024, false);  // 1024 frames of 1080p: 8192 strips, two items of 540 rows each
-    expect_cut("1080p x 1024, aperture 5", hd, 1024, a5, false, 6, 540, 2, 16384);
+    expect_cut("1080p x 1024, aperture 5", hd, 1024, a5, false, HC_FORM_O_APERTURE5, 540, 2, 16384);
     // test_gpu_mode_o_chunks.py: one strip, 6144 frames -> two items per strip, 12288 -> one spans the frame
     const Ctx s3 = make_ctx(HC_MODE_O, 3, 64, 26, 0, 12288, false), s1 = make_ctx(HC_MODE_O, 1, 64, 26, 0, 12288, false);
-    expect_cut("two per strip", s3, 6144, d, false, -1, 13, 2, 12288);
-    expect_cut("one per strip", s3, 12288, d, false, -1, 26, 1, 12288);
-    expect_cut("two per strip, aperture 5", s1, 6144, a5, false, 6, 13, 2, 12288);
-    expect_cut("one per strip, aperture 5", s1, 12288, a5, false, 6, 26, 1, 12288);
-    expect_cut("two per strip, gradients", s1, 6144, d, true, 7, 13, 2, 12288);
-    expect_cut("one per strip, gradients", s1, 12288, d, true, 7, 26, 1, 12288);
+    expect_cut("two per strip", s3, 6144, d, false, HC_FORM_FRONT_O, 13, 2, 12288);
+    expect_cut("one per strip", s3, 12288, d, false, HC_FORM_FRONT_O, 26, 1, 12288);
+    expect_cut("two per strip, aperture 5", s1, 6144, a5, false, HC_FORM_O_APERTURE5, 13, 2, 12288);
+    expect_cut("one per strip, aperture 5", s1, 12288, a5, false, HC_FORM_O_APERTURE5, 26, 1, 12288);
+    expect_cut("two per strip, gradients", s1, 6144, d, true, HC_FORM_O_GRADIENTS, 13, 2, 12288);
+    expect_cut("one per strip, gradients", s1, 12288, d, true, HC_FORM_O_GRADIENTS, 26, 1, 12288);
     for (int chunk : { 1, 7, 17, 300 }) {  // ... and a set length, as it is
       FrontOpts t = a5; t.chunk = chunk;
       const int rows = std::min(chunk, 97), items = (97 + rows - 1) / rows;
-      expect_cut("set length", one, 1, t, false, 6, rows, items, 2 * items);
+      expect_cut("set length", one, 1, t, false, HC_FORM_O_APERTURE5, rows, items, 2 * items);
     }
   }
   for (int mx = 0; mx <= 1; ++mx) {  // test_gpu_views: a 4 GiB-reaching view of a wide parent, w x h = 64 x 1024 rows of a 4 MiB pitch
@@ -331,16 +376,16 @@ static void pinned()
     o = d; o.half_mode = 0; o.mx_mode = mx;
     const View far{ 0x40000000u, pitch, pitch * h };
     FrontIn fi = make_in(c, 1, true, o, tight(c), far);
-    const FrontPlan P = plan_front(fi);
-    if (P.prov || P.in_staged || P.out_staged || P.form != (mx ? 5 : 2)) { ++g_fail; std::printf("FAIL pinned far output view\n"); }
-    expect("far input view", c, 1, true, o, far, tout(c), 1, 0, mx ? 5 : 2);
+    const FrontPlan P = plan_folded(fi);
+    if (P.prov || P.in_staged || P.out_staged || P.form != (mx ? HC_FORM_FRONT_MX : HC_FORM_FRONT8)) { ++g_fail; std::printf("FAIL pinned far output view\n"); }
+    expect("far input view", c, 1, true, o, far, tout(c), 1, 0, mx ? HC_FORM_FRONT_MX : HC_FORM_FRONT8);
   }
   {  // non-final stages plan no front kernel
     const Ctx c = make_ctx(HC_MODE_R, 3, 100, 50, 0, 2, false);
     FrontIn fi = make_in(c, 2, false, d, tight(c), tout(c));
     fi.stage = HC_STAGE_NMS;
-    const FrontPlan P = plan_front(fi);
-    if (P.form != -1 || P.in_staged || P.out_staged || !P.gray) { ++g_fail; std::printf("FAIL pinned stage tap\n"); }
+    const FrontPlan P = plan_folded(fi);
+    if (P.form != HC_FORM_FRONT_O || P.in_staged || P.out_staged || !P.gray) { ++g_fail; std::printf("FAIL pinned stage tap\n"); }
   }
 }
 
@@ -434,6 +479,6 @@ int main()
   chain_watch();
   if (plane_row_dwords(8184) != 256 || plane_row_dwords(8185) != 0) { ++g_fail; std::printf("FAIL width limit\n"); }
   if (g_fail) { std::printf("%ld violations in %ld plans\n", g_fail, g_plans); return 1; }
-  std::printf("ok %ld\n", g_plans);
+  std::printf("ok %ld %016llx\n", g_plans, g_digest);
   return 0;
 }

@@ -18,21 +18,46 @@ slot rule calls big), and the whole option product where width and height are bo
 * the forms the GPU tests pin (half strips, k_front_mx, k_front_o_ext, the 4 GiB views, the smoke run);
 * ChainWatch on synthetic traces: trial after three outlasting runs and run >= 5, kept only below 0.97 x the pre-trial
   mean, back-off 64 doubling to 4096, back to two slots after 16 light runs doubling to 1024, one wave above 0.25 and
-  back below 0.03, the chain_told overrides."""
+  back below 0.03, the chain_told overrides.
+
+The driver also folds every field of every front plan it makes into a 64-bit FNV-1a digest.  tests/golden/
+plan_front_digest.json holds the plan count and the digests of both builds (the product's, and -DHC_LEGACY_FRONT) as the
+planner of the commit named there gave them: a planner that is restructured must still plan exactly that.  The legacy
+digest leaves out two values no kernel reads (`subchunks` but for form 0, `run_rows` of forms -1 / 6 / 7)."""
+import json
 import os
 import subprocess
 
 from test_sanitizers import ENV, ROOT, SAN, _cc
 
 
+DRIVER = os.path.join(ROOT, "tests", "cpp", "plan_driver.cpp")
+with open(os.path.join(ROOT, "tests", "golden", "plan_front_digest.json")) as _f:
+    GOLDEN = json.load(_f)
+
+
+def _run_driver(exe, env=None):
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=1500, env=env)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-4000:] + out.stderr[-4000:]
+    return out.stdout.split()
+
+
 def test_planner_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "plan_driver")
-    _cc(["g++", "-std=c++17", "-Wall", "-Werror", *SAN, "-o", exe, os.path.join(ROOT, "tests", "cpp", "plan_driver.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=1500, env=ENV)
-    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-4000:] + out.stderr[-4000:]
-    assert int(out.stdout.split()[1]) > 10 * 1000 * 1000
+    _cc(["g++", "-std=c++17", "-Wall", "-Werror", *SAN, "-o", exe, DRIVER])
+    words = _run_driver(exe, ENV)
+    assert int(words[1]) > 10 * 1000 * 1000
+    assert (int(words[1]), words[2]) == (GOLDEN["plans"], GOLDEN["digest"])
 
 
 def test_planner_builds_for_the_legacy_library(tmp_path):
     """The round-1 arithmetic (HC_LEGACY_FRONT) stays behind its macro and compiles without HIP as well."""
-    _cc(["g++", "-std=c++17", "-Wall", "-Werror", "-DHC_LEGACY_FRONT", "-fsyntax-only", os.path.join(ROOT, "tests", "cpp", "plan_driver.cpp")])
+    _cc(["g++", "-std=c++17", "-Wall", "-Werror", "-DHC_LEGACY_FRONT", "-fsyntax-only", DRIVER])
+
+
+def test_legacy_planner_plans_what_the_golden_commit_planned(tmp_path):
+    """The -DHC_LEGACY_FRONT build run as well (-O2, no sanitizers): its invariants, pinned plans and digest."""
+    exe = str(tmp_path / "plan_driver_legacy")
+    _cc(["g++", "-std=c++17", "-Wall", "-Werror", "-O2", "-DHC_LEGACY_FRONT", "-o", exe, DRIVER])
+    words = _run_driver(exe)
+    assert (int(words[1]), words[2]) == (GOLDEN["plans"], GOLDEN["digest_legacy"])
