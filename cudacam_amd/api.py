@@ -54,6 +54,8 @@ OPT_FRONT_MX = 12
 OPT_APERTURE = 13   # mode O: cv::Canny's apertureSize, 3 (default) or 5
 OPT_TEST_HYST_LATE_GRID, OPT_TEST_HYST_LOOP, OPT_TEST_HYST_DIAG, OPT_TEST_HYST_GEOM, OPT_TEST_DENSE_ENTER, OPT_TEST_DENSE_LEAVE = 100, 101, 102, 103, 104, 105   # test / diagnostic hooks
 TAP_BLUR, TAP_THRESH = 1, 2
+# front forms hc_last_run_info reports for canny_device at apertures 7 / -1 (the header's HC_FORM_O_APERTURE7 / HC_FORM_O_SCHARR)
+FORM_O_APERTURE7, FORM_O_SCHARR = 8, 9
 # words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
 SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
@@ -64,7 +66,7 @@ ABI_SYMBOLS = [
     "hc_device_ptrs", "hc_last_hysteresis_info", "hc_hysteresis_stats", "hc_set_tuning", "hc_set_option", "hc_selftest", "hc_last_error", "hc_version",
     "hc_host_alloc", "hc_host_free", "hc_profile_get_front", "hc_debug_tap", "hc_use_own_stream", "hc_profile_get_intervals", "hc_last_run_info", "hc_pipeline_depth", "hc_pipeline_slots_in_use", "hc_front_waves_per_workgroup",
     "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
-    "hc_derivatives_device",
+    "hc_derivatives_device", "hc_canny_device",
 ]
 
 _lib = None
@@ -119,6 +121,7 @@ def load_library(legacy=False):
     L.hc_hysteresis_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i]
     L.hc_run_gradients_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, i]
     L.hc_derivatives_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, sz, i, i]
+    L.hc_canny_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, C.c_double, C.c_double, i, i]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -380,6 +383,28 @@ class Context:
         row = self.c * self.w
         self.derivatives_device(src.data_ptr(), row, row * self.h, dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * self.h, n, ksize)
         self.run_gradients_device(dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * self.h, out.data_ptr(), self.w, self.w * self.h, n)
+        self.sync()
+        return out.cpu().numpy()
+
+    def canny_device(self, d_in, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes, low, high, aperture=3, l2gradient=False):
+        """cv::Canny(img, edges, low, high, aperture, l2gradient) on device memory (mode O, hc_canny_device): thresholds in
+        cv::Canny's units, aperture 3, 5, 7 or -1 (Scharr), all per call -- the context's thresholds and options are neither
+        read nor changed.  Apertures 7 / -1 run one fused kernel (FORM_O_APERTURE7 / FORM_O_SCHARR).  Asynchronous, as run_device."""
+        _ck(self.lib.hc_canny_device(self.handle, C.c_void_p(d_in), in_pitch, in_fs, C.c_void_p(d_out), out_pitch, out_fs,
+                                     int(nframes), float(low), float(high), int(aperture), int(bool(l2gradient))))
+
+    def canny(self, frames, low, high, aperture=3, l2gradient=False):
+        """cv::Canny convenience (mode O): numpy u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, uint8 (n,H,W) edge maps out,
+        through device tensors and canny_device."""
+        import torch
+        a = self._frames_u8(frames, "canny")
+        n = a.shape[0]
+        dev = torch.device("cuda", self.device)
+        src = torch.from_numpy(a).to(dev)
+        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
+        row = self.c * self.w
+        self.canny_device(src.data_ptr(), row, row * self.h, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
         self.sync()
         return out.cpu().numpy()
 

@@ -65,15 +65,16 @@ struct FrontParams {
   u32 wrap_limit;  // S >= wrap_limit: gradient >= 256, the wrap bands apply (0xFFFFFFFF: saturating variant)
 };
 
-// Mode O beyond k_front_o (front_o_ext.hip): the 5x5 Sobel of u8 frames (aperture 5), or caller-given int16 derivatives
-// (cv::Canny's (dx, dy) overload).  f as for k_front_o (thresholds in a_lo[0] / a_hi[0], chunk_rows, l2gradient); with
-// gradients != 0, f.in is dx and dy the dy planes, both with f.in_pitch / f.in_frame_stride (bytes, even), `channels`
-// interleaved int16 per pixel.
+// Mode O beyond k_front_o (front_o_ext.hip): the 5x5 / 7x7 Sobel or the Scharr derivatives of u8 frames (apertures 5, 7,
+// -1), or caller-given int16 derivatives (cv::Canny's (dx, dy) overload).  f as for k_front_o (thresholds in a_lo[0] /
+// a_hi[0], chunk_rows, l2gradient); with gradients != 0, f.in is dx and dy the dy planes, both with f.in_pitch /
+// f.in_frame_stride (bytes, even), `channels` interleaved int16 per pixel.
 struct FrontExtParams {
   FrontParams f;
   int gradients;
   int channels;
   const uint8_t *dy;
+  int aperture = 5;  // gradients == 0: the kind of the u8 source, 5, 7 (sums / 16, half to even) or -1 (Scharr)
 };
 
 // k_deriv16 (deriv.hip): the Sobel / Scharr derivatives cv::Canny computes before its NMS, u8 frames -> int16 dx / dy planes

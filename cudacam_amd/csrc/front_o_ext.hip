@@ -1,17 +1,26 @@
-// front_o_ext.hip -- the rest of cv::Canny's surface for Mode O: aperture 5, and the (dx, dy) overload.
+// front_o_ext.hip -- the rest of cv::Canny's surface for Mode O: apertures 5, 7 and -1 (Scharr), and the (dx, dy) overload.
 //
-// One kernel template, two row sources and a shared back half:
+// One kernel template, four row sources and a shared back half:
 //   SRC 0  u8 rows (1 or 3 interleaved channels) -> the 5x5 Sobel of cv::Canny(img, low, high, 5, L2gradient):
 //          Sobel(src, CV_16S, ksize 5, scale 1, BORDER_REPLICATE), computed separably in packed 16-bit math
 //          (every partial and final sum fits int16: |dx|, |dy| <= 12240)
 //   SRC 1  int16 dx / dy rows given by the caller (cv::Canny(dx, dy, edges, low, high, L2gradient))
+//   SRC 2  u8 rows -> the 7x7 Sobel of cv::Canny(img, low, high, 7, L2gradient), k_deriv16's arithmetic (deriv.hip): horizontal
+//          [-1 -4 -5 0 5 4 1] / [1 6 15 20 15 6 1] in packed pairs (|hd| <= 2550, hs <= 16320), symmetric rows added or
+//          subtracted in packed halves, the products summed in 32 bits (|S| <= 163200), then S / 16 rounded half to even
+//   SRC 3  u8 rows -> the Scharr derivatives of cv::Canny(img, low, high, -1, L2gradient): [-1 0 1] / [3 10 3], all packed
+//          int16 (+-4080)
 //   back   32-bit magnitude (L1 |dx| + |dy| or L2 dx^2 + dy^2, two's complement with wrap-around as canny.cpp's `int`),
 //          the 3-channel "first channel with the largest m" select, the integer tangent test (TG22 = 13573), asymmetric
 //          non-maximum suppression and the two thresholds -> STRONG / CANDIDATE bit planes that k_hyst finishes.
 // Layout as k_front_o (canny_kernels.hip): a wave owns a 248-column strip, lane l the 4 pixels at strip * 248 - 4 + 4 l,
-// lanes 0 and 63 are halo (aperture 5 needs 2 Sobel + 1 NMS columns of the 4 a halo lane holds); a work item is
-// (frame, strip, chunk of rows) with a warm-up of 3 (SRC 0) / 1 (SRC 1) rows; registers only, nothing but the bit
-// planes goes to memory.
+// lanes 0 and 63 are halo (aperture 5 needs 2 Sobel + 1 NMS columns of the 4 a halo lane holds, aperture 7 all of them: 3
+// Sobel + 1 NMS); a work item is (frame, strip, chunk of rows) with a warm-up of 3 (SRC 0) / 1 (SRC 1) / 4 (SRC 2) / 2
+// (SRC 3) rows; registers only, nothing but the bit planes goes to memory.
+// Rings: the source ring holds 6 (SRC 0), 7 (SRC 2) or 3 (SRC 3) rows, the magnitude ring 3, the dx / dy ring 2.  SRC 0, 1
+// and 3 unroll 6 steps per loop trip, the common period, so every ring slot is a compile-time register.  A 7-row source
+// ring would make that period 42: SRC 2 unrolls the 7 steps of its source ring and advances the two small rings by
+// register moves instead (the unrolled body renames them: the moves that remain sit at the loop's back edge).
 #include "canny_device.h"
 
 namespace hc {
@@ -24,9 +33,27 @@ static __device__ __forceinline__ u32 W32(i16x2v v) { return __builtin_bit_cast(
 static __device__ __forceinline__ int lo16(u32 v) { return (int)(short)(v & 0xFFFFu); }
 static __device__ __forceinline__ int hi16(u32 v) { return (int)v >> 16; }
 
+// the u8 sources' separable taps (SRC 2 / 3; SRC 0 spells its own out)
+constexpr int src_taps(int src) { return src == 2 ? 7 : 3; }
+constexpr int smooth_tap(int src, int t)
+{
+  constexpr int s7[7] = { 1, 6, 15, 20, 15, 6, 1 }, sc[3] = { 3, 10, 3 };
+  return src == 2 ? s7[t] : sc[t];
+}
+constexpr int deriv_tap(int src, int t)
+{
+  constexpr int d7[7] = { -1, -4, -5, 0, 5, 4, 1 }, d3[3] = { -1, 0, 1 };
+  return src == 2 ? d7[t] : d3[t];
+}
+static __device__ __forceinline__ i16x2v splat(int c) { return i16x2v{ (short)c, (short)c }; }
+
 template <int SRC, bool L2, int NC>
 __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
 {
+  constexpr bool U8 = SRC != 1;                            // u8 rows: SRC 0, 2, 3
+  constexpr int RING = SRC == 2 ? 7 : SRC == 3 ? 3 : 6;    // source rows kept
+  constexpr int PERIOD = SRC == 2 ? 7 : 6;                 // steps per loop trip
+  constexpr bool MOVE = SRC == 2;                          // the magnitude and dx / dy rings advance by register moves
   const FrontParams &p = e.f;
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
@@ -38,7 +65,7 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
   const int W = p.W, H = p.H, CH = p.chunk_rows;
   const int r0 = chunk * CH, rend = min(r0 + CH, H);
   const int c0 = strip * STRIP_W - STRIP_HALO + lane * PX_PER_LANE;
-  constexpr int LAG = SRC == 0 ? 2 : 0;        // gradient row = source row - LAG
+  constexpr int LAG = SRC == 0 ? 2 : SRC == 2 ? 3 : SRC == 3 ? 1 : 0;  // gradient row = source row - LAG
   const int rlast = min(H - 1, rend + LAG);    // last source row this item needs
 
   bool cin[4];  // the lane's columns inside the image (m = 0 outside)
@@ -49,10 +76,10 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
 #pragma unroll
     for (int q = 0; q < 4; ++q) oknib |= cin[q] ? (0x101u << q) : 0u;
 
-  // ---- SRC 0: u8 rows, BORDER_REPLICATE by clamping (rows) and a per-lane byte selector (columns), as k_front_o ----
+  // ---- SRC 0, 2, 3: u8 rows, BORDER_REPLICATE by clamping (rows) and a per-lane byte selector (columns), as k_front_o ----
   u32 rsel = 0;
   int ld_col = 0;
-  if constexpr (SRC == 0) {
+  if constexpr (U8) {
     const int cl0 = min(max(c0, 0), W - 1);
     ld_col = cl0 & ~3;
 #pragma unroll
@@ -61,7 +88,7 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
   const uint8_t *fbase = p.in + (size_t)frame * p.in_frame_stride;   // SRC 1: dx
   const uint8_t *fbase_y = e.dy + (size_t)frame * p.in_frame_stride; // SRC 1: dy (same pitch / frame stride)
   const int ne = NC * W, e0 = NC * c0;  // SRC 1: int16 elements per row, the lane's first element (even)
-  constexpr int ND = SRC == 0 ? NC : 4 * NC;  // dwords per lane and row: 4 px x NC bytes, or 2 planes x 4 px x NC int16
+  constexpr int ND = U8 ? NC : 4 * NC;  // dwords per lane and row: 4 px x NC bytes, or 2 planes x 4 px x NC int16
   struct Raw { u32 d[ND]; };
   // one int16 pair (elements ei, ei + 1) of a row; reads nothing outside [row start, row start + 2 * ne)
   auto ld_pair = [&](const uint8_t *rp, bool al, int ei) -> u32 {
@@ -75,7 +102,7 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
   auto load_row = [&](int row) -> Raw {
     const int rr = min(max(row, 0), rlast);
     Raw r;
-    if constexpr (SRC == 0) {
+    if constexpr (U8) {
       const u32 *q = reinterpret_cast<const u32 *>(fbase + (size_t)rr * p.in_pitch + (size_t)(NC * ld_col));
 #pragma unroll
       for (int i = 0; i < NC; ++i) r.d[i] = q[i];
@@ -90,10 +117,10 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
     }
     return r;
   };
-  // SRC 0: channel ch of the lane's 4 pixels as one dword, replicated at the borders
+  // u8 rows: channel ch of the lane's 4 pixels as one dword, replicated at the borders
   auto use_row = [&](const Raw &raw, int ch) -> u32 {
     u32 v = raw.d[0];
-    if constexpr (SRC == 0 && NC == 3) {
+    if constexpr (U8 && NC == 3) {
       const u32 selA = ch == 0 ? 0x0c060300u : ch == 1 ? 0x0c070401u : 0x0c0c0502u;
       const u32 selB = ch == 0 ? 0x05020100u : ch == 1 ? 0x06020100u : 0x07040100u;
       v = __builtin_amdgcn_perm(raw.d[NC > 2 ? 2 : 0], __builtin_amdgcn_perm(raw.d[NC > 1 ? 1 : 0], raw.d[0], selA), selB);
@@ -101,13 +128,13 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
     return __builtin_amdgcn_perm(0u, v, rsel);
   };
 
-  // SRC 0: per channel, the horizontal derivative / smoothing rows of the last six source rows, packed pairs [ring][pair]
-  constexpr int NR = SRC == 0 ? NC : 1;
-  u32 HD[NR][6][2], HS[NR][6][2];
+  // u8 rows: per channel, the horizontal derivative / smoothing rows of the last RING source rows, packed pairs [ring][pair]
+  constexpr int NR = U8 ? NC : 1;
+  u32 HD[NR][RING][2], HS[NR][RING][2];
 #pragma unroll
   for (int ch = 0; ch < NR; ++ch)
 #pragma unroll
-    for (int a = 0; a < 6; ++a) HD[ch][a][0] = HD[ch][a][1] = HS[ch][a][0] = HS[ch][a][1] = 0;
+    for (int a = 0; a < RING; ++a) HD[ch][a][0] = HD[ch][a][1] = HS[ch][a][0] = HS[ch][a][1] = 0;
   int Mr[3][6];      // magnitude rows: [ring][0] = left neighbour, [1..4] = own 4 px, [5] = right neighbour
   int Xr[2][4], Yr[2][4];  // dx / dy of the two newest gradient rows
 #pragma unroll
@@ -130,9 +157,15 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
   // one step: source row k arrives -> gradient row g = k - LAG -> NMS / threshold row g - 1
   auto step = [&](auto uc, int k, const Raw &raw) {
     constexpr int u = decltype(uc)::value;
-    constexpr int rn = u % 2, rp = (u + 1) % 2;
-    constexpr int sN = u % 3, sC = (u + 2) % 3, sU = (u + 1) % 3;
+    constexpr int rn = MOVE ? 1 : u % 2, rp = MOVE ? 0 : (u + 1) % 2;
+    constexpr int sN = MOVE ? 2 : u % 3, sC = MOVE ? 1 : (u + 2) % 3, sU = MOVE ? 0 : (u + 1) % 3;
     const int g = k - LAG;
+    if constexpr (MOVE) {
+#pragma unroll
+      for (int b = 0; b < 6; ++b) { Mr[0][b] = Mr[1][b]; Mr[1][b] = Mr[2][b]; }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { Xr[0][q] = Xr[1][q]; Yr[0][q] = Yr[1][q]; }
+    }
     int X[4], Y[4], M[4];
 #pragma unroll
     for (int ch = 0; ch < NC; ++ch) {
@@ -156,6 +189,59 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
           const u32 dyp = W32(V(HS[ch][s4][h]) - V(HS[ch][s0][h]) + two * (V(HS[ch][s3][h]) - V(HS[ch][s1][h])));
           x[2 * h] = lo16(dxp); x[2 * h + 1] = hi16(dxp);
           y[2 * h] = lo16(dyp); y[2 * h + 1] = hi16(dyp);
+        }
+      } else if constexpr (SRC == 2 || SRC == 3) {
+        constexpr int K = src_taps(SRC), RAD = K / 2, us = u % RING;
+        // horizontal pass on the new row.  P[t + 4] = the pixel pair that starts t columns from the lane's first
+        const u32 b = use_row(raw, ch);
+        u32 P[11];
+        P[4] = unpack_lo(b); P[6] = unpack_hi(b);
+        P[2] = from_lane_below(P[6]); P[8] = from_lane_above(P[4]);
+        P[0] = from_lane_below(P[4]); P[10] = from_lane_above(P[6]);
+        P[1] = pair_shift(P[2], P[0]); P[3] = pair_shift(P[4], P[2]); P[5] = pair_shift(P[6], P[4]);
+        P[7] = pair_shift(P[8], P[6]); P[9] = pair_shift(P[10], P[8]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int c = 4 + 2 * h;
+          i16x2v hs = V(P[c]) * splat(smooth_tap(SRC, RAD)), hd = splat(0);
+#pragma unroll
+          for (int t = 0; t < RAD; ++t) {
+            hs += (V(P[c - RAD + t]) + V(P[c + RAD - t])) * splat(smooth_tap(SRC, t));
+            hd += (V(P[c + RAD - t]) - V(P[c - RAD + t])) * splat(deriv_tap(SRC, K - 1 - t));
+          }
+          HS[ch][us][h] = W32(hs);
+          HD[ch][us][h] = W32(hd);
+        }
+        // vertical pass over source rows k - K + 1 .. k: ring slot of tap t (t = 0: the oldest row) is (us + 1 + t) % K
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if constexpr (SRC == 3) {
+            i16x2v vx = V(HD[ch][(us + 1 + RAD) % K][h]) * splat(smooth_tap(SRC, RAD)), vy = splat(0);
+#pragma unroll
+            for (int t = 0; t < RAD; ++t) {
+              const int so = (us + 1 + t) % K, sn = (us + K - t) % K;  // rows g - RAD + t and g + RAD - t
+              vx += (V(HD[ch][so][h]) + V(HD[ch][sn][h])) * splat(smooth_tap(SRC, t));
+              vy += (V(HS[ch][sn][h]) - V(HS[ch][so][h])) * splat(deriv_tap(SRC, K - 1 - t));
+            }
+            x[2 * h] = lo16(W32(vx)); x[2 * h + 1] = hi16(W32(vx));
+            y[2 * h] = lo16(W32(vy)); y[2 * h + 1] = hi16(W32(vy));
+          } else {
+            // symmetric rows first, still packed (|hd| <= 2550, hs <= 16320: sums and differences fit int16), then 32 bits
+            const u32 mid = HD[ch][(us + 1 + RAD) % K][h];
+            int sx0 = lo16(mid) * smooth_tap(SRC, RAD), sx1 = hi16(mid) * smooth_tap(SRC, RAD), sy0 = 0, sy1 = 0;
+#pragma unroll
+            for (int t = 0; t < RAD; ++t) {
+              const int so = (us + 1 + t) % K, sn = (us + K - t) % K;
+              const u32 a = W32(V(HD[ch][so][h]) + V(HD[ch][sn][h]));
+              const u32 d = W32(V(HS[ch][sn][h]) - V(HS[ch][so][h]));
+              sx0 += lo16(a) * smooth_tap(SRC, t); sx1 += hi16(a) * smooth_tap(SRC, t);
+              sy0 += lo16(d) * deriv_tap(SRC, K - 1 - t); sy1 += hi16(d) * deriv_tap(SRC, K - 1 - t);
+            }
+            // S / 16 rounded half to even (what cvRound gives for the exact float S / 16)
+            auto rnd = [](int s) -> int { return (s + 7 + ((s >> 4) & 1)) >> 4; };
+            x[2 * h] = rnd(sx0); x[2 * h + 1] = rnd(sx1);
+            y[2 * h] = rnd(sy0); y[2 * h + 1] = rnd(sy1);
+          }
         }
       } else {
 #pragma unroll
@@ -212,33 +298,34 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
     }
   };
 
-  // source rows r0 - LAG - 1 .. rend + LAG, six steps per loop trip (the ring period); a row is requested six steps
+  // source rows r0 - LAG - 1 .. rend + LAG, PERIOD steps per loop trip (the ring period); a row is requested PERIOD steps
   // before it is used (as k_front_o)
   const int k0 = r0 - LAG - 1, kend = rend + LAG + 1;
-  Raw bn[6];
+  Raw bn[PERIOD];
 #pragma unroll
-  for (int j = 0; j < 6; ++j) bn[j] = load_row(k0 + j);
+  for (int j = 0; j < PERIOD; ++j) bn[j] = load_row(k0 + j);
   auto advance = [&](auto uc, int k) {
     constexpr int j = decltype(uc)::value;
     const Raw b = bn[j];
-    bn[j] = load_row(k + 6);
+    bn[j] = load_row(k + PERIOD);
     step(uc, k, b);
   };
 #pragma nounroll
-  for (int k = k0; k < kend; k += 6) {
+  for (int k = k0; k < kend; k += PERIOD) {
     advance(std::integral_constant<int, 0>{}, k + 0);
     advance(std::integral_constant<int, 1>{}, k + 1);
     advance(std::integral_constant<int, 2>{}, k + 2);
     advance(std::integral_constant<int, 3>{}, k + 3);
     advance(std::integral_constant<int, 4>{}, k + 4);
     advance(std::integral_constant<int, 5>{}, k + 5);
+    if constexpr (PERIOD == 7) advance(std::integral_constant<int, 6>{}, k + 6);
   }
 }
 
 template <int SRC>
 hipError_t launch_src(const FrontExtParams &e, const dim3 grid, const dim3 block, hipStream_t s)
 {
-  const bool three = SRC == 0 ? e.f.bgr != 0 : e.channels == 3;
+  const bool three = SRC != 1 ? e.f.bgr != 0 : e.channels == 3;
   if (three) {
     if (e.f.l2gradient) hipLaunchKernelGGL((k_front_o_ext<SRC, true, 3>), grid, block, 0, s, e);
     else hipLaunchKernelGGL((k_front_o_ext<SRC, false, 3>), grid, block, 0, s, e);
@@ -252,7 +339,7 @@ hipError_t launch_src(const FrontExtParams &e, const dim3 grid, const dim3 block
 }  // namespace
 
 // gradients == 0: u8 frames at f.in (f.bgr: 3 interleaved channels; rows hold whole 4-pixel groups, pitch >= C * round_up(W, 4),
-// multiple of 4); gradients != 0: int16 dx at f.in, dy at e.dy, `channels` interleaved, even pitch >= 2 * channels * W
+// multiple of 4), e.aperture 5, 7 or -1 picks the source; gradients != 0: int16 dx at f.in, dy at e.dy, `channels` interleaved, even pitch >= 2 * channels * W
 hipError_t launch_front_o_ext(const FrontExtParams &e, hipStream_t s)
 {
   const FrontParams &p = e.f;
@@ -265,7 +352,12 @@ hipError_t launch_front_o_ext(const FrontExtParams &e, hipStream_t s)
     return launch_src<1>(e, grid, block, s);
   }
   if ((p.in_pitch & 3u) || p.in_pitch < (size_t)(p.bgr ? 3 : 1) * (((size_t)p.W + 3) / 4 * 4)) return hipErrorInvalidValue;
-  return launch_src<0>(e, grid, block, s);
+  switch (e.aperture) {
+  case 5: return launch_src<0>(e, grid, block, s);
+  case 7: return launch_src<2>(e, grid, block, s);
+  case -1: return launch_src<3>(e, grid, block, s);
+  default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace hc

@@ -524,12 +524,13 @@ int finish_overlapping(hc_ctx *c, uintptr_t o0, uintptr_t o1, bool *with_previou
 int launch_front_form(hc_ctx *c, const FrontPlan &P, FrontParams &fp, const uint8_t *in_dy, hipStream_t sf)
 {
   switch (P.form) {
-  case HC_FORM_O_APERTURE5: case HC_FORM_O_GRADIENTS: {
+  case HC_FORM_O_APERTURE5: case HC_FORM_O_GRADIENTS: case HC_FORM_O_APERTURE7: case HC_FORM_O_SCHARR: {
     FrontExtParams ep{};
     ep.f = fp;
     ep.gradients = in_dy ? 1 : 0;
     ep.channels = c->C;
     ep.dy = in_dy;
+    ep.aperture = P.form == HC_FORM_O_APERTURE7 ? 7 : P.form == HC_FORM_O_SCHARR ? -1 : 5;
     HIPCK(launch_front_o_ext(ep, sf));
     break;
   }
@@ -582,8 +583,9 @@ int queue_stage_taps(hc_ctx *c, int stage, const uint8_t *mono, size_t mp, size_
 
 // in_dy != null: `in` and `in_dy` are the int16 dx / dy planes of cv::Canny's (dx, dy) overload (Mode O, HC_STAGE_HYSTER,
 // even addresses / pitch / frame stride: k_front_o_ext reads them as they are, nothing is staged)
+// call_opt != null (hc_canny_device): the front path is planned with these choices instead of the context's
 int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_t *out, size_t out_pitch, size_t out_fs, int n, int stage,
-             const uint8_t *in_dy = nullptr)
+             const uint8_t *in_dy = nullptr, const FrontOpts *call_opt = nullptr)
 {
   if (c->mode == HC_MODE_O && stage != HC_STAGE_HYSTER)
     return fail(HC_E_ARG, "mode O (cv::Canny) produces the final edge map only (cv::Canny has no intermediate outputs)");
@@ -599,7 +601,7 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
   FrontIn fi{ c->mode, c->C, W, H, c->RD, c->nstrips, c->per_channel, stage, n };
   fi.in = View{ (uintptr_t)in, in_pitch, in_fs }; fi.out = View{ (uintptr_t)out, out_pitch, out_fs }; fi.in_dy = (uintptr_t)in_dy;
   fi.own_in = View{ 0, c->in_pitch, c->in_fs }; fi.own_mono = View{ 0, c->mono_pitch, c->mono_fs }; fi.own_out = View{ 0, c->out_pitch, c->out_fs };
-  fi.o = c->opt; fi.dump_region = c->dump_region; fi.piped = piped; fi.nslot_use = c->nslot_use; fi.front_one = c->watch.front_one; fi.wl_cap = s.wl_cap;
+  fi.o = call_opt ? *call_opt : c->opt; fi.dump_region = c->dump_region; fi.piped = piped; fi.nslot_use = c->nslot_use; fi.front_one = c->watch.front_one; fi.wl_cap = s.wl_cap;
   const bool out_internal = out_view_staged(fi.out);
   uint8_t *dst = out_internal ? c->d_out : out;
   if (piped) {
@@ -914,8 +916,8 @@ int hc_set_option(hc_ctx *c, int option, int value)
     if (c->mode != HC_MODE_O) return fail(HC_E_ARG, "HC_OPT_APERTURE applies to mode O contexts");
     if (value == 7)
       return fail(HC_E_ARG, "HC_OPT_APERTURE 7 is not offered: cv::Canny scales the 7x7 Sobel and its thresholds to stay within "
-                            "int16, which HC_OPT_APERTURE does not restate; hc_derivatives_device computes those derivatives (ksize 7, and -1 for "
-                            "Scharr) for hc_run_gradients_device");
+                            "int16, which HC_OPT_APERTURE does not restate; hc_canny_device takes the aperture (7, and -1 for Scharr) and "
+                            "cv::Canny's own thresholds per call; hc_derivatives_device computes those derivatives for hc_run_gradients_device");
     if (value != 3 && value != 5) return fail(HC_E_ARG, "HC_OPT_APERTURE: 3 (default) or 5");
     c->opt.aperture = value;
   } else if (option == HC_OPT_DEBUG_TAPS) {
@@ -993,6 +995,24 @@ int hc_run_gradients_device(hc_ctx *c, const void *d_dx, const void *d_dy, size_
   HIPCK(hipSetDevice(c->device));
   return run_impl(c, (const uint8_t *)d_dx, pitch, frame_stride, (uint8_t *)d_out, out_pitch, out_frame_stride, n, HC_STAGE_HYSTER,
                   (const uint8_t *)d_dy);
+}
+
+int hc_canny_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n, double low,
+                    double high, int aperture, int l2gradient)
+{
+  if (!c || !d_in || !d_out) return fail(HC_E_ARG, "hc_canny_device: null argument");
+  if (c->mode != HC_MODE_O) return fail(HC_E_ARG, "hc_canny_device: mode O contexts only (cv::Canny)");
+  if (!deriv_ksize_ok(aperture)) return fail(HC_E_ARG, "hc_canny_device: aperture 3, 5, 7 or -1 (Scharr)");
+  CallThresholds t;
+  if (!canny_call_thresholds(low, high, aperture, l2gradient != 0, &t)) return fail(HC_E_ARG, "hc_canny_device: thresholds must be finite and not negative");
+  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_canny_device: nframes out of range");
+  if (in_pitch < (size_t)c->W * c->C || out_pitch < (size_t)c->W) return fail(HC_E_ARG, "hc_canny_device: pitch smaller than a row");
+  if (n > 1 && (in_fs < in_pitch * (size_t)c->H || out_fs < out_pitch * (size_t)c->H)) return fail(HC_E_ARG, "hc_canny_device: frame stride smaller than a frame");
+  HIPCK(hipSetDevice(c->device));
+  // the call's own choices, on a copy: the context's thresholds, HC_OPT_APERTURE and HC_OPT_L2_GRADIENT stay as they are
+  FrontOpts o = c->opt;
+  o.aperture = aperture; o.l2gradient = l2gradient != 0; o.call_lo = t.k_lo; o.call_hi = t.k_hi;
+  return run_impl(c, (const uint8_t *)d_in, in_pitch, in_fs, (uint8_t *)d_out, out_pitch, out_fs, n, HC_STAGE_HYSTER, nullptr, &o);
 }
 
 // Not a run: one kernel on the context stream, in order with whatever is queued there (a following hc_run_gradients_device

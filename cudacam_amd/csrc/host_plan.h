@@ -7,6 +7,7 @@
 #include "canny_params.h"
 
 #include <algorithm>
+#include <cmath>
 
 namespace hc {
 
@@ -143,7 +144,8 @@ struct FrontOpts {
   int nms_saturate = 0;
   int split = 2;        // Mode R front path: 2 = k_front8 (one kernel, 8 px per lane; default), 1 = k_blur + k_nms, 0 = the 4-px fused k_front
   int l2gradient = 0;   // Mode O: cv::Canny's L2gradient flag
-  int aperture = 3;     // Mode O: cv::Canny's apertureSize (HC_OPT_APERTURE: 3 = k_front8o / k_front_o, 5 = k_front_o_ext)
+  int aperture = 3;     // Mode O: cv::Canny's apertureSize (HC_OPT_APERTURE: 3 = k_front8o / k_front_o, 5 = k_front_o_ext; hc_canny_device also 7 and -1 = Scharr, per call)
+  int call_lo = -1, call_hi = -1;  // >= 0 (hc_canny_device): the thresholds as the Mode O kernels compare them (canny_call_thresholds) instead of low / high
   int half_mode = -1;   // HC_OPT_FRONT_HALF: -1 automatic, 0 never, 1 whenever the buffers allow it
   int dense_mode = -1;  // HC_OPT_FRONT_DENSE: -1 automatic, 0 never, 1 every window
   int mx_mode = 0;      // HC_OPT_FRONT_MX: 1 = k_front_mx whenever the run allows it (opt-in: include/hipcanny.h)
@@ -194,6 +196,32 @@ inline void band_thresholds(int T, bool saturate, u32 a[3])
   if (saturate && T >= 255) a[0] = 0xFFFFFFFFu;
 }
 
+// hc_canny_device's thresholds, as canny.cpp derives them from cv::Canny(img, edges, low, high, apertureSize, L2gradient)'s
+// arguments: ordered; at aperture 7 both divided by 16 (the scale of its Sobel); with L2gradient min(32767, t) and then
+// t * t for t > 0; floored.  lo / hi: those values.  k_lo / k_hi: what the kernels compare the magnitude with, "m > t" in
+// int: the L1 thresholds clamped to 32767 (no L1 magnitude of any aperture on a u8 source reaches 32767 -- at most 24480,
+// at aperture 5 -- so the clamp changes no result), the L2 ones as they are (at most 32767^2).
+// false: a threshold is negative or not finite, or the aperture is none of 3, 5, 7, -1.
+struct CallThresholds { long long lo, hi; int k_lo, k_hi; };
+inline bool canny_call_thresholds(double low, double high, int aperture, bool l2, CallThresholds *t)
+{
+  if (aperture != 3 && aperture != 5 && aperture != 7 && aperture != -1) return false;
+  if (!std::isfinite(low) || !std::isfinite(high) || low < 0.0 || high < 0.0) return false;
+  if (low > high) std::swap(low, high);
+  if (aperture == 7) { low /= 16.0; high /= 16.0; }
+  if (l2) {
+    low = std::min(32767.0, low); high = std::min(32767.0, high);
+    if (low > 0.0) low *= low;
+    if (high > 0.0) high *= high;
+  }
+  const double top = 9.0e18;  // (beyond every magnitude by far; keeps the conversion defined)
+  t->lo = (long long)std::floor(std::min(low, top));
+  t->hi = (long long)std::floor(std::min(high, top));
+  t->k_lo = (int)(l2 ? t->lo : std::min<long long>(t->lo, 32767));
+  t->k_hi = (int)(l2 ? t->hi : std::min<long long>(t->hi, 32767));
+  return true;
+}
+
 #ifdef HC_LEGACY_FRONT
 // rows per work item: about 16 rounds of the whole chip (8192 resident waves) when the batch allows it -- the tail of a
 // launch is one work item long, measured optimum 68-135 rows at 1024 frames -- but never runs shorter than 64 rows
@@ -211,12 +239,14 @@ inline bool out_view_staged(const View &out) { return !aligned4(out.p, out.pitch
 
 // groups of front forms (HC_FORM_*, include/hipcanny.h) that share a rule
 inline bool form_8px(int f) { return f == HC_FORM_FRONT8 || f == HC_FORM_FRONT8O || f == HC_FORM_FRONT8_HALF; }
-inline bool form_o_4px(int f) { return f == HC_FORM_FRONT_O || f == HC_FORM_O_APERTURE5 || f == HC_FORM_O_GRADIENTS; }
+inline bool form_o_ext(int f) { return f == HC_FORM_O_APERTURE5 || f == HC_FORM_O_GRADIENTS || f == HC_FORM_O_APERTURE7 || f == HC_FORM_O_SCHARR; }  // k_front_o_ext's
+inline bool form_o_4px(int f) { return f == HC_FORM_FRONT_O || form_o_ext(f); }
 inline bool form_zeroes_flags(int f) { return form_8px(f) || f == HC_FORM_FRONT_MX; }  // these kernels zero the run's hysteresis flag words on their way in
 
 inline int front_out_frames(const FrontIn &in) { return in.per_channel ? 3 * in.n : in.n; }  // output frames (= bit-plane frames)
-// Mode O forms of k_front_o_ext: caller-given gradients (HC_FORM_O_GRADIENTS), or aperture 5 on u8 frames (HC_FORM_O_APERTURE5)
-inline bool front_o_ext(const FrontIn &in) { return in.mode == HC_MODE_O && (in.in_dy != 0 || in.o.aperture == 5); }
+// Mode O forms of k_front_o_ext: caller-given gradients (HC_FORM_O_GRADIENTS), or aperture 5, 7 or -1 on u8 frames
+// (HC_FORM_O_APERTURE5 / HC_FORM_O_APERTURE7 / HC_FORM_O_SCHARR)
+inline bool front_o_ext(const FrontIn &in) { return in.mode == HC_MODE_O && (in.in_dy != 0 || in.o.aperture == 5 || in.o.aperture == 7 || in.o.aperture == -1); }
 // the fused kernel converts BGR while loading (needs whole 12-byte pixel groups inside each row)
 inline bool whole_bgr_groups(const View &src, int W) { return src.pitch >= round_up((size_t)W, 4) * 3; }
 inline bool fuses_bgr(const FrontIn &in, const FrontPlan &P) { return in.C == 3 && in.stage == HC_STAGE_HYSTER && whole_bgr_groups(P.src, in.W); }
@@ -257,7 +287,7 @@ inline void stage_views(const FrontIn &in, FrontPlan &P)
 // (Narrow frames: k_front8's HALF form, choose_form.  Round 2 sent 640-column batches to k_blur + k_nms instead.)
 inline int asked_form(const FrontIn &in)
 {
-  if (front_o_ext(in)) return in.in_dy != 0 ? HC_FORM_O_GRADIENTS : HC_FORM_O_APERTURE5;
+  if (front_o_ext(in)) return in.in_dy != 0 ? HC_FORM_O_GRADIENTS : in.o.aperture == 7 ? HC_FORM_O_APERTURE7 : in.o.aperture == -1 ? HC_FORM_O_SCHARR : HC_FORM_O_APERTURE5;
   if (in.mode != HC_MODE_R) return (in.C == 1 && in.o.split == 2) ? HC_FORM_FRONT8O : HC_FORM_FRONT_O;
   return in.o.split;  // HC_FORM_FRONT8 / HC_FORM_SPLIT / HC_FORM_FRONT4 are HC_OPT_FRONT_SPLIT's values
 }
@@ -384,7 +414,7 @@ inline void cut_front_mx_runs(const FrontIn &in, FrontPlan &P)
   fp.total_items = (int)(units * fp.nchunks);
 }
 
-// k_front_o, and k_front_o_ext with its strips and work split (a 6-row warm-up for aperture 5, 2 rows for gradients):
+// k_front_o, and k_front_o_ext with its strips and work split (a 6-row warm-up for aperture 5, 8 rows for 7, 4 for Scharr, 2 for gradients):
 // strips of 248 columns (FrontIn::nstrips), long chunks (no LDS slab, 4-row warm-up)
 inline void cut_front_o_chunks(const FrontIn &in, FrontPlan &P)
 {
@@ -445,6 +475,7 @@ inline void plan_thresholds_and_masks(const FrontIn &in, FrontPlan &P)
       fp.a_lo[0] = (u32)o.low * (u32)o.low;
       fp.a_hi[0] = (u32)o.high * (u32)o.high;
     }
+    if (o.call_lo >= 0 && o.call_hi >= 0) { fp.a_lo[0] = (u32)o.call_lo; fp.a_hi[0] = (u32)o.call_hi; }  // hc_canny_device: squared already where L2
     // cv::Canny has no blur stage; given gradients leave NMS + thresholds only (GRADIENT did not run)
     P.mask = (in.in_dy != 0 ? 0u : B_GRAD) | B_NMS | B_THR;
     return;
@@ -495,7 +526,7 @@ inline FrontPlan plan_front(const FrontIn &in)
   switch (P.form) {
   case HC_FORM_FRONT8: case HC_FORM_FRONT8_HALF: case HC_FORM_FRONT8O: cut_front8_runs(in, P); break;
   case HC_FORM_FRONT_MX: cut_front_mx_runs(in, P); break;
-  case HC_FORM_FRONT_O: case HC_FORM_O_APERTURE5: case HC_FORM_O_GRADIENTS: cut_front_o_chunks(in, P); break;
+  case HC_FORM_FRONT_O: case HC_FORM_O_APERTURE5: case HC_FORM_O_GRADIENTS: case HC_FORM_O_APERTURE7: case HC_FORM_O_SCHARR: cut_front_o_chunks(in, P); break;
 #ifdef HC_LEGACY_FRONT
   case HC_FORM_FRONT4: cut_front4_runs(in, P); break;
   case HC_FORM_SPLIT: cut_split_runs(in, P); break;

@@ -106,6 +106,32 @@ int hc_run_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_fram
 int hc_run_gradients_device(hc_ctx *ctx, const void *d_dx, const void *d_dy, size_t pitch, size_t frame_stride, void *d_out,
                             size_t out_pitch, size_t out_frame_stride, int nframes);
 
+/* Mode O: cv::Canny(img, edges, low, high, apertureSize, L2gradient) in one call on caller-owned device memory, with
+ * cv::Canny's own argument list: any of its apertures -- 3, 5, 7, -1 (Scharr) -- and thresholds in cv::Canny's units.
+ * `d_in` / `d_out` as for hc_run_device: u8 frames of the context's width, height and channels (1, or 3 interleaved: the
+ * first channel with the largest magnitude gives a pixel's gradient), u8 edge maps out.  Always runs to HC_STAGE_HYSTER.
+ * low, high, aperture and l2gradient belong to the call: they neither read nor change the context's thresholds,
+ * HC_OPT_APERTURE or HC_OPT_L2_GRADIENT, and a following hc_run_device behaves as if this call had not happened.
+ * Thresholds, as canny.cpp: swapped if low > high; at aperture 7 both are divided by 16 (cv::Canny scales that Sobel by
+ * 1/16: see hc_derivatives_device); with l2gradient min(32767, t), then t * t for t > 0; then floored -- in this order, so
+ * that L2 thresholds that are no multiples of 16 are exact at aperture 7 too (which integer context thresholds cannot
+ * express).  The floored L1 thresholds are clamped to 32767; no L1 magnitude of any aperture on a u8 source reaches 32767
+ * (at most 24480, at aperture 5), so the clamp changes no result.  Thresholds that are negative or not finite are HC_E_ARG.
+ * Kernels: apertures 3 and 5 run what hc_run_device runs with HC_OPT_APERTURE 3 / 5 (same kernels, same bytes; hc_last_run_info
+ * reports HC_FORM_FRONT8O / HC_FORM_FRONT_O / HC_FORM_O_APERTURE5).  Apertures 7 and -1 run k_front_o_ext's fused sources
+ * (HC_FORM_O_APERTURE7 / HC_FORM_O_SCHARR): one kernel from the u8 frames to the bit planes, the derivatives (those of
+ * hc_derivatives_device, bit for bit) never leave the registers -- no int16 planes to allocate, write and read back.
+ * It is a run in every sense hc_run_device is one: pipeline slots and HC_OPT_PIPELINE, the stage timers (the front kernel's
+ * time is divided over GRADIENT, NMS and THRESH, as for HC_FORM_O_APERTURE5), the hysteresis history and schedule,
+ * hc_last_run_info, hc_set_stream, hc_set_tuning's rows per work item, HC_OPT_DEBUG_TAPS.
+ * Views: exactly the rules of a HC_OPT_APERTURE 5 run of hc_run_device -- input rows without whole 4-pixel groups (pitch <
+ * channels * round_up(width, 4)), pointers / pitches / frame strides that are no multiples of 4 and input views of 4 GiB
+ * are staged; only [row, row + width) of every output row is written; the input is never written.
+ * HC_E_ARG: a mode R context; an aperture outside {3, 5, 7, -1}; the thresholds above; otherwise whatever hc_run_device
+ * gives for the same pointers, pitches and nframes. */
+int hc_canny_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
+                    size_t out_frame_stride, int nframes, double low, double high, int aperture, int l2gradient);
+
 /* The derivatives cv::Canny(img, low, high, apertureSize, L2gradient) computes before its NMS, on their own (k_deriv16):
  * `d_in` holds nframes u8 frames of width * channels bytes per row (1 or 3 interleaved channels, as the context's);
  * `d_dx` / `d_dy` receive int16 planes with the same interleave (CV_16SC1 / CV_16SC3), both with `pitch` and `frame_stride`
@@ -126,7 +152,8 @@ int hc_run_gradients_device(hc_ctx *ctx, const void *d_dx, const void *d_dy, siz
  * Thresholds at 7: cv::Canny(img, low, high, 7) also divides low and high by 16 before it floors them.  The context
  * thresholds used with these derivatives are therefore in the SCALED units: a caller porting cv::Canny(img, low, high, 7)
  * sets floor(low / 16), floor(high / 16).  That mapping is exact for the L1 magnitude; with L2gradient (squared thresholds)
- * it is exact only for low / high that are multiples of 16.  The library does not rescale thresholds.
+ * it is exact only for low / high that are multiples of 16.  This entry does not rescale thresholds; hc_canny_device, which
+ * takes cv::Canny's own thresholds and aperture per call and fuses these derivatives into its front kernel, does.
  * Asynchronous on the context stream (hc_set_stream honoured), in order with everything else queued there: a following
  * hc_run_gradients_device on the same context needs no synchronisation in between, in plain and in pipelined mode.  It is not
  * a run: hc_last_run_info, the stage timers, the hysteresis schedule / history and the pipeline slots stay as they were, and
@@ -179,7 +206,7 @@ int hc_use_own_stream(hc_ctx *ctx);
  * books a stage only when it ran.  Attribution: the plain per-stage kernels behind final_stage < HYSTER each have their
  * own interval.  On the HYSTER fast path one kernel covers several reference stages and has no internal boundary to
  * time: k_blur covers MONO (3-channel input) + GAUSSIAN, k_nms covers GRADIENT + NMS + THRESH, a fused front kernel
- * covers all of them, k_front_o (mode O) GRADIENT + NMS + THRESH, as does k_front_o_ext at aperture 5 (HC_FORM_O_APERTURE5);
+ * covers all of them, k_front_o (mode O) GRADIENT + NMS + THRESH, as does k_front_o_ext at apertures 5, 7 and -1 (HC_FORM_O_APERTURE5 / _APERTURE7 / _SCHARR);
  * on given gradients (hc_run_gradients_device, HC_FORM_O_GRADIENTS) it covers NMS + THRESH and GRADIENT reads -1; a kernel's time is divided EQUALLY among the stages
  * it covers, so every stage that ran shows a non-zero share and the sum over stages -- what the reference's UI totals
  * up to the selected stage (src/imgui/imguiApp.cpp:364-376) -- is the measured time.  Off by default on the batch path. */
@@ -247,7 +274,9 @@ enum {
   HC_FORM_FRONT8_HALF = 4,  /* Mode R: k_front8 in its half-strip form (HC_OPT_FRONT_HALF) */
   HC_FORM_FRONT_MX = 5,     /* Mode R: k_front_mx (HC_OPT_FRONT_MX) */
   HC_FORM_O_APERTURE5 = 6,  /* Mode O: k_front_o_ext at HC_OPT_APERTURE 5 */
-  HC_FORM_O_GRADIENTS = 7   /* Mode O: k_front_o_ext on given gradients (hc_run_gradients_device) */
+  HC_FORM_O_GRADIENTS = 7,  /* Mode O: k_front_o_ext on given gradients (hc_run_gradients_device) */
+  HC_FORM_O_APERTURE7 = 8,  /* Mode O: k_front_o_ext's fused 7x7 Sobel (hc_canny_device, aperture 7) */
+  HC_FORM_O_SCHARR = 9      /* Mode O: k_front_o_ext's fused Scharr derivatives (hc_canny_device, aperture -1) */
 };
 
 /* What the last hc_run / hc_run_device did with the caller's buffers -- no silent cliffs: *input_staged / *output_staged are
@@ -276,7 +305,7 @@ int hc_front_waves_per_workgroup(hc_ctx *ctx);
 int hc_hysteresis_stats(hc_ctx *ctx, unsigned *stats, int nwords);
 
 /* Tuning knobs: rows per front-path work item (0 = auto; k_front8 / k_front8o round it up to whole 6-row windows, 2 rows at
- * least; the 4-px Mode O kernels -- k_front_o, and k_front_o_ext for aperture 5 and given gradients -- take any number of
+ * least; the 4-px Mode O kernels -- k_front_o, and k_front_o_ext in all its forms -- take any number of
  * rows from 1 to the frame height as it is; larger values mean one item per strip); hysteresis launches queued per run (0 = auto:
  * 6, or one more than the row tiles + column panels of a frame, or what the last runs needed + 4, at most 96; launches
  * after convergence exit at once, and
@@ -321,7 +350,8 @@ int hc_set_tuning(hc_ctx *ctx, int chunk_rows, int hyst_launches);
  * and NMS as at 3.  Runs k_front_o_ext (HC_FORM_O_APERTURE5; 1 or 3 channels; rows without whole 4-pixel groups are staged).
  * Any other value, and any mode R context, is HC_E_ARG; 7 and -1 (Scharr) are not offered as options (cv::Canny scales the
  * 7x7 Sobel and its thresholds to stay within int16): such callers chain hc_derivatives_device (ksize 7 / -1, which states
- * the scaling and what it means for the thresholds) with hc_run_gradients_device.  Mode O thresholds stay clamped to 0..32767 at every aperture (L1 thresholds above 32767
+ * the scaling and what it means for the thresholds) with hc_run_gradients_device, or call hc_canny_device, which takes the
+ * aperture (any of 3, 5, 7, -1) and cv::Canny's own thresholds per call and runs one fused kernel.  Mode O thresholds stay clamped to 0..32767 at every aperture (L1 thresholds above 32767
  * cannot be expressed).
  * Pipelined mode (HC_OPT_PIPELINE) gives exact maps on both k_front_o_ext forms (HC_FORM_O_APERTURE5 and HC_FORM_O_GRADIENTS); they write no provisional map,
  * so the hysteresis writes the whole output map of their runs. */

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Timing of k_deriv16 (hc_derivatives_device) beside its yardstick, k_front_o_ext on given gradients (front form 7), and of
-the chained aperture-7 Canny beside the fused aperture 5.
+the chained aperture-7 / Scharr Canny beside the fused aperture 5 and the fused forms of hc_canny_device.
 
 Usage: tools/deriv_bench.py [--steps 20] [--frames 512] [--only a,b] [--out FILE]
 Every configuration runs in a fresh process under `timeout`: 1080p, 512 frames per launch (3-channel: 256), `steps` timed
@@ -9,7 +9,11 @@ launches after two warm-up ones, median.
                              + 4 C B/px of int16 planes = 5 C B/px
   gradients_<mono|bgr>       form 7 (hc_profile_get_front_each): 4 C B/px of planes + 0.25 B/px of bit planes
   canny7_chain_<..>          hc_derivatives_device(7) + hc_run_gradients_device, pipelined, wall clock: frames/s
+  scharr_chain_<..>          the same with ksize -1
   canny5_fused_<..>          HC_OPT_APERTURE 5, pipelined, wall clock: frames/s
+  canny7_fused_<..>          hc_canny_device at aperture 7 (front form 8; thresholds x 16: the chain's map), pipelined, wall
+                             clock: frames/s; also the front kernel's own median over `steps` plain profiled runs (front_ms_median)
+  scharr_fused_<..>          hc_canny_device at aperture -1 (front form 9), likewise
 Fractions are of 6.29 TB/s at the median."""
 import argparse
 import json
@@ -25,7 +29,9 @@ KNAME = {3: "3", 5: "5", 7: "7", -1: "scharr"}
 CONFIGS = ([(f"deriv_{KNAME[k]}_{'mono' if ch == 1 else 'bgr'}", ch, "deriv", k) for ch in (1, 3) for k in (3, 5, 7, -1)]
            + [("gradients_mono", 1, "grad", 3), ("gradients_bgr", 3, "grad", 3)]
            + [("canny7_chain_mono", 1, "chain", 7), ("canny5_fused_mono", 1, "ap5", 5),
-              ("canny7_chain_bgr", 3, "chain", 7), ("canny5_fused_bgr", 3, "ap5", 5)])
+              ("canny7_chain_bgr", 3, "chain", 7), ("canny5_fused_bgr", 3, "ap5", 5)]
+           + [("canny7_fused_mono", 1, "fused", 7), ("scharr_chain_mono", 1, "chain", -1), ("scharr_fused_mono", 1, "fused", -1),
+              ("canny7_fused_bgr", 3, "fused", 7), ("scharr_chain_bgr", 3, "chain", -1), ("scharr_fused_bgr", 3, "fused", -1)])
 
 
 def child(name, ch, form, ks, n, steps):
@@ -43,7 +49,7 @@ def child(name, ch, form, ks, n, steps):
     px = n * W * H
     res = {"config": name, "channels": ch, "frames": n, "steps": steps, "ksize": ks}
     ctx = api.Context(W, H, ch, n, api.MODE_O)
-    if form != "ap5":
+    if form not in ("ap5", "fused"):
         dx, dy = torch.empty(src.shape, dtype=torch.int16, device="cuda"), torch.empty(src.shape, dtype=torch.int16, device="cuda")
 
     def deriv(k):
@@ -96,6 +102,27 @@ def child(name, ch, form, ks, n, steps):
             ctx.set_option(api.OPT_APERTURE, 5)
         else:
             ctx.set_thresholds(150, 450)
+        scale = 16.0 if ks == 7 else 1.0
+
+        def fused(o):
+            ctx.canny_device(src.data_ptr(), row, row * H, o.data_ptr(), W, W * H, n, 150 * scale, 450 * scale, ks, False)
+        if form == "fused":   # the front kernel alone first: plain profiled runs
+            o0 = torch.empty((n, H, W), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            ctx.enable_profiling(1)
+            for _ in range(2):
+                fused(o0)
+            ctx.sync()
+            ctx.profile_get(reset=True)
+            for _ in range(steps):
+                fused(o0)
+                ctx.sync()
+            fe = sorted(ctx.profile_front_each())
+            ctx.enable_profiling(0)
+            bpp = ch + 0.25
+            res.update(front_ms_median=round(fe[len(fe) // 2], 4), front_ms_min=round(fe[0], 4), front_ms_max=round(fe[-1], 4), bytes_per_px=bpp,
+                       frac_hbm=round(px * bpp / (fe[len(fe) // 2] / 1e3) / HBM, 3))
+            del o0
         ctx.set_option(api.OPT_PIPELINE, 1)
         depth = max(1, ctx.pipeline_depth(n))
         out = [torch.empty((n, H, W), dtype=torch.uint8, device="cuda") for _ in range(depth)]
@@ -104,6 +131,8 @@ def child(name, ch, form, ks, n, steps):
         def run(o):
             if form == "ap5":
                 ctx.run_device(src.data_ptr(), row, row * H, o.data_ptr(), W, W * H, n)
+            elif form == "fused":
+                fused(o)
             else:
                 deriv(ks)
                 ctx.run_gradients_device(dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * H, o.data_ptr(), W, W * H, n)
