@@ -41,6 +41,10 @@
 #define F8_ABL 0  // timing measurements with parts left out (tools/build_variant.sh, WRONG results): 1 no NMS batches, 2 no fix-up, 4 no phase 2 (Sobel, test, queue) and no batches, 8 no zero stores of the provisional map
 #endif
 
+#ifndef F8_WQ_HIST
+#define F8_WQ_HIST 0  // measurement build (tools/dense_sweep.py --hist; plain form only): with HC_OPT_DEBUG_TAPS every window leaves its count of half-lanes above the low threshold, and which path it took, in the blur tap instead of the blur rows
+#endif
+
 namespace hc {
 
 // (F8_STRIP_W, F8_HSTRIP_W, F8_SUB and the strip / run arithmetic: canny_params.h, shared with the host planner)
@@ -486,11 +490,19 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
   // passes, two batches per row -- it costs 2.6 x a natural frame (round 2: 132 k frames/s against 225 k with round 1's
   // wave-wide k_nms).  A window that follows one with more than p.dense_enter queued half-lanes is therefore processed
   // whole, by every lane for its own 8 pixels: the 10 blur rows of the ring -> d / s -> the Sobel sums and the exact S2
-  // of 8 rows (two more than it outputs: no state is carried from the window before) -> thresholds, direction bins and
-  // the non-strict NMS of the 6 output rows against the rows above / below in registers and the neighbours' columns by
+  // of 8 rows (two more than it outputs: the cold form, which carries no state in from the window before) -> thresholds,
+  // direction bins and the non-strict NMS of the 6 output rows against the rows above / below in registers and the neighbours' columns by
   // DPP -> one byte of each plane and 8 bytes of provisional map per lane and row, stored once (no zero-stores, no queue,
   // no LDS beyond the 10 row reads).  ~260 instructions per row whatever the content.  The arithmetic is the batch's.
-  auto dense_window = [&](int bw0, u32 sbase) {
+  // The WARM form follows another dense window of the same run.  That window's last four blur rows are this one's first
+  // four, so what it derived from them is still in registers and is not formed again: the S2 of Sobel rows bw0 - 3 and
+  // bw0 - 2 with their halo entries (cSC, cSN), the Sobel sums of row bw0 - 2 (cXn, cYn) and the d / s of blur rows bw0 - 2
+  // and bw0 - 1 (sr / dr [1], which the queue path is handed too, and cdL / csL).  It reads 6 blur rows instead of 10.  The
+  // cold form (the first dense window of a stretch: after a sparse window, or at the start of a run) carries nothing in.
+  // (Zeroed only to be defined on every path: a cold window writes all of them before a warm one reads any.)
+  u32 cSC[10] = {}, cSN[10] = {}, cXn[4] = {}, cYn[4] = {}, cdL[4] = {}, csL[4] = {};
+  auto dense_window = [&](auto warm_c, int bw0, u32 sbase) {
+    constexpr bool WARM = decltype(warm_c)::value;
     // pixels outside the image have zero gradients (cannyEdgeD.cu:142-149, 222-229): half-word masks of the lane's aligned pairs
     const u32 pm[4] = { __builtin_amdgcn_perm(0u, cmask[0], 0x01010000u), __builtin_amdgcn_perm(0u, cmask[0], 0x03030202u),
                         __builtin_amdgcn_perm(0u, cmask[1], 0x01010000u), __builtin_amdgcn_perm(0u, cmask[1], 0x03030202u) };
@@ -498,12 +510,18 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     u32 SU[10], SC[10], SN[10];          // S2 of three Sobel rows: [0] = pixel -1 (the lane below), [1 + q] = pixel q, [9] = pixel 8
     u32 Xc[4], Yc[4], Xn[4], Yn[4];      // the Sobel sums of the centre row / the newest row (packed pairs)
 #pragma unroll
-    for (int k = 0; k < 10; ++k) SU[k] = SC[k] = SN[k] = 0;
+    for (int k = 0; k < 10; ++k) { SU[k] = 0; SC[k] = WARM ? cSC[k] : 0u; SN[k] = WARM ? cSN[k] : 0u; }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) dP[0][j] = dP[1][j] = sP[0][j] = sP[1][j] = Xc[j] = Yc[j] = Xn[j] = Yn[j] = 0;
+    for (int j = 0; j < 4; ++j) {
+      // (blur row bw0 - 2 is row i = 2 of the loop below and bw0 - 1 is row 3: they sit where rows of that parity go)
+      dP[0][j] = WARM ? dr[1][j] : 0u; sP[0][j] = WARM ? sr[1][j] : 0u;
+      dP[1][j] = WARM ? cdL[j] : 0u; sP[1][j] = WARM ? csL[j] : 0u;
+      Xc[j] = Yc[j] = 0;
+      Xn[j] = WARM ? cXn[j] : 0u; Yn[j] = WARM ? cYn[j] : 0u;
+    }
     int cnt = 0;
 #pragma unroll
-    for (int i = 0; i < 10; ++i) {  // blur row bw0 - 4 + i
+    for (int i = WARM ? 4 : 0; i < 10; ++i) {  // blur row bw0 - 4 + i
       u32 slot = sbase + (u32)i;
       slot = slot >= (u32)F8_RING ? slot - (u32)F8_RING : slot;
       const u32x2 b = *reinterpret_cast<const u32x2 *>(bring + slot * (u32)F8_ROW_BYTES + lane * 8);
@@ -542,6 +560,10 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
       if (i == 7 || i == 8) {  // what the next window's first steps expect: d / s of blur rows bw0 + 3 and bw0 + 4
 #pragma unroll
         for (int j = 0; j < 4; ++j) { dr[i - 7][j] = dk[j]; sr[i - 7][j] = sk[j]; }
+      }
+      if (i == 9) {  // ... and a warm window: d / s of blur row bw0 + 5
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { cdL[j] = dk[j]; csL[j] = sk[j]; }
       }
       if (i >= 4) {  // NMS of output row bw0 - 6 + i: centre SC, above SU, below SN
         int c = bw0 - 6 + i;
@@ -586,6 +608,10 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
         }
       }
     }
+#pragma unroll
+    for (int k = 0; k < 10; ++k) { cSC[k] = SC[k]; cSN[k] = SN[k]; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { cXn[j] = Xn[j]; cYn[j] = Yn[j]; }
     wq = cnt;
   };
 
@@ -609,9 +635,11 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
   for (int j = 0; j < G; ++j) xn[j] = load_raw(r0 + j);
   const int nwin = (rend + 2 - (r0 - 2) + F8_SUB - 1) / F8_SUB;
   int bslot0 = 0;  // blur-ring slot of the window's first blur row (blur row r0 - 2 sits in slot 0)
-  // one window; DENSE: its phase 2 is the dense path.  (A lambda instantiated twice, for two separate loops below.)
-  auto window = [&](auto dense_c, int w) {
-    constexpr bool DENSE = decltype(dense_c)::value;
+  // one window; PATH: its phase 2 is 0 the queue path, 1 the dense path's cold form, 2 its warm form.  (A lambda instantiated
+  // three times, for the separate loops below.)
+  auto window = [&](auto path_c, int w) {
+    constexpr int PATH = decltype(path_c)::value;
+    constexpr bool DENSE = PATH != 0;
     const int bw0 = r0 - 2 + w * F8_SUB;  // the window's blur rows are bw0 .. bw0+5 (its last input row is bw0 + 7)
     qn = 0;
 #pragma unroll
@@ -672,7 +700,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
       bs = bs < 0 ? bs + F8_RING : bs >= F8_RING ? bs - F8_RING : bs;
       bq[j] = *reinterpret_cast<const u32x2 *>(bring + bs * F8_ROW_BYTES + lane * 8);
     }
-    if (p.dbg_blur && own_lane && c0 < W) {  // diagnostics (HC_OPT_DEBUG_TAPS): the fixed-up blur rows of this run
+    if (!F8_WQ_HIST && p.dbg_blur && own_lane && c0 < W) {  // diagnostics (HC_OPT_DEBUG_TAPS): the fixed-up blur rows of this run
 #pragma unroll
       for (int j = 0; j < F8_SUB; ++j) {
         const int k = bw0 - 1 + j;
@@ -682,7 +710,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     int sb = bslot0 - 4;  // blur-ring slot of blur row bw0 - 4
     if (sb < 0) sb += F8_RING;
     if constexpr (DENSE) {
-      dense_window(bw0, (u32)sb);
+      dense_window(std::integral_constant<bool, PATH == 2>{}, bw0, (u32)sb);
     } else {
       wq = 0;
       if (!(F8_ABL & 4)) {
@@ -698,6 +726,11 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
         while (qcount > 0) nms_batch(min(qcount, 64), bw0, (u32)sb);
       }
     }
+    if (F8_WQ_HIST && !HALF && p.dbg_blur && lane == 0) {  // one record per (frame, strip, run, window): row r0 + w of the tap, 8 bytes per strip
+      u32 *rec = reinterpret_cast<u32 *>(p.dbg_blur + (size_t)frame * p.dbg_fs + (size_t)(r0 + w) * p.dbg_pitch + (u32)strip * 8u);
+      rec[0] = 0xA5000000u | (DENSE ? 0x10000u : 0u) | (u32)wq;  // wq: the queue path's necessary-condition count, or the dense path's exact one
+      rec[1] = (u32)(bw0 - 2 + 0x8000);                          // the window's first output row
+    }
     wave_lds_sync();  // the next window's phase 1 overwrites the oldest ring rows
     if (IN == 2) __syncthreads();  // the three channels of this run stay within a window of each other (see above)
     bslot0 = bslot0 + F8_SUB >= F8_RING ? bslot0 + F8_SUB - F8_RING : bslot0 + F8_SUB;
@@ -705,19 +738,26 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
   // Two loops, not one loop with a branch in it: the dense path needs more SGPRs than the kernel has (its compare masks),
   // and with the branch inside the window loop the spills it caused were paid by every window of every frame (+2 % on
   // frames that never take the path).  A window that queued more than p.dense_enter half-lanes hands over to the dense
-  // loop, a dense window that counted fewer than p.dense_leave hands back.
+  // loop, a dense window that counted fewer than p.dense_leave hands back.  The first window of a dense stretch is the
+  // cold form and the rest of the stretch, a loop of its own again, the warm one: what a warm window starts from is live
+  // in that loop only, never across a sparse window, a run or a frame.
   int w = 0;
   bool dense = p.dense_enter < 0;  // HC_OPT_FRONT_DENSE = 1: every window (tests)
   while (w < nwin) {
 #pragma nounroll
     for (; w < nwin && !dense; ++w) {
-      window(std::false_type{}, w);
+      window(std::integral_constant<int, 0>{}, w);
       dense = wq > p.dense_enter;
     }
-#pragma nounroll
-    for (; w < nwin && dense; ++w) {
-      window(std::true_type{}, w);
+    if (w < nwin) {
+      window(std::integral_constant<int, 1>{}, w);
       dense = wq > p.dense_leave;
+      ++w;
+#pragma nounroll
+      for (; w < nwin && dense; ++w) {
+        window(std::integral_constant<int, 2>{}, w);
+        dense = wq > p.dense_leave;
+      }
     }
   }
 }

@@ -347,10 +347,14 @@ inline void plan_zeroing_and_dense(const FrontIn &in, FrontPlan &P)
   FrontParams &fp = P.fp;
   P.zeroed_words = run_flag_words(std::min(in.wl_cap, slot_wl_cap((size_t)front_out_frames(in), in.H, in.RD)));
   fp.zero_count = (u32)P.zeroed_words;
-  // dense path of k_front8 (wave-wide NMS): enter above 512 half-lanes per window of 768, leave below 384.  (The batch
-  // scheme costs 27 + 41 + 3.6 e instructions per row for e queued half-lanes, the dense path ~260: break-even near
-  // 320 per window -- but the zero padding makes the first two rows of every frame candidates across the whole
-  // width, and with 320 the window after them went dense on every natural frame: +1.2 % on the benchmark's frames.)
+  // dense path of k_front8 (wave-wide NMS): enter above 512 half-lanes per window of 768, leave below 384.  Both paths
+  // count the half-lanes above the low threshold in the window's rows 2 .. H-3 only (the zero padding makes the frame's
+  // first and last two rows candidates across the whole width).  Measured (profiles/r10_dense/, 1080p, 1024 frames):
+  // of the interior windows 1.1 % (natural), 1.0 % (natural-B), 2.1 % (blend) and none (noise) count 320 .. 512, so the
+  // thresholds decide little; lowering dense_enter from 512 to 192 (leave at 3/4) raises the front kernel on natural
+  // frames step by step from 2.12 to 2.18 ms, and no lower value reached the rotation's 302.9 k frames/s at 512 (192:
+  // 301.2 k, 256: 300.0 k, 320: 300.7 k, 384: 302.1 k, 448: 302.1 k).  On noise only 192 differs (3.26 -> 3.16 ms): a run's first window has two rows of its own and counts
+  // 248, so with any higher value the second window still takes the queue path.
   // (k_front_mx has no dense path and reads neither value; its plans have always carried them and still do)
   fp.dense_enter = o.dense_mode == 0 ? 0x7FFFFFFF : o.dense_mode == 1 ? -1 : o.dense_enter;
   fp.dense_leave = o.dense_mode == 0 ? 0x7FFFFFFF : o.dense_mode == 1 ? -1 : o.dense_leave;
