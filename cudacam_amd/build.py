@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libhipcanny.so")
 LIB_LEGACY = os.path.join(HERE, "libhipcanny_legacy.so")
 SOURCES = ["canny_kernels.hip", "hyst.hip", "front8.hip", "front_mx.hip", "front_o_ext.hip", "deriv.hip", "hipcanny.hip"]
 LEGACY_SOURCES = SOURCES + ["legacy_front.hip"]
-DEPS = LEGACY_SOURCES + ["canny_common.h", "canny_params.h", "host_plan.h", "canny_device.h", os.path.join("..", "..", "include", "hipcanny.h")]
+DEPS = LEGACY_SOURCES + ["canny_common.h", "canny_params.h", "host_plan.h", "canny_device.h", "sep_deriv.h", os.path.join("..", "..", "include", "hipcanny.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

@@ -1,57 +1,28 @@
 // deriv.hip -- k_deriv16: the derivatives cv::Canny computes before its NMS, on their own.
 //
 //   u8 frames (1 or 3 interleaved channels) -> int16 dx / dy planes with the same interleave (CV_16SC1 / CV_16SC3), the
-//   layout hc_run_gradients_device reads.  Sobel(src, CV_16S, 1, 0 / 0, 1, ksize, scale, 0, BORDER_REPLICATE) restated:
-//     ksize  3   smoothing [1 2 1]               derivative [-1 0 1]              scale 1
-//     ksize  5             [1 4 6 4 1]                      [-1 -2 0 2 1]         scale 1
-//     ksize  7             [1 6 15 20 15 6 1]               [-1 -4 -5 0 5 4 1]    scale 1/16, rounded half to even
-//     ksize -1 (Scharr)    [3 10 3]                         [-1 0 1]              scale 1
-//   a correlation, dx = derivative taps along x and smoothing taps along y, dy the other way round.
-// Layout as k_front_o_ext's Source A: a wave owns a 248-column strip, lane l the 4 pixels at strip * 248 - 4 + 4 l, lanes 0
+//   layout hc_run_gradients_device reads: cv::Sobel at ksize 3, 5, 7 or -1 (Scharr), the taps and both passes of sep_deriv.h.
+// Layout as k_front_o_ext's u8 sources: a wave owns a 248-column strip, lane l the 4 pixels at strip * 248 - 4 + 4 l, lanes 0
 // and 63 are halo; columns replicate through a per-lane byte selector, rows by clamping the row index.  The horizontal
-// passes run in packed int16 pairs (every horizontal partial fits int16 for all four kinds) and stay in a register ring of
-// ksize rows; the vertical pass is packed too, except at ksize 7, whose sums (|S| <= 163200) need 32 bits before the
-// division.  A work item is (frame, strip, DERIV_CHUNK_ROWS rows) with a warm-up of ksize - 1 rows.  Registers only.
+// passes stay in a register ring of ksize rows.  A work item is (frame, strip, DERIV_CHUNK_ROWS rows) with a warm-up of
+// ksize - 1 rows.  Registers only.
 // Memory: no byte outside [row, row + C W) of an input row is read, none outside [row, row + 2 C W) of an output row is
 // written, at any alignment: dword loads only for whole 4-pixel groups of 4-aligned rows (byte loads otherwise), 8- or
 // 4-byte stores only for whole groups of rows aligned that far (int16 stores otherwise).
-#include "canny_device.h"
+#include "sep_deriv.h"
 
 namespace hc {
 
 namespace {
 
-typedef short i16x2v __attribute__((ext_vector_type(2)));
-typedef u32 u32x2v __attribute__((ext_vector_type(2)));
-static __device__ __forceinline__ i16x2v V(u32 v) { return __builtin_bit_cast(i16x2v, v); }
-static __device__ __forceinline__ u32 W32(i16x2v v) { return __builtin_bit_cast(u32, v); }
-static __device__ __forceinline__ i16x2v splat(int c) { return i16x2v{ (short)c, (short)c }; }
-static __device__ __forceinline__ int lo16(u32 v) { return (int)(short)(v & 0xFFFFu); }
-static __device__ __forceinline__ int hi16(u32 v) { return (int)v >> 16; }
-// (half LH of lo_src, half HH of hi_src) as one int16 pair
-template <int LH, int HH>
-static __device__ __forceinline__ u32 pick2(u32 lo_src, u32 hi_src)
-{
-  return __builtin_amdgcn_perm(hi_src, lo_src, (LH ? 0x0302u : 0x0100u) | ((HH ? 0x0706u : 0x0504u) << 16));
-}
+using namespace sep;
 
-constexpr int deriv_taps(int kind) { return kind == -1 ? 3 : kind; }
-constexpr int smooth_tap(int kind, int t)
-{
-  constexpr int s3[3] = { 1, 2, 1 }, s5[5] = { 1, 4, 6, 4, 1 }, s7[7] = { 1, 6, 15, 20, 15, 6, 1 }, sc[3] = { 3, 10, 3 };
-  return kind == 3 ? s3[t] : kind == 5 ? s5[t] : kind == 7 ? s7[t] : sc[t];
-}
-constexpr int deriv_tap(int kind, int t)
-{
-  constexpr int d3[3] = { -1, 0, 1 }, d5[5] = { -1, -2, 0, 2, 1 }, d7[7] = { -1, -4, -5, 0, 5, 4, 1 };
-  return kind == 5 ? d5[t] : kind == 7 ? d7[t] : d3[t];
-}
+typedef u32 u32x2v __attribute__((ext_vector_type(2)));
 
 template <int KIND, int NC>
 __global__ __launch_bounds__(256) void k_deriv16(const DerivParams p)
 {
   constexpr int K = deriv_taps(KIND), R = K / 2;
-  constexpr bool WIDE = KIND == 7;  // 32-bit vertical sums, then / 16 half to even
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
   const int item = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x) * 4 + wib);
@@ -94,17 +65,6 @@ __global__ __launch_bounds__(256) void k_deriv16(const DerivParams p)
     }
     return r;
   };
-  // channel ch of the lane's 4 pixels as one dword, replicated at the borders
-  auto use_row = [&](const Raw &raw, int ch) -> u32 {
-    u32 v = raw.d[0];
-    if constexpr (NC == 3) {
-      const u32 selA = ch == 0 ? 0x0c060300u : ch == 1 ? 0x0c070401u : 0x0c0c0502u;
-      const u32 selB = ch == 0 ? 0x05020100u : ch == 1 ? 0x06020100u : 0x07040100u;
-      v = __builtin_amdgcn_perm(raw.d[NC > 2 ? 2 : 0], __builtin_amdgcn_perm(raw.d[NC > 1 ? 1 : 0], raw.d[0], selA), selB);
-    }
-    return __builtin_amdgcn_perm(0u, v, rsel);
-  };
-
   // per channel: horizontal derivative / smoothing rows of the last K source rows, packed pairs [ring][pair]
   u32 HD[NC][K][2], HS[NC][K][2];
 #pragma unroll
@@ -141,56 +101,18 @@ __global__ __launch_bounds__(256) void k_deriv16(const DerivParams p)
     u32 X[NC][2], Y[NC][2];                 // per channel: (px 0, px 1), (px 2, px 3)
 #pragma unroll
     for (int ch = 0; ch < NC; ++ch) {
-      // horizontal pass on the new row.  P[t + 4] = the pixel pair that starts t columns from the lane's first
-      const u32 b = use_row(raw, ch);
-      u32 P[11];
-      P[4] = unpack_lo(b); P[6] = unpack_hi(b);
-      P[2] = from_lane_below(P[6]); P[8] = from_lane_above(P[4]);
-      P[0] = from_lane_below(P[4]); P[10] = from_lane_above(P[6]);
-      P[1] = pair_shift(P[2], P[0]); P[3] = pair_shift(P[4], P[2]); P[5] = pair_shift(P[6], P[4]);
-      P[7] = pair_shift(P[8], P[6]); P[9] = pair_shift(P[10], P[8]);
+      const PairWindow P = sep_window(pick_channel(raw.d, ch, rsel));
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int c = 4 + 2 * h;
-        i16x2v hs = V(P[c]) * splat(smooth_tap(KIND, R)), hd = splat(0);
-#pragma unroll
-        for (int t = 0; t < R; ++t) {
-          hs += (V(P[c - R + t]) + V(P[c + R - t])) * splat(smooth_tap(KIND, t));
-          hd += (V(P[c + R - t]) - V(P[c - R + t])) * splat(deriv_tap(KIND, K - 1 - t));
-        }
-        HS[ch][u][h] = W32(hs);
-        HD[ch][u][h] = W32(hd);
-      }
-      if (emit) {
-        // vertical pass over source rows k - K + 1 .. k: ring slot of tap t (t = 0: the oldest row) is (u + 1 + t) % K
+      for (int h = 0; h < 2; ++h) sep_hpass<KIND>(P, h, HD[ch][u][h], HS[ch][u][h]);
+      if (emit) {  // vertical pass over source rows k - K + 1 .. k
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          if constexpr (!WIDE) {
-            i16x2v vx = V(HD[ch][(u + 1 + R) % K][h]) * splat(smooth_tap(KIND, R)), vy = splat(0);
-#pragma unroll
-            for (int t = 0; t < R; ++t) {
-              const int so = (u + 1 + t) % K, sn = (u + K - t) % K;  // rows g - R + t and g + R - t
-              vx += (V(HD[ch][so][h]) + V(HD[ch][sn][h])) * splat(smooth_tap(KIND, t));
-              vy += (V(HS[ch][sn][h]) - V(HS[ch][so][h])) * splat(deriv_tap(KIND, K - 1 - t));
-            }
-            X[ch][h] = W32(vx);
-            Y[ch][h] = W32(vy);
-          } else {
-            // symmetric rows first, still packed (|hd| <= 2550, hs <= 16320: sums and differences fit int16), then 32 bits
-            const u32 mid = HD[ch][(u + 1 + R) % K][h];
-            int sx0 = lo16(mid) * smooth_tap(KIND, R), sx1 = hi16(mid) * smooth_tap(KIND, R), sy0 = 0, sy1 = 0;
-#pragma unroll
-            for (int t = 0; t < R; ++t) {
-              const int so = (u + 1 + t) % K, sn = (u + K - t) % K;
-              const u32 a = W32(V(HD[ch][so][h]) + V(HD[ch][sn][h]));
-              const u32 d = W32(V(HS[ch][sn][h]) - V(HS[ch][so][h]));
-              sx0 += lo16(a) * smooth_tap(KIND, t); sx1 += hi16(a) * smooth_tap(KIND, t);
-              sy0 += lo16(d) * deriv_tap(KIND, K - 1 - t); sy1 += hi16(d) * deriv_tap(KIND, K - 1 - t);
-            }
-            // S / 16 rounded half to even (what cvRound gives for the exact float S / 16)
-            auto rnd = [](int s) -> u32 { return (u32)((s + 7 + ((s >> 4) & 1)) >> 4); };
-            X[ch][h] = (rnd(sx0) & 0xFFFFu) | (rnd(sx1) << 16);
-            Y[ch][h] = (rnd(sy0) & 0xFFFFu) | (rnd(sy1) << 16);
+          if constexpr (KIND != 7) sep_vpass_pk<KIND, K, u>(HD[ch], HS[ch], h, X[ch][h], Y[ch][h]);
+          else {
+            int x0, x1, y0, y1;
+            sep_vpass_wide<K, u>(HD[ch], HS[ch], h, x0, x1, y0, y1);
+            X[ch][h] = ((u32)x0 & 0xFFFFu) | ((u32)x1 << 16);
+            Y[ch][h] = ((u32)y0 & 0xFFFFu) | ((u32)y1 << 16);
           }
         }
       }

@@ -1,15 +1,13 @@
 // front_o_ext.hip -- the rest of cv::Canny's surface for Mode O: apertures 5, 7 and -1 (Scharr), and the (dx, dy) overload.
 //
 // One kernel template, four row sources and a shared back half:
-//   SRC 0  u8 rows (1 or 3 interleaved channels) -> the 5x5 Sobel of cv::Canny(img, low, high, 5, L2gradient):
-//          Sobel(src, CV_16S, ksize 5, scale 1, BORDER_REPLICATE), computed separably in packed 16-bit math
-//          (every partial and final sum fits int16: |dx|, |dy| <= 12240)
+//   SRC 0  u8 rows (1 or 3 interleaved channels) -> the 5x5 Sobel of cv::Canny(img, low, high, 5, L2gradient), separably in
+//          packed 16-bit math, spelled out below (every partial and final sum fits int16: |dx|, |dy| <= 12240)
 //   SRC 1  int16 dx / dy rows given by the caller (cv::Canny(dx, dy, edges, low, high, L2gradient))
-//   SRC 2  u8 rows -> the 7x7 Sobel of cv::Canny(img, low, high, 7, L2gradient), k_deriv16's arithmetic (deriv.hip): horizontal
-//          [-1 -4 -5 0 5 4 1] / [1 6 15 20 15 6 1] in packed pairs (|hd| <= 2550, hs <= 16320), symmetric rows added or
-//          subtracted in packed halves, the products summed in 32 bits (|S| <= 163200), then S / 16 rounded half to even
-//   SRC 3  u8 rows -> the Scharr derivatives of cv::Canny(img, low, high, -1, L2gradient): [-1 0 1] / [3 10 3], all packed
-//          int16 (+-4080)
+//   SRC 2  u8 rows -> the 7x7 Sobel (scale 1/16) of cv::Canny(img, low, high, 7, L2gradient)
+//   SRC 3  u8 rows -> the Scharr derivatives of cv::Canny(img, low, high, -1, L2gradient)
+//          SRC 2 and 3 are sep_deriv.h's horizontal and vertical pass at ksize 7 and -1, the arithmetic of k_deriv16
+//          (deriv.hip); the taps and the int16 ranges are stated there
 //   back   32-bit magnitude (L1 |dx| + |dy| or L2 dx^2 + dy^2, two's complement with wrap-around as canny.cpp's `int`),
 //          the 3-channel "first channel with the largest m" select, the integer tangent test (TG22 = 13573), asymmetric
 //          non-maximum suppression and the two thresholds -> STRONG / CANDIDATE bit planes that k_hyst finishes.
@@ -21,31 +19,16 @@
 // and 3 unroll 6 steps per loop trip, the common period, so every ring slot is a compile-time register.  A 7-row source
 // ring would make that period 42: SRC 2 unrolls the 7 steps of its source ring and advances the two small rings by
 // register moves instead (the unrolled body renames them: the moves that remain sit at the loop's back edge).
-#include "canny_device.h"
+#include "sep_deriv.h"
 
 namespace hc {
 
 namespace {
 
-typedef short i16x2v __attribute__((ext_vector_type(2)));
-static __device__ __forceinline__ i16x2v V(u32 v) { return __builtin_bit_cast(i16x2v, v); }
-static __device__ __forceinline__ u32 W32(i16x2v v) { return __builtin_bit_cast(u32, v); }
-static __device__ __forceinline__ int lo16(u32 v) { return (int)(short)(v & 0xFFFFu); }
-static __device__ __forceinline__ int hi16(u32 v) { return (int)v >> 16; }
+using namespace sep;
 
-// the u8 sources' separable taps (SRC 2 / 3; SRC 0 spells its own out)
-constexpr int src_taps(int src) { return src == 2 ? 7 : 3; }
-constexpr int smooth_tap(int src, int t)
-{
-  constexpr int s7[7] = { 1, 6, 15, 20, 15, 6, 1 }, sc[3] = { 3, 10, 3 };
-  return src == 2 ? s7[t] : sc[t];
-}
-constexpr int deriv_tap(int src, int t)
-{
-  constexpr int d7[7] = { -1, -4, -5, 0, 5, 4, 1 }, d3[3] = { -1, 0, 1 };
-  return src == 2 ? d7[t] : d3[t];
-}
-static __device__ __forceinline__ i16x2v splat(int c) { return i16x2v{ (short)c, (short)c }; }
+// the u8 sources' cv ksize.  0 -> 5 only documents the map: SRC 0 spells its passes out and never asks (static_assert below)
+constexpr int src_kind(int src) { return src == 0 ? 5 : src == 2 ? 7 : -1; }
 
 template <int SRC, bool L2, int NC>
 __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
@@ -117,17 +100,6 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
     }
     return r;
   };
-  // u8 rows: channel ch of the lane's 4 pixels as one dword, replicated at the borders
-  auto use_row = [&](const Raw &raw, int ch) -> u32 {
-    u32 v = raw.d[0];
-    if constexpr (U8 && NC == 3) {
-      const u32 selA = ch == 0 ? 0x0c060300u : ch == 1 ? 0x0c070401u : 0x0c0c0502u;
-      const u32 selB = ch == 0 ? 0x05020100u : ch == 1 ? 0x06020100u : 0x07040100u;
-      v = __builtin_amdgcn_perm(raw.d[NC > 2 ? 2 : 0], __builtin_amdgcn_perm(raw.d[NC > 1 ? 1 : 0], raw.d[0], selA), selB);
-    }
-    return __builtin_amdgcn_perm(0u, v, rsel);
-  };
-
   // u8 rows: per channel, the horizontal derivative / smoothing rows of the last RING source rows, packed pairs [ring][pair]
   constexpr int NR = U8 ? NC : 1;
   u32 HD[NR][RING][2], HS[NR][RING][2];
@@ -171,8 +143,9 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
     for (int ch = 0; ch < NC; ++ch) {
       int x[4], y[4];
       if constexpr (SRC == 0) {
+        // spelled out: through sep_deriv.h's loops at ksize 5 in a ring of 6 the fused aperture-5 runs measured 0.6-0.9 % slower
         // horizontal pass on the new row: hd = [-1 -2 0 2 1], hs = [1 4 6 4 1] (pairs of int16, wrapping sums that end in range)
-        const u32 b = use_row(raw, ch);
+        const u32 b = pick_channel(raw.d, ch, rsel);
         const u32 A = unpack_lo(b), B = unpack_hi(b);           // (x0, x1), (x2, x3)
         const u32 Bl = from_lane_below(B), Ar = from_lane_above(A);  // (x-2, x-1), (x4, x5)
         const u32 m1 = pair_shift(A, Bl), p1 = pair_shift(B, A), p3 = pair_shift(Ar, B);  // (x-1, x0), (x1, x2), (x3, x4)
@@ -190,57 +163,21 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
           x[2 * h] = lo16(dxp); x[2 * h + 1] = hi16(dxp);
           y[2 * h] = lo16(dyp); y[2 * h + 1] = hi16(dyp);
         }
-      } else if constexpr (SRC == 2 || SRC == 3) {
-        constexpr int K = src_taps(SRC), RAD = K / 2, us = u % RING;
-        // horizontal pass on the new row.  P[t + 4] = the pixel pair that starts t columns from the lane's first
-        const u32 b = use_row(raw, ch);
-        u32 P[11];
-        P[4] = unpack_lo(b); P[6] = unpack_hi(b);
-        P[2] = from_lane_below(P[6]); P[8] = from_lane_above(P[4]);
-        P[0] = from_lane_below(P[4]); P[10] = from_lane_above(P[6]);
-        P[1] = pair_shift(P[2], P[0]); P[3] = pair_shift(P[4], P[2]); P[5] = pair_shift(P[6], P[4]);
-        P[7] = pair_shift(P[8], P[6]); P[9] = pair_shift(P[10], P[8]);
+      } else if constexpr (U8) {
+        // sep_deriv.h's two passes; the vertical one over the newest deriv_taps(KIND) rows of the ring
+        static_assert(SRC == 2 || SRC == 3, "the shared passes serve aperture 7 and Scharr");
+        constexpr int KIND = src_kind(SRC), us = u % RING;
+        const PairWindow P = sep_window(pick_channel(raw.d, ch, rsel));
+#pragma unroll
+        for (int h = 0; h < 2; ++h) sep_hpass<KIND>(P, h, HD[ch][us][h], HS[ch][us][h]);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          const int c = 4 + 2 * h;
-          i16x2v hs = V(P[c]) * splat(smooth_tap(SRC, RAD)), hd = splat(0);
-#pragma unroll
-          for (int t = 0; t < RAD; ++t) {
-            hs += (V(P[c - RAD + t]) + V(P[c + RAD - t])) * splat(smooth_tap(SRC, t));
-            hd += (V(P[c + RAD - t]) - V(P[c - RAD + t])) * splat(deriv_tap(SRC, K - 1 - t));
-          }
-          HS[ch][us][h] = W32(hs);
-          HD[ch][us][h] = W32(hd);
-        }
-        // vertical pass over source rows k - K + 1 .. k: ring slot of tap t (t = 0: the oldest row) is (us + 1 + t) % K
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          if constexpr (SRC == 3) {
-            i16x2v vx = V(HD[ch][(us + 1 + RAD) % K][h]) * splat(smooth_tap(SRC, RAD)), vy = splat(0);
-#pragma unroll
-            for (int t = 0; t < RAD; ++t) {
-              const int so = (us + 1 + t) % K, sn = (us + K - t) % K;  // rows g - RAD + t and g + RAD - t
-              vx += (V(HD[ch][so][h]) + V(HD[ch][sn][h])) * splat(smooth_tap(SRC, t));
-              vy += (V(HS[ch][sn][h]) - V(HS[ch][so][h])) * splat(deriv_tap(SRC, K - 1 - t));
-            }
-            x[2 * h] = lo16(W32(vx)); x[2 * h + 1] = hi16(W32(vx));
-            y[2 * h] = lo16(W32(vy)); y[2 * h + 1] = hi16(W32(vy));
-          } else {
-            // symmetric rows first, still packed (|hd| <= 2550, hs <= 16320: sums and differences fit int16), then 32 bits
-            const u32 mid = HD[ch][(us + 1 + RAD) % K][h];
-            int sx0 = lo16(mid) * smooth_tap(SRC, RAD), sx1 = hi16(mid) * smooth_tap(SRC, RAD), sy0 = 0, sy1 = 0;
-#pragma unroll
-            for (int t = 0; t < RAD; ++t) {
-              const int so = (us + 1 + t) % K, sn = (us + K - t) % K;
-              const u32 a = W32(V(HD[ch][so][h]) + V(HD[ch][sn][h]));
-              const u32 d = W32(V(HS[ch][sn][h]) - V(HS[ch][so][h]));
-              sx0 += lo16(a) * smooth_tap(SRC, t); sx1 += hi16(a) * smooth_tap(SRC, t);
-              sy0 += lo16(d) * deriv_tap(SRC, K - 1 - t); sy1 += hi16(d) * deriv_tap(SRC, K - 1 - t);
-            }
-            // S / 16 rounded half to even (what cvRound gives for the exact float S / 16)
-            auto rnd = [](int s) -> int { return (s + 7 + ((s >> 4) & 1)) >> 4; };
-            x[2 * h] = rnd(sx0); x[2 * h + 1] = rnd(sx1);
-            y[2 * h] = rnd(sy0); y[2 * h + 1] = rnd(sy1);
+          if constexpr (KIND == 7) sep_vpass_wide<RING, us>(HD[ch], HS[ch], h, x[2 * h], x[2 * h + 1], y[2 * h], y[2 * h + 1]);
+          else {
+            u32 px, py;
+            sep_vpass_pk<KIND, RING, us>(HD[ch], HS[ch], h, px, py);
+            x[2 * h] = lo16(px); x[2 * h + 1] = hi16(px);
+            y[2 * h] = lo16(py); y[2 * h + 1] = hi16(py);
           }
         }
       } else {
