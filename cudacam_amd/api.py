@@ -56,6 +56,8 @@ OPT_TEST_HYST_LATE_GRID, OPT_TEST_HYST_LOOP, OPT_TEST_HYST_DIAG, OPT_TEST_HYST_G
 TAP_BLUR, TAP_THRESH = 1, 2
 # front forms hc_last_run_info reports for canny_device at apertures 7 / -1 (the header's HC_FORM_O_APERTURE7 / HC_FORM_O_SCHARR)
 FORM_O_APERTURE7, FORM_O_SCHARR = 8, 9
+# rules of hc_auto_thresholds_device (the header's HC_AUTO_MEDIAN / HC_AUTO_OTSU)
+AUTO_MEDIAN, AUTO_OTSU = 0, 1
 # words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
 SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
@@ -66,7 +68,7 @@ ABI_SYMBOLS = [
     "hc_device_ptrs", "hc_last_hysteresis_info", "hc_hysteresis_stats", "hc_set_tuning", "hc_set_option", "hc_selftest", "hc_last_error", "hc_version",
     "hc_host_alloc", "hc_host_free", "hc_profile_get_front", "hc_debug_tap", "hc_use_own_stream", "hc_profile_get_intervals", "hc_last_run_info", "hc_pipeline_depth", "hc_pipeline_slots_in_use", "hc_front_waves_per_workgroup",
     "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
-    "hc_derivatives_device", "hc_canny_device",
+    "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
 ]
 
 _lib = None
@@ -122,6 +124,9 @@ def load_library(legacy=False):
     L.hc_run_gradients_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, i]
     L.hc_derivatives_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, sz, i, i]
     L.hc_canny_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, C.c_double, C.c_double, i, i]
+    L.hc_frame_thresholds_device.argtypes = [vp, vp, i]
+    L.hc_histogram_device.argtypes = [vp, vp, sz, sz, i, vp]
+    L.hc_auto_thresholds_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, vp]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -407,6 +412,62 @@ class Context:
         self.canny_device(src.data_ptr(), row, row * self.h, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
         self.sync()
         return out.cpu().numpy()
+
+    def frame_thresholds_device(self, d_thr, nframes=0):
+        """Per-frame thresholds for the runs that follow (mode O, hc_frame_thresholds_device): d_thr is device memory, int32
+        [nframes][2] = (low, high) per frame, read by each run's front kernel on the context stream.  None / 0: back to the
+        context's pair."""
+        _ck(self.lib.hc_frame_thresholds_device(self.handle, C.c_void_p(d_thr or None), int(nframes)))
+
+    def histogram_device(self, d_in, in_pitch, in_fs, nframes, d_hist):
+        """256-bin histograms of u8 frames on the device (hc_histogram_device): d_hist is uint32 [nframes][256], the channels
+        of 3-channel frames pooled.  Any alignment of the input view.  Asynchronous on the context stream; not a run."""
+        _ck(self.lib.hc_histogram_device(self.handle, C.c_void_p(d_in), in_pitch, in_fs, int(nframes), C.c_void_p(d_hist)))
+
+    def auto_thresholds_device(self, d_in, in_pitch, in_fs, nframes, rule, param, d_thr):
+        """Automatic (low, high) per frame on the device (hc_auto_thresholds_device): rule AUTO_MEDIAN with param = sigma, or
+        AUTO_OTSU with param = ratio; d_thr is int32 [nframes][2], as frame_thresholds_device reads it.  Asynchronous on the
+        context stream; not a run."""
+        _ck(self.lib.hc_auto_thresholds_device(self.handle, C.c_void_p(d_in), in_pitch, in_fs, int(nframes), int(rule), float(param),
+                                               C.c_void_p(d_thr)))
+
+    def histogram(self, frames):
+        """numpy u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, uint32 (n,256) histograms out, through device tensors."""
+        import torch
+        a = self._frames_u8(frames, "histogram")
+        n = a.shape[0]
+        dev = torch.device("cuda", self.device)
+        src = torch.from_numpy(a).to(dev)
+        hist = torch.empty((n, 256), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
+        row = self.c * self.w
+        self.histogram_device(src.data_ptr(), row, row * self.h, n, hist.data_ptr())
+        self.sync()
+        return hist.cpu().numpy().view(np.uint32)
+
+    def canny_auto(self, frames, rule="median", param=0.33):
+        """cv::Canny with thresholds chosen per frame on the device (mode O): auto thresholds -> per-frame table -> run, queued
+        back to back on the context stream with no host synchronisation in between.  rule: "median" (param = sigma) or "otsu"
+        (param = ratio), or AUTO_MEDIAN / AUTO_OTSU.  Returns (uint8 (n,H,W) edge maps, int32 (n,2) thresholds).  The
+        context's aperture and L2 options apply; the table is taken off the context again before returning."""
+        import torch
+        rule = {"median": AUTO_MEDIAN, "otsu": AUTO_OTSU}.get(rule, rule)
+        a = self._frames_u8(frames, "canny_auto")
+        n = a.shape[0]
+        dev = torch.device("cuda", self.device)
+        src = torch.from_numpy(a).to(dev)
+        thr = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
+        row = self.c * self.w
+        self.auto_thresholds_device(src.data_ptr(), row, row * self.h, n, rule, param, thr.data_ptr())
+        self.frame_thresholds_device(thr.data_ptr(), n)
+        try:
+            self.run_device(src.data_ptr(), row, row * self.h, out.data_ptr(), self.w, self.w * self.h, n)
+        finally:
+            self.frame_thresholds_device(None)
+        self.sync()
+        return out.cpu().numpy(), thr.cpu().numpy()
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -13,6 +13,10 @@ hipError_t check_gauss_coeffs(const float gk[25]);
 hipError_t launch_front_o(const FrontParams &p, hipStream_t s);
 hipError_t launch_front_o_ext(const FrontExtParams &p, hipStream_t s);  // front_o_ext.hip
 hipError_t launch_deriv16(const DerivParams &p, hipStream_t s);  // deriv.hip: Sobel 3 / 5 / 7 and Scharr derivatives, u8 -> int16 dx / dy
+#ifndef HC_LEGACY_FRONT  // stats.hip (the product library only): frame histograms and the automatic thresholds of Mode O
+hipError_t launch_hist256(const HistParams &p, hipStream_t s);  // p.hist must be zero when the kernel starts
+hipError_t launch_auto_thr(const u32 *hist, int nframes, int rule, double param, int32_t *thr, hipStream_t s);  // hist [nframes][256] -> thr [nframes][2]
+#endif
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

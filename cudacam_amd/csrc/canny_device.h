@@ -126,6 +126,18 @@ static __device__ __forceinline__ u64 uniform64(u64 v)
 }
 static __device__ __forceinline__ u32 mbcnt64(u64 m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
 
+// Mode O, per-frame thresholds (FrontParams::frame_thr != null): the pair of the work item's frame as the kernel compares
+// it (the normalisation itself is frame_threshold_pair, canny_params.h, which the host can call too).  `frame` is wave-uniform:
+// one scalar load of the pair's 8 bytes and a few scalar instructions per work item, the results in SGPRs.
+static __device__ __forceinline__ void frame_thresholds(const int32_t *thr, int frame, bool l2, u32 &low, u32 &high)
+{
+  u32 a, b;
+  frame_threshold_pair(thr[2 * (size_t)frame], thr[2 * (size_t)frame + 1], l2 ? 1 : 0, &a, &b);
+  // (uniform already; said again so that the pair stays in SGPRs, where the kernel argument's pair lives without a table)
+  low = (u32)__builtin_amdgcn_readfirstlane((int)a);
+  high = (u32)__builtin_amdgcn_readfirstlane((int)b);
+}
+
 // XCD-aware work-item order: blocks are dealt round-robin over the 8 XCDs, so block b and b+8 share
 // an L2.  Give each XCD a contiguous range of work items (neighbouring chunks share halo rows).
 static __device__ __forceinline__ int xcd_remap(int bid, int nblocks)

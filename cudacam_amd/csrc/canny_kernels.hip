@@ -83,7 +83,9 @@ hipError_t launch_selftest(u32 *d_result, hipStream_t s)
 // (frame, strip, chunk of p.chunk_rows rows) with a 4-row warm-up.
 // NC: channels of the (interleaved) source.  cv::Canny on a 3-channel image computes the Sobel derivatives of every
 // channel and keeps, per pixel, those of the channel with the largest magnitude -- the first one on ties (canny.cpp).
-template <bool L2, int NC>
+// TAB: the thresholds come from the per-frame table p.frame_thr (non-null) instead of p.a_lo[0] / p.a_hi[0]; the launcher picks
+// the instantiation, so runs without a table execute the code they always did
+template <bool L2, int NC, bool TAB = false>
 __global__ __launch_bounds__(256) void k_front_o(const FrontParams p)
 {
   const int lane = threadIdx.x & 63;
@@ -163,7 +165,8 @@ __global__ __launch_bounds__(256) void k_front_o(const FrontParams p)
   const bool store_lane = (lane & 1) && lane < 63;
   const u32 st_off = (u32)(strip * 31 + (lane >> 1));
   const u32 plane_pitch = (u32)p.RD * 4u;
-  const u32 low = p.a_lo[0], high = p.a_hi[0];  // Mode O: plain thresholds on m
+  u32 low = p.a_lo[0], high = p.a_hi[0];  // Mode O: plain thresholds on m
+  if constexpr (TAB) frame_thresholds(p.frame_thr, frame, L2, low, high);  // ... or the frame's own
   const u32 k_tg22 = 13573u, k_m32768 = 0x8000u;  // 16-bit multiplier operands (low halves): TG22 and -2^15
 
   // one step: source row k arrives -> gradient row k-1 -> NMS / threshold row k-2
@@ -330,12 +333,19 @@ hipError_t launch_front_o(const FrontParams &p, hipStream_t s)
   if (p.prov_out && (unsigned long long)p.H * p.prov_pitch >= (1ull << 32)) return hipErrorInvalidValue;  // (32-bit row offsets into the provisional map)
   if (p.in_pitch < (size_t)(p.bgr ? 3 : 1) * (((size_t)p.W + 3) / 4 * 4)) return hipErrorInvalidValue;
   const dim3 grid((p.total_items + 3) / 4), block(256);
+  auto go = [&](auto l2, auto nc) {
+    constexpr bool L2 = decltype(l2)::value;
+    constexpr int NC = decltype(nc)::value;
+    if (p.frame_thr) hipLaunchKernelGGL((k_front_o<L2, NC, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((k_front_o<L2, NC, false>), grid, block, 0, s, p);
+  };
+  using std::integral_constant;
   if (p.bgr) {
-    if (p.l2gradient) hipLaunchKernelGGL((k_front_o<true, 3>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((k_front_o<false, 3>), grid, block, 0, s, p);
+    if (p.l2gradient) go(integral_constant<bool, true>{}, integral_constant<int, 3>{});
+    else go(integral_constant<bool, false>{}, integral_constant<int, 3>{});
   } else {
-    if (p.l2gradient) hipLaunchKernelGGL((k_front_o<true, 1>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((k_front_o<false, 1>), grid, block, 0, s, p);
+    if (p.l2gradient) go(integral_constant<bool, true>{}, integral_constant<int, 1>{});
+    else go(integral_constant<bool, false>{}, integral_constant<int, 1>{});
   }
   return hipGetLastError();
 }

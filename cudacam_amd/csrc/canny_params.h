@@ -63,7 +63,30 @@ struct FrontParams {
   // (wave-wide NMS in registers), and the windows after it while they count more than dense_leave (0x7FFFFFFF: never)
   int dense_enter, dense_leave;
   u32 wrap_limit;  // S >= wrap_limit: gradient >= 256, the wrap bands apply (0xFFFFFFFF: saturating variant)
+  // Mode O (k_front_o, k_front8o, k_front_o_ext at aperture 5 / on given gradients): null, or int32 [nframes][2] = (low, high)
+  // per frame in the units of hc_set_thresholds (hc_frame_thresholds_device) -- frame f is then cut with
+  // frame_threshold_pair(frame_thr[2f], frame_thr[2f + 1]) (below; on the device through frame_thresholds, canny_device.h) instead
+  // of a_lo[0] / a_hi[0], by the kernels' TAB instantiations, which their launchers pick when it is set.  A device pointer the launcher
+  // patches in: no plan sets it
+  const int32_t *frame_thr;
 };
+
+#if defined(__HIPCC__)
+#define HC_HOST_DEVICE __host__ __device__
+#else
+#define HC_HOST_DEVICE
+#endif
+// One (low, high) pair of a per-frame table as the Mode O kernels compare it: what hc_set_thresholds followed by
+// plan_thresholds_and_masks (host_plan.h) make of the same pair for a context -- clamped to 0..32767, ordered, squared
+// for L2gradient (32767^2 < 2^31).  The kernels call it per work item, the CPU test on a grid of pairs.
+HC_HOST_DEVICE inline void frame_threshold_pair(int low, int high, int l2gradient, u32 *a_lo, u32 *a_hi)
+{
+  low = low < 0 ? 0 : low > 32767 ? 32767 : low;
+  high = high < 0 ? 0 : high > 32767 ? 32767 : high;
+  const int lo = low > high ? high : low, hi = low > high ? low : high;
+  *a_lo = l2gradient ? (u32)lo * (u32)lo : (u32)lo;
+  *a_hi = l2gradient ? (u32)hi * (u32)hi : (u32)hi;
+}
 
 // Mode O beyond k_front_o (front_o_ext.hip): the 5x5 / 7x7 Sobel or the Scharr derivatives of u8 frames (apertures 5, 7,
 // -1), or caller-given int16 derivatives (cv::Canny's (dx, dy) overload).  f as for k_front_o (thresholds in a_lo[0] /
@@ -96,6 +119,29 @@ struct DerivParams {
   int in_aligned;          // the input rows may be read as dwords (whole 4-pixel groups inside the row only)
   int out_align;           // 8, 4 or 2: what base, pitch and frame stride of BOTH outputs are multiples of
   int nstrips, nchunks, total_items;
+};
+
+// k_hist256 (stats.hip): 256-bin histograms of u8 frames, all channels pooled.  A work item is (frame, chunk of rows); a wave
+// counts its rows into a wave-private LDS histogram and adds the non-zero bins to hist[frame] with global atomics.
+constexpr int HIST_MAX_CHUNK_ROWS = 64, HIST_MIN_CHUNK_ROWS = 8;
+// rows per work item: about 8192 items per launch (32 waves for each of the 256 CUs: 20 are resident, profiles/auto_thr) where
+// the batch allows it, in chunks of 8 to 64 rows -- a chunk ends with up to 256 atomics per wave, which 8 rows of any width
+// worth counting outweigh.  Chosen by that reasoning; the rule has not been swept (1024 frames of 1080p run at the 64-row cap:
+// 17 items per frame, 0.96 ms, profiles/auto_thr/README.md)
+inline int hist_chunk_rows(int H, int nframes)
+{
+  const long long rows = (long long)H * nframes;
+  const long long want = (rows + 8191) / 8192;
+  const int r = (int)(want < HIST_MIN_CHUNK_ROWS ? HIST_MIN_CHUNK_ROWS : want > HIST_MAX_CHUNK_ROWS ? HIST_MAX_CHUNK_ROWS : want);
+  return r < H ? r : H;
+}
+struct HistParams {
+  const uint8_t *in;       // u8 frames, any alignment of base, pitch and frame stride
+  size_t in_pitch, in_frame_stride;
+  u32 *hist;               // [nframes][256], zeroed before the launch
+  int row_bytes;           // width * channels: no byte outside [row, row + row_bytes) is read
+  int H, nframes;
+  int chunk_rows, nchunks, total_items;  // hist_chunk_rows; ceil(H / chunk_rows); nframes * nchunks
 };
 
 struct HystParams {

@@ -780,7 +780,8 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
 // dx^2 + dy^2 summed over the pair (two v_dot2) >= low + 1.
 constexpr int F8O_WAVE_BYTES = F8_RING * F8_ROW_BYTES + (F8_NQ + 4) * 4;  // 7,184 B per wave
 
-template <bool L2, bool PROV>
+// TAB: per-frame thresholds from p.frame_thr (as k_front_o: the launcher picks the instantiation)
+template <bool L2, bool PROV, bool TAB = false>
 __global__ __launch_bounds__(256) void k_front8o(const FrontParams p)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -830,7 +831,8 @@ __global__ __launch_bounds__(256) void k_front8o(const FrontParams p)
   const bool st_lane = own_lane && col_any;
   const u32 st_off = st_lane ? (u32)(strip * 62 + lane - 1) : (u32)(strip * 62);
   const u32 prov_voff = st_lane ? (u32)c0 : (u32)(strip * F8_STRIP_W);
-  const u32 low = p.a_lo[0], high = p.a_hi[0];  // plain thresholds on m (squared by the host for L2gradient)
+  u32 low = p.a_lo[0], high = p.a_hi[0];  // plain thresholds on m (squared by the host for L2gradient)
+  if constexpr (TAB) frame_thresholds(p.frame_thr, frame, L2, low, high);  // ... or the frame's own
   // phase 2's test.  L2gradient: pair-summed dx^2 + dy^2 >= low + 1 (necessary).  L1: the exact magnitudes, packed; `nec`
   // is the per-half bias that carries "m > low" into bit 15 (thresholds are capped at 32767 by hc_set_thresholds)
   const u32 nec = L2 ? low + 1u : (0x7FFFu - min(low, 0x7FFFu)) * 0x10001u;
@@ -1130,12 +1132,18 @@ hipError_t launch_front8o(const FrontParams &p, hipStream_t s)
   if (!p.dump) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((p.total_items + 3) / 4)), block(256);
   const size_t lds = (size_t)4 * F8O_WAVE_BYTES;
+  auto go = [&](auto l2, auto prov) {
+    constexpr bool L2 = decltype(l2)::value, PROV = decltype(prov)::value;
+    if (p.frame_thr) hipLaunchKernelGGL((k_front8o<L2, PROV, true>), grid, block, lds, s, p);
+    else hipLaunchKernelGGL((k_front8o<L2, PROV, false>), grid, block, lds, s, p);
+  };
+  using std::integral_constant;
   if (p.l2gradient) {
-    if (p.prov_out) hipLaunchKernelGGL((k_front8o<true, true>), grid, block, lds, s, p);
-    else hipLaunchKernelGGL((k_front8o<true, false>), grid, block, lds, s, p);
+    if (p.prov_out) go(integral_constant<bool, true>{}, integral_constant<bool, true>{});
+    else go(integral_constant<bool, true>{}, integral_constant<bool, false>{});
   } else {
-    if (p.prov_out) hipLaunchKernelGGL((k_front8o<false, true>), grid, block, lds, s, p);
-    else hipLaunchKernelGGL((k_front8o<false, false>), grid, block, lds, s, p);
+    if (p.prov_out) go(integral_constant<bool, false>{}, integral_constant<bool, true>{});
+    else go(integral_constant<bool, false>{}, integral_constant<bool, false>{});
   }
   return hipGetLastError();
 }

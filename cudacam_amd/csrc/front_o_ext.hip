@@ -30,7 +30,8 @@ using namespace sep;
 // the u8 sources' cv ksize.  0 -> 5 only documents the map: SRC 0 spells its passes out and never asks (static_assert below)
 constexpr int src_kind(int src) { return src == 0 ? 5 : src == 2 ? 7 : -1; }
 
-template <int SRC, bool L2, int NC>
+// TAB (SRC 0 and 1 only): per-frame thresholds from f.frame_thr (as k_front_o: the launcher picks the instantiation)
+template <int SRC, bool L2, int NC, bool TAB = false>
 __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
 {
   constexpr bool U8 = SRC != 1;                            // u8 rows: SRC 0, 2, 3
@@ -124,7 +125,9 @@ __global__ __launch_bounds__(256) void k_front_o_ext(const FrontExtParams e)
   const bool store_lane = (lane & 1) && lane < 63;
   const size_t st_off = (size_t)(strip * 31 + (lane >> 1));
   const size_t plane_pitch = (size_t)p.RD * 4u;
-  const int low = (int)p.a_lo[0], high = (int)p.a_hi[0];
+  u32 low_u = p.a_lo[0], high_u = p.a_hi[0];
+  if constexpr (TAB) frame_thresholds(p.frame_thr, frame, L2, low_u, high_u);  // ... or the frame's own
+  const int low = (int)low_u, high = (int)high_u;
 
   // one step: source row k arrives -> gradient row g = k - LAG -> NMS / threshold row g - 1
   auto step = [&](auto uc, int k, const Raw &raw) {
@@ -263,12 +266,23 @@ template <int SRC>
 hipError_t launch_src(const FrontExtParams &e, const dim3 grid, const dim3 block, hipStream_t s)
 {
   const bool three = SRC != 1 ? e.f.bgr != 0 : e.channels == 3;
+  // a per-frame table applies to aperture 5 and given gradients (hc_canny_device's fused sources take the call's pair)
+  auto go = [&](auto l2, auto nc) {
+    constexpr bool L2 = decltype(l2)::value;
+    constexpr int NC = decltype(nc)::value;
+    if constexpr (SRC <= 1) {
+      if (e.f.frame_thr) { hipLaunchKernelGGL((k_front_o_ext<SRC, L2, NC, true>), grid, block, 0, s, e); return; }
+    }
+    hipLaunchKernelGGL((k_front_o_ext<SRC, L2, NC, false>), grid, block, 0, s, e);
+  };
+  using std::integral_constant;
+  if (SRC > 1 && e.f.frame_thr) return hipErrorInvalidValue;
   if (three) {
-    if (e.f.l2gradient) hipLaunchKernelGGL((k_front_o_ext<SRC, true, 3>), grid, block, 0, s, e);
-    else hipLaunchKernelGGL((k_front_o_ext<SRC, false, 3>), grid, block, 0, s, e);
+    if (e.f.l2gradient) go(integral_constant<bool, true>{}, integral_constant<int, 3>{});
+    else go(integral_constant<bool, false>{}, integral_constant<int, 3>{});
   } else {
-    if (e.f.l2gradient) hipLaunchKernelGGL((k_front_o_ext<SRC, true, 1>), grid, block, 0, s, e);
-    else hipLaunchKernelGGL((k_front_o_ext<SRC, false, 1>), grid, block, 0, s, e);
+    if (e.f.l2gradient) go(integral_constant<bool, true>{}, integral_constant<int, 1>{});
+    else go(integral_constant<bool, false>{}, integral_constant<int, 1>{});
   }
   return hipGetLastError();
 }

@@ -6,6 +6,7 @@
 #include "../../include/hipcanny.h"
 #include "canny_common.h"
 #include "host_plan.h"
+#include "auto_thr.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -200,6 +201,11 @@ struct hc_ctx {
     int slot = 0;  // slot of the most recent fused run
   } last;
   int uploaded = 0;
+  // Mode O: the per-frame threshold table of the runs that follow (hc_frame_thresholds_device; caller-owned device memory,
+  // read by the front kernels only) and how many frames it holds; null: the context's pair
+  const int32_t *frame_thr = nullptr;
+  int frame_thr_n = 0;
+  u32 *d_hist = nullptr;  // hc_auto_thresholds_device: histograms [max_batch][256] between k_hist256 and k_auto_thr (lazy)
 };
 
 namespace {
@@ -591,6 +597,9 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
     return fail(HC_E_ARG, "mode O (cv::Canny) produces the final edge map only (cv::Canny has no intermediate outputs)");
   if (c->mode == HC_MODE_O && c->per_channel) return fail(HC_E_ARG, "HC_OPT_PER_CHANNEL applies to mode R contexts");
   if (c->per_channel && stage != HC_STAGE_HYSTER) return fail(HC_E_ARG, "per-channel mode only produces the final edge maps (HC_STAGE_HYSTER)");
+  // a per-frame threshold table applies to the runs that go by the context's thresholds (hc_canny_device brings its own)
+  const int32_t *frame_thr = (c->mode == HC_MODE_O && !call_opt) ? c->frame_thr : nullptr;
+  if (frame_thr && n > c->frame_thr_n) return fail(HC_E_ARG, "the run has more frames than the table of hc_frame_thresholds_device holds");
   const int W = c->W, H = c->H;
   const int n_out = c->per_channel ? 3 * n : n;  // output frames (= bit-plane frames)
   const bool piped = c->pipeline && stage == HC_STAGE_HYSTER;
@@ -642,6 +651,7 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
     // 4. the front kernel of the planned form, with the device pointers patched in
     FrontParams fp = P.fp;
     fp.in = mono; fp.sbits = s.d_sbits; fp.cbits = s.d_cbits;
+    fp.frame_thr = frame_thr;
     s.prov = P.prov;
     if (P.prov) fp.prov_out = dst;
     if (c->opt.debug_taps) {
@@ -779,7 +789,7 @@ void hc_destroy(hc_ctx *c)
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump }) (void)hipFree(q);
+  for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump, (void *)c->d_hist }) (void)hipFree(q);
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);
@@ -798,6 +808,18 @@ int hc_set_thresholds(hc_ctx *c, int low, int high)
   high = std::max(0, std::min(tmax, high));
   if (low > high) std::swap(low, high);
   c->opt.low = low; c->opt.high = high;
+  return HC_OK;
+}
+
+// Only the pointer is kept: the front kernels of the following runs read the table on the context stream.
+int hc_frame_thresholds_device(hc_ctx *c, const void *d_thr, int nframes)
+{
+  if (!c) return fail(HC_E_ARG, "null context");
+  if (c->mode != HC_MODE_O) return fail(HC_E_ARG, "hc_frame_thresholds_device: mode O contexts only");
+  if (!d_thr) { c->frame_thr = nullptr; c->frame_thr_n = 0; return HC_OK; }
+  if ((uintptr_t)d_thr & 3u) return fail(HC_E_ARG, "hc_frame_thresholds_device: the table must be 4-byte aligned");
+  if (nframes <= 0 || nframes > c->max_batch) return fail(HC_E_ARG, "hc_frame_thresholds_device: nframes out of range");
+  c->frame_thr = (const int32_t *)d_thr; c->frame_thr_n = nframes;
   return HC_OK;
 }
 
@@ -1046,6 +1068,66 @@ int hc_derivatives_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t i
   HIPCK(launch_deriv16(dp, c->stream));
   return HC_OK;
 }
+
+#ifndef HC_LEGACY_FRONT
+namespace {
+// what hc_histogram_device and hc_auto_thresholds_device refuse alike, before anything is allocated or queued
+int check_histogram_view(hc_ctx *c, const char *who, size_t in_pitch, size_t in_fs, int n)
+{
+  const std::string w(who);
+  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, w + ": nframes out of range");
+  if (in_pitch < (size_t)c->C * c->W) return fail(HC_E_ARG, w + ": in_pitch smaller than a row");
+  if (n > 1 && in_fs < in_pitch * (size_t)c->H) return fail(HC_E_ARG, w + ": frame stride smaller than a frame");
+  if ((u64)c->H * in_pitch >= (1ull << 32)) return fail(HC_E_ARG, w + ": views of 4 GiB and more (height * pitch >= 2^32) are not supported by this entry");
+  return HC_OK;
+}
+// k_hist256 on the context stream behind the zeroing of d_hist (the view has been checked)
+int queue_histogram(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, u32 *d_hist)
+{
+  HistParams hp{};
+  hp.in = (const uint8_t *)d_in; hp.in_pitch = in_pitch; hp.in_frame_stride = in_fs; hp.hist = d_hist;
+  hp.row_bytes = c->W * c->C; hp.H = c->H; hp.nframes = n;
+  hp.chunk_rows = hist_chunk_rows(c->H, n); hp.nchunks = (c->H + hp.chunk_rows - 1) / hp.chunk_rows;
+  hp.total_items = n * hp.nchunks;  // (at most 1024 frames x 1024 chunks of 8 rows or more)
+  HIPCK(hipMemsetAsync(d_hist, 0, sizeof(u32) * 256 * (size_t)n, c->stream));
+  HIPCK(launch_hist256(hp, c->stream));
+  return HC_OK;
+}
+}  // namespace
+
+// Not a run (as hc_derivatives_device): the zeroing and one kernel on the context stream.
+int hc_histogram_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, void *d_hist)
+{
+  if (!c || !d_in || !d_hist) return fail(HC_E_ARG, "hc_histogram_device: null argument");
+  if ((uintptr_t)d_hist & 3u) return fail(HC_E_ARG, "hc_histogram_device: d_hist must be 4-byte aligned");
+  if (int rc = check_histogram_view(c, "hc_histogram_device", in_pitch, in_fs, n)) return rc;
+  HIPCK(hipSetDevice(c->device));
+  return queue_histogram(c, d_in, in_pitch, in_fs, n, (u32 *)d_hist);
+}
+
+// k_hist256 into the context's scratch table, then k_auto_thr: both on the context stream, so a table the following runs
+// read through hc_frame_thresholds_device needs no synchronisation.  Not a run either.  Successive calls share the scratch
+// table and are ordered by the stream they are queued on (hc_set_stream between two of them: include/hipcanny.h).
+int hc_auto_thresholds_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, int rule, double param, void *d_thr)
+{
+  if (!c || !d_in || !d_thr) return fail(HC_E_ARG, "hc_auto_thresholds_device: null argument");
+  if ((uintptr_t)d_thr & 3u) return fail(HC_E_ARG, "hc_auto_thresholds_device: d_thr must be 4-byte aligned");
+  if (rule != HC_AUTO_MEDIAN && rule != HC_AUTO_OTSU) return fail(HC_E_ARG, "hc_auto_thresholds_device: rule must be HC_AUTO_MEDIAN or HC_AUTO_OTSU");
+  if (!auto_param_ok(rule, param)) return fail(HC_E_ARG, "hc_auto_thresholds_device: param (sigma / ratio) must lie in [0, 1]");
+  if ((long long)c->W * c->H * c->C > AUTO_MAX_SAMPLES) return fail(HC_E_ARG, "hc_auto_thresholds_device: more than 2^27 samples per frame");
+  if (int rc = check_histogram_view(c, "hc_auto_thresholds_device", in_pitch, in_fs, n)) return rc;
+  HIPCK(hipSetDevice(c->device));
+  // every refusal lies above: the table is allocated (once; the first call may synchronise the device) only by a call that runs
+  if (!c->d_hist) HIPCK(hipMalloc((void **)&c->d_hist, sizeof(u32) * 256 * (size_t)c->max_batch));
+  if (int rc = queue_histogram(c, d_in, in_pitch, in_fs, n, c->d_hist)) return rc;
+  HIPCK(launch_auto_thr(c->d_hist, n, rule, param, (int32_t *)d_thr, c->stream));
+  return HC_OK;
+}
+#else
+// the test library (round-1 front kernels) is built without stats.hip
+int hc_histogram_device(hc_ctx *, const void *, size_t, size_t, int, void *) { return fail(HC_E_ARG, "hc_histogram_device: not part of the test library"); }
+int hc_auto_thresholds_device(hc_ctx *, const void *, size_t, size_t, int, int, double, void *) { return fail(HC_E_ARG, "hc_auto_thresholds_device: not part of the test library"); }
+#endif
 
 int hc_hysteresis_device(hc_ctx *c, const void *d_thresh, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n)
 {

@@ -57,6 +57,25 @@ void hc_destroy(hc_ctx *ctx);
 int hc_set_thresholds(hc_ctx *ctx, int low, int high);
 int hc_get_thresholds(const hc_ctx *ctx, int *low, int *high);
 
+/* Mode O: thresholds per frame for the runs that follow (hc_run, hc_run_device, hc_run_gradients_device): frame f of a run
+ * is cut with d_thr[2f], d_thr[2f+1] exactly as if hc_set_thresholds(d_thr[2f], d_thr[2f+1]) had preceded a run of that
+ * frame alone.  d_thr: device memory, int32 [nframes][2], 4-byte aligned, caller-owned; it is read by the run's front
+ * kernel on the context stream (plain and pipelined mode alike), so work queued on that stream before the run may
+ * write it and work queued after the run may overwrite it -- no host synchronisation.  NULL: back to the context's pair.
+ * Each pair is normalised on the device as hc_set_thresholds does it on the host: clamped to 0..32767, swapped if
+ * low > high, squared under HC_OPT_L2_GRADIENT (frame_threshold_pair, cudacam_amd/csrc/canny_params.h).  Kernels: k_front_o,
+ * k_front8o and k_front_o_ext at HC_OPT_APERTURE 5 and on given gradients each have an instantiation that reads the table, which
+ * the launcher picks when one is installed; runs without a table execute the code they did before the table existed.  Forms
+ * and work split are the same either way.
+ * HC_E_ARG: a mode R context (its thresholds are the reference's u8 sliders through the wrap bands; per-frame thresholds
+ * for mode R are not offered); a pointer that is not 4-byte aligned; nframes outside 1..max_batch; and, from the run
+ * itself, a run of more frames than the table holds.
+ * hc_canny_device keeps its per-call thresholds and ignores the table; it leaves the table installed, as it leaves the
+ * context's settings untouched.  The table changes nothing else: hc_get_thresholds still reports the context's pair; the
+ * hysteresis schedule and history, hc_last_run_info, the stage timers, HC_OPT_DEBUG_TAPS and the staging of views are as
+ * without it; the provisional map of pipelined k_front8o runs uses the frame's own `high`. */
+int hc_frame_thresholds_device(hc_ctx *ctx, const void *d_thr, int nframes);
+
 /* Replaces _loadInputImage (cannyEdgeH.cu:122-152): host frames -> device.  row_stride = cv::Mat::step,
  * frame_stride = bytes between consecutive frames.  Asynchronous on the context stream when the
  * host memory is pinned. */
@@ -168,6 +187,44 @@ int hc_canny_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_fr
  * with a frame stride smaller than height * pitch on either side. */
 int hc_derivatives_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, void *d_dx, void *d_dy,
                           size_t pitch, size_t frame_stride, int nframes, int ksize);
+
+/* 256-bin histograms of u8 frames: d_hist[f][v] = number of samples of value v among the width * height * channels
+ * samples of frame f (3-channel frames: all three channels pooled).  d_hist: uint32 [nframes][256], 4-byte aligned.
+ * Contexts of either mode; width, height, channels and max_batch are the context's.  Asynchronous on the context stream
+ * (hc_set_stream honoured), in order with everything else queued there; the entry zeroes d_hist on that stream first.  It is
+ * not a run, exactly as hc_derivatives_device is none: hc_last_run_info, the stage timers, the hysteresis schedule /
+ * history and the pipeline slots stay as they were, and runs in flight are neither finished nor waited for.
+ * Views, as hc_derivatives_device: any alignment of base, pitch and frame stride (the dwords that lie whole inside a row
+ * are read as dwords, the ragged head and tail bytewise); no byte outside [row, row + channels * width) of a row is read,
+ * so `d_in` may be an ROI of a larger image.  Counts are integer sums: exact, whatever the work split (k_hist256).
+ * HC_E_ARG: a null pointer; d_hist not 4-byte aligned; in_pitch < channels * width; nframes outside 1..max_batch; nframes
+ * > 1 with a frame stride smaller than height * in_pitch; height * in_pitch >= 2^32. */
+int hc_histogram_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, int nframes, void *d_hist);
+
+/* Automatic thresholds per frame, on the device: the histogram of every frame (k_hist256, into a table the context owns:
+ * allocated on first use, freed by hc_destroy), then one wave per frame turns it into the frame's (low, high) by `rule`
+ * (k_auto_thr; the arithmetic is cudacam_amd/csrc/auto_thr.h, restated in tests/auto_thr_ref.py):
+ *   HC_AUTO_MEDIAN, param = sigma in [0, 1] (the usual recipe: 0.33): with the N samples sorted, a = s[(N-1)/2],
+ *     b = s[N/2], v = (a + b) / 2.0 (np.median, exact in double); low = (int)max(0.0, (1.0 - sigma) * v),
+ *     high = (int)min(255.0, (1.0 + sigma) * v).
+ *   HC_AUTO_OTSU, param = ratio in [0, 1] (the usual recipe: 0.5): high = t*, low = (int)(ratio * t*), where t* in 0..254
+ *     is the smallest threshold whose between-class score ((double)d * (double)d) / ((double)w0 * (double)w1) is strictly the
+ *     largest -- w0 = samples <= t, w1 = N - w0, d = S w0 - N s0 in int64 (S, s0: sums of the values of all samples / of those
+ *     <= t) -- among the t with w0, w1 > 0; t* = 0 if there is none (a flat frame).  The textbook rule with an exact integer
+ *     numerator, stated here; not pinned against OpenCV's getThreshVal_Otsu_8u, which accumulates in floating point and
+ *     may differ at near-ties.
+ * d_thr: int32 [nframes][2], 4-byte aligned, as hc_frame_thresholds_device reads it, in the units of hc_set_thresholds.  With
+ * derivatives of aperture 7 or Scharr (hc_derivatives_device chained with hc_run_gradients_device) the pairs mean what that
+ * entry says about units; nothing is rescaled here.  Asynchronous on the context stream, not a run (as hc_histogram_device):
+ * chained with hc_frame_thresholds_device and a run on the same context, no synchronisation is needed in between.
+ * Successive calls on one context share that table and are ordered by the stream they are queued on: a caller who changes
+ * the stream between two calls (hc_set_stream, hc_use_own_stream) must order the two streams itself, or synchronise, as for any
+ * other memory that work on both streams touches; hc_histogram_device, which writes caller memory only, has no such state.
+ * HC_E_ARG: an unknown rule; param outside [0, 1] or not finite; width * height * channels > 2^27 (up to there the integer
+ * sums above are exact); d_thr null or not 4-byte aligned; otherwise what hc_histogram_device refuses. */
+enum { HC_AUTO_MEDIAN = 0, HC_AUTO_OTSU = 1 };
+int hc_auto_thresholds_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, int nframes,
+                              int rule, double param, void *d_thr /* int32 [nframes][2], as hc_frame_thresholds_device reads */);
 
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
