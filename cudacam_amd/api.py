@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "hc_host_alloc", "hc_host_free", "hc_profile_get_front", "hc_debug_tap", "hc_use_own_stream", "hc_profile_get_intervals", "hc_last_run_info", "hc_pipeline_depth", "hc_pipeline_slots_in_use", "hc_front_waves_per_workgroup",
     "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
     "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
+    "hc_edge_points_device",
 ]
 
 _lib = None
@@ -127,6 +128,7 @@ def load_library(legacy=False):
     L.hc_frame_thresholds_device.argtypes = [vp, vp, i]
     L.hc_histogram_device.argtypes = [vp, vp, sz, sz, i, vp]
     L.hc_auto_thresholds_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, vp]
+    L.hc_edge_points_device.argtypes = [vp, vp, sz, sz, i, vp, vp, sz]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -468,6 +470,66 @@ class Context:
             self.frame_thresholds_device(None)
         self.sync()
         return out.cpu().numpy(), thr.cpu().numpy()
+
+    def edge_points_device(self, d_map, pitch, fs, nframes, d_counts, d_points, capacity):
+        """cv::findNonZero / cv::countNonZero per frame on the device (hc_edge_points_device): d_map holds one-channel u8 maps
+        (any alignment), d_counts is uint32 [nframes] (always the full counts), d_points int32 [nframes][capacity][2] = (x, y)
+        in raster order, the first min(count, capacity) of each frame; capacity 0 (d_points None / 0): counts only.
+        Asynchronous on the context stream; not a run, but a pipelined run in flight that writes the map is completed first."""
+        _ck(self.lib.hc_edge_points_device(self.handle, C.c_void_p(d_map), pitch, fs, int(nframes), C.c_void_p(d_counts),
+                                           C.c_void_p(d_points or None), int(capacity)))
+
+    def _edge_points_of(self, d_maps, n, capacity):
+        """(counts, lists) of n tight maps on the device (a torch u8 tensor [n, H, W] the context stream may read)."""
+        import torch
+        counts = torch.empty((n,), dtype=torch.int32, device=d_maps.device)
+        fs = self.w * self.h
+        if capacity is None:   # two passes: the counts size the list buffer
+            self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, counts.data_ptr(), None, 0)
+            self.sync()
+            capacity = int(counts.cpu().numpy().view(np.uint32).max())
+        capacity = int(capacity)
+        pts = torch.empty((n, max(capacity, 1), 2), dtype=torch.int32, device=d_maps.device)
+        torch.cuda.current_stream().synchronize()
+        self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, counts.data_ptr(), pts.data_ptr() if capacity else None, capacity)
+        self.sync()
+        cnt = counts.cpu().numpy().view(np.uint32)
+        host = pts.cpu().numpy()
+        return cnt, [host[f, :min(int(cnt[f]), capacity)].copy() for f in range(n)]
+
+    def edge_points(self, maps, capacity=None):
+        """Host or torch u8 maps [n, H, W] (or one map) in; (uint32 counts [n], [int32 array of shape (min(count_f, capacity), 2)
+        = (x, y) per frame]) out.  capacity=None: two passes, counts first, then a list buffer sized by the largest count."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(maps, torch.Tensor):
+            d = maps.to(device=dev, dtype=torch.uint8).contiguous()
+            if d.ndim == 2:
+                d = d[None]
+        else:
+            a = np.ascontiguousarray(maps, dtype=np.uint8)
+            d = torch.from_numpy(a[None] if a.ndim == 2 else a).to(dev)
+        if d.ndim != 3 or tuple(d.shape[1:]) != (self.h, self.w):
+            raise HipCannyError(f"edge_points: maps {tuple(d.shape)} do not match the context's {(self.h, self.w)}")
+        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
+        return self._edge_points_of(d, d.shape[0], capacity)
+
+    def canny_points(self, frames, low, high, aperture=3, l2gradient=False, capacity=None):
+        """cv::Canny followed by cv::findNonZero (mode O): canny_device and edge_points_device chained on the device, with no
+        host copy of the maps in between.  Returns (uint8 (n,H,W) edge maps, uint32 counts, lists as edge_points gives them)."""
+        import torch
+        a = self._frames_u8(frames, "canny_points")
+        n = a.shape[0]
+        dev = torch.device("cuda", self.device)
+        src = torch.from_numpy(a).to(dev)
+        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
+        row = self.c * self.w
+        self.canny_device(src.data_ptr(), row, row * self.h, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        counts, lists = self._edge_points_of(out, n, capacity)
+        if self.hysteresis_info()[1]:   # the run was continued from the host (adversarial content): the maps changed after the lists were taken
+            counts, lists = self._edge_points_of(out, n, capacity)
+        return out.cpu().numpy(), counts, lists
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -144,6 +144,21 @@ struct HistParams {
   int chunk_rows, nchunks, total_items;  // hist_chunk_rows; ceil(H / chunk_rows); nframes * nchunks
 };
 
+// k_edge_count / k_edge_scan / k_edge_emit (edge_points.hip): the coordinates of the non-zero pixels of u8 maps in raster order
+// (cv::findNonZero) and their number (cv::countNonZero).  A work item is (frame, chunk of rows) as for k_hist256, by the same
+// rule (hist_chunk_rows): an item's cost is dominated by reading its rows, as there, and chunks of 8 rows and more keep the
+// table of per-item counts small (8K frames at 8-row chunks: 540 per frame).
+struct EdgePointsParams {
+  const uint8_t *map;      // u8 maps of W x H, one channel, any alignment of base, pitch and frame stride
+  size_t pitch, frame_stride;
+  u32 *items;              // scratch [nframes][nchunks]: the items' counts (k_edge_count), then their offsets in the frame's list (k_edge_scan)
+  u32 *counts;             // [nframes]: the full number of non-zero pixels of each frame
+  int32_t *points;         // [nframes][capacity][2] = (x, y), 8-byte aligned; unused when capacity == 0
+  size_t capacity;
+  int W, H, nframes;       // no byte outside [row, row + W) is read
+  int chunk_rows, nchunks, total_items;  // hist_chunk_rows; ceil(H / chunk_rows); nframes * nchunks
+};
+
 struct HystParams {
   u32 *sbits;
   const u32 *cbits;

@@ -206,6 +206,7 @@ struct hc_ctx {
   const int32_t *frame_thr = nullptr;
   int frame_thr_n = 0;
   u32 *d_hist = nullptr;  // hc_auto_thresholds_device: histograms [max_batch][256] between k_hist256 and k_auto_thr (lazy)
+  u32 *d_edge_items = nullptr;  // hc_edge_points_device: per-work-item counts / offsets between its three kernels (lazy)
 };
 
 namespace {
@@ -789,7 +790,7 @@ void hc_destroy(hc_ctx *c)
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump, (void *)c->d_hist }) (void)hipFree(q);
+  for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump, (void *)c->d_hist, (void *)c->d_edge_items }) (void)hipFree(q);
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);
@@ -1123,10 +1124,67 @@ int hc_auto_thresholds_device(hc_ctx *c, const void *d_in, size_t in_pitch, size
   HIPCK(launch_auto_thr(c->d_hist, n, rule, param, (int32_t *)d_thr, c->stream));
   return HC_OK;
 }
+
+namespace {
+// Pipelined runs still in flight that write into [m0, m1): each is completed, oldest first, before the map is read -- its
+// hysteresis runs on another stream than the reader, and should its queued launches not have reached the fixpoint, its
+// host-side continuation (finish_slot) rewrites whole maps.  As finish_overlapping, for a reader; the caller's buffer a
+// staged run copies its maps to counts as well.  Runs that write elsewhere stay in flight.
+int finish_writers_of(hc_ctx *c, uintptr_t m0, uintptr_t m1)
+{
+  for (int k = 0; k < c->nslot_use; ++k) {
+    Slot &o = c->slot[(c->cur + k) % c->nslot_use];
+    if (!o.pending || o.stream == c->stream) continue;  // (a plain run is ordered before the reader by the context stream)
+    bool hit = o.out0 < m1 && m0 < o.out1;
+    if (o.copy_dst && o.n > 0) {
+      const uintptr_t d0 = (uintptr_t)o.copy_dst, d1 = d0 + (size_t)(o.n - 1) * o.copy_fs + (size_t)(c->H - 1) * o.copy_pitch + (size_t)c->W;
+      hit = hit || (d0 < m1 && m0 < d1);
+    }
+    if (hit)
+      if (int rc = finish_slot(c, o)) return rc;
+  }
+  return HC_OK;
+}
+}  // namespace
+
+// k_edge_count, k_edge_scan, k_edge_emit on the context stream (edge_points.hip).  Not a run, as hc_histogram_device -- except
+// that a pipelined run in flight whose output the map overlaps is completed first (finish_writers_of).  Successive calls share
+// the table of per-item counts and are ordered by the stream they are queued on (include/hipcanny.h).
+int hc_edge_points_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs, int n, void *d_counts, void *d_points, size_t capacity)
+{
+  if (!c || !d_map || !d_counts) return fail(HC_E_ARG, "hc_edge_points_device: null argument");
+  if (capacity && !d_points) return fail(HC_E_ARG, "hc_edge_points_device: d_points is null with capacity > 0");
+  if ((uintptr_t)d_counts & 3u) return fail(HC_E_ARG, "hc_edge_points_device: d_counts must be 4-byte aligned");
+  if ((uintptr_t)d_points & 7u) return fail(HC_E_ARG, "hc_edge_points_device: d_points must be 8-byte aligned");
+  const int max_frames = c->max_batch * (c->per_channel ? 3 : 1);  // the output frames of a max_batch run
+  if (n <= 0 || n > max_frames) return fail(HC_E_ARG, "hc_edge_points_device: nframes out of range");
+  if (pitch < (size_t)c->W) return fail(HC_E_ARG, "hc_edge_points_device: pitch smaller than a row");
+  if (n > 1 && fs < pitch * (size_t)c->H) return fail(HC_E_ARG, "hc_edge_points_device: frame stride smaller than a frame");
+  if ((u64)c->H * pitch >= (1ull << 32)) return fail(HC_E_ARG, "hc_edge_points_device: views of 4 GiB and more (height * pitch >= 2^32) are not supported by this entry");
+  if (capacity > SIZE_MAX / 8 / (size_t)n) return fail(HC_E_ARG, "hc_edge_points_device: capacity * 8 * nframes overflows size_t");
+  EdgePointsParams ep{};
+  ep.map = (const uint8_t *)d_map; ep.pitch = pitch; ep.frame_stride = fs; ep.counts = (u32 *)d_counts;
+  ep.points = (int32_t *)d_points; ep.capacity = capacity; ep.W = c->W; ep.H = c->H; ep.nframes = n;
+  ep.chunk_rows = hist_chunk_rows(c->H, n); ep.nchunks = (c->H + ep.chunk_rows - 1) / ep.chunk_rows;
+  // chunks have min(8, H) rows or more: the table below holds the items of any batch the context takes
+  const size_t table_items = (size_t)c->max_batch * (c->C == 3 ? 3 : 1) * (size_t)((c->H + std::min(HIST_MIN_CHUNK_ROWS, c->H) - 1) / std::min(HIST_MIN_CHUNK_ROWS, c->H));
+  const long long items = (long long)n * ep.nchunks;
+  if (items > 0x7FFFFFF0ll || table_items > 0x7FFFFFF0ull) return fail(HC_E_ARG, "hc_edge_points_device: too many work items (nframes x row chunks)");
+  ep.total_items = (int)items;
+  HIPCK(hipSetDevice(c->device));
+  const uintptr_t m0 = (uintptr_t)d_map;
+  if (int rc = finish_writers_of(c, m0, m0 + (size_t)(n - 1) * fs + (size_t)(c->H - 1) * pitch + (size_t)c->W)) return rc;
+  // every refusal lies above: the table is allocated (once; the first call may synchronise the device) only by a call that runs
+  if (!c->d_edge_items) HIPCK(hipMalloc((void **)&c->d_edge_items, sizeof(u32) * table_items));
+  ep.items = c->d_edge_items;
+  HIPCK(launch_edge_points(ep, c->stream));
+  return HC_OK;
+}
 #else
-// the test library (round-1 front kernels) is built without stats.hip
+// the test library (round-1 front kernels) is built without stats.hip and edge_points.hip
 int hc_histogram_device(hc_ctx *, const void *, size_t, size_t, int, void *) { return fail(HC_E_ARG, "hc_histogram_device: not part of the test library"); }
 int hc_auto_thresholds_device(hc_ctx *, const void *, size_t, size_t, int, int, double, void *) { return fail(HC_E_ARG, "hc_auto_thresholds_device: not part of the test library"); }
+int hc_edge_points_device(hc_ctx *, const void *, size_t, size_t, int, void *, void *, size_t) { return fail(HC_E_ARG, "hc_edge_points_device: not part of the test library"); }
 #endif
 
 int hc_hysteresis_device(hc_ctx *c, const void *d_thresh, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n)

@@ -226,6 +226,41 @@ enum { HC_AUTO_MEDIAN = 0, HC_AUTO_OTSU = 1 };
 int hc_auto_thresholds_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, int nframes,
                               int rule, double param, void *d_thr /* int32 [nframes][2], as hc_frame_thresholds_device reads */);
 
+/* The edge pixels of u8 maps as point lists and counts, on the device: cv::findNonZero / cv::countNonZero per frame
+ * (k_edge_count, k_edge_scan, k_edge_emit: cudacam_amd/csrc/edge_points.hip).  Semantics stated here and restated in
+ * tests/edge_points_ref.py (numpy), not pinned against a build of OpenCV.
+ * `d_map` holds nframes u8 images of the context's width x height with ONE channel, whatever `channels` the context has (an
+ * edge map is single-channel; after an HC_OPT_PER_CHANNEL run the caller passes its 3 maps per input frame).  A pixel belongs to
+ * the list iff its byte is non-zero: the 255 of a final map, and the 128 and 255 of an HC_STAGE_THRESH map alike.
+ *   d_counts[f]  uint32: the number of non-zero pixels of frame f -- always the full number, also above `capacity`.
+ *   d_points     int32 [nframes][capacity][2]: the slot of frame f, at byte f * capacity * 8, receives the first
+ *                min(d_counts[f], capacity) points of the frame in raster order (rows top to bottom, columns left to right
+ *                inside a row), each as (int32 x, int32 y) -- the memory of a cv::Mat(count, 1, CV_32SC2) / a
+ *                std::vector<cv::Point> as cv::findNonZero fills it.
+ * Nothing else is written: the bytes of a slot behind its written points, the other slots and the map stay untouched.
+ * capacity == 0 (d_points null or not) gives the counts only: cv::countNonZero per frame.  The order is part of the contract:
+ * the result is a function of the map alone, whatever the work split.
+ * Views, as hc_histogram_device: any alignment of base, pitch and frame stride; no byte outside [row, row + width) of a row is
+ * read, so `d_map` may be an ROI of a larger image.  d_counts is 4-byte aligned, d_points 8-byte aligned.
+ * Asynchronous on the context stream (hc_set_stream honoured), in order with everything else queued there.  It is not a run,
+ * exactly as hc_histogram_device is none: hc_last_run_info, the stage timers, the hysteresis schedule / history and the pipeline
+ * slots stay as they were.  One addition, because a run's output is this entry's natural input: with HC_OPT_PIPELINE, a run
+ * still in flight whose output overlaps the bytes of `d_map` is completed first (its hysteresis runs on another stream and may
+ * be continued from the host), as a later run that writes there would complete it; runs whose outputs do not overlap are
+ * neither finished nor waited for.  In plain mode the order of the context stream suffices (as for any reader of a plain run's
+ * output on that stream: a run that had to be continued from the host, hc_last_hysteresis_info, is complete after hc_sync).
+ * Scratch: one table of per-work-item counts the context owns (allocated on first use, freed by hc_destroy).  Successive calls
+ * on one context share it and are ordered by the stream they are queued on: a caller who changes the stream between two calls
+ * (hc_set_stream, hc_use_own_stream) must order the two streams itself, or synchronise, as for hc_auto_thresholds_device.
+ * HC_E_ARG: ctx, d_map or d_counts null; d_points null with capacity > 0; d_counts not 4-byte / d_points not 8-byte aligned;
+ * pitch < width; nframes outside 1..(output frames of a max_batch run: max_batch, 3 * max_batch with HC_OPT_PER_CHANNEL);
+ * nframes > 1 with a frame stride smaller than height * pitch; height * pitch >= 2^32; capacity * 8 * nframes overflowing
+ * size_t. */
+int hc_edge_points_device(hc_ctx *ctx, const void *d_map, size_t pitch, size_t frame_stride, int nframes,
+                          void *d_counts /* uint32 [nframes] */,
+                          void *d_points /* int32 [nframes][capacity][2] = (x, y); may be NULL when capacity == 0 */,
+                          size_t capacity);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
