@@ -325,22 +325,13 @@ class Context:
     def process_gradients(self, dx, dy):
         """cv::Canny(dx, dy, ...) convenience (mode O): numpy int16 (n,H,W) / (n,H,W,3) -- or one frame -- in, uint8
         (n,H,W) edge maps out, through device tensors."""
-        import torch
-        shape = (self.h, self.w) if self.c == 1 else (self.h, self.w, 3)
-        a, b = (np.ascontiguousarray(v) for v in (dx, dy))
-        if a.dtype != np.int16 or b.dtype != np.int16:
-            raise HipCannyError("process_gradients: dx and dy must be int16 (CV_16SC1 / CV_16SC3)")
-        if a.ndim == len(shape):
-            a, b = a[None], b[None]
-        if a.shape != b.shape or a.shape[1:] != shape:
-            raise HipCannyError(f"process_gradients: dx {a.shape} / dy {b.shape} do not match the context's {shape}")
-        n = a.shape[0]
-        dev = torch.device("cuda", self.device)
-        tx, ty = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
-        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
-        pitch = 2 * self.c * self.w
-        self.run_gradients_device(tx.data_ptr(), ty.data_ptr(), pitch, pitch * self.h, out.data_ptr(), self.w, self.w * self.h, n)
+        tx, n, pitch, fs = self._device_view(dx, "process_gradients: dx", np.int16)
+        ty, ny, _, _ = self._device_view(dy, "process_gradients: dy", np.int16)
+        if ny != n:
+            raise HipCannyError(f"process_gradients: {n} dx planes, {ny} dy planes")
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        self.run_gradients_device(tx.data_ptr(), ty.data_ptr(), pitch, fs, out.data_ptr(), self.w, self.w * self.h, n)
         self.sync()
         return out.cpu().numpy()
 
@@ -351,27 +342,43 @@ class Context:
         _ck(self.lib.hc_derivatives_device(self.handle, C.c_void_p(d_in), in_pitch, in_fs, C.c_void_p(d_dx), C.c_void_p(d_dy),
                                            pitch, fs, int(nframes), int(ksize)))
 
-    def _frames_u8(self, frames, who):
+    def _frames_u8(self, frames, who, dtype=np.uint8):
+        """(n,H,W) / (n,H,W,3) frames -- or one frame -- of the context's shape.  uint8: converted; int16: required as they come."""
         shape = (self.h, self.w) if self.c == 1 else (self.h, self.w, 3)
-        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        a = np.ascontiguousarray(frames, dtype=np.uint8 if dtype == np.uint8 else None)
+        if a.dtype != dtype:
+            raise HipCannyError(f"{who}: must be int16 (CV_16SC1 / CV_16SC3), not {a.dtype}")
         if a.ndim == len(shape):
             a = a[None]
         if a.shape[1:] != shape:
             raise HipCannyError(f"{who}: frames {a.shape} do not match the context's {shape}")
         return a
 
+    def _device_view(self, frames, who, dtype=np.uint8):
+        """Host frames as a tight device view: (torch tensor, n, row bytes, frame stride in bytes)."""
+        import torch
+        a = self._frames_u8(frames, who, dtype)
+        row = self.c * self.w * a.itemsize
+        return torch.from_numpy(a).to(torch.device("cuda", self.device)), a.shape[0], row, row * self.h
+
+    def _device_maps(self, n):
+        """Uninitialised uint8 (n,H,W) maps on the device: pitch W, frame stride W * H."""
+        import torch
+        return torch.empty((n, self.h, self.w), dtype=torch.uint8, device=torch.device("cuda", self.device))
+
+    @staticmethod
+    def _wait_for_torch():   # the context stream does not wait for torch's: uploads and allocations first, then its calls
+        import torch
+        torch.cuda.current_stream().synchronize()
+
     def derivatives(self, frames, ksize):
         """numpy u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, (dx, dy) numpy int16 of the same shape out, through device
         tensors (either mode)."""
         import torch
-        a = self._frames_u8(frames, "derivatives")
-        n = a.shape[0]
-        dev = torch.device("cuda", self.device)
-        src = torch.from_numpy(a).to(dev)
-        dx, dy = torch.empty(a.shape, dtype=torch.int16, device=dev), torch.empty(a.shape, dtype=torch.int16, device=dev)
-        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
-        row = self.c * self.w
-        self.derivatives_device(src.data_ptr(), row, row * self.h, dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * self.h, n, ksize)
+        src, n, row, fs = self._device_view(frames, "derivatives")
+        dx, dy = torch.empty_like(src, dtype=torch.int16), torch.empty_like(src, dtype=torch.int16)
+        self._wait_for_torch()
+        self.derivatives_device(src.data_ptr(), row, fs, dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * fs, n, ksize)
         self.sync()
         return dx.cpu().numpy(), dy.cpu().numpy()
 
@@ -380,16 +387,12 @@ class Context:
         run_gradients_device -> uint8 (n,H,W) edge maps, with no host round trip in between.  Uses the context's thresholds
         as they are (at 7 they are in the units of the scaled derivatives: see hc_derivatives_device)."""
         import torch
-        a = self._frames_u8(frames, "process_aperture")
-        n = a.shape[0]
-        dev = torch.device("cuda", self.device)
-        src = torch.from_numpy(a).to(dev)
-        dx, dy = torch.empty(a.shape, dtype=torch.int16, device=dev), torch.empty(a.shape, dtype=torch.int16, device=dev)
-        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream().synchronize()
-        row = self.c * self.w
-        self.derivatives_device(src.data_ptr(), row, row * self.h, dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * self.h, n, ksize)
-        self.run_gradients_device(dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * row * self.h, out.data_ptr(), self.w, self.w * self.h, n)
+        src, n, row, fs = self._device_view(frames, "process_aperture")
+        dx, dy = torch.empty_like(src, dtype=torch.int16), torch.empty_like(src, dtype=torch.int16)
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        self.derivatives_device(src.data_ptr(), row, fs, dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * fs, n, ksize)
+        self.run_gradients_device(dx.data_ptr(), dy.data_ptr(), 2 * row, 2 * fs, out.data_ptr(), self.w, self.w * self.h, n)
         self.sync()
         return out.cpu().numpy()
 
@@ -403,15 +406,10 @@ class Context:
     def canny(self, frames, low, high, aperture=3, l2gradient=False):
         """cv::Canny convenience (mode O): numpy u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, uint8 (n,H,W) edge maps out,
         through device tensors and canny_device."""
-        import torch
-        a = self._frames_u8(frames, "canny")
-        n = a.shape[0]
-        dev = torch.device("cuda", self.device)
-        src = torch.from_numpy(a).to(dev)
-        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
-        row = self.c * self.w
-        self.canny_device(src.data_ptr(), row, row * self.h, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        src, n, row, fs = self._device_view(frames, "canny")
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
         self.sync()
         return out.cpu().numpy()
 
@@ -436,14 +434,10 @@ class Context:
     def histogram(self, frames):
         """numpy u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, uint32 (n,256) histograms out, through device tensors."""
         import torch
-        a = self._frames_u8(frames, "histogram")
-        n = a.shape[0]
-        dev = torch.device("cuda", self.device)
-        src = torch.from_numpy(a).to(dev)
-        hist = torch.empty((n, 256), dtype=torch.int32, device=dev)
-        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
-        row = self.c * self.w
-        self.histogram_device(src.data_ptr(), row, row * self.h, n, hist.data_ptr())
+        src, n, row, fs = self._device_view(frames, "histogram")
+        hist = torch.empty((n, 256), dtype=torch.int32, device=src.device)
+        self._wait_for_torch()
+        self.histogram_device(src.data_ptr(), row, fs, n, hist.data_ptr())
         self.sync()
         return hist.cpu().numpy().view(np.uint32)
 
@@ -454,18 +448,14 @@ class Context:
         context's aperture and L2 options apply; the table is taken off the context again before returning."""
         import torch
         rule = {"median": AUTO_MEDIAN, "otsu": AUTO_OTSU}.get(rule, rule)
-        a = self._frames_u8(frames, "canny_auto")
-        n = a.shape[0]
-        dev = torch.device("cuda", self.device)
-        src = torch.from_numpy(a).to(dev)
-        thr = torch.empty((n, 2), dtype=torch.int32, device=dev)
-        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
-        row = self.c * self.w
-        self.auto_thresholds_device(src.data_ptr(), row, row * self.h, n, rule, param, thr.data_ptr())
+        src, n, row, fs = self._device_view(frames, "canny_auto")
+        thr = torch.empty((n, 2), dtype=torch.int32, device=src.device)
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        self.auto_thresholds_device(src.data_ptr(), row, fs, n, rule, param, thr.data_ptr())
         self.frame_thresholds_device(thr.data_ptr(), n)
         try:
-            self.run_device(src.data_ptr(), row, row * self.h, out.data_ptr(), self.w, self.w * self.h, n)
+            self.run_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n)
         finally:
             self.frame_thresholds_device(None)
         self.sync()
@@ -517,15 +507,10 @@ class Context:
     def canny_points(self, frames, low, high, aperture=3, l2gradient=False, capacity=None):
         """cv::Canny followed by cv::findNonZero (mode O): canny_device and edge_points_device chained on the device, with no
         host copy of the maps in between.  Returns (uint8 (n,H,W) edge maps, uint32 counts, lists as edge_points gives them)."""
-        import torch
-        a = self._frames_u8(frames, "canny_points")
-        n = a.shape[0]
-        dev = torch.device("cuda", self.device)
-        src = torch.from_numpy(a).to(dev)
-        out = torch.empty((n, self.h, self.w), dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
-        row = self.c * self.w
-        self.canny_device(src.data_ptr(), row, row * self.h, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        src, n, row, fs = self._device_view(frames, "canny_points")
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
         counts, lists = self._edge_points_of(out, n, capacity)
         if self.hysteresis_info()[1]:   # the run was continued from the host (adversarial content): the maps changed after the lists were taken
             counts, lists = self._edge_points_of(out, n, capacity)

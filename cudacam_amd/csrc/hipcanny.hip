@@ -349,6 +349,15 @@ int copy_frames_d2d(hc_ctx *c, hipStream_t st, void *dst, size_t dpitch, size_t 
   return HC_OK;
 }
 
+// n maps of the internal output buffer to the caller's view (out_view_staged), on st.  remember: a host-side continuation of
+// the run in slot s rewrites the maps and repeats the copy (finish_slot)
+int copy_out_staged(hc_ctx *c, Slot &s, hipStream_t st, void *out, size_t out_pitch, size_t out_fs, int n, bool remember)
+{
+  if (int rc = copy_frames_d2d(c, st, out, out_pitch, out_fs, c->d_out, c->out_pitch, c->out_fs, (size_t)c->W, n)) return rc;
+  if (remember) { s.copy_dst = out; s.copy_pitch = out_pitch; s.copy_fs = out_fs; }
+  return HC_OK;
+}
+
 // Feeds ChainWatch (host_plan.h) when run i is complete: the chain of run i-1 ran beside the front kernel of run i, and
 // the timestamps of all three events involved -- end of front i-1, end of chain i-1, end of front i -- can be read.
 void watch_chain(hc_ctx *c, const Slot &s)
@@ -693,10 +702,8 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
   }
 
   // 8. copy-out, end of the run
-  if (out_internal) {
-    if (int rc = copy_frames_d2d(c, sh, out, out_pitch, out_fs, c->d_out, c->out_pitch, c->out_fs, (size_t)W, n_out)) return rc;
-    if (s.pending) { s.copy_dst = out; s.copy_pitch = out_pitch; s.copy_fs = out_fs; }
-  }
+  if (out_internal)
+    if (int rc = copy_out_staged(c, s, sh, out, out_pitch, out_fs, n_out, s.pending)) return rc;
   // the hysteresis (and the copy-out of an unaligned caller buffer) end the run; for the earlier stages the copy-out
   // belongs to the last stage that ran
   if (stage == HC_STAGE_HYSTER) HIPCK(prof.mark(sh, B_HYST, ProfRing::K_HYST));
@@ -710,6 +717,27 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
   c->last.slot = piped ? c->cur : 0;
   if (piped) c->cur = (c->cur + 1) % c->nslot_use;
   c->last.run_n = n_out;
+  return HC_OK;
+}
+
+// A caller's view as an entry point names it, and what the entry demands of it (check_view, host_plan.h)
+struct ViewArg { const char *name; const void *p; size_t pitch, fs, row_bytes; unsigned align = 1; bool below_4g = false; };
+// Every refusal of a pitched batch view: nframes within 1 .. max_frames, then each view -> HC_E_ARG "<entry>: <view>: <rule>"
+int check_views(const hc_ctx *c, const char *entry, int n, int max_frames, std::initializer_list<ViewArg> views)
+{
+  const std::string who(entry);
+  if (n <= 0 || n > max_frames) return fail(HC_E_ARG, who + ": nframes out of range");
+  for (const ViewArg &a : views)
+    if (const ViewFault f = check_view(View{ (uintptr_t)a.p, a.pitch, a.fs }, a.row_bytes, c->H, n, a.align, a.below_4g))
+      return fail(HC_E_ARG, who + ": " + a.name + ": " + VIEW_FAULT_TEXT[f]);
+  return HC_OK;
+}
+// the view hc_histogram_device and hc_auto_thresholds_device take: any alignment, below 4 GiB
+ViewArg hist_view(const hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs) { return { "d_in (in_pitch, in_fs)", d_in, in_pitch, in_fs, (size_t)c->C * c->W, 1, true }; }
+// host views (hc_upload, hc_download, hc_download_begin, hc_debug_tap): the rows only, as ever -- their frames may lie anywhere
+int check_host_rows(const char *entry, size_t row_stride, size_t row_bytes)
+{
+  if (const ViewFault f = check_view(View{ 0, row_stride, 0 }, row_bytes, 1, 1, 1, false)) return fail(HC_E_ARG, std::string(entry) + ": row_stride: " + VIEW_FAULT_TEXT[f]);
   return HC_OK;
 }
 
@@ -961,7 +989,7 @@ int hc_upload(hc_ctx *c, const uint8_t *host, size_t row_stride, size_t frame_st
   if (!c || !host) return fail(HC_E_ARG, "hc_upload: null argument");
   if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_upload: nframes out of range");
   const size_t rb = (size_t)c->W * c->C;
-  if (row_stride < rb) return fail(HC_E_ARG, "hc_upload: row_stride smaller than a row");
+  if (int rc = check_host_rows("hc_upload", row_stride, rb)) return rc;
   HIPCK(hipSetDevice(c->device));
   if (int rc = finish_all(c)) return rc;
   // cannyEdgeH.cu:136/144 (cudaMemcpy2D host -> pitched device).  Tight rows on both sides: one contiguous block, one DMA
@@ -997,9 +1025,7 @@ int hc_run_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, vo
 {
   if (!c || !d_in || !d_out) return fail(HC_E_ARG, "hc_run_device: null argument");
   if (final_stage < HC_STAGE_MONO || final_stage > HC_STAGE_HYSTER) return fail(HC_E_ARG, "Canny Stage Not Recognized");
-  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_run_device: nframes out of range");
-  if (in_pitch < (size_t)c->W * c->C || out_pitch < (size_t)c->W) return fail(HC_E_ARG, "hc_run_device: pitch smaller than a row");
-  if (n > 1 && (in_fs < in_pitch * (size_t)c->H || out_fs < out_pitch * (size_t)c->H)) return fail(HC_E_ARG, "hc_run_device: frame stride smaller than a frame");
+  if (int rc = check_views(c, "hc_run_device", n, c->max_batch, { { "d_in (in_pitch, in_fs)", d_in, in_pitch, in_fs, (size_t)c->W * c->C }, { "d_out (out_pitch, out_fs)", d_out, out_pitch, out_fs, (size_t)c->W } })) return rc;
   HIPCK(hipSetDevice(c->device));
   return run_impl(c, (const uint8_t *)d_in, in_pitch, in_fs, (uint8_t *)d_out, out_pitch, out_fs, n, final_stage);
 }
@@ -1009,12 +1035,9 @@ int hc_run_gradients_device(hc_ctx *c, const void *d_dx, const void *d_dy, size_
 {
   if (!c || !d_dx || !d_dy || !d_out) return fail(HC_E_ARG, "hc_run_gradients_device: null argument");
   if (c->mode != HC_MODE_O) return fail(HC_E_ARG, "hc_run_gradients_device: mode O contexts only (cv::Canny's (dx, dy) overload)");
-  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_run_gradients_device: nframes out of range");
-  if ((((uintptr_t)d_dx | (uintptr_t)d_dy | pitch | frame_stride) & 1u) != 0)
-    return fail(HC_E_ARG, "hc_run_gradients_device: int16 planes need even addresses, pitch and frame stride");
-  if (pitch < (size_t)2 * c->C * c->W || out_pitch < (size_t)c->W) return fail(HC_E_ARG, "hc_run_gradients_device: pitch smaller than a row");
-  if (n > 1 && (frame_stride < pitch * (size_t)c->H || out_frame_stride < out_pitch * (size_t)c->H))
-    return fail(HC_E_ARG, "hc_run_gradients_device: frame stride smaller than a frame");
+  const size_t row16 = (size_t)2 * c->C * c->W;
+  if (int rc = check_views(c, "hc_run_gradients_device", n, c->max_batch, { { "d_dx (pitch, frame_stride)", d_dx, pitch, frame_stride, row16, 2 }, { "d_dy (pitch, frame_stride)", d_dy, pitch, frame_stride, row16, 2 },
+                                                                            { "d_out (out_pitch, out_frame_stride)", d_out, out_pitch, out_frame_stride, (size_t)c->W } })) return rc;
   HIPCK(hipSetDevice(c->device));
   return run_impl(c, (const uint8_t *)d_dx, pitch, frame_stride, (uint8_t *)d_out, out_pitch, out_frame_stride, n, HC_STAGE_HYSTER,
                   (const uint8_t *)d_dy);
@@ -1028,9 +1051,7 @@ int hc_canny_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, 
   if (!deriv_ksize_ok(aperture)) return fail(HC_E_ARG, "hc_canny_device: aperture 3, 5, 7 or -1 (Scharr)");
   CallThresholds t;
   if (!canny_call_thresholds(low, high, aperture, l2gradient != 0, &t)) return fail(HC_E_ARG, "hc_canny_device: thresholds must be finite and not negative");
-  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_canny_device: nframes out of range");
-  if (in_pitch < (size_t)c->W * c->C || out_pitch < (size_t)c->W) return fail(HC_E_ARG, "hc_canny_device: pitch smaller than a row");
-  if (n > 1 && (in_fs < in_pitch * (size_t)c->H || out_fs < out_pitch * (size_t)c->H)) return fail(HC_E_ARG, "hc_canny_device: frame stride smaller than a frame");
+  if (int rc = check_views(c, "hc_canny_device", n, c->max_batch, { { "d_in (in_pitch, in_fs)", d_in, in_pitch, in_fs, (size_t)c->W * c->C }, { "d_out (out_pitch, out_fs)", d_out, out_pitch, out_fs, (size_t)c->W } })) return rc;
   HIPCK(hipSetDevice(c->device));
   // the call's own choices, on a copy: the context's thresholds, HC_OPT_APERTURE and HC_OPT_L2_GRADIENT stay as they are
   FrontOpts o = c->opt;
@@ -1045,51 +1066,23 @@ int hc_derivatives_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t i
 {
   if (!c || !d_in || !d_dx || !d_dy) return fail(HC_E_ARG, "hc_derivatives_device: null argument");
   if (!deriv_ksize_ok(ksize)) return fail(HC_E_ARG, "hc_derivatives_device: ksize 3, 5, 7 (scaled by 1/16, as in cv::Canny) or -1 (Scharr)");
-  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_derivatives_device: nframes out of range");
-  if ((((uintptr_t)d_dx | (uintptr_t)d_dy | pitch | fs) & 1u) != 0)
-    return fail(HC_E_ARG, "hc_derivatives_device: int16 planes need even addresses, pitch and frame stride");
-  if (in_pitch < (size_t)c->C * c->W) return fail(HC_E_ARG, "hc_derivatives_device: in_pitch smaller than a row");
-  if (pitch < (size_t)2 * c->C * c->W) return fail(HC_E_ARG, "hc_derivatives_device: pitch smaller than a row of int16");
-  if (n > 1 && (in_fs < in_pitch * (size_t)c->H || fs < pitch * (size_t)c->H))
-    return fail(HC_E_ARG, "hc_derivatives_device: frame stride smaller than a frame");
-  if ((u64)c->H * in_pitch >= (1ull << 32) || (u64)c->H * pitch >= (1ull << 32))
-    return fail(HC_E_ARG, "hc_derivatives_device: views of 4 GiB and more (height * pitch >= 2^32) are not supported by this entry");
-  DerivParams dp{};
-  dp.in = (const uint8_t *)d_in; dp.in_pitch = in_pitch; dp.in_frame_stride = in_fs;
-  dp.dx = (uint8_t *)d_dx; dp.dy = (uint8_t *)d_dy; dp.pitch = pitch; dp.frame_stride = fs;
-  dp.W = c->W; dp.H = c->H; dp.nframes = n; dp.channels = c->C; dp.ksize = ksize;
-  dp.in_aligned = (((uintptr_t)d_in | in_pitch | in_fs) & 3u) == 0;
-  const uintptr_t oa = (uintptr_t)d_dx | (uintptr_t)d_dy | pitch | fs;
-  dp.out_align = (oa & 7u) == 0 ? 8 : (oa & 3u) == 0 ? 4 : 2;
-  dp.nstrips = deriv_strips(c->W); dp.nchunks = deriv_chunks(c->H);
-  const long long items = (long long)n * dp.nstrips * dp.nchunks;
-  if (items > 0x7FFFFFF0ll) return fail(HC_E_ARG, "hc_derivatives_device: too many work items (nframes x strips x row chunks)");
-  dp.total_items = (int)items;
+  const size_t row = (size_t)c->C * c->W;
+  if (int rc = check_views(c, "hc_derivatives_device", n, c->max_batch, { { "d_in (in_pitch, in_fs)", d_in, in_pitch, in_fs, row, 1, true }, { "d_dx (pitch, fs)", d_dx, pitch, fs, 2 * row, 2, true },
+                                                                          { "d_dy (pitch, fs)", d_dy, pitch, fs, 2 * row, 2, true } })) return rc;
+  const DerivPlan P = plan_derivatives(c->W, c->H, c->C, View{ (uintptr_t)d_in, in_pitch, in_fs }, View{ (uintptr_t)d_dx, pitch, fs }, (uintptr_t)d_dy, n, ksize);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_derivatives_device: ") + P.error);
   HIPCK(hipSetDevice(c->device));
-  HIPCK(launch_deriv16(dp, c->stream));
+  HIPCK(launch_deriv16(P.dp, c->stream));
   return HC_OK;
 }
 
 #ifndef HC_LEGACY_FRONT
 namespace {
-// what hc_histogram_device and hc_auto_thresholds_device refuse alike, before anything is allocated or queued
-int check_histogram_view(hc_ctx *c, const char *who, size_t in_pitch, size_t in_fs, int n)
-{
-  const std::string w(who);
-  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, w + ": nframes out of range");
-  if (in_pitch < (size_t)c->C * c->W) return fail(HC_E_ARG, w + ": in_pitch smaller than a row");
-  if (n > 1 && in_fs < in_pitch * (size_t)c->H) return fail(HC_E_ARG, w + ": frame stride smaller than a frame");
-  if ((u64)c->H * in_pitch >= (1ull << 32)) return fail(HC_E_ARG, w + ": views of 4 GiB and more (height * pitch >= 2^32) are not supported by this entry");
-  return HC_OK;
-}
 // k_hist256 on the context stream behind the zeroing of d_hist (the view has been checked)
 int queue_histogram(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, u32 *d_hist)
 {
-  HistParams hp{};
-  hp.in = (const uint8_t *)d_in; hp.in_pitch = in_pitch; hp.in_frame_stride = in_fs; hp.hist = d_hist;
-  hp.row_bytes = c->W * c->C; hp.H = c->H; hp.nframes = n;
-  hp.chunk_rows = hist_chunk_rows(c->H, n); hp.nchunks = (c->H + hp.chunk_rows - 1) / hp.chunk_rows;
-  hp.total_items = n * hp.nchunks;  // (at most 1024 frames x 1024 chunks of 8 rows or more)
+  HistParams hp = plan_histogram(c->W, c->H, c->C, View{ (uintptr_t)d_in, in_pitch, in_fs }, n);
+  hp.hist = d_hist;
   HIPCK(hipMemsetAsync(d_hist, 0, sizeof(u32) * 256 * (size_t)n, c->stream));
   HIPCK(launch_hist256(hp, c->stream));
   return HC_OK;
@@ -1101,7 +1094,7 @@ int hc_histogram_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_
 {
   if (!c || !d_in || !d_hist) return fail(HC_E_ARG, "hc_histogram_device: null argument");
   if ((uintptr_t)d_hist & 3u) return fail(HC_E_ARG, "hc_histogram_device: d_hist must be 4-byte aligned");
-  if (int rc = check_histogram_view(c, "hc_histogram_device", in_pitch, in_fs, n)) return rc;
+  if (int rc = check_views(c, "hc_histogram_device", n, c->max_batch, { hist_view(c, d_in, in_pitch, in_fs) })) return rc;
   HIPCK(hipSetDevice(c->device));
   return queue_histogram(c, d_in, in_pitch, in_fs, n, (u32 *)d_hist);
 }
@@ -1116,7 +1109,7 @@ int hc_auto_thresholds_device(hc_ctx *c, const void *d_in, size_t in_pitch, size
   if (rule != HC_AUTO_MEDIAN && rule != HC_AUTO_OTSU) return fail(HC_E_ARG, "hc_auto_thresholds_device: rule must be HC_AUTO_MEDIAN or HC_AUTO_OTSU");
   if (!auto_param_ok(rule, param)) return fail(HC_E_ARG, "hc_auto_thresholds_device: param (sigma / ratio) must lie in [0, 1]");
   if ((long long)c->W * c->H * c->C > AUTO_MAX_SAMPLES) return fail(HC_E_ARG, "hc_auto_thresholds_device: more than 2^27 samples per frame");
-  if (int rc = check_histogram_view(c, "hc_auto_thresholds_device", in_pitch, in_fs, n)) return rc;
+  if (int rc = check_views(c, "hc_auto_thresholds_device", n, c->max_batch, { hist_view(c, d_in, in_pitch, in_fs) })) return rc;
   HIPCK(hipSetDevice(c->device));
   // every refusal lies above: the table is allocated (once; the first call may synchronise the device) only by a call that runs
   if (!c->d_hist) HIPCK(hipMalloc((void **)&c->d_hist, sizeof(u32) * 256 * (size_t)c->max_batch));
@@ -1156,28 +1149,16 @@ int hc_edge_points_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs,
   if (capacity && !d_points) return fail(HC_E_ARG, "hc_edge_points_device: d_points is null with capacity > 0");
   if ((uintptr_t)d_counts & 3u) return fail(HC_E_ARG, "hc_edge_points_device: d_counts must be 4-byte aligned");
   if ((uintptr_t)d_points & 7u) return fail(HC_E_ARG, "hc_edge_points_device: d_points must be 8-byte aligned");
-  const int max_frames = c->max_batch * (c->per_channel ? 3 : 1);  // the output frames of a max_batch run
-  if (n <= 0 || n > max_frames) return fail(HC_E_ARG, "hc_edge_points_device: nframes out of range");
-  if (pitch < (size_t)c->W) return fail(HC_E_ARG, "hc_edge_points_device: pitch smaller than a row");
-  if (n > 1 && fs < pitch * (size_t)c->H) return fail(HC_E_ARG, "hc_edge_points_device: frame stride smaller than a frame");
-  if ((u64)c->H * pitch >= (1ull << 32)) return fail(HC_E_ARG, "hc_edge_points_device: views of 4 GiB and more (height * pitch >= 2^32) are not supported by this entry");
-  if (capacity > SIZE_MAX / 8 / (size_t)n) return fail(HC_E_ARG, "hc_edge_points_device: capacity * 8 * nframes overflows size_t");
-  EdgePointsParams ep{};
-  ep.map = (const uint8_t *)d_map; ep.pitch = pitch; ep.frame_stride = fs; ep.counts = (u32 *)d_counts;
-  ep.points = (int32_t *)d_points; ep.capacity = capacity; ep.W = c->W; ep.H = c->H; ep.nframes = n;
-  ep.chunk_rows = hist_chunk_rows(c->H, n); ep.nchunks = (c->H + ep.chunk_rows - 1) / ep.chunk_rows;
-  // chunks have min(8, H) rows or more: the table below holds the items of any batch the context takes
-  const size_t table_items = (size_t)c->max_batch * (c->C == 3 ? 3 : 1) * (size_t)((c->H + std::min(HIST_MIN_CHUNK_ROWS, c->H) - 1) / std::min(HIST_MIN_CHUNK_ROWS, c->H));
-  const long long items = (long long)n * ep.nchunks;
-  if (items > 0x7FFFFFF0ll || table_items > 0x7FFFFFF0ull) return fail(HC_E_ARG, "hc_edge_points_device: too many work items (nframes x row chunks)");
-  ep.total_items = (int)items;
+  if (int rc = check_views(c, "hc_edge_points_device", n, c->max_batch * (c->per_channel ? 3 : 1), { { "d_map (pitch, fs)", d_map, pitch, fs, (size_t)c->W, 1, true } })) return rc;  // (n: at most the output frames of a max_batch run)
+  EdgePlan P = plan_edge_points(c->W, c->H, c->C, c->max_batch, View{ (uintptr_t)d_map, pitch, fs }, n, (uintptr_t)d_counts, (uintptr_t)d_points, capacity);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_edge_points_device: ") + P.error);
   HIPCK(hipSetDevice(c->device));
   const uintptr_t m0 = (uintptr_t)d_map;
   if (int rc = finish_writers_of(c, m0, m0 + (size_t)(n - 1) * fs + (size_t)(c->H - 1) * pitch + (size_t)c->W)) return rc;
   // every refusal lies above: the table is allocated (once; the first call may synchronise the device) only by a call that runs
-  if (!c->d_edge_items) HIPCK(hipMalloc((void **)&c->d_edge_items, sizeof(u32) * table_items));
-  ep.items = c->d_edge_items;
-  HIPCK(launch_edge_points(ep, c->stream));
+  if (!c->d_edge_items) HIPCK(hipMalloc((void **)&c->d_edge_items, sizeof(u32) * P.table_items));
+  P.ep.items = c->d_edge_items;
+  HIPCK(launch_edge_points(P.ep, c->stream));
   return HC_OK;
 }
 #else
@@ -1190,25 +1171,20 @@ int hc_edge_points_device(hc_ctx *, const void *, size_t, size_t, int, void *, v
 int hc_hysteresis_device(hc_ctx *c, const void *d_thresh, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n)
 {
   if (!c || !d_thresh || !d_out) return fail(HC_E_ARG, "hc_hysteresis_device: null argument");
-  if (n <= 0 || n > c->max_batch) return fail(HC_E_ARG, "hc_hysteresis_device: nframes out of range");
-  if (in_pitch < (size_t)c->W || out_pitch < (size_t)c->W) return fail(HC_E_ARG, "hc_hysteresis_device: pitch smaller than a row");
-  if (n > 1 && (in_fs < in_pitch * (size_t)c->H || out_fs < out_pitch * (size_t)c->H)) return fail(HC_E_ARG, "hc_hysteresis_device: frame stride smaller than a frame");
+  if (int rc = check_views(c, "hc_hysteresis_device", n, c->max_batch, { { "d_thresh (in_pitch, in_fs)", d_thresh, in_pitch, in_fs, (size_t)c->W }, { "d_out (out_pitch, out_fs)", d_out, out_pitch, out_fs, (size_t)c->W } })) return rc;
   HIPCK(hipSetDevice(c->device));
   if (int rc = finish_all(c)) return rc;
   Slot &s = c->slot[0];
   PackParams pp{};
   pp.in = (const uint8_t *)d_thresh; pp.in_pitch = in_pitch; pp.in_frame_stride = in_fs; pp.sbits = s.d_sbits; pp.cbits = s.d_cbits; pp.RD = c->RD; pp.W = c->W; pp.H = c->H; pp.nframes = n;
   HIPCK(launch_pack(pp, c->stream));
-  uint8_t *dst = (uint8_t *)d_out;
-  size_t dp = out_pitch, dfs = out_fs;
-  const bool out_internal = !aligned4((uintptr_t)d_out, out_pitch, out_fs);
-  if (out_internal) { dst = c->d_out; dp = c->out_pitch; dfs = c->out_fs; }
+  const View out{ (uintptr_t)d_out, out_pitch, out_fs };
+  const bool out_internal = out_view_staged(out);
+  const View dst = out_internal ? View{ (uintptr_t)c->d_out, c->out_pitch, c->out_fs } : out;
   s.prov = false;  // nothing has written a provisional map into this output (a pipelined run may have left the flag set)
-  if (int rc = queue_hyst_expand(c, s, c->stream, dst, dp, dfs, n, false)) return rc;
-  if (out_internal) {
-    if (int rc = copy_frames_d2d(c, c->stream, d_out, out_pitch, out_fs, c->d_out, c->out_pitch, c->out_fs, (size_t)c->W, n)) return rc;
-    s.copy_dst = d_out; s.copy_pitch = out_pitch; s.copy_fs = out_fs;
-  }
+  if (int rc = queue_hyst_expand(c, s, c->stream, (uint8_t *)dst.p, dst.pitch, dst.fs, n, false)) return rc;
+  if (out_internal)
+    if (int rc = copy_out_staged(c, s, c->stream, d_out, out_pitch, out_fs, n, true)) return rc;
   HIPCK(hipEventRecord(s.ev_done, c->stream));
   return HC_OK;
 }
@@ -1229,7 +1205,7 @@ int hc_download(hc_ctx *c, uint8_t *host, size_t row_stride, size_t frame_stride
 {
   if (!c || !host) return fail(HC_E_ARG, "hc_download: null argument");
   if (n <= 0 || n > c->last.run_n) return fail(HC_E_STATE, "hc_download: more frames than the last run produced");
-  if (row_stride < (size_t)c->W) return fail(HC_E_ARG, "hc_download: row_stride smaller than a row");
+  if (int rc = check_host_rows("hc_download", row_stride, (size_t)c->W)) return rc;
   if (int rc = hc_sync(c)) return rc;
   if (int rc = copy_out_d2h(c, host, row_stride, frame_stride, n, c->stream)) return rc;
   HIPCK(hipStreamSynchronize(c->stream));
@@ -1256,7 +1232,7 @@ int hc_download_begin(hc_ctx *c, uint8_t *host, size_t row_stride, size_t frame_
 {
   if (!c || !host) return fail(HC_E_ARG, "hc_download_begin: null argument");
   if (n <= 0 || n > c->last.run_n) return fail(HC_E_STATE, "hc_download_begin: more frames than the last run produced");
-  if (row_stride < (size_t)c->W) return fail(HC_E_ARG, "hc_download_begin: row_stride smaller than a row");
+  if (int rc = check_host_rows("hc_download_begin", row_stride, (size_t)c->W)) return rc;
   if (c->dl.host) return fail(HC_E_STATE, "hc_download_begin: a download is already in flight (hc_download_end first)");
   HIPCK(hipSetDevice(c->device));
   // behind the run: its hysteresis may sit on the slot's own stream (pipelined mode)
@@ -1357,7 +1333,7 @@ int hc_debug_tap(hc_ctx *c, int what, uint8_t *host, size_t row_stride, size_t f
 {
   if (!c || !host) return fail(HC_E_ARG, "hc_debug_tap: null argument");
   if (what != HC_TAP_BLUR && what != HC_TAP_THRESH) return fail(HC_E_ARG, "hc_debug_tap: unknown tap");
-  if (row_stride < (size_t)c->W) return fail(HC_E_ARG, "hc_debug_tap: row_stride smaller than a row");
+  if (int rc = check_host_rows("hc_debug_tap", row_stride, (size_t)c->W)) return rc;
   if (int rc = hc_sync(c)) return rc;
   if (!c->opt.debug_taps || n <= 0 || n > c->dbg.frames) return fail(HC_E_STATE, "hc_debug_tap: set HC_OPT_DEBUG_TAPS and run HC_STAGE_HYSTER first");
   const int W = c->W, H = c->H;

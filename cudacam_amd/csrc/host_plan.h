@@ -1,6 +1,8 @@
 // host_plan.h -- every scheduling decision of the library as plain functions: which front kernel form a run gets and
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
-// (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch).  No HIP, no hc_ctx: hipcanny.hip fills
+// (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
+// caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
+// plan_histogram, plan_edge_points).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
 #include "../../include/hipcanny.h"
@@ -13,7 +15,22 @@ namespace hc {
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline bool aligned4(uintptr_t p, size_t a, size_t b) { return ((p | a | b) & 3u) == 0; }
-inline bool reaches_4g(int H, size_t pitch) { return (unsigned long long)H * pitch >= (1ull << 32); }
+inline bool reaches_4g(int H, size_t pitch) { return pitch > 0xFFFFFFFFull / (size_t)H; }  // H * pitch >= 2^32, by a division: no pitch wraps it
+
+// ---- caller views ---------------------------------------------------------------------------------
+struct View { uintptr_t p; size_t pitch, fs; };  // a pitched batch of frames: address, bytes per row, bytes per frame
+enum ViewFault { VIEW_OK = 0, VIEW_PITCH, VIEW_STRIDE, VIEW_ALIGN, VIEW_4G };
+constexpr const char *VIEW_FAULT_TEXT[] = { "", "pitch smaller than a row", "frame stride below height * pitch", "address, pitch and frame stride must be multiples of the element size (int16 planes: even)", "views of 4 GiB and more (height * pitch >= 2^32) are not supported by this entry" };
+// What every device entry point asks of a view (hipcanny.hip: check_views), the first rule broken: the pitch holds a row; n > 1: the
+// frame stride holds a frame; address, pitch and frame stride are multiples of `align` (1, 2, 4); below_4g (kernels with 32-bit row
+// offsets): height * pitch < 2^32.  No product is formed, so none wraps: no huge pitch slips past the stride and 4 GiB tests.
+inline ViewFault check_view(const View &v, size_t row_bytes, int H, int n, unsigned align, bool below_4g)
+{
+  if (v.pitch < row_bytes) return VIEW_PITCH;
+  if (n > 1 && v.fs / (size_t)H < v.pitch) return VIEW_STRIDE;
+  if ((v.p | v.pitch | v.fs) & (align - 1)) return VIEW_ALIGN;
+  return below_4g && reaches_4g(H, v.pitch) ? VIEW_4G : VIEW_OK;
+}
 
 constexpr int MAX_HYST_LAUNCHES = 96;  // (48 until a weak edge wobbling along a tile boundary needed 52: one launch per crossing)
 constexpr int FLAG_WORDS = MAX_HYST_LAUNCHES * 4;  // [0 .. MAX) launch flags, then 3 diagnostic words per launch
@@ -154,8 +171,6 @@ struct FrontOpts {
   int chunk = 0;        // hc_set_tuning: rows per work item (0: by the rules)
   bool debug_taps = false;
 };
-
-struct View { uintptr_t p; size_t pitch, fs; };  // a pitched batch of frames: address, bytes per row, bytes per frame
 
 struct FrontIn {
   int mode, C, W, H, RD, nstrips, per_channel, stage, n;
@@ -702,6 +717,55 @@ inline HystPlan plan_hyst(int RD, int H, int n, bool small_tiles, const HystOpts
       p.late_grid[k] = (int)std::min<size_t>(p.wl_stride, std::max<size_t>((size_t)2048, 2 * (size_t)h.wl_prev[k] + 256));
   }
   return p;
+}
+
+// ---- the entries that are not runs ----------------------------------------------------------------
+// hc_derivatives_device, hc_histogram_device / hc_auto_thresholds_device, hc_edge_points_device: their kernel parameters from views
+// that passed check_view, complete but for the context's scratch (HistParams::hist, EdgePointsParams::items).  error: HC_E_ARG
+// with this text, nothing may be allocated or launched.
+struct DerivPlan { const char *error = nullptr; DerivParams dp{}; };
+inline DerivPlan plan_derivatives(int W, int H, int C, const View &in, const View &dx, uintptr_t dy, int n, int ksize)
+{
+  DerivPlan P;
+  DerivParams &d = P.dp;
+  d.in = (const uint8_t *)in.p; d.in_pitch = in.pitch; d.in_frame_stride = in.fs;
+  d.dx = (uint8_t *)dx.p; d.dy = (uint8_t *)dy; d.pitch = dx.pitch; d.frame_stride = dx.fs;  // (both planes: one pitch, one frame stride)
+  d.W = W; d.H = H; d.nframes = n; d.channels = C; d.ksize = ksize;
+  d.in_aligned = aligned4(in.p, in.pitch, in.fs);
+  const uintptr_t oa = dx.p | dy | dx.pitch | dx.fs;
+  d.out_align = (oa & 7u) == 0 ? 8 : (oa & 3u) == 0 ? 4 : 2;
+  d.nstrips = deriv_strips(W); d.nchunks = deriv_chunks(H);
+  const long long items = (long long)n * d.nstrips * d.nchunks;
+  if (items > 0x7FFFFFF0ll) P.error = "too many work items (nframes x strips x row chunks)";
+  else d.total_items = (int)items;
+  return P;
+}
+
+inline HistParams plan_histogram(int W, int H, int C, const View &in, int n)
+{
+  HistParams h{};
+  h.in = (const uint8_t *)in.p; h.in_pitch = in.pitch; h.in_frame_stride = in.fs; h.row_bytes = W * C; h.H = H; h.nframes = n;
+  h.chunk_rows = hist_chunk_rows(H, n); h.nchunks = (H + h.chunk_rows - 1) / h.chunk_rows;
+  h.total_items = n * h.nchunks;  // (at most 1024 frames x 1024 chunks of 8 rows or more)
+  return h;
+}
+
+// table_items: the context's table of per-item counts -- chunks have min(8, H) rows or more, so it holds any batch the context takes (3-channel contexts: three maps per frame, HC_OPT_PER_CHANNEL)
+struct EdgePlan { const char *error = nullptr; EdgePointsParams ep{}; size_t table_items = 0; };
+inline EdgePlan plan_edge_points(int W, int H, int C, int max_batch, const View &map, int n, uintptr_t counts, uintptr_t points, size_t capacity)
+{
+  EdgePlan P;
+  EdgePointsParams &e = P.ep;
+  e.map = (const uint8_t *)map.p; e.pitch = map.pitch; e.frame_stride = map.fs; e.counts = (u32 *)counts;
+  e.points = (int32_t *)points; e.capacity = capacity; e.W = W; e.H = H; e.nframes = n;
+  e.chunk_rows = hist_chunk_rows(H, n); e.nchunks = (H + e.chunk_rows - 1) / e.chunk_rows;
+  const int min_rows = std::min(HIST_MIN_CHUNK_ROWS, H);
+  P.table_items = (size_t)max_batch * (C == 3 ? 3 : 1) * (size_t)((H + min_rows - 1) / min_rows);
+  const long long items = (long long)n * e.nchunks;
+  if (capacity > SIZE_MAX / 8 / (size_t)n) P.error = "capacity * 8 * nframes overflows size_t";
+  else if (items > 0x7FFFFFF0ll || P.table_items > 0x7FFFFFF0ull) P.error = "too many work items (nframes x row chunks)";
+  else e.total_items = (int)items;
+  return P;
 }
 
 }  // namespace hc

@@ -3,7 +3,9 @@
 // plane_row_dwords, half_pays, half_dump_region, slot_wl_cap); every plan of the sweep must keep the capacity claims the
 // launchers and kernels rest on.  Every front plan the driver makes is also folded into a 64-bit FNV-1a digest, field by field:
 // tests/golden/plan_front_digest.json holds the value of the commit named there, so a restructured planner proves that it
-// plans what that one planned.  Prints "ok <plans checked> <digest>" or the first violations.
+// plans what that one planned.  check_view (every entry point's view rules) and the plans of the entries that are not runs
+// (plan_derivatives, plan_histogram, plan_edge_points) are checked beside them, outside the count and the digest.
+// Prints "ok <plans checked> <digest>" or the first violations.
 #include "../../cudacam_amd/csrc/host_plan.h"
 
 #include <cstdio>
@@ -462,6 +464,131 @@ static void chain_watch()
   }
 }
 
+// ---- check_view and the plans of the entries that are not runs ----------------------------------------------------
+// (no front plans: they are neither counted in g_plans nor folded into the digest)
+#define VCHECK(cond, ...) do { if (!(cond) && ++g_fail <= 20) { std::printf("FAIL line %d: ", __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
+struct ViewSpec { const char *entry; size_t row_bytes; unsigned align; bool below_4g; };
+
+// Each entry's view specification (hipcanny.hip) on frames of W x H x C: the tight view and a padded, offset one pass; each
+// single defect is reported as its own rule -- the cases of test_gpu_derivatives.py::test_errors and of the `bad` table of
+// test_gpu_edge_points.py -- and no pitch gets past through a height * pitch that wrapped 64 bits.
+static void view_table(int W, int H, int C)
+{
+  const size_t u8 = (size_t)W * C, i16 = 2 * u8, G4 = (size_t)1 << 32, top = SIZE_MAX;
+  const ViewSpec specs[] = { { "hc_run_device / hc_canny_device in", u8, 1, false }, { "run / canny / gradients / hysteresis out, hysteresis in", (size_t)W, 1, false },
+                             { "hc_run_gradients_device dx / dy", i16, 2, false }, { "hc_derivatives_device in, histogram entries", u8, 1, true },
+                             { "hc_derivatives_device dx / dy", i16, 2, true }, { "hc_edge_points_device map", (size_t)W, 1, true } };
+  const uintptr_t base = 0x10000000u;
+  for (const ViewSpec &s : specs) {
+    const size_t row = s.row_bytes, a = s.align, fs = row * H;
+    auto rule = [&](uintptr_t p, size_t pitch, size_t stride, int n) { return check_view(View{ p, pitch, stride }, row, H, n, s.align, s.below_4g); };
+    VCHECK(rule(base, row, fs, 2) == VIEW_OK && rule(base, row, fs, 1) == VIEW_OK, "%s: tight view", s.entry);
+    VCHECK(rule(base + a, row + 3 * a, (row + 3 * a) * H + 5 * a, 2) == VIEW_OK, "%s: padded view at an offset", s.entry);
+    VCHECK(rule(base, row - 1, fs, 1) == VIEW_PITCH && rule(base, 0, fs, 2) == VIEW_PITCH, "%s: pitch = row - 1", s.entry);
+    VCHECK(rule(base, row, fs - 1, 2) == VIEW_STRIDE && rule(base, row + a, fs, 2) == VIEW_STRIDE, "%s: stride = pitch * H - 1, n = 2", s.entry);
+    VCHECK(rule(base, row, fs - a, 1) == VIEW_OK && rule(base, row, 0, 1) == VIEW_OK, "%s: one frame has no stride to keep", s.entry);
+    if (a == 1) VCHECK(rule(base + 1, row + 1, (row + 1) * H + 1, 2) == VIEW_OK && rule(base, row, fs - 1, 1) == VIEW_OK, "%s: u8 views of any alignment", s.entry);
+    if (a == 2) {
+      VCHECK(rule(base + 1, row, fs, 2) == VIEW_ALIGN && rule(base, row + 1, (row + 1) * H + (H & 1), 2) == VIEW_ALIGN && rule(base, row, fs + 1, 2) == VIEW_ALIGN
+             && rule(base, row, fs + 1, 1) == VIEW_ALIGN, "%s: odd address, pitch, stride", s.entry);
+      VCHECK(rule(base + 2, row + 2, (row + 2) * H + 2, 2) == VIEW_OK, "%s: even is enough", s.entry);
+    }
+    // both sides of 4 GiB: height * pitch = 2^32 exactly (where H divides it), the last pitch of this alignment below, the first at or above
+    const ViewFault far = s.below_4g ? VIEW_4G : VIEW_OK;
+    const size_t first = (G4 + H - 1) / H, at = (first + 3) / 4 * 4, under = (G4 - 1) / H / 4 * 4;
+    VCHECK((unsigned long long)H * at >= G4 && (unsigned long long)H * under < G4 && (G4 % H || H * first == G4), "the limit itself");
+    VCHECK(rule(base, at, at * H, 2) == far && rule(base, at, fs, 1) == far, "%s: H * pitch reaches 2^32", s.entry);
+    if (under >= row) VCHECK(rule(base, under, under * H, 2) == VIEW_OK && rule(base, under, fs, 1) == VIEW_OK, "%s: H * pitch just below 2^32", s.entry);
+    VCHECK(rule(base, (size_t)1 << 31, ((size_t)1 << 31) * H, 2) == (H > 1 ? far : VIEW_OK) && rule(base, G4 / H, G4 / H * H, 1) == (a == 2 && (G4 / H & 1) ? VIEW_ALIGN : G4 % H ? VIEW_OK : far), "%s: pitch 1 << 31, (1 << 32) / H", s.entry);
+    VCHECK(reaches_4g(H, at) && !reaches_4g(H, under) && reaches_4g(H, top) && reaches_4g(H, top / H + (H > 1)), "reaches_4g");
+    // pitches whose height * pitch wraps 64 bits (from 2^64 / H, rounded up, to SIZE_MAX): no frame stride holds such a frame,
+    // whatever the wrapped product let through
+    for (size_t pitch : { top / H + (H > 1), top - (H > 1), top })
+      for (size_t stride : { fs, pitch * H, (size_t)0, top - 1 }) {
+        if (H == 1 && stride >= pitch) continue;  // (one row: height * pitch is the pitch, and such a stride holds it)
+        VCHECK(rule(base, pitch, stride, 2) == VIEW_STRIDE, "%s: wrapping pitch %zx, stride %zx, n = 2", s.entry, pitch, stride);
+        VCHECK(rule(base, pitch, stride, 1) == (s.align == 2 && ((pitch | stride) & 1) ? VIEW_ALIGN : far), "%s: wrapping pitch %zx, stride %zx, n = 1", s.entry, pitch, stride);
+      }
+  }
+}
+
+// chunks of `rows` rows cover H, the last one is not empty
+static bool chunks_cover(int nchunks, int rows, int H) { return rows >= 1 && (long)nchunks * rows >= H && (long)(nchunks - 1) * rows < H; }
+static int largest_power_dividing(uintptr_t bits) { return bits % 8 == 0 ? 8 : bits % 4 == 0 ? 4 : 2; }
+
+static void call_plans(int W, int H, int C, int max_batch)
+{
+  const int k = 7 * W + 3 * H + C;  // (every residue of address, pitch and frame stride comes by over the sweep)
+  const size_t ip = (size_t)W * C + (k & 3), ifs = ip * H + ((k >> 2) & 3), op = (size_t)2 * W * C + 2 * ((k >> 4) & 3), ofs = op * H + 2 * ((k >> 6) & 3);
+  const View in{ 0x10000000u + ((unsigned)(k >> 8) & 3), ip, ifs }, dx{ 0x20000000u + 2 * ((unsigned)(k >> 10) & 3), op, ofs };
+  const uintptr_t dy = 0x30000000u + 2 * ((unsigned)(k >> 12) & 3);
+  for (int n : { 1, std::min(2, max_batch), max_batch }) {
+    const DerivPlan D = plan_derivatives(W, H, C, in, dx, dy, n, 3);
+    const DerivParams &d = D.dp;
+    VCHECK(!D.error && chunks_cover(d.nchunks, DERIV_CHUNK_ROWS, H) && (long)d.nstrips * DERIV_STRIP_W >= W && (long)(d.nstrips - 1) * DERIV_STRIP_W < W
+           && d.total_items == n * d.nstrips * d.nchunks, "derivatives %d x %d x %d n %d: strips, chunks, items", W, H, C, n);
+    VCHECK(d.out_align == largest_power_dividing(dx.p | dy | op | ofs) && (d.in_aligned != 0) == (in.p % 4 == 0 && ip % 4 == 0 && ifs % 4 == 0), "derivatives %d x %d x %d: alignments", W, H, C);
+    VCHECK(d.in == (const uint8_t *)in.p && d.in_pitch == ip && d.in_frame_stride == ifs && d.dx == (uint8_t *)dx.p && d.dy == (uint8_t *)dy && d.pitch == op && d.frame_stride == ofs
+           && d.W == W && d.H == H && d.nframes == n && d.channels == C && d.ksize == 3, "derivatives %d x %d x %d n %d: views", W, H, C, n);
+    const HistParams h = plan_histogram(W, H, C, in, n);
+    VCHECK(chunks_cover(h.nchunks, h.chunk_rows, H) && h.chunk_rows <= HIST_MAX_CHUNK_ROWS && h.total_items == n * h.nchunks && h.row_bytes == W * C && h.H == H && h.nframes == n
+           && h.in == (const uint8_t *)in.p && h.in_pitch == ip && h.in_frame_stride == ifs && h.hist == nullptr, "histogram %d x %d x %d n %d", W, H, C, n);
+  }
+  // the maps of a run: one per frame, three with HC_OPT_PER_CHANNEL; the table of per-item counts holds any batch of them
+  const View map{ 0x40000000u + ((unsigned)k & 7), (size_t)W + (k & 3), ((size_t)W + (k & 3)) * H + ((k >> 2) & 7) };
+  for (int per_channel = 0; per_channel <= (C == 3); ++per_channel)
+    for (int n : { 1, std::min(2, max_batch), max_batch * (per_channel ? 3 : 1) }) {  // (every n the entry lets through)
+      const EdgePlan E = plan_edge_points(W, H, C, max_batch, map, n, 0x50000000u, 0x60000000u, 100);
+      const EdgePointsParams &e = E.ep;
+      VCHECK(!E.error && chunks_cover(e.nchunks, e.chunk_rows, H) && e.total_items == n * e.nchunks && (size_t)e.total_items <= E.table_items && e.items == nullptr,
+             "edge points %d x %d x %d n %d of %d: chunks, items, table of %zu", W, H, C, n, max_batch, E.table_items);
+      VCHECK(e.map == (const uint8_t *)map.p && e.pitch == map.pitch && e.frame_stride == map.fs && e.counts == (u32 *)0x50000000u && e.points == (int32_t *)0x60000000u && e.capacity == 100
+             && e.W == W && e.H == H && e.nframes == n, "edge points %d x %d x %d n %d: views", W, H, C, n);
+    }
+}
+
+// Plans worked out by hand from the expressions of the commit before these functions, where hc_derivatives_device, queue_histogram and
+// hc_edge_points_device formed them inline: nstrips = ceil(W / 248), nchunks = ceil(H / 64), total_items = n * nstrips * nchunks
+// (derivatives); chunk_rows = min(H, clamp(ceil(H * n / 8192), 8, 64)), nchunks = ceil(H / chunk_rows), total_items = n * nchunks
+// (histogram, edge points); table_items = max_batch * (C == 3 ? 3 : 1) * ceil(H / min(8, H)).
+static void pinned_call_plans()
+{
+  const struct { int W, H, C, max_batch, n; int d_strips, d_chunks, d_items, rows, chunks, items; size_t table; } pins[] = {
+    { 64, 32, 3, 2, 2, 1, 1, 2, 8, 4, 8, 24 },  // test_gpu_derivatives.py::test_errors; H * n = 64 rows: the 8-row floor
+    { 1920, 1080, 1, 1024, 1024, 8, 17, 139264, 64, 17, 17408, 138240 },  // 1 105 920 rows / 8192 = 135: the 64-row cap; 135 chunks of 8 rows
+    { 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1 },
+  };
+  for (const auto &p : pins) {
+    const View in{ 0x10000000u, (size_t)p.W * p.C, (size_t)p.W * p.C * p.H }, dx{ 0x20000000u, 2 * in.pitch, 2 * in.fs }, map{ 0x40000000u, (size_t)p.W, (size_t)p.W * p.H };
+    const DerivPlan D = plan_derivatives(p.W, p.H, p.C, in, dx, 0x30000000u, p.n, 5);
+    VCHECK(!D.error && D.dp.nstrips == p.d_strips && D.dp.nchunks == p.d_chunks && D.dp.total_items == p.d_items && D.dp.in_aligned == (in.pitch % 4 == 0) && D.dp.out_align == (in.pitch % 4 == 0 ? 8 : in.pitch % 2 == 0 ? 4 : 2),
+           "pinned derivatives %d x %d: %d strips x %d chunks, %d items", p.W, p.H, D.dp.nstrips, D.dp.nchunks, D.dp.total_items);
+    const HistParams h = plan_histogram(p.W, p.H, p.C, in, p.n);
+    VCHECK(h.chunk_rows == p.rows && h.nchunks == p.chunks && h.total_items == p.items && h.row_bytes == p.W * p.C, "pinned histogram %d x %d: %d rows x %d, %d items", p.W, p.H, h.chunk_rows, h.nchunks, h.total_items);
+    const EdgePlan E = plan_edge_points(p.W, p.H, p.C, p.max_batch, map, p.n, 0x50000000u, 0, 0);
+    VCHECK(!E.error && E.ep.chunk_rows == p.rows && E.ep.nchunks == p.chunks && E.ep.total_items == p.items && E.table_items == p.table, "pinned edge points %d x %d: %d rows x %d, %d items, table %zu", p.W, p.H,
+           E.ep.chunk_rows, E.ep.nchunks, E.ep.total_items, E.table_items);
+  }
+  // the refusals: work items beyond an int, a list buffer beyond size_t
+  const View v{ 0x10000000u, 8184, (size_t)8184 << 24 };
+  VCHECK(plan_derivatives(8184, 1 << 24, 1, v, v, 0x30000000u, 1 << 20, 3).error && !plan_derivatives(8184, 1 << 24, 1, v, v, 0x30000000u, 1, 3).error, "derivatives: too many work items");
+  VCHECK(plan_edge_points(64, 1 << 24, 1, 1 << 30, v, 1, 4, 8, 1).error && plan_edge_points(64, 1 << 24, 1, 1 << 30, v, 1 << 30, 4, 8, 1).error && !plan_edge_points(64, 1 << 24, 1, 1 << 9, v, 1 << 9, 4, 8, 1).error,
+         "edge points: too many work items / table entries");
+  VCHECK(plan_edge_points(16, 8, 1, 2, v, 2, 4, 8, SIZE_MAX / 16 + 1).error && !plan_edge_points(16, 8, 1, 2, v, 2, 4, 8, SIZE_MAX / 16).error && plan_edge_points(16, 8, 1, 2, v, 1, 4, 8, SIZE_MAX / 8 + 1).error,
+         "edge points: capacity * 8 * nframes");
+}
+
+static void views_and_call_plans()
+{
+  for (int H : { 1, 2, 32, 37, 1080, 4320 })
+    for (int W : { 1, 16, 64, 641, 1920 })
+      for (int C : { 1, 3 }) view_table(W, H, C);
+  for (int W = 1; W <= 600; ++W)
+    for (int H = 1; H <= 300; ++H)
+      for (int C : { 1, 3 }) call_plans(W, H, C, 1 + (W + 5 * H) % 11);
+  pinned_call_plans();
+}
+
 int main()
 {
   const int heights[] = { 1, 8, 480, 1080, 4320 };  // every width at these heights, every height at these widths; the full option product where both are special
@@ -477,6 +604,7 @@ int main()
   pinned();
   pinned_front8_runs();
   chain_watch();
+  views_and_call_plans();
   if (plane_row_dwords(8184) != 256 || plane_row_dwords(8185) != 0) { ++g_fail; std::printf("FAIL width limit\n"); }
   if (g_fail) { std::printf("%ld violations in %ld plans\n", g_fail, g_plans); return 1; }
   std::printf("ok %ld %016llx\n", g_plans, g_digest);

@@ -18,7 +18,15 @@ slot rule calls big), and the whole option product where width and height are bo
 * the forms the GPU tests pin (half strips, k_front_mx, k_front_o_ext, the 4 GiB views, the smoke run);
 * ChainWatch on synthetic traces: trial after three outlasting runs and run >= 5, kept only below 0.97 x the pre-trial
   mean, back-off 64 doubling to 4096, back to two slots after 16 light runs doubling to 1024, one wave above 0.25 and
-  back below 0.03, the chain_told overrides.
+  back below 0.03, the chain_told overrides;
+* check_view on each entry point's view specification (row bytes, alignment, 4 GiB rule): tight and padded views pass,
+  each single defect is its own rule (pitch = row - 1; stride = pitch * H - 1 at n = 2, accepted at n = 1; odd address,
+  pitch, stride of int16 views; both sides of H * pitch = 2^32, pitch 1 << 31 and (1 << 32) / H), and pitches from
+  2^64 / H to SIZE_MAX, whose H * pitch wraps 64 bits, are refused with UBSan silent;
+* plan_derivatives, plan_histogram, plan_edge_points over W 1..600 x H 1..300, C 1 / 3, n 1 / 2 / max_batch: the chunks
+  cover H with no empty one, total_items = n x strips x chunks, out_align and in_aligned by the low bits, the edge-item
+  table holds every batch; 64 x 32 x 3 (n 2), 1920 x 1080 (n 1024) and 1 x 1 pinned by hand; the refusals.
+  (Neither counted as plans nor folded into the digest.)
 
 The driver also folds every field of every front plan it makes into a 64-bit FNV-1a digest.  tests/golden/
 plan_front_digest.json holds the plan count and the digests of both builds (the product's, and -DHC_LEGACY_FRONT) as the
