@@ -58,6 +58,8 @@ TAP_BLUR, TAP_THRESH = 1, 2
 FORM_O_APERTURE7, FORM_O_SCHARR = 8, 9
 # rules of hc_auto_thresholds_device (the header's HC_AUTO_MEDIAN / HC_AUTO_OTSU)
 AUTO_MEDIAN, AUTO_OTSU = 0, 1
+# borders of hc_gaussian_blur_device (the header's HC_BORDER_REFLECT_101 / HC_BORDER_REPLICATE)
+BORDER_REFLECT_101, BORDER_REPLICATE = 0, 1
 # words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
 SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
@@ -69,8 +71,10 @@ ABI_SYMBOLS = [
     "hc_host_alloc", "hc_host_free", "hc_profile_get_front", "hc_debug_tap", "hc_use_own_stream", "hc_profile_get_intervals", "hc_last_run_info", "hc_pipeline_depth", "hc_pipeline_slots_in_use", "hc_front_waves_per_workgroup",
     "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
     "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
-    "hc_edge_points_device",
+    "hc_edge_points_device", "hc_gaussian_blur_device",
 ]
+# ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
+ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
 
 _lib = None
 _lib_legacy = None
@@ -129,6 +133,8 @@ def load_library(legacy=False):
     L.hc_histogram_device.argtypes = [vp, vp, sz, sz, i, vp]
     L.hc_auto_thresholds_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, vp]
     L.hc_edge_points_device.argtypes = [vp, vp, sz, sz, i, vp, vp, sz]
+    L.hc_gaussian_blur_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, C.POINTER(C.c_uint16), i]
+    L.hc_gaussian_taps_q8.argtypes = [i, C.c_double, C.POINTER(C.c_uint16)]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -160,7 +166,7 @@ def load_library(legacy=False):
     L.hc_host_free.argtypes = [vp]
     L.hc_last_error.restype = C.c_char_p
     L.hc_version.restype = C.c_char_p
-    for name in ABI_SYMBOLS:
+    for name in ABI_SYMBOLS + ABI_SYMBOLS_HOST:
         getattr(L, name)
     if legacy:
         _lib_legacy = L
@@ -181,6 +187,38 @@ def last_error():
 def _ck(rc):
     if rc != 0:
         raise HipCannyError(f"hipcanny error {rc}: {last_error()}")
+
+
+_FIXED_TAPS_Q8 = {3: [64, 128, 64], 5: [16, 64, 96, 64, 16], 7: [8, 28, 56, 72, 56, 28, 8]}
+
+
+def gaussian_taps_q8(ksize, sigma=0.0):
+    """The Q8 taps (256 = 1.0) of a ksize Gaussian for gaussian_blur_device, by the rule include/hipcanny.h states for
+    hc_gaussian_taps_q8 -- pure Python, the same result: ksize 3, 5 or 7; sigma <= 0 gives OpenCV's small fixed kernels."""
+    import math
+    ksize, sigma = int(ksize), float(sigma)
+    if ksize not in _FIXED_TAPS_Q8:
+        raise HipCannyError("gaussian_taps_q8: ksize 3, 5 or 7")
+    if not math.isfinite(sigma):
+        raise HipCannyError("gaussian_taps_q8: sigma must be finite")
+    if sigma <= 0:
+        return list(_FIXED_TAPS_Q8[ksize])
+    r = ksize // 2
+    den = 2.0 * sigma * sigma
+    g = [1.0 if i == r else math.exp(-float((i - r) * (i - r)) / den) if den > 0 else 0.0 for i in range(ksize)]
+    total = 0.0
+    for v in g:   # (added in index order, as the C function adds them: the built-in sum compensates)
+        total += v
+    taps, err = [0] * ksize, 0.0
+    for i in range(r):
+        x = 256.0 * (g[i] / total) + err
+        v = round(x)   # half to even, as nearbyint
+        err = x - v
+        taps[i] = taps[ksize - 1 - i] = int(v)
+    taps[r] = 256 - sum(taps)
+    if min(taps) < 0 or max(taps) > 256:
+        raise HipCannyError("gaussian_taps_q8: sigma gives taps outside 0 .. 256")
+    return taps
 
 
 class Context:
@@ -396,6 +434,54 @@ class Context:
         self.sync()
         return out.cpu().numpy()
 
+    def gaussian_blur_device(self, d_in, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes, ksize, taps, border=BORDER_REFLECT_101):
+        """cv::GaussianBlur's fixed-point path for u8 frames on device memory (hc_gaussian_blur_device, either mode): ksize 3, 5
+        or 7, `taps` ksize Q8 values (256 = 1.0, sum 256: gaussian_taps_q8), the same along x and y.  Pitches and frame strides
+        in bytes, any alignment; the views must not overlap.  Asynchronous on the context stream; not a run."""
+        vals = [int(v) for v in taps]
+        if any(v < 0 or v > 0xFFFF for v in vals) or (int(ksize) in _FIXED_TAPS_Q8 and len(vals) != int(ksize)):
+            raise HipCannyError(f"hc_gaussian_blur_device: `taps` must hold ksize = {int(ksize)} uint16 values, not {vals}")
+        t = (C.c_uint16 * max(len(vals), 1))(*vals)
+        _ck(self.lib.hc_gaussian_blur_device(self.handle, C.c_void_p(d_in), in_pitch, in_fs, C.c_void_p(d_out), out_pitch, out_fs,
+                                             int(nframes), int(ksize), t, int(border)))
+
+    def gaussian_blur(self, frames, ksize, sigma=0.0, border=BORDER_REFLECT_101, taps=None):
+        """numpy u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, the blurred frames of the same shape out, through device tensors
+        (either mode).  taps: ksize Q8 values instead of gaussian_taps_q8(ksize, sigma)."""
+        import torch
+        src, n, row, fs = self._device_view(frames, "gaussian_blur")
+        out = torch.empty_like(src)
+        self._wait_for_torch()
+        self.gaussian_blur_device(src.data_ptr(), row, fs, out.data_ptr(), row, fs, n, ksize,
+                                  gaussian_taps_q8(ksize, sigma) if taps is None else taps, border)
+        self.sync()
+        return out.cpu().numpy()
+
+    def _blurred(self, src, n, row, fs, blur, border=BORDER_REFLECT_101):
+        """Queues the blur = (ksize, sigma) of a tight device view into a scratch tensor on the context stream and returns the
+        tensor; blur None: src itself, nothing queued.  The caller has waited for torch's stream."""
+        import torch
+        if blur is None:
+            return src
+        ksize, sigma = blur
+        taps = gaussian_taps_q8(ksize, sigma)
+        tmp = torch.empty_like(src)
+        self._wait_for_torch()
+        self.gaussian_blur_device(src.data_ptr(), row, fs, tmp.data_ptr(), row, fs, n, ksize, taps, border)
+        return tmp
+
+    def blur_canny(self, frames, ksize, sigma, low, high, aperture=3, l2gradient=False, border=BORDER_REFLECT_101):
+        """cv::GaussianBlur(.., Size(ksize, ksize), sigma) followed by cv::Canny(.., low, high, aperture, l2gradient) (mode O):
+        gaussian_blur_device into a scratch tensor, then canny_device, queued back to back on the context stream with no
+        synchronisation in between.  numpy u8 frames in, uint8 (n,H,W) edge maps out."""
+        src, n, row, fs = self._device_view(frames, "blur_canny")
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        tmp = self._blurred(src, n, row, fs, (ksize, sigma), border)
+        self.canny_device(tmp.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        self.sync()
+        return out.cpu().numpy()
+
     def canny_device(self, d_in, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes, low, high, aperture=3, l2gradient=False):
         """cv::Canny(img, edges, low, high, aperture, l2gradient) on device memory (mode O, hc_canny_device): thresholds in
         cv::Canny's units, aperture 3, 5, 7 or -1 (Scharr), all per call -- the context's thresholds and options are neither
@@ -441,17 +527,20 @@ class Context:
         self.sync()
         return hist.cpu().numpy().view(np.uint32)
 
-    def canny_auto(self, frames, rule="median", param=0.33):
+    def canny_auto(self, frames, rule="median", param=0.33, blur=None):
         """cv::Canny with thresholds chosen per frame on the device (mode O): auto thresholds -> per-frame table -> run, queued
         back to back on the context stream with no host synchronisation in between.  rule: "median" (param = sigma) or "otsu"
         (param = ratio), or AUTO_MEDIAN / AUTO_OTSU.  Returns (uint8 (n,H,W) edge maps, int32 (n,2) thresholds).  The
-        context's aperture and L2 options apply; the table is taken off the context again before returning."""
+        context's aperture and L2 options apply; the table is taken off the context again before returning.
+        blur = (ksize, sigma): the frames are blurred first (gaussian_blur_device, chained on the device too); thresholds and
+        maps are those of the blurred frames."""
         import torch
         rule = {"median": AUTO_MEDIAN, "otsu": AUTO_OTSU}.get(rule, rule)
-        src, n, row, fs = self._device_view(frames, "canny_auto")
-        thr = torch.empty((n, 2), dtype=torch.int32, device=src.device)
+        raw, n, row, fs = self._device_view(frames, "canny_auto")
+        thr = torch.empty((n, 2), dtype=torch.int32, device=raw.device)
         out = self._device_maps(n)
         self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)
         self.auto_thresholds_device(src.data_ptr(), row, fs, n, rule, param, thr.data_ptr())
         self.frame_thresholds_device(thr.data_ptr(), n)
         try:
@@ -504,12 +593,14 @@ class Context:
         torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
         return self._edge_points_of(d, d.shape[0], capacity)
 
-    def canny_points(self, frames, low, high, aperture=3, l2gradient=False, capacity=None):
+    def canny_points(self, frames, low, high, aperture=3, l2gradient=False, capacity=None, blur=None):
         """cv::Canny followed by cv::findNonZero (mode O): canny_device and edge_points_device chained on the device, with no
-        host copy of the maps in between.  Returns (uint8 (n,H,W) edge maps, uint32 counts, lists as edge_points gives them)."""
-        src, n, row, fs = self._device_view(frames, "canny_points")
+        host copy of the maps in between.  Returns (uint8 (n,H,W) edge maps, uint32 counts, lists as edge_points gives them).
+        blur = (ksize, sigma): the frames are blurred first (gaussian_blur_device, chained on the device too)."""
+        raw, n, row, fs = self._device_view(frames, "canny_points")
         out = self._device_maps(n)
         self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
         self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
         counts, lists = self._edge_points_of(out, n, capacity)
         if self.hysteresis_info()[1]:   # the run was continued from the host (adversarial content): the maps changed after the lists were taken

@@ -18,6 +18,7 @@ hipError_t launch_hist256(const HistParams &p, hipStream_t s);  // p.hist must b
 hipError_t launch_auto_thr(const u32 *hist, int nframes, int rule, double param, int32_t *thr, hipStream_t s);  // hist [nframes][256] -> thr [nframes][2]
 // edge_points.hip (the product library only): k_edge_count, k_edge_scan and, with p.capacity > 0, k_edge_emit
 hipError_t launch_edge_points(const EdgePointsParams &p, hipStream_t s);
+hipError_t launch_gauss8(const BlurParams &p, hipStream_t s);  // blur.hip (the product library only): separable Q8 smoothing filter, u8 -> u8
 #endif
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);

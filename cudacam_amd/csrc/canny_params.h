@@ -121,6 +121,40 @@ struct DerivParams {
   int nstrips, nchunks, total_items;
 };
 
+// k_gauss8 (blur.hip): a separable K x K smoothing filter with Q8 taps, u8 frames -> u8 frames of the same interleave
+// (hc_gaussian_blur_device, where the arithmetic is stated).  Strips, lanes and chunks as k_deriv16.
+constexpr int BLUR_STRIP_W = 248;        // output columns per wave
+static_assert(BLUR_STRIP_W == STRIP_W, "k_gauss8 uses the lane layout of the 4-px front kernels");
+constexpr int BLUR_CHUNK_ROWS = 64;      // output rows per work item
+constexpr int BLUR_MAX_TAPS = 7;
+constexpr int BLUR_REFLECT_101 = 0, BLUR_REPLICATE = 1;  // HC_BORDER_* (host_plan.h asserts the match)
+constexpr bool blur_ksize_ok(int ksize) { return ksize == 3 || ksize == 5 || ksize == 7; }
+inline int blur_strips(int W) { return (W + BLUR_STRIP_W - 1) / BLUR_STRIP_W; }
+inline int blur_chunks(int H) { return (H + BLUR_CHUNK_ROWS - 1) / BLUR_CHUNK_ROWS; }
+// cv::borderInterpolate for the two borders: index i of an axis of n >= 1 elements, clamped (BLUR_REPLICATE) or reflected
+// about the edge elements without repeating them, until it lies inside (BLUR_REFLECT_101; n == 1: 0).  The kernel calls it
+// for indices within 3 of the axis, the CPU tests for any.
+HC_HOST_DEVICE inline int border_index(int i, int n, int border)
+{
+  if (border == BLUR_REPLICATE) return i < 0 ? 0 : i >= n ? n - 1 : i;
+  if (n == 1) return 0;
+  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
+  return i;
+}
+struct BlurParams {
+  const uint8_t *in;       // u8 frames, `channels` interleaved; any alignment (in_aligned: base, pitch and frame stride are multiples of 4)
+  size_t in_pitch, in_frame_stride;
+  uint8_t *out;            // u8 frames of the same shape; any alignment (out_aligned as in_aligned); no byte shared with the input view
+  size_t out_pitch, out_frame_stride;
+  int W, H, nframes, channels;
+  int ksize;               // 3, 5 or 7
+  int border;              // BLUR_REFLECT_101 or BLUR_REPLICATE
+  int in_aligned;          // the input rows may be read as dwords (whole 4-pixel groups inside the row only)
+  int out_aligned;         // the output rows may be written as dwords (likewise)
+  int nstrips, nchunks, total_items;
+  uint16_t taps[BLUR_MAX_TAPS + 1];  // Q8 (256 = 1.0), each <= 256, sum 256; [ksize ..]: 0
+};
+
 // k_hist256 (stats.hip): 256-bin histograms of u8 frames, all channels pooled.  A work item is (frame, chunk of rows); a wave
 // counts its rows into a wave-private LDS histogram and adds the non-zero bins to hist[frame] with global atomics.
 constexpr int HIST_MAX_CHUNK_ROWS = 64, HIST_MIN_CHUNK_ROWS = 8;

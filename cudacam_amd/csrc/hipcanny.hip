@@ -1161,12 +1161,42 @@ int hc_edge_points_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs,
   HIPCK(launch_edge_points(P.ep, c->stream));
   return HC_OK;
 }
+
+// k_gauss8 on the context stream (blur.hip).  Not a run, as hc_derivatives_device -- except that a pipelined run in flight whose
+// output overlaps either view is completed first (finish_writers_of, as hc_edge_points_device): a run's output is a natural
+// neighbour of both views, and its hysteresis runs on another stream.
+int hc_gaussian_blur_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n,
+                            int ksize, const uint16_t *taps, int border)
+{
+  if (!c || !d_in || !d_out || !taps) return fail(HC_E_ARG, "hc_gaussian_blur_device: null argument");
+  const size_t row = (size_t)c->C * c->W;
+  if (int rc = check_views(c, "hc_gaussian_blur_device", n, c->max_batch, { { "d_in (in_pitch, in_fs)", d_in, in_pitch, in_fs, row, 1, true }, { "d_out (out_pitch, out_fs)", d_out, out_pitch, out_fs, row, 1, true } })) return rc;
+  const BlurPlan P = plan_gaussian_blur(c->W, c->H, c->C, View{ (uintptr_t)d_in, in_pitch, in_fs }, View{ (uintptr_t)d_out, out_pitch, out_fs }, n, ksize, taps, border);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_gaussian_blur_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  const size_t in_frame = (size_t)(c->H - 1) * in_pitch + row, out_frame = (size_t)(c->H - 1) * out_pitch + row;
+  const uintptr_t i0 = (uintptr_t)d_in, o0 = (uintptr_t)d_out;
+  if (int rc = finish_writers_of(c, i0, i0 + (size_t)(n - 1) * in_fs + in_frame)) return rc;
+  if (int rc = finish_writers_of(c, o0, o0 + (size_t)(n - 1) * out_fs + out_frame)) return rc;
+  HIPCK(launch_gauss8(P.bp, c->stream));
+  return HC_OK;
+}
 #else
-// the test library (round-1 front kernels) is built without stats.hip and edge_points.hip
+// the test library (round-1 front kernels) is built without stats.hip, edge_points.hip and blur.hip
+int hc_gaussian_blur_device(hc_ctx *, const void *, size_t, size_t, void *, size_t, size_t, int, int, const uint16_t *, int) { return fail(HC_E_ARG, "hc_gaussian_blur_device: not part of the test library"); }
 int hc_histogram_device(hc_ctx *, const void *, size_t, size_t, int, void *) { return fail(HC_E_ARG, "hc_histogram_device: not part of the test library"); }
 int hc_auto_thresholds_device(hc_ctx *, const void *, size_t, size_t, int, int, double, void *) { return fail(HC_E_ARG, "hc_auto_thresholds_device: not part of the test library"); }
 int hc_edge_points_device(hc_ctx *, const void *, size_t, size_t, int, void *, void *, size_t) { return fail(HC_E_ARG, "hc_edge_points_device: not part of the test library"); }
 #endif
+
+// host only: the rule is stated in include/hipcanny.h, the arithmetic is gaussian_taps_q8 (host_plan.h)
+int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps)
+{
+  if (!taps) return fail(HC_E_ARG, "hc_gaussian_taps_q8: null argument");
+  if (!blur_ksize_ok(ksize)) return fail(HC_E_ARG, "hc_gaussian_taps_q8: ksize 3, 5 or 7");
+  if (!gaussian_taps_q8(ksize, sigma, taps)) return fail(HC_E_ARG, "hc_gaussian_taps_q8: sigma must be finite and give taps of 0 .. 256");
+  return HC_OK;
+}
 
 int hc_hysteresis_device(hc_ctx *c, const void *d_thresh, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n)
 {

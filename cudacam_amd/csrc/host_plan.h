@@ -2,7 +2,7 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points).  No HIP, no hc_ctx: hipcanny.hip fills
+// plan_histogram, plan_edge_points, plan_gaussian_blur; the taps rule of hc_gaussian_taps_q8).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
 #include "../../include/hipcanny.h"
@@ -720,7 +720,7 @@ inline HystPlan plan_hyst(int RD, int H, int n, bool small_tiles, const HystOpts
 }
 
 // ---- the entries that are not runs ----------------------------------------------------------------
-// hc_derivatives_device, hc_histogram_device / hc_auto_thresholds_device, hc_edge_points_device: their kernel parameters from views
+// hc_derivatives_device, hc_histogram_device / hc_auto_thresholds_device, hc_edge_points_device, hc_gaussian_blur_device: their kernel parameters from views
 // that passed check_view, complete but for the context's scratch (HistParams::hist, EdgePointsParams::items).  error: HC_E_ARG
 // with this text, nothing may be allocated or launched.
 struct DerivPlan { const char *error = nullptr; DerivParams dp{}; };
@@ -738,6 +738,77 @@ inline DerivPlan plan_derivatives(int W, int H, int C, const View &in, const Vie
   const long long items = (long long)n * d.nstrips * d.nchunks;
   if (items > 0x7FFFFFF0ll) P.error = "too many work items (nframes x strips x row chunks)";
   else d.total_items = (int)items;
+  return P;
+}
+
+// hc_gaussian_taps_q8: the Q8 taps of a ksize Gaussian as include/hipcanny.h states the rule.  false: ksize not 3 / 5 / 7, a
+// sigma that is not finite, or taps that would break the contract of hc_gaussian_blur_device (nothing is written then)
+inline bool gaussian_taps_q8(int ksize, double sigma, uint16_t *taps)
+{
+  if (!blur_ksize_ok(ksize) || !std::isfinite(sigma) || !taps) return false;
+  static const uint16_t fixed[3][BLUR_MAX_TAPS] = { { 64, 128, 64 }, { 16, 64, 96, 64, 16 }, { 8, 28, 56, 72, 56, 28, 8 } };
+  const int R = ksize / 2;
+  if (sigma <= 0) {
+    for (int i = 0; i < ksize; ++i) taps[i] = fixed[R - 1][i];
+    return true;
+  }
+  double g[BLUR_MAX_TAPS], sum = 0;
+  const double den = 2.0 * sigma * sigma;  // (0 for a sigma below 1e-154 or so: the centre tap alone, with no 0 / 0)
+  for (int i = 0; i < ksize; ++i) { g[i] = i == R ? 1.0 : den > 0 ? std::exp(-(double)((i - R) * (i - R)) / den) : 0.0; sum += g[i]; }
+  long t[BLUR_MAX_TAPS], rest = 0;
+  double err = 0;
+  for (int i = 0; i < R; ++i) {  // from the outside inwards, the rounding error carried to the next tap
+    const double x = 256.0 * (g[i] / sum) + err, v = std::nearbyint(x);
+    err = x - v;
+    t[i] = t[ksize - 1 - i] = (long)v;
+    rest += 2 * (long)v;
+  }
+  t[R] = 256 - rest;
+  for (int i = 0; i < ksize; ++i)
+    if (t[i] < 0 || t[i] > 256) return false;
+  for (int i = 0; i < ksize; ++i) taps[i] = (uint16_t)t[i];
+  return true;
+}
+
+static_assert(BLUR_REFLECT_101 == HC_BORDER_REFLECT_101 && BLUR_REPLICATE == HC_BORDER_REPLICATE, "canny_params.h names the header's borders");
+// hc_gaussian_blur_device: everything the entry refuses but nframes > max_batch (check_views), and k_gauss8's parameters.  The
+// views' byte ranges [p, p + (n - 1) fs + (H - 1) pitch + C W) must not overlap: the entry owns no scratch to stage through
+struct BlurPlan { const char *error = nullptr; BlurParams bp{}; };
+inline BlurPlan plan_gaussian_blur(int W, int H, int C, const View &in, const View &out, int n, int ksize, const uint16_t *taps, int border)
+{
+  BlurPlan P;
+  BlurParams &b = P.bp;
+  const size_t row = (size_t)C * W;
+  if (!in.p || !out.p || !taps) return P.error = "null argument", P;
+  if (!blur_ksize_ok(ksize)) return P.error = "ksize 3, 5 or 7", P;
+  if (border != BLUR_REFLECT_101 && border != BLUR_REPLICATE) return P.error = "border must be HC_BORDER_REFLECT_101 or HC_BORDER_REPLICATE", P;
+  unsigned sum = 0;
+  for (int i = 0; i < ksize; ++i) {
+    if (taps[i] > 256) return P.error = "a tap above 256 (Q8: 256 = 1.0)", P;
+    sum += taps[i];
+  }
+  if (sum != 256) return P.error = "the taps must sum to 256 (Q8: 256 = 1.0)", P;
+  if (n < 1) return P.error = "nframes out of range", P;
+  for (const View *v : { &in, &out })
+    if (const ViewFault f = check_view(*v, row, H, n, 1, true)) return P.error = VIEW_FAULT_TEXT[f], P;
+  uintptr_t end[2];
+  int k = 0;
+  for (const View *v : { &in, &out }) {
+    const size_t frame = (size_t)(H - 1) * v->pitch + row;  // (below 2^32 + a row)
+    if (n > 1 && v->fs > (UINTPTR_MAX - v->p - frame) / (size_t)(n - 1)) return P.error = "a view wraps the address space", P;
+    if (v->p > UINTPTR_MAX - frame) return P.error = "a view wraps the address space", P;
+    end[k++] = v->p + (size_t)(n - 1) * v->fs + frame;
+  }
+  if (in.p < end[1] && out.p < end[0]) return P.error = "the input and output views overlap (in-place operation is not supported: blur into another buffer)", P;
+  b.in = (const uint8_t *)in.p; b.in_pitch = in.pitch; b.in_frame_stride = in.fs;
+  b.out = (uint8_t *)out.p; b.out_pitch = out.pitch; b.out_frame_stride = out.fs;
+  b.W = W; b.H = H; b.nframes = n; b.channels = C; b.ksize = ksize; b.border = border;
+  b.in_aligned = aligned4(in.p, in.pitch, in.fs); b.out_aligned = aligned4(out.p, out.pitch, out.fs);
+  for (int i = 0; i < ksize; ++i) b.taps[i] = taps[i];
+  b.nstrips = blur_strips(W); b.nchunks = blur_chunks(H);
+  const long long items = (long long)n * b.nstrips * b.nchunks;
+  if (items > 0x7FFFFFF0ll) P.error = "too many work items (nframes x strips x row chunks)";
+  else b.total_items = (int)items;
   return P;
 }
 

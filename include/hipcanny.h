@@ -261,6 +261,50 @@ int hc_edge_points_device(hc_ctx *ctx, const void *d_map, size_t pitch, size_t f
                           void *d_points /* int32 [nframes][capacity][2] = (x, y); may be NULL when capacity == 0 */,
                           size_t capacity);
 
+/* cv::GaussianBlur(src, dst, Size(ksize, ksize), sigma) for CV_8U frames on the device -- the step almost every cv::Canny
+ * caller runs first, cv::Canny having no smoothing of its own (k_gauss8: cudacam_amd/csrc/blur.hip).  The semantics are stated
+ * here and restated in tests/gauss_blur_ref.py (numpy); like the rest of Mode O they are not pinned against a build of OpenCV.
+ * Taps: K = ksize is 3, 5 or 7; the same K taps serve x and y.  `taps` points to K uint16 values t[0 .. K-1] in HOST memory
+ * (read before the call returns), Q8 fixed point: 256 = 1.0, each tap <= 256, their sum exactly 256; symmetry is not required.
+ * Filter: a correlation -- tap i multiplies the pixel i - K/2 columns (rows) from the output pixel; the channels of 3-channel
+ * frames filter independently and stay interleaved.  Per pixel and channel:
+ *     h   = sum_i t[i] * src      along the row      (exact in 16 bits unsigned: at most 255 * 256 = 65280)
+ *     v   = sum_j t[j] * h        along the column   (exact in 32 bits: below 2^24)
+ *     out = (v + 32768) >> 16
+ * which is cv::GaussianBlur's fixed-point path for CV_8U: 8.8 coefficients, a 16.16 accumulator, rounding by adding one half.
+ * Constant frames come back unchanged.
+ * Border: HC_BORDER_REFLECT_101 (cv::GaussianBlur's default: gfedcb|abcdefgh|gfedcba) or HC_BORDER_REPLICATE (aaaaaa|abcdefgh|
+ * hhhhhhh), as cv::borderInterpolate defines them: an index outside the axis is clamped, or reflected about the edge pixels
+ * without repeating them until it lies inside; an axis of length 1 maps to index 0.  That is np.pad(mode="reflect") /
+ * np.pad(mode="edge"), axes shorter than the radius included.
+ * Contexts of either mode; width, height, channels and max_batch are the context's.  Both views are u8 rows of channels * width
+ * bytes with any alignment of base, pitch and frame stride (4-byte aligned ones get dword loads / stores); no byte outside
+ * [row, row + channels * width) of a row is read or written on either side, so both may be ROIs of larger images.  Rows are
+ * addressed with 32-bit offsets: height * pitch >= 2^32 on either side is HC_E_ARG.  The byte ranges of the two views must not
+ * overlap: in-place operation is refused, not staged (cv::GaussianBlur clones its source in that case; this entry owns no
+ * scratch) -- views that merely touch, one ending where the other begins, are fine.
+ * Asynchronous on the context stream (hc_set_stream honoured), in order with everything else queued there: a following
+ * hc_canny_device / hc_run_device that reads d_out needs no synchronisation in between.  It is not a run, exactly as
+ * hc_derivatives_device is none: hc_last_run_info, the stage timers, the hysteresis schedule / history and the pipeline slots
+ * stay as they were.  One addition, as for hc_edge_points_device: with HC_OPT_PIPELINE, a run still in flight whose output
+ * overlaps either view is completed first.
+ * HC_E_ARG: a null pointer; ksize not in {3, 5, 7}; a border outside the enum; a tap above 256 or a tap sum other than 256; a
+ * pitch < channels * width; nframes outside 1..max_batch; nframes > 1 with a frame stride smaller than height * pitch; height *
+ * pitch >= 2^32; overlapping views. */
+enum { HC_BORDER_REFLECT_101 = 0, HC_BORDER_REPLICATE = 1 };
+int hc_gaussian_blur_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
+                            size_t out_frame_stride, int nframes, int ksize, const uint16_t *taps /* host, ksize values */, int border);
+
+/* The Q8 taps of a Gaussian for the entry above, on the host (no context, no GPU): cv::getGaussianKernel followed by the 8.8
+ * conversion of cv::GaussianBlur's fixed-point path, restated; not pinned against a build of OpenCV.  With K = ksize (3, 5, 7):
+ *   sigma <= 0: OpenCV's small fixed kernels times 256: [64 128 64], [16 64 96 64 16], [8 28 56 72 56 28 8].
+ *   sigma > 0:  g[i] = exp(-(i - K/2)^2 / (2 sigma^2)) for i = 0 .. K-1 (the centre is 1; where 2 sigma^2 underflows to 0 the
+ *     others are 0), divided by their sum (added in that order), all in double.  From the outside inwards, i = 0 .. K/2 - 1, with err = 0 at the start: x = 256 g[i] + err, v = nearbyint(x)
+ *     (round half to even), err = x - v, t[i] = t[K-1-i] = v.  The centre tap is 256 minus the sum of the others.
+ * The result is symmetric and sums to 256.  HC_E_ARG: taps null; ksize not in {3, 5, 7}; a sigma that is not finite, or one
+ * whose taps would leave 0 .. 256. */
+int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
