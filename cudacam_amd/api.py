@@ -9,6 +9,7 @@ There is no CPU fallback: if the shared library or a GPU is missing, constructio
 """
 import ctypes as C
 import enum
+import math
 import os
 import sys
 
@@ -53,6 +54,8 @@ OPT_FRONT_WPB = 11
 OPT_FRONT_MX = 12
 OPT_APERTURE = 13   # mode O: cv::Canny's apertureSize, 3 (default) or 5
 OPT_TEST_HYST_LATE_GRID, OPT_TEST_HYST_LOOP, OPT_TEST_HYST_DIAG, OPT_TEST_HYST_GEOM, OPT_TEST_DENSE_ENTER, OPT_TEST_DENSE_LEAVE = 100, 101, 102, 103, 104, 105   # test / diagnostic hooks
+OPT_TEST_HOUGH_ROWS = 107      # angles per workgroup of k_hough_vote (measurements; 0: by the plan's rule)
+OPT_TEST_HOUGH_SCRATCH = 106   # bytes: the bound of hough_lines_device's scratch (tests: several passes on a small batch)
 TAP_BLUR, TAP_THRESH = 1, 2
 # front forms hc_last_run_info reports for canny_device at apertures 7 / -1 (the header's HC_FORM_O_APERTURE7 / HC_FORM_O_SCHARR)
 FORM_O_APERTURE7, FORM_O_SCHARR = 8, 9
@@ -71,7 +74,7 @@ ABI_SYMBOLS = [
     "hc_host_alloc", "hc_host_free", "hc_profile_get_front", "hc_debug_tap", "hc_use_own_stream", "hc_profile_get_intervals", "hc_last_run_info", "hc_pipeline_depth", "hc_pipeline_slots_in_use", "hc_front_waves_per_workgroup",
     "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
     "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
-    "hc_edge_points_device", "hc_gaussian_blur_device",
+    "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -135,6 +138,9 @@ def load_library(legacy=False):
     L.hc_edge_points_device.argtypes = [vp, vp, sz, sz, i, vp, vp, sz]
     L.hc_gaussian_blur_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, C.POINTER(C.c_uint16), i]
     L.hc_gaussian_taps_q8.argtypes = [i, C.c_double, C.POINTER(C.c_uint16)]
+    d, fp = C.c_double, C.POINTER(C.c_float)
+    L.hc_hough_lines_device.argtypes = [vp, vp, vp, sz, i, d, d, i, d, d, vp, vp, sz]
+    L.hc_hough_tables.argtypes = [i, i, d, d, d, d, C.POINTER(i), C.POINTER(i), fp, fp, fp, sz]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -219,6 +225,19 @@ def gaussian_taps_q8(ksize, sigma=0.0):
     if min(taps) < 0 or max(taps) > 256:
         raise HipCannyError("gaussian_taps_q8: sigma gives taps outside 0 .. 256")
     return taps
+
+
+def hough_tables(width, height, rho, theta, min_theta=0.0, max_theta=math.pi):
+    """Geometry and tables of hough_lines_device for width x height frames (hc_hough_tables: the host function the device entry
+    itself uses; no context, no GPU).  Returns (numangle, numrho, tab_cos, tab_sin, tab_theta), the tables float32 [numangle]."""
+    L = load_library()
+    na, nr = C.c_int(0), C.c_int(0)
+    args = (int(width), int(height), float(rho), float(theta), float(min_theta), float(max_theta))
+    _ck(L.hc_hough_tables(*args, C.byref(na), C.byref(nr), None, None, None, 0))
+    tabs = [np.empty(na.value, np.float32) for _ in range(3)]
+    fp = C.POINTER(C.c_float)
+    _ck(L.hc_hough_tables(*args, C.byref(na), C.byref(nr), *[t.ctypes.data_as(fp) for t in tabs], na.value))
+    return (na.value, nr.value, *tabs)
 
 
 class Context:
@@ -606,6 +625,81 @@ class Context:
         if self.hysteresis_info()[1]:   # the run was continued from the host (adversarial content): the maps changed after the lists were taken
             counts, lists = self._edge_points_of(out, n, capacity)
         return out.cpu().numpy(), counts, lists
+
+    def hough_lines_device(self, d_points, d_point_counts, point_capacity, nframes, rho, theta, threshold, min_theta, max_theta,
+                           d_line_counts, d_lines, line_capacity):
+        """cv::HoughLines' standard transform per frame on the device (hc_hough_lines_device, either mode), from what
+        edge_points_device wrote: d_points int32 [nframes][point_capacity][2], d_point_counts uint32 [nframes].  d_line_counts is
+        uint32 [nframes] (always the full number of peaks), d_lines float32 [nframes][line_capacity][3] = (rho, theta, votes),
+        the strongest min(count, line_capacity) of each frame in cv::HoughLines' order; line_capacity 0 (d_lines None / 0):
+        counts only.  Asynchronous on the context stream; not a run."""
+        _ck(self.lib.hc_hough_lines_device(self.handle, C.c_void_p(d_points), C.c_void_p(d_point_counts), int(point_capacity), int(nframes),
+                                           float(rho), float(theta), int(threshold), float(min_theta), float(max_theta),
+                                           C.c_void_p(d_line_counts), C.c_void_p(d_lines or None), int(line_capacity)))
+
+    def _hough_lines_of(self, d_maps, n, rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity):
+        """(counts, lines) of n tight maps on the device: edge points, then lines, chained on the context stream."""
+        import torch
+        dev, fs = d_maps.device, self.w * self.h
+        pcounts = torch.empty((n,), dtype=torch.int32, device=dev)
+        lcounts = torch.empty((n,), dtype=torch.int32, device=dev)
+        if point_capacity is None:   # the counts size the list buffer
+            torch.cuda.current_stream().synchronize()
+            self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, pcounts.data_ptr(), None, 0)
+            self.sync()
+            point_capacity = int(pcounts.cpu().numpy().view(np.uint32).max())
+        pcap = max(int(point_capacity), 1)
+        pts = torch.empty((n, pcap, 2), dtype=torch.int32, device=dev)
+        geo = (float(rho), float(theta), int(threshold), float(min_theta), float(max_theta))
+        torch.cuda.current_stream().synchronize()
+        self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, pcounts.data_ptr(), pts.data_ptr(), pcap)
+        if max_lines is None:        # likewise: a counts pass first
+            self.hough_lines_device(pts.data_ptr(), pcounts.data_ptr(), pcap, n, *geo, lcounts.data_ptr(), None, 0)
+            self.sync()
+            max_lines = int(lcounts.cpu().numpy().view(np.uint32).max())
+        cap = int(max_lines)
+        lines = torch.empty((n, max(cap, 1), 3), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream().synchronize()
+        self.hough_lines_device(pts.data_ptr(), pcounts.data_ptr(), pcap, n, *geo, lcounts.data_ptr(), lines.data_ptr() if cap else None, cap)
+        self.sync()
+        cnt = lcounts.cpu().numpy().view(np.uint32)
+        host = lines.cpu().numpy()
+        return cnt, [host[f, :min(int(cnt[f]), cap)].copy() for f in range(n)]
+
+    def hough_lines(self, maps, rho, theta, threshold, min_theta=0.0, max_theta=math.pi, max_lines=None, point_capacity=None):
+        """cv::HoughLines(map, lines, rho, theta, threshold, 0, 0, min_theta, max_theta) per map: host or torch u8 maps [n, H, W]
+        (or one map) in; (uint32 counts [n], [float32 (min(count_f, max_lines), 3) = (rho, theta, votes) per frame]) out --
+        edge_points_device then hough_lines_device on the device.  max_lines=None: a counts pass first, then a buffer sized by the
+        largest count; point_capacity=None likewise for the point lists (a smaller one cuts them: the lines are then those of
+        the cut lists)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(maps, torch.Tensor):
+            d = maps.to(device=dev, dtype=torch.uint8).contiguous()
+            if d.ndim == 2:
+                d = d[None]
+        else:
+            a = np.ascontiguousarray(maps, dtype=np.uint8)
+            d = torch.from_numpy(a[None] if a.ndim == 2 else a).to(dev)
+        if d.ndim != 3 or tuple(d.shape[1:]) != (self.h, self.w):
+            raise HipCannyError(f"hough_lines: maps {tuple(d.shape)} do not match the context's {(self.h, self.w)}")
+        return self._hough_lines_of(d, d.shape[0], rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity)
+
+    def canny_lines(self, frames, low, high, rho, theta, threshold, aperture=3, l2gradient=False, blur=None, min_theta=0.0, max_theta=math.pi,
+                    max_lines=None, point_capacity=None):
+        """cv::GaussianBlur (blur = (ksize, sigma), optional), cv::Canny, cv::findNonZero and cv::HoughLines chained on the device
+        (mode O), with no host copy of maps or point lists in between.  Returns (uint8 (n,H,W) edge maps, uint32 line counts,
+        lines as hough_lines gives them)."""
+        raw, n, row, fs = self._device_view(frames, "canny_lines")
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
+        self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        tail = (rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity)
+        counts, lines = self._hough_lines_of(out, n, *tail)
+        if self.hysteresis_info()[1]:   # the run was continued from the host (adversarial content): the maps changed after the lists were taken
+            counts, lines = self._hough_lines_of(out, n, *tail)
+        return out.cpu().numpy(), counts, lines
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

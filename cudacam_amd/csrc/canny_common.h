@@ -19,6 +19,9 @@ hipError_t launch_auto_thr(const u32 *hist, int nframes, int rule, double param,
 // edge_points.hip (the product library only): k_edge_count, k_edge_scan and, with p.capacity > 0, k_edge_emit
 hipError_t launch_edge_points(const EdgePointsParams &p, hipStream_t s);
 hipError_t launch_gauss8(const BlurParams &p, hipStream_t s);  // blur.hip (the product library only): separable Q8 smoothing filter, u8 -> u8
+// hough.hip (the product library only): one pass of k_hough_vote, k_hough_peaks (count), k_hough_scan, k_hough_peaks (emit) and,
+// with p.line_capacity > 0, k_hough_rank
+hipError_t launch_hough(const HoughParams &p, hipStream_t s);
 #endif
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);

@@ -193,6 +193,31 @@ struct EdgePointsParams {
   int chunk_rows, nchunks, total_items;  // hist_chunk_rows; ceil(H / chunk_rows); nframes * nchunks
 };
 
+// k_hough_vote / k_hough_peaks / k_hough_scan / k_hough_rank (hough.hip): cv::HoughLines' standard transform from the point
+// lists of k_edge_emit.  One block describes one pass: `nframes` frames whose accumulators, peak lists and per-row counts lie in
+// the context's scratch together (plan_hough_lines, host_plan.h, cuts a batch into passes and moves the frame pointers on).
+constexpr int HOUGH_LDS_BYTES = 160 * 1024;  // one workgroup's LDS on gfx950: the longest accumulator row k_hough_vote can hold
+constexpr int HOUGH_MAX_ROWS = 8;            // angles (accumulator rows) per workgroup of k_hough_vote, at most
+constexpr int HOUGH_VOTE_THREADS = 512;
+constexpr int HOUGH_RANK_THREADS = 256;      // peaks per workgroup of k_hough_rank, and per LDS tile of its comparison loop
+constexpr int HOUGH_CUS = 256;               // the plan keeps k_hough_vote's grid at this many workgroups where the batch allows it
+struct HoughParams {
+  const int32_t *points;     // [nframes][point_capacity][2] = (x, y), 8-byte aligned: what k_edge_emit wrote
+  const u32 *point_counts;   // [nframes]: frame f votes with its first min(count, point_capacity) points
+  size_t point_capacity;
+  const float *tab_cos, *tab_sin, *tab_theta;  // [numangle] each (hough_fill_tables), device memory of the context
+  int32_t *accum;            // scratch [nframes][numangle + 2][numrho + 2]: written whole by k_hough_vote
+  u32 *items;                // scratch [nframes][numangle]: peaks of each angle row (k_hough_peaks), then their offsets (k_hough_scan)
+  u32 *peaks;                // scratch [nframes][peak_cap][2] = (votes, accumulator index) in index order
+  u32 *line_counts;          // [nframes]: the full number of peaks of each frame
+  float *lines;              // [nframes][line_capacity][3] = (rho, theta, votes); unused when line_capacity == 0
+  size_t line_capacity, peak_cap;  // peak_cap = numangle * ceil(numrho / 2): no frame has more peaks
+  int numangle, numrho, nframes;
+  int rows, groups;          // angles per workgroup of k_hough_vote (1 .. HOUGH_MAX_ROWS, rows * (numrho + 2) * 4 <= HOUGH_LDS_BYTES); ceil(numangle / rows)
+  int threshold;             // a peak has more votes than this (>= 0)
+  float rho;                 // (float)rho of the call: a line's distance is (r - (numrho - 1) * 0.5f) * rho
+};
+
 struct HystParams {
   u32 *sbits;
   const u32 *cbits;

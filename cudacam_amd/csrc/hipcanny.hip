@@ -207,6 +207,14 @@ struct hc_ctx {
   int frame_thr_n = 0;
   u32 *d_hist = nullptr;  // hc_auto_thresholds_device: histograms [max_batch][256] between k_hist256 and k_auto_thr (lazy)
   u32 *d_edge_items = nullptr;  // hc_edge_points_device: per-work-item counts / offsets between its three kernels (lazy)
+  // hc_hough_lines_device (lazy): the scratch of one pass [peak lists | accumulators | per-row counts], grown when a call needs
+  // more; the tables [3][numangle] on the device and the four arguments they were made from (width and height are the context's)
+  void *d_hough = nullptr;
+  size_t hough_bytes = 0, hough_bound = HOUGH_SCRATCH_BYTES;  // (HC_OPT_TEST_HOUGH_SCRATCH)
+  int hough_rows = 0;  // HC_OPT_TEST_HOUGH_ROWS: angles per workgroup of k_hough_vote; 0: by the plan's rule
+  float *d_hough_tab = nullptr;
+  int hough_tab_cap = 0, hough_tab_n = 0;
+  double hough_tab_args[4] = { 0, 0, 0, 0 };
 };
 
 namespace {
@@ -818,7 +826,7 @@ void hc_destroy(hc_ctx *c)
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump, (void *)c->d_hist, (void *)c->d_edge_items }) (void)hipFree(q);
+  for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump, (void *)c->d_hist, (void *)c->d_edge_items, c->d_hough, (void *)c->d_hough_tab }) (void)hipFree(q);
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);
@@ -952,6 +960,10 @@ int hc_set_option(hc_ctx *c, int option, int value)
     c->opt.dense_enter = std::max(0, value);
   } else if (option == HC_OPT_TEST_DENSE_LEAVE) {
     c->opt.dense_leave = std::max(0, value);
+  } else if (option == HC_OPT_TEST_HOUGH_SCRATCH) {  // tests: a small bound cuts a small batch into several passes; <= 0: the default
+    c->hough_bound = value > 0 ? (size_t)value : HOUGH_SCRATCH_BYTES;
+  } else if (option == HC_OPT_TEST_HOUGH_ROWS) {  // measurements: the angles per workgroup of k_hough_vote (capped by LDS, HOUGH_MAX_ROWS and numangle); <= 0: by the rule
+    c->hough_rows = std::max(0, value);
   } else if (option == HC_OPT_FRONT_HALF) {
     if (value < -1 || value > 1) return fail(HC_E_ARG, "HC_OPT_FRONT_HALF: -1 (automatic), 0 (never) or 1 (whenever possible)");
     HIPCK(hipSetDevice(c->device));
@@ -1181,8 +1193,51 @@ int hc_gaussian_blur_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t
   HIPCK(launch_gauss8(P.bp, c->stream));
   return HC_OK;
 }
+
+// k_hough_vote, k_hough_peaks, k_hough_scan, k_hough_rank on the context stream (hough.hip), pass after pass.  Not a run, as
+// hc_histogram_device; no run writes a point list, so nothing is completed first.  Successive calls share the scratch and the
+// tables and are ordered by the stream they are queued on (include/hipcanny.h).
+int hc_hough_lines_device(hc_ctx *c, const void *d_points, const void *d_point_counts, size_t point_capacity, int n, double rho, double theta,
+                          int threshold, double min_theta, double max_theta, void *d_line_counts, void *d_lines, size_t line_capacity)
+{
+  if (!c) return fail(HC_E_ARG, "hc_hough_lines_device: null argument");
+  const HoughPlan P = plan_hough_lines(c->W, c->H, c->max_batch * (c->per_channel ? 3 : 1), (uintptr_t)d_points, (uintptr_t)d_point_counts, point_capacity, n, rho,
+                                       theta, threshold, min_theta, max_theta, (uintptr_t)d_line_counts, (uintptr_t)d_lines, line_capacity, c->hough_bound, c->hough_rows);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_hough_lines_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  // every refusal lies above.  New tables or a larger scratch: what is queued on the context stream may still read the old ones
+  const int na = P.hp.numangle;
+  const double args[4] = { rho, theta, min_theta, max_theta };
+  const bool new_tab = !c->d_hough_tab || c->hough_tab_n != na || std::memcmp(args, c->hough_tab_args, sizeof args) != 0;
+  if (new_tab || P.scratch_bytes > c->hough_bytes) HIPCK(hipStreamSynchronize(c->stream));
+  if (new_tab) {
+    std::vector<float> tab(3 * (size_t)na);
+    int a2 = 0, r2 = 0;
+    if (hough_tables(c->W, c->H, rho, theta, min_theta, max_theta, &a2, &r2, tab.data(), tab.data() + na, tab.data() + 2 * (size_t)na, (size_t)na) || a2 != na)
+      return fail(HC_E_STATE, "hc_hough_lines_device: the tables disagree with the plan");
+    if (na > c->hough_tab_cap) {
+      (void)hipFree(c->d_hough_tab);
+      c->d_hough_tab = nullptr; c->hough_tab_cap = 0; c->hough_tab_n = 0;
+      HIPCK(hipMalloc((void **)&c->d_hough_tab, sizeof(float) * 3 * (size_t)na));
+      c->hough_tab_cap = na;
+    }
+    c->hough_tab_n = 0;
+    HIPCK(hipMemcpy(c->d_hough_tab, tab.data(), sizeof(float) * 3 * (size_t)na, hipMemcpyHostToDevice));  // (complete when it returns)
+    c->hough_tab_n = na;
+    std::memcpy(c->hough_tab_args, args, sizeof args);
+  }
+  if (P.scratch_bytes > c->hough_bytes) {
+    (void)hipFree(c->d_hough);
+    c->d_hough = nullptr; c->hough_bytes = 0;
+    HIPCK(hipMalloc(&c->d_hough, P.scratch_bytes));
+    c->hough_bytes = P.scratch_bytes;
+  }
+  for (int k = 0; k < P.passes; ++k) HIPCK(launch_hough(hough_pass(P, k, (uintptr_t)c->d_hough, (uintptr_t)c->d_hough_tab), c->stream));
+  return HC_OK;
+}
 #else
-// the test library (round-1 front kernels) is built without stats.hip, edge_points.hip and blur.hip
+// the test library (round-1 front kernels) is built without stats.hip, edge_points.hip, blur.hip and hough.hip
+int hc_hough_lines_device(hc_ctx *, const void *, const void *, size_t, int, double, double, int, double, double, void *, void *, size_t) { return fail(HC_E_ARG, "hc_hough_lines_device: not part of the test library"); }
 int hc_gaussian_blur_device(hc_ctx *, const void *, size_t, size_t, void *, size_t, size_t, int, int, const uint16_t *, int) { return fail(HC_E_ARG, "hc_gaussian_blur_device: not part of the test library"); }
 int hc_histogram_device(hc_ctx *, const void *, size_t, size_t, int, void *) { return fail(HC_E_ARG, "hc_histogram_device: not part of the test library"); }
 int hc_auto_thresholds_device(hc_ctx *, const void *, size_t, size_t, int, int, double, void *) { return fail(HC_E_ARG, "hc_auto_thresholds_device: not part of the test library"); }
@@ -1195,6 +1250,15 @@ int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps)
   if (!taps) return fail(HC_E_ARG, "hc_gaussian_taps_q8: null argument");
   if (!blur_ksize_ok(ksize)) return fail(HC_E_ARG, "hc_gaussian_taps_q8: ksize 3, 5 or 7");
   if (!gaussian_taps_q8(ksize, sigma, taps)) return fail(HC_E_ARG, "hc_gaussian_taps_q8: sigma must be finite and give taps of 0 .. 256");
+  return HC_OK;
+}
+
+// host only: geometry and tables of hc_hough_lines_device by the rule include/hipcanny.h states (hough_tables, host_plan.h)
+int hc_hough_tables(int width, int height, double rho, double theta, double min_theta, double max_theta, int *numangle, int *numrho, float *tab_cos,
+                    float *tab_sin, float *tab_theta, size_t table_capacity)
+{
+  if (const char *e = hough_tables(width, height, rho, theta, min_theta, max_theta, numangle, numrho, tab_cos, tab_sin, tab_theta, table_capacity))
+    return fail(HC_E_ARG, std::string("hc_hough_tables: ") + e);
   return HC_OK;
 }
 

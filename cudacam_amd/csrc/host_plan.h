@@ -2,7 +2,8 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points, plan_gaussian_blur; the taps rule of hc_gaussian_taps_q8).  No HIP, no hc_ctx: hipcanny.hip fills
+// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines; the taps rule of hc_gaussian_taps_q8 and the table
+// rule of hc_hough_tables).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
 #include "../../include/hipcanny.h"
@@ -837,6 +838,148 @@ inline EdgePlan plan_edge_points(int W, int H, int C, int max_batch, const View 
   else if (items > 0x7FFFFFF0ll || P.table_items > 0x7FFFFFF0ull) P.error = "too many work items (nframes x row chunks)";
   else e.total_items = (int)items;
   return P;
+}
+
+// ---- hc_hough_lines_device / hc_hough_tables ------------------------------------------------------
+// The geometry of cv::HoughLines' accumulator as include/hipcanny.h states it.  nullptr and both numbers, or the refusal's text
+// and nothing written.  Every bound is tested on the doubles, before a conversion that could overflow.
+constexpr double HOUGH_PI = 3.1415926535897932384626433832795;
+inline const char *hough_geometry(int W, int H, double rho, double theta, double min_theta, double max_theta, int *numangle, int *numrho)
+{
+  if (W < 1 || H < 1) return "width and height must be positive";
+  if (!std::isfinite(rho) || !(rho > 0) || !std::isfinite(theta) || !(theta > 0)) return "rho and theta must be finite and positive";
+  if (!std::isfinite(min_theta) || !std::isfinite(max_theta) || max_theta < min_theta) return "min_theta and max_theta must be finite, min_theta <= max_theta";
+  const double na = std::floor((max_theta - min_theta) / theta) + 1.0;
+  const double nr = std::nearbyint((2.0 * ((double)W + (double)H) + 1.0) / rho);  // (half to even)
+  if (!(nr >= 0) || (nr + 2.0) * 4.0 > (double)HOUGH_LDS_BYTES) return "an accumulator row, (numrho + 2) * 4 bytes, does not fit one workgroup's LDS (160 KiB): rho is too small for the frame";
+  if (!(na >= 1) || !((na + 2.0) * (nr + 2.0) < 2147483648.0)) return "the accumulator, (numangle + 2) * (numrho + 2) cells, reaches 2^31 cells";
+  int a = (int)na;
+  if (a > 1 && std::fabs(HOUGH_PI - (double)(a - 1) * theta) < theta / 2) --a;
+  *numangle = a;
+  *numrho = (int)nr;
+  return nullptr;
+}
+
+// The tables: irho and the running angle are floats, the trigonometry is libm's in double (include/hipcanny.h)
+inline void hough_fill_tables(int numangle, double rho, double theta, double min_theta, float *tab_cos, float *tab_sin, float *tab_theta)
+{
+  const float irho = 1.0f / (float)rho;
+  float ang = (float)min_theta;
+  for (int n = 0; n < numangle; ++n) {
+    tab_cos[n] = (float)(std::cos((double)ang) * (double)irho);
+    tab_sin[n] = (float)(std::sin((double)ang) * (double)irho);
+    tab_theta[n] = ang;
+    ang += (float)theta;
+  }
+}
+
+// hc_hough_tables: geometry and, with all three tables given, the tables.  Refusals write nothing.
+inline const char *hough_tables(int W, int H, double rho, double theta, double min_theta, double max_theta, int *numangle, int *numrho, float *tab_cos,
+                                float *tab_sin, float *tab_theta, size_t table_capacity)
+{
+  if (!numangle || !numrho) return "numangle and numrho must not be null";
+  const bool tabs = tab_cos || tab_sin || tab_theta;
+  if (tabs && (!tab_cos || !tab_sin || !tab_theta)) return "the three tables are given together or not at all";
+  int a = 0, r = 0;
+  if (const char *e = hough_geometry(W, H, rho, theta, min_theta, max_theta, &a, &r)) return e;
+  if (tabs && table_capacity < (size_t)a) return "table_capacity is smaller than numangle";
+  *numangle = a;
+  *numrho = r;
+  if (tabs) hough_fill_tables(a, rho, theta, min_theta, tab_cos, tab_sin, tab_theta);
+  return nullptr;
+}
+
+constexpr size_t HOUGH_MAX_PASS_FRAMES = 65535;  // frames of a pass at most: a frame is a row of k_hough_rank's grid (gridDim.y)
+constexpr size_t HOUGH_SCRATCH_BYTES = (size_t)256 << 20;  // the context's bound by default (HC_OPT_TEST_HOUGH_SCRATCH sets another)
+// Angles per workgroup of k_hough_vote.  More rows load every point less often, but a workgroup's LDS decides how many of them
+// a CU holds, and the LDS atomics want waves to hide behind: measured at 1080p (24 KB rows, 30 frames, profiles/hough/README.md)
+// two rows -- three workgroups per CU -- are fastest on sparse and on dense lists, one and three rows 7 - 10 % behind, four to six
+// (two workgroups, then one) 25 - 50 % behind.  So: the rows that leave room for HOUGH_WGS_PER_CU workgroups, HOUGH_MAX_ROWS
+// at most (rows much shorter than 1080p's have not been measured), and fewer while the pass has fewer workgroups than the chip
+// has CUs.  hough_max_rows: what LDS, HOUGH_MAX_ROWS and numangle allow at all (HC_OPT_TEST_HOUGH_ROWS may force up to that).
+constexpr int HOUGH_WGS_PER_CU = 3;
+inline int hough_max_rows(int numangle, int numrho)
+{
+  const long long row = ((long long)numrho + 2) * 4;
+  return (int)std::min<long long>(std::min<long long>(HOUGH_MAX_ROWS, HOUGH_LDS_BYTES / row), numangle);
+}
+inline int hough_rows_per_group(int numangle, int numrho, int frames)
+{
+  const long long row = ((long long)numrho + 2) * 4;
+  int a = (int)std::min<long long>(hough_max_rows(numangle, numrho), std::max<long long>(1, HOUGH_LDS_BYTES / HOUGH_WGS_PER_CU / row));
+  while (a > 1 && (long long)frames * ((numangle + a - 1) / a) < HOUGH_CUS) --a;
+  return a;
+}
+
+// Everything hc_hough_lines_device refuses and decides, but for the context pointer.  hp describes the FIRST pass with the
+// scratch and table pointers null; hough_pass gives pass k with them patched in.  A refused plan holds nothing but its text.
+struct HoughPlan {
+  const char *error = nullptr;
+  HoughParams hp{};
+  int frames = 0, frames_per_pass = 0, passes = 0;
+  size_t frame_peaks_bytes = 0, frame_accum_bytes = 0, frame_items_bytes = 0;  // scratch per frame
+  size_t scratch_bytes = 0;   // frames_per_pass * the three: [peaks | accumulators | items]
+  long long total_work = 0;   // workgroups of k_hough_vote over all passes: frames x groups
+  unsigned vote_grid = 0, rows_grid = 0, scan_grid = 0, rank_grid_x = 0, rank_grid_y = 0;  // of a full pass (rank: 0 when line_capacity == 0 or no cell can be a peak)
+};
+inline HoughPlan plan_hough_lines(int W, int H, int max_frames, uintptr_t points, uintptr_t point_counts, size_t point_capacity, int n, double rho,
+                                  double theta, int threshold, double min_theta, double max_theta, uintptr_t line_counts, uintptr_t lines,
+                                  size_t line_capacity, size_t scratch_bound, int rows_forced = 0)
+{
+  HoughPlan P;
+  auto refuse = [](const char *text) { HoughPlan R; R.error = text; return R; };
+  if (!points || !point_counts || !line_counts) return refuse("null argument");
+  if (line_capacity && !lines) return refuse("d_lines is null with line_capacity > 0");
+  if (points & 7u) return refuse("d_points must be 8-byte aligned");
+  if ((point_counts | line_counts | lines) & 3u) return refuse("d_point_counts, d_line_counts and d_lines must be 4-byte aligned");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  if (threshold < 0) return refuse("threshold must not be negative");
+  int numangle = 0, numrho = 0;
+  if (const char *e = hough_geometry(W, H, rho, theta, min_theta, max_theta, &numangle, &numrho)) return refuse(e);
+  if (point_capacity > SIZE_MAX / 8 / (size_t)n) return refuse("point_capacity * 8 * nframes overflows size_t");
+  if (line_capacity > SIZE_MAX / 12 / (size_t)n) return refuse("line_capacity * 12 * nframes overflows size_t");
+  const size_t cells = (size_t)(numangle + 2) * (size_t)(numrho + 2), peak_cap = (size_t)numangle * (size_t)((numrho + 1) / 2);
+  P.frame_peaks_bytes = peak_cap * 8; P.frame_accum_bytes = cells * 4; P.frame_items_bytes = (size_t)numangle * 4;
+  const size_t per_frame = P.frame_peaks_bytes + P.frame_accum_bytes + P.frame_items_bytes;  // (below 2^31 * 8 + 2^33 + 2^33)
+  if (scratch_bound < per_frame) return refuse("one frame's accumulator and peak list exceed the context's scratch bound (256 MiB): a coarser rho or theta");
+  P.frames = n;
+  P.frames_per_pass = (int)std::min<size_t>(std::min<size_t>((size_t)n, scratch_bound / per_frame), HOUGH_MAX_PASS_FRAMES);
+  P.passes = (n + P.frames_per_pass - 1) / P.frames_per_pass;
+  P.scratch_bytes = (size_t)P.frames_per_pass * per_frame;
+  if ((long long)P.frames_per_pass * numangle > 0x7FFFFFF0ll) return refuse("too many work items (frames of a pass x numangle)");
+  HoughParams &h = P.hp;
+  h.points = (const int32_t *)points; h.point_counts = (const u32 *)point_counts; h.point_capacity = point_capacity;
+  h.line_counts = (u32 *)line_counts; h.lines = (float *)lines; h.line_capacity = line_capacity; h.peak_cap = peak_cap;
+  h.numangle = numangle; h.numrho = numrho; h.nframes = P.frames_per_pass; h.threshold = threshold; h.rho = (float)rho;
+  // rows_forced > 0 (HC_OPT_TEST_HOUGH_ROWS: measurements): that many rows where LDS, HOUGH_MAX_ROWS and numangle allow it
+  h.rows = rows_forced > 0 ? std::min(rows_forced, hough_max_rows(numangle, numrho)) : hough_rows_per_group(numangle, numrho, P.frames_per_pass);
+  h.groups = (numangle + h.rows - 1) / h.rows;
+  P.total_work = (long long)n * h.groups;
+  P.vote_grid = (unsigned)(P.frames_per_pass * h.groups);  // (at most frames x numangle)
+  P.rows_grid = (unsigned)(((long long)P.frames_per_pass * numangle + 3) / 4);
+  P.scan_grid = (unsigned)((P.frames_per_pass + 3) / 4);
+  if (line_capacity && peak_cap) { P.rank_grid_x = (unsigned)((peak_cap + HOUGH_RANK_THREADS - 1) / HOUGH_RANK_THREADS); P.rank_grid_y = (unsigned)P.frames_per_pass; }
+  return P;
+}
+
+// Pass k of a plan that was not refused (0 <= k < passes), on `scratch` (scratch_bytes, 8-byte aligned) and the context's tables
+// [3][numangle] = cos, sin, theta
+inline HoughParams hough_pass(const HoughPlan &P, int k, uintptr_t scratch, uintptr_t tables)
+{
+  HoughParams h = P.hp;
+  const int f0 = k * P.frames_per_pass;
+  h.nframes = std::min(P.frames_per_pass, P.frames - f0);
+  h.points += (size_t)f0 * h.point_capacity * 2;
+  h.point_counts += f0;
+  h.line_counts += f0;
+  if (h.lines) h.lines += (size_t)f0 * h.line_capacity * 3;
+  h.peaks = (u32 *)scratch;
+  h.accum = (int32_t *)(scratch + (size_t)P.frames_per_pass * P.frame_peaks_bytes);
+  h.items = (u32 *)(scratch + (size_t)P.frames_per_pass * (P.frame_peaks_bytes + P.frame_accum_bytes));
+  h.tab_cos = (const float *)tables;
+  h.tab_sin = h.tab_cos + h.numangle;
+  h.tab_theta = h.tab_sin + h.numangle;
+  return h;
 }
 
 }  // namespace hc

@@ -305,6 +305,69 @@ int hc_gaussian_blur_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size
  * whose taps would leave 0 .. 256. */
 int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps);
 
+/* cv::HoughLines(edges, lines, rho, theta, threshold, 0, 0, min_theta, max_theta) -- the standard transform, srn = stn = 0 -- on
+ * the device, fed by the point lists of hc_edge_points_device (k_hough_vote, k_hough_peaks, k_hough_scan, k_hough_rank:
+ * cudacam_amd/csrc/hough.hip).  One call returns per frame the number of lines and the strongest of them as (rho, theta, votes)
+ * in cv::HoughLines' order.  The semantics are stated here and restated in tests/hough_ref.py (numpy); like the rest of Mode O
+ * they are not pinned against a build of OpenCV.  Out of scope: cv::HoughLines' multi-scale form (srn / stn other than 0),
+ * cv::HoughLinesP and cv::HoughCircles.
+ * With W, H the context's frame size and rho, theta, min_theta, max_theta doubles:
+ * Geometry.  numangle = floor((max_theta - min_theta) / theta) + 1; if numangle > 1 and |pi - (numangle - 1) * theta| < theta / 2
+ *   it is one less.  numrho = rint((2 * (W + H) + 1) / rho), half to even.  (1920 x 1080, rho 1, theta pi / 180, [0, pi]: 180, 6001.)
+ * Tables.  irho = 1.0f / (float)rho; ang = (float)min_theta; for n = 0 .. numangle - 1: tab_cos[n] = (float)(cos((double)ang) *
+ *   (double)irho), tab_sin[n] likewise with sin, tab_theta[n] = ang, then ang += (float)theta in float.  cos / sin are libm's, on
+ *   the host (hc_hough_tables below is the function the device entry itself uses).
+ * Votes.  The accumulator is int32 [numangle + 2][numrho + 2], zero to begin with.  A point is (int32 x, int32 y).  For each n:
+ *   r = rint((float)x * tab_cos[n] + (float)y * tab_sin[n]) -- two float32 products, each rounded, and one float32 sum, no fused
+ *   multiply-add, rint half to even -- then r += (numrho - 1) / 2 (integer division) and accum[n + 1][r + 1] += 1.  A vote whose r
+ *   falls outside -1 .. numrho is dropped: no coordinate, whatever the caller passes, writes outside the accumulator.  For points
+ *   inside the frame no vote is dropped.
+ * Peaks.  Cell (n, r), 0 <= n < numangle, 0 <= r < numrho, with value a = accum[n + 1][r + 1] is a line iff a > threshold, a >
+ *   accum[n + 1][r] (left), a >= accum[n + 1][r + 2] (right), a > accum[n][r + 1] (up) and a >= accum[n + 2][r + 1] (down); the
+ *   padding cells take part as neighbours.
+ * Order.  Votes descending, ties by ascending accumulator index (n + 1) * (numrho + 2) + r + 1.  The keys are unique: the order
+ *   is total and a function of the input alone.
+ * Output.  d_line_counts[f] (uint32) is always the full number of peaks of frame f.  d_lines is float32 [nframes][line_capacity]
+ *   [3]: the slot of frame f receives its first min(count, line_capacity) lines in that order, each as ((r - (numrho - 1) * 0.5f) *
+ *   (float)rho, tab_theta[n], (float)votes) -- the memory of the CV_32FC3 matrix cv::HoughLines fills.  Nothing else is written.
+ *   line_capacity == 0 (d_lines null or not) gives the counts only.
+ * Input.  d_points (int32 [nframes][point_capacity][2], 8-byte aligned) and d_point_counts (uint32 [nframes]) are exactly what
+ *   hc_edge_points_device wrote: frame f votes with its first min(d_point_counts[f], point_capacity) points.  A list that was cut
+ *   by its capacity votes with what it holds -- the lines are then those of the cut list, not of the map.  Neither is written.
+ * Asynchronous on the context stream (hc_set_stream honoured), in order with everything else queued there: chained behind
+ * hc_canny_device and hc_edge_points_device it needs no synchronisation.  Contexts of either mode.  It is not a run, exactly as
+ * hc_edge_points_device is none (hc_last_run_info, the stage timers, the hysteresis schedule / history and the pipeline slots
+ * stay as they were), and since no run writes a point list, no run in flight is completed first.
+ * Scratch, owned by the context, allocated on first use and freed by hc_destroy: the tables on the device (made again, after a
+ * synchronisation of the context stream, only when rho, theta, min_theta or max_theta differ from the call before), and per
+ * frame of a pass the accumulator, the compacted peak list (at most ceil(numrho / 2) peaks per angle row, two horizontal
+ * neighbours never being both peaks) and a count per angle row.  The scratch is bounded at 256 MiB: a batch is cut into passes
+ * of as many frames as fit, 65535 at most (a 1080p accumulator is 4.4 MB) and is allocated again, after a synchronisation, when a call needs more
+ * than the calls before.  Successive calls on one context share scratch and tables and are ordered by the stream they are
+ * queued on: a caller who changes the stream between two calls (hc_set_stream, hc_use_own_stream) must order the two streams
+ * itself, or synchronise, as for hc_auto_thresholds_device.
+ * Cost.  Votes: points x numangle LDS atomics per frame; an accumulator row lives in one workgroup's LDS.  The ranking compares
+ * every peak of a frame with every other: quadratic in the peaks -- a few hundred at any threshold in use, a few 10^5 only at threshold 0
+ * on large noisy frames (measured on an MI355X: 0.4 ms per frame at 56 k peaks, profiles/hough/README.md; extrapolated by the
+ * square, not measured: about 10 ms at 3 x 10^5).  It is not launched when line_capacity == 0.
+ * HC_E_ARG: ctx, d_points, d_point_counts or d_line_counts null; d_lines null with line_capacity > 0; d_points not 8-byte,
+ * another pointer not 4-byte aligned; nframes outside 1..(max_batch, 3 * max_batch with HC_OPT_PER_CHANNEL); rho or theta <= 0
+ * or not finite; max_theta < min_theta or either not finite; threshold < 0; an accumulator row of (numrho + 2) * 4 bytes that
+ * does not fit one workgroup's LDS (160 KiB); (numangle + 2) * (numrho + 2) >= 2^31; one frame's scratch above the bound;
+ * point_capacity * 8 * nframes or line_capacity * 12 * nframes overflowing size_t. */
+int hc_hough_lines_device(hc_ctx *ctx, const void *d_points /* int32 [nframes][point_capacity][2] */,
+                          const void *d_point_counts /* uint32 [nframes] */, size_t point_capacity, int nframes, double rho, double theta,
+                          int threshold, double min_theta, double max_theta, void *d_line_counts /* uint32 [nframes] */,
+                          void *d_lines /* float32 [nframes][line_capacity][3]; may be NULL when line_capacity == 0 */, size_t line_capacity);
+
+/* Geometry and tables of the entry above, on the host (no context, no GPU), by the rule stated there.  *numangle and *numrho are
+ * always written on success.  The tables are given together or not at all (all three null: the geometry only); each receives
+ * numangle floats, and table_capacity, the floats each can hold, must be at least numangle.  HC_E_ARG, with nothing written:
+ * numangle or numrho null; only some tables given; width or height < 1; the rho / theta / min_theta / max_theta and accumulator
+ * refusals of hc_hough_lines_device; table_capacity < numangle. */
+int hc_hough_tables(int width, int height, double rho, double theta, double min_theta, double max_theta, int *numangle, int *numrho,
+                    float *tab_cos, float *tab_sin, float *tab_theta, size_t table_capacity);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
@@ -538,9 +601,11 @@ enum { HC_OPT_NMS_SATURATE = 1, HC_OPT_PIPELINE = 2, HC_OPT_PER_CHANNEL = 3, HC_
        HC_OPT_FRONT_DENSE = 8, HC_OPT_COPY_STREAMS = 9, HC_OPT_PIPELINE_SLOTS = 10, HC_OPT_FRONT_WPB = 11, HC_OPT_FRONT_MX = 12, HC_OPT_APERTURE = 13,
        /* test and diagnostic hooks (the library reads no environment variables): hysteresis launches >= 1 on a fixed grid with
         * worklists (-1: lists, default grid); the looping hysteresis launch of small runs off (0) / on; per-launch statistics for
-        * tools/hyst_diag.py; hysteresis workgroup shape (rows x 100 + waves, 0 = by the rule); k_front8's dense-path thresholds */
+        * tools/hyst_diag.py; hysteresis workgroup shape (rows x 100 + waves, 0 = by the rule); k_front8's dense-path thresholds;
+        * the bound, in bytes, of hc_hough_lines_device's scratch (<= 0: the default of 256 MiB), so that a small batch takes several passes;
+        * the angles per workgroup of k_hough_vote (measurements; capped by what LDS and numangle allow; <= 0: by the plan's rule) */
        HC_OPT_TEST_HYST_LATE_GRID = 100, HC_OPT_TEST_HYST_LOOP = 101, HC_OPT_TEST_HYST_DIAG = 102, HC_OPT_TEST_HYST_GEOM = 103,
-       HC_OPT_TEST_DENSE_ENTER = 104, HC_OPT_TEST_DENSE_LEAVE = 105 };
+       HC_OPT_TEST_DENSE_ENTER = 104, HC_OPT_TEST_DENSE_LEAVE = 105, HC_OPT_TEST_HOUGH_SCRATCH = 106, HC_OPT_TEST_HOUGH_ROWS = 107 };
 int hc_set_option(hc_ctx *ctx, int option, int value);
 
 /* The fast path's own intermediates of the last HC_STAGE_HYSTER run (HC_OPT_DEBUG_TAPS must have been set before it),
