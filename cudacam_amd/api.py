@@ -428,6 +428,38 @@ class Context:
         import torch
         torch.cuda.current_stream().synchronize()
 
+    def _maps_on_device(self, maps, who):
+        """Host or torch u8 maps [n, H, W] (or one map) as a contiguous u8 tensor [n, H, W] on the context's device."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(maps, torch.Tensor):
+            d = maps.to(device=dev, dtype=torch.uint8).contiguous()
+            if d.ndim == 2:
+                d = d[None]
+        else:
+            a = np.ascontiguousarray(maps, dtype=np.uint8)
+            d = torch.from_numpy(a[None] if a.ndim == 2 else a).to(dev)
+        if d.ndim != 3 or tuple(d.shape[1:]) != (self.h, self.w):
+            raise HipCannyError(f"{who}: maps {tuple(d.shape)} do not match the context's {(self.h, self.w)}")
+        return d
+
+    def _largest_count(self, counts):
+        """The largest of the uint32 counts a counts pass queued on the context stream writes into a device tensor: they size
+        the buffer of the pass that follows."""
+        self.sync()
+        return int(counts.cpu().numpy().view(np.uint32).max())
+
+    def _again_if_continued(self, fn):
+        """fn(), once more if the last run was continued from the host (adversarial content): its maps changed after fn read them."""
+        result = fn()
+        return fn() if self.hysteresis_info()[1] else result
+
+    @staticmethod
+    def _count_or_error(r):   # the getters that return a non-negative int or an error code
+        if r < 0:
+            _ck(r)
+        return r
+
     def derivatives(self, frames, ksize):
         """numpy u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, (dx, dy) numpy int16 of the same shape out, through device
         tensors (either mode)."""
@@ -584,11 +616,10 @@ class Context:
         fs = self.w * self.h
         if capacity is None:   # two passes: the counts size the list buffer
             self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, counts.data_ptr(), None, 0)
-            self.sync()
-            capacity = int(counts.cpu().numpy().view(np.uint32).max())
+            capacity = self._largest_count(counts)
         capacity = int(capacity)
         pts = torch.empty((n, max(capacity, 1), 2), dtype=torch.int32, device=d_maps.device)
-        torch.cuda.current_stream().synchronize()
+        self._wait_for_torch()
         self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, counts.data_ptr(), pts.data_ptr() if capacity else None, capacity)
         self.sync()
         cnt = counts.cpu().numpy().view(np.uint32)
@@ -598,18 +629,8 @@ class Context:
     def edge_points(self, maps, capacity=None):
         """Host or torch u8 maps [n, H, W] (or one map) in; (uint32 counts [n], [int32 array of shape (min(count_f, capacity), 2)
         = (x, y) per frame]) out.  capacity=None: two passes, counts first, then a list buffer sized by the largest count."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(maps, torch.Tensor):
-            d = maps.to(device=dev, dtype=torch.uint8).contiguous()
-            if d.ndim == 2:
-                d = d[None]
-        else:
-            a = np.ascontiguousarray(maps, dtype=np.uint8)
-            d = torch.from_numpy(a[None] if a.ndim == 2 else a).to(dev)
-        if d.ndim != 3 or tuple(d.shape[1:]) != (self.h, self.w):
-            raise HipCannyError(f"edge_points: maps {tuple(d.shape)} do not match the context's {(self.h, self.w)}")
-        torch.cuda.current_stream().synchronize()   # the context stream does not wait for torch's
+        d = self._maps_on_device(maps, "edge_points")
+        self._wait_for_torch()
         return self._edge_points_of(d, d.shape[0], capacity)
 
     def canny_points(self, frames, low, high, aperture=3, l2gradient=False, capacity=None, blur=None):
@@ -621,9 +642,7 @@ class Context:
         self._wait_for_torch()
         src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
         self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
-        counts, lists = self._edge_points_of(out, n, capacity)
-        if self.hysteresis_info()[1]:   # the run was continued from the host (adversarial content): the maps changed after the lists were taken
-            counts, lists = self._edge_points_of(out, n, capacity)
+        counts, lists = self._again_if_continued(lambda: self._edge_points_of(out, n, capacity))
         return out.cpu().numpy(), counts, lists
 
     def hough_lines_device(self, d_points, d_point_counts, point_capacity, nframes, rho, theta, threshold, min_theta, max_theta,
@@ -644,22 +663,20 @@ class Context:
         pcounts = torch.empty((n,), dtype=torch.int32, device=dev)
         lcounts = torch.empty((n,), dtype=torch.int32, device=dev)
         if point_capacity is None:   # the counts size the list buffer
-            torch.cuda.current_stream().synchronize()
+            self._wait_for_torch()
             self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, pcounts.data_ptr(), None, 0)
-            self.sync()
-            point_capacity = int(pcounts.cpu().numpy().view(np.uint32).max())
+            point_capacity = self._largest_count(pcounts)
         pcap = max(int(point_capacity), 1)
         pts = torch.empty((n, pcap, 2), dtype=torch.int32, device=dev)
         geo = (float(rho), float(theta), int(threshold), float(min_theta), float(max_theta))
-        torch.cuda.current_stream().synchronize()
+        self._wait_for_torch()
         self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, pcounts.data_ptr(), pts.data_ptr(), pcap)
         if max_lines is None:        # likewise: a counts pass first
             self.hough_lines_device(pts.data_ptr(), pcounts.data_ptr(), pcap, n, *geo, lcounts.data_ptr(), None, 0)
-            self.sync()
-            max_lines = int(lcounts.cpu().numpy().view(np.uint32).max())
+            max_lines = self._largest_count(lcounts)
         cap = int(max_lines)
         lines = torch.empty((n, max(cap, 1), 3), dtype=torch.float32, device=dev)
-        torch.cuda.current_stream().synchronize()
+        self._wait_for_torch()
         self.hough_lines_device(pts.data_ptr(), pcounts.data_ptr(), pcap, n, *geo, lcounts.data_ptr(), lines.data_ptr() if cap else None, cap)
         self.sync()
         cnt = lcounts.cpu().numpy().view(np.uint32)
@@ -672,17 +689,7 @@ class Context:
         edge_points_device then hough_lines_device on the device.  max_lines=None: a counts pass first, then a buffer sized by the
         largest count; point_capacity=None likewise for the point lists (a smaller one cuts them: the lines are then those of
         the cut lists)."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if isinstance(maps, torch.Tensor):
-            d = maps.to(device=dev, dtype=torch.uint8).contiguous()
-            if d.ndim == 2:
-                d = d[None]
-        else:
-            a = np.ascontiguousarray(maps, dtype=np.uint8)
-            d = torch.from_numpy(a[None] if a.ndim == 2 else a).to(dev)
-        if d.ndim != 3 or tuple(d.shape[1:]) != (self.h, self.w):
-            raise HipCannyError(f"hough_lines: maps {tuple(d.shape)} do not match the context's {(self.h, self.w)}")
+        d = self._maps_on_device(maps, "hough_lines")
         return self._hough_lines_of(d, d.shape[0], rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity)
 
     def canny_lines(self, frames, low, high, rho, theta, threshold, aperture=3, l2gradient=False, blur=None, min_theta=0.0, max_theta=math.pi,
@@ -696,9 +703,7 @@ class Context:
         src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
         self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
         tail = (rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity)
-        counts, lines = self._hough_lines_of(out, n, *tail)
-        if self.hysteresis_info()[1]:   # the run was continued from the host (adversarial content): the maps changed after the lists were taken
-            counts, lines = self._hough_lines_of(out, n, *tail)
+        counts, lines = self._again_if_continued(lambda: self._hough_lines_of(out, n, *tail))
         return out.cpu().numpy(), counts, lines
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
@@ -707,24 +712,15 @@ class Context:
 
     def front_waves_per_workgroup(self):
         """Waves per workgroup of the most recent k_front8 launch (hc_front_waves_per_workgroup): 4, 1 or 3."""
-        r = self.lib.hc_front_waves_per_workgroup(self.handle)
-        if r < 0:
-            _ck(r)
-        return r
+        return self._count_or_error(self.lib.hc_front_waves_per_workgroup(self.handle))
 
     def pipeline_slots_in_use(self):
         """Slots of the ring the most recent pipelined run used (hc_pipeline_slots_in_use)."""
-        r = self.lib.hc_pipeline_slots_in_use(self.handle)
-        if r < 0:
-            _ck(r)
-        return r
+        return self._count_or_error(self.lib.hc_pipeline_slots_in_use(self.handle))
 
     def pipeline_depth(self, nframes):
         """Runs of `nframes` frames kept in flight in pipelined mode (hc_pipeline_depth): the size of the output-buffer ring."""
-        r = self.lib.hc_pipeline_depth(self.handle, int(nframes))
-        if r < 0:
-            _ck(r)
-        return r
+        return self._count_or_error(self.lib.hc_pipeline_depth(self.handle, int(nframes)))
 
     def last_run_info(self):
         """(input_staged, output_staged, front_form) of the last run: see hc_last_run_info."""

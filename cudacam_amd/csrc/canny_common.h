@@ -13,7 +13,8 @@ hipError_t check_gauss_coeffs(const float gk[25]);
 hipError_t launch_front_o(const FrontParams &p, hipStream_t s);
 hipError_t launch_front_o_ext(const FrontExtParams &p, hipStream_t s);  // front_o_ext.hip
 hipError_t launch_deriv16(const DerivParams &p, hipStream_t s);  // deriv.hip: Sobel 3 / 5 / 7 and Scharr derivatives, u8 -> int16 dx / dy
-#ifndef HC_LEGACY_FRONT  // stats.hip (the product library only): frame histograms and the automatic thresholds of Mode O
+// stats.hip (the product library only, as the launchers down to launch_hough: the test library defines none of them): frame
+// histograms and the automatic thresholds of Mode O
 hipError_t launch_hist256(const HistParams &p, hipStream_t s);  // p.hist must be zero when the kernel starts
 hipError_t launch_auto_thr(const u32 *hist, int nframes, int rule, double param, int32_t *thr, hipStream_t s);  // hist [nframes][256] -> thr [nframes][2]
 // edge_points.hip (the product library only): k_edge_count, k_edge_scan and, with p.capacity > 0, k_edge_emit
@@ -22,7 +23,6 @@ hipError_t launch_gauss8(const BlurParams &p, hipStream_t s);  // blur.hip (the 
 // hough.hip (the product library only): one pass of k_hough_vote, k_hough_peaks (count), k_hough_scan, k_hough_peaks (emit) and,
 // with p.line_capacity > 0, k_hough_rank
 hipError_t launch_hough(const HoughParams &p, hipStream_t s);
-#endif
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

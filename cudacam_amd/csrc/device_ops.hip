@@ -1,0 +1,172 @@
+// device_ops.hip -- the entry points of libhipcanny.so that are not runs: one or a few kernels on the context stream, in order with
+// whatever is queued there.  They touch no slot, plan, timer or diagnostic of the runs (hipcanny.hip) -- except that a reader of
+// edge maps first completes the pipelined runs still writing them (finish_writers_of).  What each call does is decided in
+// host_plan.h; this file checks, allocates and launches.  Product library only: the test library (libhipcanny_legacy.so) is built
+// without this file and the kernel files behind it, and refuses these entries (legacy_front.hip).
+// A new entry of this kind goes here: view_end (host_plan.h) gives the byte range of a view, ensure_scratch its scratch.
+#include "hc_context.h"
+#include "auto_thr.h"
+
+using namespace hc;
+
+namespace {
+
+// At least `need` bytes in s: grows, never shrinks.  What is queued on the context stream may still read a buffer that is to be
+// replaced, so that stream is waited for first; a first allocation waits for nothing (it may synchronise the device by itself)
+int ensure_scratch(hc_ctx *c, DeviceScratch &s, size_t need)
+{
+  if (s.bytes >= need) return HC_OK;
+  HIPCK(hipSetDevice(c->device));
+  if (s.p) HIPCK(hipStreamSynchronize(c->stream));
+  (void)hipFree(s.p);
+  s = DeviceScratch{};
+  HIPCK(hipMalloc(&s.p, need));
+  s.bytes = need;
+  return HC_OK;
+}
+
+// k_hist256 on the context stream behind the zeroing of d_hist (the view has been checked)
+int queue_histogram(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, u32 *d_hist)
+{
+  HistParams hp = plan_histogram(c->W, c->H, c->C, View{ (uintptr_t)d_in, in_pitch, in_fs }, n);
+  hp.hist = d_hist;
+  HIPCK(hipMemsetAsync(d_hist, 0, sizeof(u32) * 256 * (size_t)n, c->stream));
+  HIPCK(launch_hist256(hp, c->stream));
+  return HC_OK;
+}
+
+// Pipelined runs still in flight that write into the n frames of view v (rows of row_bytes): each is completed, oldest first,
+// before the view is read or written -- its hysteresis runs on another stream than the caller, and should its queued launches not
+// have reached the fixpoint, its host-side continuation (finish_slot) rewrites whole maps.  As finish_overlapping, for a reader;
+// the caller's buffer a staged run copies its maps to counts as well.  Runs that write elsewhere stay in flight.  A byte range
+// that wraps the address space (view_end; no valid view) counts as written by every run.
+int finish_writers_of(hc_ctx *c, const View &v, size_t row_bytes, int n)
+{
+  uintptr_t m1 = 0;
+  const bool anywhere = !view_end(v, row_bytes, c->H, n, &m1);
+  for (int k = 0; k < c->nslot_use; ++k) {
+    Slot &o = c->slot[(c->cur + k) % c->nslot_use];
+    if (!o.pending || o.stream == c->stream) continue;  // (a plain run is ordered before the reader by the context stream)
+    bool hit = anywhere || (o.out0 < m1 && v.p < o.out1);
+    if (!hit && o.copy_dst && o.n > 0) {
+      uintptr_t d1 = 0;
+      hit = !view_end(View{ (uintptr_t)o.copy_dst, o.copy_pitch, o.copy_fs }, (size_t)c->W, c->H, o.n, &d1) || ((uintptr_t)o.copy_dst < m1 && v.p < d1);
+    }
+    if (hit)
+      if (int rc = finish_slot(c, o)) return rc;
+  }
+  return HC_OK;
+}
+
+// The tables [3][numangle] of hc_hough_lines_device on the device, made from `key` (hough_tables, host_plan.h).  What is queued on
+// the context stream may still read the old ones, whether or not the new ones fit their allocation.
+int upload_hough_tables(hc_ctx *c, const HoughTabKey &key)
+{
+  const size_t na = (size_t)key.numangle;
+  std::vector<float> tab(3 * na);
+  int a2 = 0, r2 = 0;
+  if (hough_tables(c->W, c->H, key.rho, key.theta, key.min_theta, key.max_theta, &a2, &r2, tab.data(), tab.data() + na, tab.data() + 2 * na, na) || a2 != key.numangle)
+    return fail(HC_E_STATE, "hc_hough_lines_device: the tables disagree with the plan");
+  HIPCK(hipStreamSynchronize(c->stream));
+  c->hough_key = HoughTabKey{};  // (nothing valid on the device until the copy is complete)
+  if (int rc = ensure_scratch(c, c->hough_tab, sizeof(float) * 3 * na)) return rc;
+  HIPCK(hipMemcpy(c->hough_tab.p, tab.data(), sizeof(float) * 3 * na, hipMemcpyHostToDevice));  // (complete when it returns)
+  c->hough_key = key;
+  return HC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Not a run (as hc_derivatives_device): the zeroing and one kernel on the context stream.
+int hc_histogram_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, void *d_hist)
+{
+  if (!c || !d_in || !d_hist) return fail(HC_E_ARG, "hc_histogram_device: null argument");
+  if ((uintptr_t)d_hist & 3u) return fail(HC_E_ARG, "hc_histogram_device: d_hist must be 4-byte aligned");
+  if (int rc = check_views(c, "hc_histogram_device", n, c->max_batch, { hist_view(c, d_in, in_pitch, in_fs) })) return rc;
+  HIPCK(hipSetDevice(c->device));
+  return queue_histogram(c, d_in, in_pitch, in_fs, n, (u32 *)d_hist);
+}
+
+// k_hist256 into the context's scratch table, then k_auto_thr: both on the context stream, so a table the following runs
+// read through hc_frame_thresholds_device needs no synchronisation.  Not a run either.  Successive calls share the scratch
+// table and are ordered by the stream they are queued on (hc_set_stream between two of them: include/hipcanny.h).
+int hc_auto_thresholds_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, int rule, double param, void *d_thr)
+{
+  if (!c || !d_in || !d_thr) return fail(HC_E_ARG, "hc_auto_thresholds_device: null argument");
+  if ((uintptr_t)d_thr & 3u) return fail(HC_E_ARG, "hc_auto_thresholds_device: d_thr must be 4-byte aligned");
+  if (rule != HC_AUTO_MEDIAN && rule != HC_AUTO_OTSU) return fail(HC_E_ARG, "hc_auto_thresholds_device: rule must be HC_AUTO_MEDIAN or HC_AUTO_OTSU");
+  if (!auto_param_ok(rule, param)) return fail(HC_E_ARG, "hc_auto_thresholds_device: param (sigma / ratio) must lie in [0, 1]");
+  if ((long long)c->W * c->H * c->C > AUTO_MAX_SAMPLES) return fail(HC_E_ARG, "hc_auto_thresholds_device: more than 2^27 samples per frame");
+  if (int rc = check_views(c, "hc_auto_thresholds_device", n, c->max_batch, { hist_view(c, d_in, in_pitch, in_fs) })) return rc;
+  HIPCK(hipSetDevice(c->device));
+  // every refusal lies above: the table is allocated (once; the first call may synchronise the device) only by a call that runs
+  if (int rc = ensure_scratch(c, c->hist256, sizeof(u32) * 256 * (size_t)c->max_batch)) return rc;
+  if (int rc = queue_histogram(c, d_in, in_pitch, in_fs, n, (u32 *)c->hist256.p)) return rc;
+  HIPCK(launch_auto_thr((const u32 *)c->hist256.p, n, rule, param, (int32_t *)d_thr, c->stream));
+  return HC_OK;
+}
+
+// k_edge_count, k_edge_scan, k_edge_emit on the context stream (edge_points.hip).  Not a run, as hc_histogram_device -- except
+// that a pipelined run in flight whose output the map overlaps is completed first (finish_writers_of).  Successive calls share
+// the table of per-item counts and are ordered by the stream they are queued on (include/hipcanny.h).
+int hc_edge_points_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs, int n, void *d_counts, void *d_points, size_t capacity)
+{
+  if (!c || !d_map || !d_counts) return fail(HC_E_ARG, "hc_edge_points_device: null argument");
+  if (capacity && !d_points) return fail(HC_E_ARG, "hc_edge_points_device: d_points is null with capacity > 0");
+  if ((uintptr_t)d_counts & 3u) return fail(HC_E_ARG, "hc_edge_points_device: d_counts must be 4-byte aligned");
+  if ((uintptr_t)d_points & 7u) return fail(HC_E_ARG, "hc_edge_points_device: d_points must be 8-byte aligned");
+  if (int rc = check_views(c, "hc_edge_points_device", n, c->max_batch * (c->per_channel ? 3 : 1), { { "d_map (pitch, fs)", d_map, pitch, fs, (size_t)c->W, 1, true } })) return rc;  // (n: at most the output frames of a max_batch run)
+  const View map{ (uintptr_t)d_map, pitch, fs };
+  EdgePlan P = plan_edge_points(c->W, c->H, c->C, c->max_batch, map, n, (uintptr_t)d_counts, (uintptr_t)d_points, capacity);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_edge_points_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  if (int rc = finish_writers_of(c, map, (size_t)c->W, n)) return rc;
+  // every refusal lies above: the table is allocated (once; the first call may synchronise the device) only by a call that runs
+  if (int rc = ensure_scratch(c, c->edge_items, sizeof(u32) * P.table_items)) return rc;
+  P.ep.items = (u32 *)c->edge_items.p;
+  HIPCK(launch_edge_points(P.ep, c->stream));
+  return HC_OK;
+}
+
+// k_gauss8 on the context stream (blur.hip).  Not a run, as hc_derivatives_device -- except that a pipelined run in flight whose
+// output overlaps either view is completed first (finish_writers_of, as hc_edge_points_device): a run's output is a natural
+// neighbour of both views, and its hysteresis runs on another stream.
+int hc_gaussian_blur_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n,
+                            int ksize, const uint16_t *taps, int border)
+{
+  if (!c || !d_in || !d_out || !taps) return fail(HC_E_ARG, "hc_gaussian_blur_device: null argument");
+  const size_t row = (size_t)c->C * c->W;
+  if (int rc = check_views(c, "hc_gaussian_blur_device", n, c->max_batch, { { "d_in (in_pitch, in_fs)", d_in, in_pitch, in_fs, row, 1, true }, { "d_out (out_pitch, out_fs)", d_out, out_pitch, out_fs, row, 1, true } })) return rc;
+  const View in{ (uintptr_t)d_in, in_pitch, in_fs }, out{ (uintptr_t)d_out, out_pitch, out_fs };
+  const BlurPlan P = plan_gaussian_blur(c->W, c->H, c->C, in, out, n, ksize, taps, border);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_gaussian_blur_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  if (int rc = finish_writers_of(c, in, row, n)) return rc;
+  if (int rc = finish_writers_of(c, out, row, n)) return rc;
+  HIPCK(launch_gauss8(P.bp, c->stream));
+  return HC_OK;
+}
+
+// k_hough_vote, k_hough_peaks, k_hough_scan, k_hough_rank on the context stream (hough.hip), pass after pass.  Not a run, as
+// hc_histogram_device; no run writes a point list, so nothing is completed first.  Successive calls share the scratch and the
+// tables and are ordered by the stream they are queued on (include/hipcanny.h).
+int hc_hough_lines_device(hc_ctx *c, const void *d_points, const void *d_point_counts, size_t point_capacity, int n, double rho, double theta,
+                          int threshold, double min_theta, double max_theta, void *d_line_counts, void *d_lines, size_t line_capacity)
+{
+  if (!c) return fail(HC_E_ARG, "hc_hough_lines_device: null argument");
+  const HoughPlan P = plan_hough_lines(c->W, c->H, c->max_batch * (c->per_channel ? 3 : 1), (uintptr_t)d_points, (uintptr_t)d_point_counts, point_capacity, n, rho,
+                                       theta, threshold, min_theta, max_theta, (uintptr_t)d_line_counts, (uintptr_t)d_lines, line_capacity, c->hough_bound, c->hough_rows);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_hough_lines_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  // every refusal lies above.  New tables or a larger scratch: what is queued on the context stream may still read the old ones
+  const HoughTabKey key{ P.hp.numangle, rho, theta, min_theta, max_theta };
+  if (!(c->hough_key == key))
+    if (int rc = upload_hough_tables(c, key)) return rc;
+  if (int rc = ensure_scratch(c, c->hough, P.scratch_bytes)) return rc;
+  for (int k = 0; k < P.passes; ++k) HIPCK(launch_hough(hough_pass(P, k, (uintptr_t)c->hough.p, (uintptr_t)c->hough_tab.p), c->stream));
+  return HC_OK;
+}
+
+}  // extern "C"

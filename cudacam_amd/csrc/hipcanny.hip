@@ -3,10 +3,7 @@
 // the stage switch of CannyEdge::run, the hysteresis launch loop and the output copy.
 // This file owns the context and queues the GPU work; what a run does is decided in host_plan.h (plan_front, plan_hyst).
 // There is no CPU fallback anywhere in this file: without a gfx950 device hc_create fails.
-#include "../../include/hipcanny.h"
-#include "canny_common.h"
-#include "host_plan.h"
-#include "auto_thr.h"
+#include "hc_context.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -18,206 +15,13 @@
 
 using namespace hc;
 
+thread_local std::string hc::g_err;  // (declared in hc_context.h: device_ops.hip and legacy_front.hip fail through it too)
+
 namespace {
 // the two copy streams all HC_OPT_COPY_STREAMS contexts of a device share (created on first use, kept for the process)
 constexpr int MAX_DEVICES = 64;
 hipStream_t g_h2d[MAX_DEVICES] = { nullptr }, g_d2h[MAX_DEVICES] = { nullptr };
 std::mutex g_copy_streams_mutex;  // contexts of different host threads may ask for them at the same time
-thread_local std::string g_err;
-int fail(int code, const std::string &msg)
-{
-  g_err = msg;
-  return code;
-}
-#define HIPCK(expr)                                                                                   \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) return fail(HC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));  \
-  } while (0)
-
-// Everything one in-flight fused run owns (how many slots a context uses: pipeline_slots, host_plan.h); the plain mode
-// only uses slot 0.
-struct Slot {
-  bool complete = false;                       // every allocation below succeeded (alloc_slot)
-  u32 *d_sbits = nullptr, *d_cbits = nullptr;  // bit planes [max_batch][H][RD]
-  u32 *d_wl_list = nullptr;  // hysteresis worklists (HystParams::wl_list)
-  size_t wl_cap = 0;         // tiles a run can have
-  u32 *d_flags = nullptr, *h_flags = nullptr;
-  hipEvent_t ev_front = nullptr, ev_done = nullptr;  // front kernel finished / hysteresis + expand finished
-  bool pending = false;                              // convergence flag not yet checked by the host
-  HystParams ph{};  // parameters of this run's hysteresis launches (lists, late_grid, iter, stats: set per launch from `plan`)
-  HystPlan plan;    // its schedule: what was queued, what a continuation repeats, what hc_last_hysteresis_schedule reports
-  void *copy_dst = nullptr;  // caller buffer when the expand went to the internal one
-  size_t copy_pitch = 0, copy_fs = 0;
-  int n = 0;
-  bool prov = false;             // this run's k_nms wrote the provisional output
-  hipStream_t stream = nullptr;  // stream the hysteresis of this run was queued on
-  hipStream_t s_hyst = nullptr;  // this slot's hysteresis stream (pipelined mode)
-  uintptr_t out0 = 0, out1 = 0;  // output range of this (pipelined, still pending) run: a later run into the same memory waits for it
-  unsigned long long seq = 0;    // number of the pipelined run that uses the slot (hc_ctx::run_seq)
-};
-
-// hipEvent ring of the profiled runs: up to EV_PER_RUN events per run.  Interval i = ev[i] -> ev[i + 1] covers the reference
-// stages in RunProf::mask[i] (one kernel may cover several: its time is divided equally among them, see hc_stage_time_ms)
-struct ProfRing {
-  static constexpr int EV_RUNS = 256;
-  static constexpr int EV_PER_RUN = 8;
-  enum { K_STAGE0 = 0, K_FRONT_A = 1, K_FRONT_B = 2, K_HYST = 3 };  // grey kernel / k_blur / k_nms, the fused front kernel or the tap kernels / hysteresis
-  struct RunProf { int nint = 0; bool after_gap = false; uint8_t mask[EV_PER_RUN - 1] = { 0 }; uint8_t kind[EV_PER_RUN - 1] = { 0 }; };
-  bool on = false;
-  bool gap = false;  // a run went untimed since the last timed one (ring full)
-  std::vector<hipEvent_t> evpool;
-  std::vector<RunProf> runprof;
-  int head = 0, count = 0;    // runs recorded since the last collect
-  hipEvent_t *ev = nullptr;   // the events of the run being queued (null: it goes untimed)
-  RunProf *rp = nullptr;
-  float stage_ms[6] = { 0, 0, 0, 0, 0, 0 };
-  unsigned stage_ran = 0;         // stages the last profiled run executed (bit per stage)
-  double sum[3] = { 0, 0, 0 };
-  double split_sum[2] = { 0, 0 };  // k_blur, k_nms (split front path only)
-  long split_runs = 0;
-  long runs = 0;
-  std::vector<float> step_ms;     // end-of-run to end-of-run intervals of consecutive profiled runs (steady-state step time)
-  std::vector<float> front_each;  // the front kernels' time of every profiled HYSTER run (hc_profile_get_front_each)
-  hipEvent_t prev_end = nullptr;  // last event of the previous profiled run (its ring slot is not reused before the next collect: at most EV_RUNS - 1 runs are in flight)
-
-  hipError_t begin_run(hipStream_t st)
-  {
-    ev = nullptr; rp = nullptr;
-    // ring full: this run goes untimed.  One slot stays free: `prev_end` still points at the last event of the run collected
-    // last, and a 256th queued run would record over it
-    if (!on || count >= EV_RUNS - 1) {
-      if (on) gap = true;  // the next timed run's step interval would span this one
-      return hipSuccess;
-    }
-    const size_t slot_i = (size_t)((head + count) % EV_RUNS);
-    ev = &evpool[slot_i * EV_PER_RUN];
-    rp = &runprof[slot_i];
-    *rp = RunProf{};
-    rp->after_gap = gap;
-    gap = false;
-    return hipEventRecord(ev[0], st);
-  }
-  // closes the interval that began at the previous event: it covered `mask` (bit per reference stage)
-  hipError_t mark(hipStream_t st, unsigned mask, int kind)
-  {
-    if (!rp || rp->nint >= EV_PER_RUN - 1) return hipSuccess;
-    rp->mask[rp->nint] = (uint8_t)mask;
-    rp->kind[rp->nint] = (uint8_t)kind;
-    rp->nint++;
-    return hipEventRecord(ev[rp->nint], st);
-  }
-  void end_run() { if (rp) count++; }
-  // the event intervals of every run recorded since the last collect (all of them complete: hc_sync)
-  int collect()
-  {
-    for (; count > 0; head = (head + 1) % EV_RUNS, count--) {
-      hipEvent_t *e = &evpool[(size_t)head * EV_PER_RUN];
-      const RunProf &r = runprof[(size_t)head];
-      for (float &m : stage_ms) m = 0;
-      stage_ran = 0;
-      bool has_a = false, has_h = false;
-      float front_t = 0;
-      for (int i = 0; i < r.nint; ++i) has_a = has_a || r.kind[i] == K_FRONT_A;
-      for (int i = 0; i < r.nint; ++i) has_h = has_h || r.kind[i] == K_HYST;
-      for (int i = 0; i < r.nint; ++i) {
-        float t = 0;
-        HIPCK(hipEventElapsedTime(&t, e[i], e[i + 1]));
-        if (r.kind[i] == K_FRONT_A || r.kind[i] == K_FRONT_B) front_t += t;
-        const unsigned mask = r.mask[i];
-        const int nst = __builtin_popcount(mask);
-        for (int st = 0; st < 6; ++st)
-          if (mask >> st & 1u) stage_ms[st] += t / (float)nst;
-        stage_ran |= mask;
-        const int k = r.kind[i];
-        sum[k == K_STAGE0 ? 0 : k == K_HYST ? 2 : 1] += t;
-        if (k == K_FRONT_A) split_sum[0] += t;
-        else if (k == K_FRONT_B && has_a) split_sum[1] += t;
-      }
-      if (has_a) split_runs++;
-      if (has_h && front_each.size() < 65536) front_each.push_back(front_t);
-      if (r.nint > 0) {
-        if (prev_end && !r.after_gap && step_ms.size() < 65536) {
-          float dt = 0;
-          if (hipEventElapsedTime(&dt, prev_end, e[r.nint]) == hipSuccess) step_ms.push_back(dt);
-        }
-        prev_end = e[r.nint];
-      }
-      runs++;
-    }
-    return HC_OK;
-  }
-};
-}  // namespace
-
-struct hc_ctx {
-  int device = 0, W = 0, H = 0, C = 1, max_batch = 1, mode = HC_MODE_R;
-  int RD = 0, nstrips = 0;
-  int per_channel = 0;  // 3-channel input: one edge map per channel (3 output frames per input frame)
-  FrontOpts opt;        // thresholds and the caller's choices for the front path
-  HystOpts hopt;        // hc_set_tuning, the HC_OPT_TEST_HYST_* hooks and (read ONCE at hc_create, never in the launch path) HC_HYST_DIAG / HC_HYST_GEOM
-  hipStream_t own_stream = nullptr, stream = nullptr;  // context stream (own, or the caller's)
-  // internal pitched frames
-  uint8_t *d_in = nullptr, *d_mono = nullptr, *d_out = nullptr;
-  size_t in_pitch = 0, in_fs = 0, mono_pitch = 0, mono_fs = 0, out_pitch = 0, out_fs = 0;
-  // stage-tap scratch (lazy)
-  uint8_t *d_blur = nullptr, *d_nms = nullptr;
-  int16_t *d_sx = nullptr, *d_sy = nullptr;
-  uint8_t *d_dump = nullptr;    // k_front8's dump areas (FrontParams::dump / dump_c / dump_p), followed by its page of zeros (FrontParams::zeros)
-  size_t dump_region = 0;       // 0: the plain layout (16 KiB + 32 KiB); otherwise four regions of this size (the HALF form's lane offsets reach a frame further)
-  uint8_t *d_bplane = nullptr;  // split mode: u8 blur plane between the two kernels (lazy)
-  size_t bplane_fs = 0, bplane_frames = 0;
-  // fused path
-  Slot slot[NSLOT];
-  int nslot_use = 2;  // slots the pipelined runs rotate through (4 for small batches)
-  int cur = 0;
-  bool pipeline = false;
-  unsigned long long run_seq = 0;
-  ChainWatch watch;   // two or three slots, one-wave or four-wave front workgroups: by the timestamps below (watch_chain)
-  struct { hipEvent_t f[8] = {}, d[8] = {}; unsigned long long seq[8] = {}; } ring;  // of the last pipelined runs, by run number & 7: front kernel finished / hysteresis finished
-  HystHistory hist;   // what the finished runs needed (plan_hyst)
-  ProfRing prof;
-  struct {  // hc_download_begin .. hc_download_end
-    uint8_t *host = nullptr; size_t row = 0, fs = 0; int n = 0;
-    bool stale = false;  // a host-side hysteresis continuation rewrote maps after hc_download_begin queued their copy (whichever entry point ran it)
-  } dl;
-  // HC_OPT_COPY_STREAMS: uploads / downloads on the device's shared copy streams, tied to the context stream by events
-  bool copy_streams = false;
-  hipEvent_t ev_up = nullptr, ev_ready = nullptr, ev_ready2 = nullptr, ev_down = nullptr;
-  struct {  // HC_OPT_DEBUG_TAPS: copies of the bit planes as the front kernels left them, and (fused kernel) a plain blur plane
-    u32 *s = nullptr, *c = nullptr;
-    uint8_t *blur = nullptr;
-    int frames = 0;  // output frames captured by the last run (0: nothing captured)
-    bool blur_split = false, blur_valid = false;
-  } dbg;
-  struct {  // diagnostics of the last run(s); decide nothing
-    int front_waves = 4;  // waves per workgroup of the most recent k_front8 launch
-    int in_staged = 0, out_staged = 0, front_form = HC_FORM_FRONT_O;  // what the last run did with the caller's buffers / which front kernels it used
-    int continued = 0;
-    int sched[HC_SCHED_WORDS] = { 0 };  // hc_last_hysteresis_schedule: the schedule of the last completed run
-    u32 stats[3 * MAX_HYST_LAUNCHES] = { 0 };
-    unsigned long long totals[4] = { 0, 0, 0, 0 };  // runs, continued runs, launches with work, launches queued
-    int run_n = 0;
-    int slot = 0;  // slot of the most recent fused run
-  } last;
-  int uploaded = 0;
-  // Mode O: the per-frame threshold table of the runs that follow (hc_frame_thresholds_device; caller-owned device memory,
-  // read by the front kernels only) and how many frames it holds; null: the context's pair
-  const int32_t *frame_thr = nullptr;
-  int frame_thr_n = 0;
-  u32 *d_hist = nullptr;  // hc_auto_thresholds_device: histograms [max_batch][256] between k_hist256 and k_auto_thr (lazy)
-  u32 *d_edge_items = nullptr;  // hc_edge_points_device: per-work-item counts / offsets between its three kernels (lazy)
-  // hc_hough_lines_device (lazy): the scratch of one pass [peak lists | accumulators | per-row counts], grown when a call needs
-  // more; the tables [3][numangle] on the device and the four arguments they were made from (width and height are the context's)
-  void *d_hough = nullptr;
-  size_t hough_bytes = 0, hough_bound = HOUGH_SCRATCH_BYTES;  // (HC_OPT_TEST_HOUGH_SCRATCH)
-  int hough_rows = 0;  // HC_OPT_TEST_HOUGH_ROWS: angles per workgroup of k_hough_vote; 0: by the plan's rule
-  float *d_hough_tab = nullptr;
-  int hough_tab_cap = 0, hough_tab_n = 0;
-  double hough_tab_args[4] = { 0, 0, 0, 0 };
-};
-
-namespace {
 
 // Internal frame buffers.  Rows of whole 16-byte groups are stored TIGHT (pitch = row bytes): a batch is then one contiguous
 // block, and hc_upload / hc_download move it with a single 1-D DMA instead of a strided 2-D copy per frame (16 frames of
@@ -382,10 +186,13 @@ void watch_chain(hc_ctx *c, const Slot &s)
   c->watch.update(i, c->nslot_use, front_ms, lead_ms);
 }
 
+}  // namespace
+
+// (namespace hc, declared in hc_context.h: device_ops.hip completes the writers of a map it is about to read through it)
 // Completes a queued fused run: waits for it, and if its queued hysteresis launches did not reach
 // the fixpoint (flag of the last one still set -- adversarial inputs only), keeps iterating, then
 // redoes the expand.
-int finish_slot(hc_ctx *c, Slot &s)
+int hc::finish_slot(hc_ctx *c, Slot &s)
 {
   if (!s.pending) return HC_OK;
   s.pending = false;
@@ -449,6 +256,8 @@ int finish_slot(hc_ctx *c, Slot &s)
   HIPCK(hipStreamSynchronize(st));
   return HC_OK;
 }
+
+namespace {
 
 int finish_all(hc_ctx *c)
 {
@@ -728,27 +537,6 @@ int run_impl(hc_ctx *c, const uint8_t *in, size_t in_pitch, size_t in_fs, uint8_
   return HC_OK;
 }
 
-// A caller's view as an entry point names it, and what the entry demands of it (check_view, host_plan.h)
-struct ViewArg { const char *name; const void *p; size_t pitch, fs, row_bytes; unsigned align = 1; bool below_4g = false; };
-// Every refusal of a pitched batch view: nframes within 1 .. max_frames, then each view -> HC_E_ARG "<entry>: <view>: <rule>"
-int check_views(const hc_ctx *c, const char *entry, int n, int max_frames, std::initializer_list<ViewArg> views)
-{
-  const std::string who(entry);
-  if (n <= 0 || n > max_frames) return fail(HC_E_ARG, who + ": nframes out of range");
-  for (const ViewArg &a : views)
-    if (const ViewFault f = check_view(View{ (uintptr_t)a.p, a.pitch, a.fs }, a.row_bytes, c->H, n, a.align, a.below_4g))
-      return fail(HC_E_ARG, who + ": " + a.name + ": " + VIEW_FAULT_TEXT[f]);
-  return HC_OK;
-}
-// the view hc_histogram_device and hc_auto_thresholds_device take: any alignment, below 4 GiB
-ViewArg hist_view(const hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs) { return { "d_in (in_pitch, in_fs)", d_in, in_pitch, in_fs, (size_t)c->C * c->W, 1, true }; }
-// host views (hc_upload, hc_download, hc_download_begin, hc_debug_tap): the rows only, as ever -- their frames may lie anywhere
-int check_host_rows(const char *entry, size_t row_stride, size_t row_bytes)
-{
-  if (const ViewFault f = check_view(View{ 0, row_stride, 0 }, row_bytes, 1, 1, 1, false)) return fail(HC_E_ARG, std::string(entry) + ": row_stride: " + VIEW_FAULT_TEXT[f]);
-  return HC_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -826,7 +614,8 @@ void hc_destroy(hc_ctx *c)
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump, (void *)c->d_hist, (void *)c->d_edge_items, c->d_hough, (void *)c->d_hough_tab }) (void)hipFree(q);
+  for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump }) (void)hipFree(q);
+  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab }) (void)hipFree(q->p);
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);
@@ -1087,162 +876,6 @@ int hc_derivatives_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t i
   HIPCK(launch_deriv16(P.dp, c->stream));
   return HC_OK;
 }
-
-#ifndef HC_LEGACY_FRONT
-namespace {
-// k_hist256 on the context stream behind the zeroing of d_hist (the view has been checked)
-int queue_histogram(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, u32 *d_hist)
-{
-  HistParams hp = plan_histogram(c->W, c->H, c->C, View{ (uintptr_t)d_in, in_pitch, in_fs }, n);
-  hp.hist = d_hist;
-  HIPCK(hipMemsetAsync(d_hist, 0, sizeof(u32) * 256 * (size_t)n, c->stream));
-  HIPCK(launch_hist256(hp, c->stream));
-  return HC_OK;
-}
-}  // namespace
-
-// Not a run (as hc_derivatives_device): the zeroing and one kernel on the context stream.
-int hc_histogram_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, void *d_hist)
-{
-  if (!c || !d_in || !d_hist) return fail(HC_E_ARG, "hc_histogram_device: null argument");
-  if ((uintptr_t)d_hist & 3u) return fail(HC_E_ARG, "hc_histogram_device: d_hist must be 4-byte aligned");
-  if (int rc = check_views(c, "hc_histogram_device", n, c->max_batch, { hist_view(c, d_in, in_pitch, in_fs) })) return rc;
-  HIPCK(hipSetDevice(c->device));
-  return queue_histogram(c, d_in, in_pitch, in_fs, n, (u32 *)d_hist);
-}
-
-// k_hist256 into the context's scratch table, then k_auto_thr: both on the context stream, so a table the following runs
-// read through hc_frame_thresholds_device needs no synchronisation.  Not a run either.  Successive calls share the scratch
-// table and are ordered by the stream they are queued on (hc_set_stream between two of them: include/hipcanny.h).
-int hc_auto_thresholds_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, int n, int rule, double param, void *d_thr)
-{
-  if (!c || !d_in || !d_thr) return fail(HC_E_ARG, "hc_auto_thresholds_device: null argument");
-  if ((uintptr_t)d_thr & 3u) return fail(HC_E_ARG, "hc_auto_thresholds_device: d_thr must be 4-byte aligned");
-  if (rule != HC_AUTO_MEDIAN && rule != HC_AUTO_OTSU) return fail(HC_E_ARG, "hc_auto_thresholds_device: rule must be HC_AUTO_MEDIAN or HC_AUTO_OTSU");
-  if (!auto_param_ok(rule, param)) return fail(HC_E_ARG, "hc_auto_thresholds_device: param (sigma / ratio) must lie in [0, 1]");
-  if ((long long)c->W * c->H * c->C > AUTO_MAX_SAMPLES) return fail(HC_E_ARG, "hc_auto_thresholds_device: more than 2^27 samples per frame");
-  if (int rc = check_views(c, "hc_auto_thresholds_device", n, c->max_batch, { hist_view(c, d_in, in_pitch, in_fs) })) return rc;
-  HIPCK(hipSetDevice(c->device));
-  // every refusal lies above: the table is allocated (once; the first call may synchronise the device) only by a call that runs
-  if (!c->d_hist) HIPCK(hipMalloc((void **)&c->d_hist, sizeof(u32) * 256 * (size_t)c->max_batch));
-  if (int rc = queue_histogram(c, d_in, in_pitch, in_fs, n, c->d_hist)) return rc;
-  HIPCK(launch_auto_thr(c->d_hist, n, rule, param, (int32_t *)d_thr, c->stream));
-  return HC_OK;
-}
-
-namespace {
-// Pipelined runs still in flight that write into [m0, m1): each is completed, oldest first, before the map is read -- its
-// hysteresis runs on another stream than the reader, and should its queued launches not have reached the fixpoint, its
-// host-side continuation (finish_slot) rewrites whole maps.  As finish_overlapping, for a reader; the caller's buffer a
-// staged run copies its maps to counts as well.  Runs that write elsewhere stay in flight.
-int finish_writers_of(hc_ctx *c, uintptr_t m0, uintptr_t m1)
-{
-  for (int k = 0; k < c->nslot_use; ++k) {
-    Slot &o = c->slot[(c->cur + k) % c->nslot_use];
-    if (!o.pending || o.stream == c->stream) continue;  // (a plain run is ordered before the reader by the context stream)
-    bool hit = o.out0 < m1 && m0 < o.out1;
-    if (o.copy_dst && o.n > 0) {
-      const uintptr_t d0 = (uintptr_t)o.copy_dst, d1 = d0 + (size_t)(o.n - 1) * o.copy_fs + (size_t)(c->H - 1) * o.copy_pitch + (size_t)c->W;
-      hit = hit || (d0 < m1 && m0 < d1);
-    }
-    if (hit)
-      if (int rc = finish_slot(c, o)) return rc;
-  }
-  return HC_OK;
-}
-}  // namespace
-
-// k_edge_count, k_edge_scan, k_edge_emit on the context stream (edge_points.hip).  Not a run, as hc_histogram_device -- except
-// that a pipelined run in flight whose output the map overlaps is completed first (finish_writers_of).  Successive calls share
-// the table of per-item counts and are ordered by the stream they are queued on (include/hipcanny.h).
-int hc_edge_points_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs, int n, void *d_counts, void *d_points, size_t capacity)
-{
-  if (!c || !d_map || !d_counts) return fail(HC_E_ARG, "hc_edge_points_device: null argument");
-  if (capacity && !d_points) return fail(HC_E_ARG, "hc_edge_points_device: d_points is null with capacity > 0");
-  if ((uintptr_t)d_counts & 3u) return fail(HC_E_ARG, "hc_edge_points_device: d_counts must be 4-byte aligned");
-  if ((uintptr_t)d_points & 7u) return fail(HC_E_ARG, "hc_edge_points_device: d_points must be 8-byte aligned");
-  if (int rc = check_views(c, "hc_edge_points_device", n, c->max_batch * (c->per_channel ? 3 : 1), { { "d_map (pitch, fs)", d_map, pitch, fs, (size_t)c->W, 1, true } })) return rc;  // (n: at most the output frames of a max_batch run)
-  EdgePlan P = plan_edge_points(c->W, c->H, c->C, c->max_batch, View{ (uintptr_t)d_map, pitch, fs }, n, (uintptr_t)d_counts, (uintptr_t)d_points, capacity);
-  if (P.error) return fail(HC_E_ARG, std::string("hc_edge_points_device: ") + P.error);
-  HIPCK(hipSetDevice(c->device));
-  const uintptr_t m0 = (uintptr_t)d_map;
-  if (int rc = finish_writers_of(c, m0, m0 + (size_t)(n - 1) * fs + (size_t)(c->H - 1) * pitch + (size_t)c->W)) return rc;
-  // every refusal lies above: the table is allocated (once; the first call may synchronise the device) only by a call that runs
-  if (!c->d_edge_items) HIPCK(hipMalloc((void **)&c->d_edge_items, sizeof(u32) * P.table_items));
-  P.ep.items = c->d_edge_items;
-  HIPCK(launch_edge_points(P.ep, c->stream));
-  return HC_OK;
-}
-
-// k_gauss8 on the context stream (blur.hip).  Not a run, as hc_derivatives_device -- except that a pipelined run in flight whose
-// output overlaps either view is completed first (finish_writers_of, as hc_edge_points_device): a run's output is a natural
-// neighbour of both views, and its hysteresis runs on another stream.
-int hc_gaussian_blur_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n,
-                            int ksize, const uint16_t *taps, int border)
-{
-  if (!c || !d_in || !d_out || !taps) return fail(HC_E_ARG, "hc_gaussian_blur_device: null argument");
-  const size_t row = (size_t)c->C * c->W;
-  if (int rc = check_views(c, "hc_gaussian_blur_device", n, c->max_batch, { { "d_in (in_pitch, in_fs)", d_in, in_pitch, in_fs, row, 1, true }, { "d_out (out_pitch, out_fs)", d_out, out_pitch, out_fs, row, 1, true } })) return rc;
-  const BlurPlan P = plan_gaussian_blur(c->W, c->H, c->C, View{ (uintptr_t)d_in, in_pitch, in_fs }, View{ (uintptr_t)d_out, out_pitch, out_fs }, n, ksize, taps, border);
-  if (P.error) return fail(HC_E_ARG, std::string("hc_gaussian_blur_device: ") + P.error);
-  HIPCK(hipSetDevice(c->device));
-  const size_t in_frame = (size_t)(c->H - 1) * in_pitch + row, out_frame = (size_t)(c->H - 1) * out_pitch + row;
-  const uintptr_t i0 = (uintptr_t)d_in, o0 = (uintptr_t)d_out;
-  if (int rc = finish_writers_of(c, i0, i0 + (size_t)(n - 1) * in_fs + in_frame)) return rc;
-  if (int rc = finish_writers_of(c, o0, o0 + (size_t)(n - 1) * out_fs + out_frame)) return rc;
-  HIPCK(launch_gauss8(P.bp, c->stream));
-  return HC_OK;
-}
-
-// k_hough_vote, k_hough_peaks, k_hough_scan, k_hough_rank on the context stream (hough.hip), pass after pass.  Not a run, as
-// hc_histogram_device; no run writes a point list, so nothing is completed first.  Successive calls share the scratch and the
-// tables and are ordered by the stream they are queued on (include/hipcanny.h).
-int hc_hough_lines_device(hc_ctx *c, const void *d_points, const void *d_point_counts, size_t point_capacity, int n, double rho, double theta,
-                          int threshold, double min_theta, double max_theta, void *d_line_counts, void *d_lines, size_t line_capacity)
-{
-  if (!c) return fail(HC_E_ARG, "hc_hough_lines_device: null argument");
-  const HoughPlan P = plan_hough_lines(c->W, c->H, c->max_batch * (c->per_channel ? 3 : 1), (uintptr_t)d_points, (uintptr_t)d_point_counts, point_capacity, n, rho,
-                                       theta, threshold, min_theta, max_theta, (uintptr_t)d_line_counts, (uintptr_t)d_lines, line_capacity, c->hough_bound, c->hough_rows);
-  if (P.error) return fail(HC_E_ARG, std::string("hc_hough_lines_device: ") + P.error);
-  HIPCK(hipSetDevice(c->device));
-  // every refusal lies above.  New tables or a larger scratch: what is queued on the context stream may still read the old ones
-  const int na = P.hp.numangle;
-  const double args[4] = { rho, theta, min_theta, max_theta };
-  const bool new_tab = !c->d_hough_tab || c->hough_tab_n != na || std::memcmp(args, c->hough_tab_args, sizeof args) != 0;
-  if (new_tab || P.scratch_bytes > c->hough_bytes) HIPCK(hipStreamSynchronize(c->stream));
-  if (new_tab) {
-    std::vector<float> tab(3 * (size_t)na);
-    int a2 = 0, r2 = 0;
-    if (hough_tables(c->W, c->H, rho, theta, min_theta, max_theta, &a2, &r2, tab.data(), tab.data() + na, tab.data() + 2 * (size_t)na, (size_t)na) || a2 != na)
-      return fail(HC_E_STATE, "hc_hough_lines_device: the tables disagree with the plan");
-    if (na > c->hough_tab_cap) {
-      (void)hipFree(c->d_hough_tab);
-      c->d_hough_tab = nullptr; c->hough_tab_cap = 0; c->hough_tab_n = 0;
-      HIPCK(hipMalloc((void **)&c->d_hough_tab, sizeof(float) * 3 * (size_t)na));
-      c->hough_tab_cap = na;
-    }
-    c->hough_tab_n = 0;
-    HIPCK(hipMemcpy(c->d_hough_tab, tab.data(), sizeof(float) * 3 * (size_t)na, hipMemcpyHostToDevice));  // (complete when it returns)
-    c->hough_tab_n = na;
-    std::memcpy(c->hough_tab_args, args, sizeof args);
-  }
-  if (P.scratch_bytes > c->hough_bytes) {
-    (void)hipFree(c->d_hough);
-    c->d_hough = nullptr; c->hough_bytes = 0;
-    HIPCK(hipMalloc(&c->d_hough, P.scratch_bytes));
-    c->hough_bytes = P.scratch_bytes;
-  }
-  for (int k = 0; k < P.passes; ++k) HIPCK(launch_hough(hough_pass(P, k, (uintptr_t)c->d_hough, (uintptr_t)c->d_hough_tab), c->stream));
-  return HC_OK;
-}
-#else
-// the test library (round-1 front kernels) is built without stats.hip, edge_points.hip, blur.hip and hough.hip
-int hc_hough_lines_device(hc_ctx *, const void *, const void *, size_t, int, double, double, int, double, double, void *, void *, size_t) { return fail(HC_E_ARG, "hc_hough_lines_device: not part of the test library"); }
-int hc_gaussian_blur_device(hc_ctx *, const void *, size_t, size_t, void *, size_t, size_t, int, int, const uint16_t *, int) { return fail(HC_E_ARG, "hc_gaussian_blur_device: not part of the test library"); }
-int hc_histogram_device(hc_ctx *, const void *, size_t, size_t, int, void *) { return fail(HC_E_ARG, "hc_histogram_device: not part of the test library"); }
-int hc_auto_thresholds_device(hc_ctx *, const void *, size_t, size_t, int, int, double, void *) { return fail(HC_E_ARG, "hc_auto_thresholds_device: not part of the test library"); }
-int hc_edge_points_device(hc_ctx *, const void *, size_t, size_t, int, void *, void *, size_t) { return fail(HC_E_ARG, "hc_edge_points_device: not part of the test library"); }
-#endif
 
 // host only: the rule is stated in include/hipcanny.h, the arithmetic is gaussian_taps_q8 (host_plan.h)
 int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps)

@@ -22,7 +22,7 @@ inline bool reaches_4g(int H, size_t pitch) { return pitch > 0xFFFFFFFFull / (si
 struct View { uintptr_t p; size_t pitch, fs; };  // a pitched batch of frames: address, bytes per row, bytes per frame
 enum ViewFault { VIEW_OK = 0, VIEW_PITCH, VIEW_STRIDE, VIEW_ALIGN, VIEW_4G };
 constexpr const char *VIEW_FAULT_TEXT[] = { "", "pitch smaller than a row", "frame stride below height * pitch", "address, pitch and frame stride must be multiples of the element size (int16 planes: even)", "views of 4 GiB and more (height * pitch >= 2^32) are not supported by this entry" };
-// What every device entry point asks of a view (hipcanny.hip: check_views), the first rule broken: the pitch holds a row; n > 1: the
+// What every device entry point asks of a view (hc_context.h: check_views), the first rule broken: the pitch holds a row; n > 1: the
 // frame stride holds a frame; address, pitch and frame stride are multiples of `align` (1, 2, 4); below_4g (kernels with 32-bit row
 // offsets): height * pitch < 2^32.  No product is formed, so none wraps: no huge pitch slips past the stride and 4 GiB tests.
 inline ViewFault check_view(const View &v, size_t row_bytes, int H, int n, unsigned align, bool below_4g)
@@ -31,6 +31,20 @@ inline ViewFault check_view(const View &v, size_t row_bytes, int H, int n, unsig
   if (n > 1 && v.fs / (size_t)H < v.pitch) return VIEW_STRIDE;
   if ((v.p | v.pitch | v.fs) & (align - 1)) return VIEW_ALIGN;
   return below_4g && reaches_4g(H, v.pitch) ? VIEW_4G : VIEW_OK;
+}
+// [v.p, *end): n frames of H rows of row_bytes.  false: the range wraps the address space (*end untouched)
+// The one statement of a view's byte range, p + (n - 1) fs + (H - 1) pitch + row_bytes (H, n >= 1).  As check_view, it forms no
+// product or sum before a division or subtraction has shown that it fits.
+inline bool view_end(const View &v, size_t row_bytes, int H, int n, uintptr_t *end)
+{
+  const size_t rows = (size_t)(H - 1), steps = (size_t)(n - 1);
+  if (rows && v.pitch > (UINTPTR_MAX - row_bytes) / rows) return false;
+  const size_t frame = rows * v.pitch + row_bytes;
+  if (steps && v.fs > (UINTPTR_MAX - frame) / steps) return false;
+  const size_t bytes = steps * v.fs + frame;
+  if (v.p > UINTPTR_MAX - bytes) return false;
+  *end = v.p + bytes;
+  return true;
 }
 
 constexpr int MAX_HYST_LAUNCHES = 96;  // (48 until a weak edge wobbling along a tile boundary needed 52: one launch per crossing)
@@ -793,13 +807,7 @@ inline BlurPlan plan_gaussian_blur(int W, int H, int C, const View &in, const Vi
   for (const View *v : { &in, &out })
     if (const ViewFault f = check_view(*v, row, H, n, 1, true)) return P.error = VIEW_FAULT_TEXT[f], P;
   uintptr_t end[2];
-  int k = 0;
-  for (const View *v : { &in, &out }) {
-    const size_t frame = (size_t)(H - 1) * v->pitch + row;  // (below 2^32 + a row)
-    if (n > 1 && v->fs > (UINTPTR_MAX - v->p - frame) / (size_t)(n - 1)) return P.error = "a view wraps the address space", P;
-    if (v->p > UINTPTR_MAX - frame) return P.error = "a view wraps the address space", P;
-    end[k++] = v->p + (size_t)(n - 1) * v->fs + frame;
-  }
+  if (!view_end(in, row, H, n, &end[0]) || !view_end(out, row, H, n, &end[1])) return P.error = "a view wraps the address space", P;
   if (in.p < end[1] && out.p < end[0]) return P.error = "the input and output views overlap (in-place operation is not supported: blur into another buffer)", P;
   b.in = (const uint8_t *)in.p; b.in_pitch = in.pitch; b.in_frame_stride = in.fs;
   b.out = (uint8_t *)out.p; b.out_pitch = out.pitch; b.out_frame_stride = out.fs;

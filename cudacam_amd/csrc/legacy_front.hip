@@ -5,6 +5,7 @@
 // the same arithmetic that the parity tests run every case through (tests/test_gpu_taps.py, tests/test_gpu_parity.py,
 // tests/fuzz_parity.py).
 #include "canny_device.h"
+#include "hc_context.h"  // (fail: the refusing entries at the end of the file)
 #include <algorithm>
 
 namespace hc {
@@ -993,5 +994,15 @@ hipError_t launch_nms(const FrontParams &p, hipStream_t s)
   return hipGetLastError();
 }
 
-
 }  // namespace hc
+
+using namespace hc;
+
+extern "C" {
+// the test library (round-1 front kernels) is built without stats.hip, edge_points.hip, blur.hip and hough.hip
+int hc_hough_lines_device(hc_ctx *, const void *, const void *, size_t, int, double, double, int, double, double, void *, void *, size_t) { return fail(HC_E_ARG, "hc_hough_lines_device: not part of the test library"); }
+int hc_gaussian_blur_device(hc_ctx *, const void *, size_t, size_t, void *, size_t, size_t, int, int, const uint16_t *, int) { return fail(HC_E_ARG, "hc_gaussian_blur_device: not part of the test library"); }
+int hc_histogram_device(hc_ctx *, const void *, size_t, size_t, int, void *) { return fail(HC_E_ARG, "hc_histogram_device: not part of the test library"); }
+int hc_auto_thresholds_device(hc_ctx *, const void *, size_t, size_t, int, int, double, void *) { return fail(HC_E_ARG, "hc_auto_thresholds_device: not part of the test library"); }
+int hc_edge_points_device(hc_ctx *, const void *, size_t, size_t, int, void *, void *, size_t) { return fail(HC_E_ARG, "hc_edge_points_device: not part of the test library"); }
+}  // extern "C"

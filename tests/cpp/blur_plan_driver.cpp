@@ -1,7 +1,8 @@
-// blur_plan_driver.cpp -- plan_gaussian_blur, border_index and gaussian_taps_q8 of cudacam_amd/csrc/host_plan.h /
+// blur_plan_driver.cpp -- plan_gaussian_blur, view_end, border_index and gaussian_taps_q8 of cudacam_amd/csrc/host_plan.h /
 // canny_params.h, checked without a GPU (tests/test_blur_plan_cpu.py builds this with g++ under ASan + UBSan): the item
 // counts at strip and chunk boundaries, the alignment flags, every refusal hc_gaussian_blur_device documents but nframes >
-// max_batch (check_views' own), overlapping and touching views, and the border map against its definition.
+// max_batch (check_views' own), overlapping and touching views, the byte range of a view up to the end of the address space and
+// past it, and the border map against its definition.
 // Prints "ok <checks>" or the first violations.
 #include "../../cudacam_amd/csrc/host_plan.h"
 
@@ -84,6 +85,72 @@ static void refusals()
   VCHECK(plan_gaussian_blur(8184, 1 << 19, 1, View{ 0x10000000u, 8184, (size_t)8184 << 19 }, View{ 0x100000000000ull, 8184, (size_t)8184 << 19 }, 1 << 20, 3, T3, 0).error, "too many work items");
 }
 
+// view_end: the byte range [p, p + (n - 1) fs + (H - 1) pitch + row) of a view, and `false` with *end untouched where it wraps
+static void view_ends()
+{
+  const uintptr_t M = UINTPTR_MAX, KEEP = 0x5A5A5A5Au;
+  auto ends = [&](const View &v, size_t row, int H, int n, uintptr_t want) { uintptr_t e = KEEP; return view_end(v, row, H, n, &e) && e == want; };
+  auto wraps = [&](const View &v, size_t row, int H, int n) { uintptr_t e = KEEP; return !view_end(v, row, H, n, &e) && e == KEEP; };
+  for (int H : { 1, 2, 33, 1080 })
+    for (int n : { 1, 2, 7 })
+      for (size_t row : { (size_t)1, (size_t)192, (size_t)5760 }) {
+        const uintptr_t p = 0x10000000u + 3;
+        VCHECK(ends(View{ p, row, row * H }, row, H, n, p + (size_t)n * H * row), "tight view %d x %zu x %d ends at p + n H row", H, row, n);
+        const size_t pitch = row + 61, fs = pitch * H + 1000;
+        VCHECK(ends(View{ p, pitch, fs }, row, H, n, p + (size_t)(n - 1) * fs + (size_t)(H - 1) * pitch + row), "padded, offset view %d x %zu x %d", H, row, n);
+        VCHECK(ends(View{ p, pitch, 0 }, row, H, 1, p + (size_t)(H - 1) * pitch + row) && ends(View{ p, pitch, M }, row, H, 1, p + (size_t)(H - 1) * pitch + row), "n = 1 ignores fs (%d x %zu)", H, row);
+        VCHECK(ends(View{ p, n > 1 ? 0 : pitch, fs }, row, 1, n, p + (size_t)(n - 1) * fs + row) && (n > 1 || ends(View{ p, M, fs }, row, 1, 1, p + row)), "H = 1 ignores the pitch (%zu x %d)", row, n);
+        // the largest view that does not wrap ends at UINTPTR_MAX; one byte more on p, on the pitch, on fs wraps
+        const size_t ext = (size_t)(n - 1) * fs + (size_t)(H - 1) * pitch + row;
+        const View top{ M - ext, pitch, fs };
+        VCHECK(ends(top, row, H, n, M), "the largest view %d x %zu x %d ends at UINTPTR_MAX", H, row, n);
+        VCHECK(wraps(View{ top.p + 1, pitch, fs }, row, H, n), "one byte more on p (%d x %zu x %d)", H, row, n);
+        // (a pitch one byte larger lengthens the range by H - 1 bytes: moved down by as many, the view fits again)
+        if (H > 1) VCHECK(wraps(View{ top.p, pitch + 1, fs }, row, H, n) && ends(View{ top.p - (size_t)(H - 1), pitch + 1, fs }, row, H, n, M), "one byte more on the pitch (%d x %zu x %d)", H, row, n);
+        if (n > 1) VCHECK(wraps(View{ top.p, pitch, fs + 1 }, row, H, n) && ends(View{ top.p - (size_t)(n - 1), pitch, fs + 1 }, row, H, n, M), "one byte more on fs (%d x %zu x %d)", H, row, n);
+      }
+  // at address 0 the whole space is one view: the largest pitch and the largest frame stride by division, one more wraps
+  for (int H : { 2, 3, 33, 1080 }) {
+    const size_t row = 7, pitch = (M - row) / (size_t)(H - 1);
+    VCHECK(ends(View{ 0, pitch, 0 }, row, H, 1, (size_t)(H - 1) * pitch + row) && wraps(View{ 0, pitch + 1, 0 }, row, H, 1), "the largest pitch of %d rows", H);
+    VCHECK(ends(View{ M - row - (size_t)(H - 1) * pitch, pitch, 0 }, row, H, 1, M) && wraps(View{ M - row - (size_t)(H - 1) * pitch + 1, pitch, 0 }, row, H, 1), "the largest pitch of %d rows, up to UINTPTR_MAX", H);
+  }
+  for (int n : { 2, 3, 7, 512 }) {
+    const size_t row = 64, pitch = 64, frame = 31 * pitch + row, fs = (M - frame) / (size_t)(n - 1);
+    VCHECK(ends(View{ 0, pitch, fs }, row, 32, n, (size_t)(n - 1) * fs + frame) && wraps(View{ 0, pitch, fs + 1 }, row, 32, n), "the largest frame stride of %d frames", n);
+    VCHECK(ends(View{ M - frame - (size_t)(n - 1) * fs, pitch, fs }, row, 32, n, M) && wraps(View{ M - frame - (size_t)(n - 1) * fs + 1, pitch, fs }, row, 32, n), "the largest frame stride of %d frames, up to UINTPTR_MAX", n);
+  }
+  // pitches and strides whose product with H - 1 / n - 1 wraps 64 bits, some of them to a small number
+  const size_t HALF = (size_t)1 << 63, THIRD = M / 3 + 1;  // 2 HALF = 0 and 3 THIRD = 2 (mod 2^64)
+  VCHECK(wraps(View{ 0x1000, HALF, 0 }, 16, 3, 1) && wraps(View{ 0x1000, THIRD, 0 }, 16, 4, 1) && wraps(View{ 0x1000, M, 0 }, 16, 2, 1) && wraps(View{ 0x1000, M / 2 + 2, 0 }, 16, 3, 1), "pitches whose product with H - 1 wraps");
+  VCHECK(wraps(View{ 0x1000, 16, HALF }, 16, 2, 3) && wraps(View{ 0x1000, 16, THIRD }, 16, 2, 4) && wraps(View{ 0x1000, 16, M }, 16, 2, 2) && wraps(View{ 0x1000, 16, SIZE_MAX / 2 }, 16, 2, 3), "frame strides whose product with n - 1 wraps");
+  VCHECK(wraps(View{ 0x1000, HALF, HALF }, 16, 3, 3) && wraps(View{ M, 1, 1 }, 1, 1, 1) && ends(View{ M - 1, 1, 1 }, 1, 1, 1, M) && wraps(View{ 0, 16, 0 }, M, 2, 1) && ends(View{ 0, 0, 0 }, M, 1, 1, M), "both at once; the last byte; a row as long as the space");
+}
+
+// the overlap cases of refusals(), as (input, output, frames): "view_end of both views, then the interval test" gives the verdict
+// plan_gaussian_blur gives
+static void overlap_by_view_end()
+{
+  const int W = 64, H = 32, C = 3;
+  const size_t row = (size_t)W * C;
+  const View in{ 0x10000000u, row, row * H };
+  const size_t ext1 = (size_t)(H - 1) * row + row, ext2 = row * H + ext1;
+  const struct { View in, out; int n; bool overlap; } cases[] = {
+    { in, View{ in.p, row, row * H }, 1, true }, { in, View{ in.p + ext1 - 1, row, row * H }, 1, true }, { in, View{ in.p - ext1 + 1, row, row * H }, 1, true },
+    { in, View{ in.p + ext1, row, row * H }, 1, false }, { in, View{ in.p - ext1, row, row * H }, 1, false }, { in, View{ in.p + ext2 - 1, row, row * H }, 2, true },
+    { in, View{ in.p + ext2, row, row * H }, 2, false }, { in, View{ in.p + ext1, row, row * H }, 2, true }, { in, View{ 0x20000000u, row + 4, (row + 4) * H }, 2, false },
+    { View{ in.p, 4 * row, 4 * row * H }, View{ in.p + row, 4 * row, 4 * row * H }, 1, true }, { View{ in.p, 4 * row, 4 * row * H }, View{ in.p + row, 4 * row, 4 * row * H }, 2, true },
+  };
+  for (const auto &c : cases) {
+    const BlurPlan P = plan_gaussian_blur(W, H, C, c.in, c.out, c.n, 3, T3, 0);
+    uintptr_t e_in = 0, e_out = 0;
+    const bool whole = view_end(c.in, row, H, c.n, &e_in) && view_end(c.out, row, H, c.n, &e_out);
+    const bool by_ends = c.in.p < e_out && c.out.p < e_in;
+    VCHECK(whole && by_ends == c.overlap && (P.error != nullptr) == c.overlap && (!P.error || std::strstr(P.error, "overlap")), "overlap case out %#zx n %d: by view_end %d, plan \"%s\"", (size_t)c.out.p, c.n, (int)by_ends,
+           P.error ? P.error : "");
+  }
+}
+
 static int reflect_by_walking(int i, int n)  // the definition: walk outwards from the axis, turning at the edge pixels without repeating them
 {
   if (n == 1) return 0;
@@ -127,6 +194,8 @@ int main()
 {
   counts_and_flags();
   refusals();
+  view_ends();
+  overlap_by_view_end();
   borders();
   taps();
   if (g_fail) { std::printf("%ld violations in %ld checks\n", g_fail, g_checks); return 1; }

@@ -469,7 +469,7 @@ static void chain_watch()
 #define VCHECK(cond, ...) do { if (!(cond) && ++g_fail <= 20) { std::printf("FAIL line %d: ", __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
 struct ViewSpec { const char *entry; size_t row_bytes; unsigned align; bool below_4g; };
 
-// Each entry's view specification (hipcanny.hip) on frames of W x H x C: the tight view and a padded, offset one pass; each
+// Each entry's view specification (hipcanny.hip, device_ops.hip) on frames of W x H x C: the tight view and a padded, offset one pass; each
 // single defect is reported as its own rule -- the cases of test_gpu_derivatives.py::test_errors and of the `bad` table of
 // test_gpu_edge_points.py -- and no pitch gets past through a height * pitch that wrapped 64 bits.
 static void view_table(int W, int H, int C)

@@ -45,9 +45,9 @@ def _points(w, h, count, seed):
     return pts[keep]
 
 
-def _call(ctx, w, h, lists, geo, threshold, line_capacity, point_capacity=None, null_lines=False, what=""):
-    """One call on the point lists `lists` (int32 (k, 2) per frame); everything is compared with the restatement.  Returns
-    (counts, lines per frame)."""
+def _upload(lists, line_capacity, point_capacity=None):
+    """The buffers of one call on the point lists `lists` (int32 (k, 2) per frame): the lists and their counts on the device, the
+    counts between two guard words and the line slots between guards, pre-filled with the canary."""
     import torch
     n = len(lists)
     pcap = max(max(len(p) for p in lists), 1) if point_capacity is None else point_capacity
@@ -55,21 +55,30 @@ def _call(ctx, w, h, lists, geo, threshold, line_capacity, point_capacity=None, 
     for f, p in enumerate(lists):
         pts[f, :min(len(p), pcap)] = p[:pcap]
     pcounts = np.array([len(p) for p in lists], np.uint32)   # the full counts, as hc_edge_points_device reports them above the capacity
-    d_pts, d_pc = torch.from_numpy(pts).cuda(), torch.from_numpy(pcounts.view(np.int32)).cuda()
-    counts = torch.full((n + 2,), CANARY, dtype=torch.int32, device="cuda")
-    lines = torch.full((2 * GUARD + 3 * n * line_capacity,), CANARY, dtype=torch.int32, device="cuda")
-    torch.cuda.synchronize()
+    return dict(lists=lists, n=n, pcap=pcap, line_capacity=line_capacity, pts=pts, pcounts=pcounts,
+                d_pts=torch.from_numpy(pts).cuda(), d_pc=torch.from_numpy(pcounts.view(np.int32)).cuda(),
+                counts=torch.full((n + 2,), CANARY, dtype=torch.int32, device="cuda"),
+                lines=torch.full((2 * GUARD + 3 * n * line_capacity,), CANARY, dtype=torch.int32, device="cuda"))
+
+
+def _queue(ctx, b, geo, threshold, null_lines=False):
+    """The call itself, on uploaded buffers (torch's stream has been waited for); nothing is waited for afterwards."""
     rho, theta, lo, hi = geo
-    ctx.hough_lines_device(d_pts.data_ptr(), d_pc.data_ptr(), pcap, n, rho, theta, threshold, lo, hi, counts.data_ptr() + 4,
-                           None if null_lines else lines.data_ptr() + 4 * GUARD, line_capacity)
-    ctx.sync()
-    assert np.array_equal(d_pts.cpu().numpy(), pts) and np.array_equal(d_pc.cpu().numpy().view(np.uint32), pcounts), f"{what}: the point lists were written"
-    c = counts.cpu().numpy()
+    ctx.hough_lines_device(b["d_pts"].data_ptr(), b["d_pc"].data_ptr(), b["pcap"], b["n"], rho, theta, threshold, lo, hi, b["counts"].data_ptr() + 4,
+                           None if null_lines else b["lines"].data_ptr() + 4 * GUARD, b["line_capacity"])
+
+
+def _check(b, w, h, geo, threshold, what=""):
+    """What a call left behind (the context has been synchronised), compared with the restatement.  Returns (counts, lines per frame)."""
+    lists, n, pcap, line_capacity = b["lists"], b["n"], b["pcap"], b["line_capacity"]
+    rho, theta, lo, hi = geo
+    assert np.array_equal(b["d_pts"].cpu().numpy(), b["pts"]) and np.array_equal(b["d_pc"].cpu().numpy().view(np.uint32), b["pcounts"]), f"{what}: the point lists were written"
+    c = b["counts"].cpu().numpy()
     assert c[0] == CANARY and c[-1] == CANARY, f"{what}: a word beside d_line_counts was written"
     got_counts = c[1:-1].view(np.uint32)
     want_counts, want = R.hough_lines_batch([p[:pcap] for p in lists], w, h, rho, theta, threshold, lo, hi, line_capacity)
     assert got_counts.tolist() == want_counts.tolist(), f"{what}: counts {got_counts.tolist()} != {want_counts.tolist()}"
-    l = lines.cpu().numpy()
+    l = b["lines"].cpu().numpy()
     assert (l[:GUARD] == CANARY).all() and (l[len(l) - GUARD:] == CANARY).all(), f"{what}: the guard around d_lines was written"
     slots = l[GUARD:len(l) - GUARD].reshape(n, line_capacity, 3)
     for f in range(n):
@@ -82,6 +91,17 @@ def _call(ctx, w, h, lists, geo, threshold, line_capacity, point_capacity=None, 
                                  f"{[(int(i), slots[f, i].view(np.float32).tolist(), want[f][i].tolist()) for i in bad[:6]]}")
         assert (slots[f, k:] == CANARY).all(), f"{what}: frame {f}: the slot was written behind its {k} lines"
     return got_counts, want
+
+
+def _call(ctx, w, h, lists, geo, threshold, line_capacity, point_capacity=None, null_lines=False, what=""):
+    """One call on the point lists `lists` (int32 (k, 2) per frame); everything is compared with the restatement.  Returns
+    (counts, lines per frame)."""
+    import torch
+    b = _upload(lists, line_capacity, point_capacity)
+    torch.cuda.synchronize()
+    _queue(ctx, b, geo, threshold, null_lines)
+    ctx.sync()
+    return _check(b, w, h, geo, threshold, what)
 
 
 @pytest.mark.parametrize("size", SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
@@ -174,6 +194,28 @@ def test_several_passes_equal_one():
         ctx.set_option(api.OPT_TEST_HOUGH_SCRATCH, 0)   # the default again
         _call(ctx, w, h, lists, GEOS[1], 6, 30, what="other tables on the same context")
         _call(ctx, w, h, lists, GEOS[0], 6, 30, what="and back")
+
+
+def test_scratch_and_tables_replaced_with_calls_in_flight():
+    """Four calls on one context with no synchronisation between them: each finds the one before it still queued or running on the
+    context stream when it replaces what that call reads -- (b) a larger scratch than (a)'s, (c) other tables in the same
+    allocation, (d) more angles than the table allocation holds (and a larger scratch again).  Each writes into buffers of its
+    own, which are compared only after the one synchronisation at the end."""
+    import torch
+    w, h = 64, 48
+    lists = [_points(w, h, 300 + 100 * k, 50 + k) for k in range(4)]
+    steps = [("a: one frame", lists[:1], (1.0, PI / 180, 0.0, PI)), ("b: four frames, the scratch grows", lists, (1.0, PI / 180, 0.0, PI)),
+             ("c: 90 angles, new tables in the old allocation", lists, (1.0, PI / 90, 0.0, PI)), ("d: 360 angles, the tables are reallocated", lists, (1.0, PI / 360, 0.0, PI))]
+    assert R.geometry(w, h, 1.0, PI / 90)[0] < R.geometry(w, h, 1.0, PI / 180)[0] < R.geometry(w, h, 1.0, PI / 360)[0]
+    bufs = [_upload(ls, 30) for _, ls, _ in steps]
+    torch.cuda.synchronize()
+    with api.Context(w, h, 1, 4) as ctx:
+        for b, (_, _, geo) in zip(bufs, steps):
+            _queue(ctx, b, geo, 6)
+        ctx.sync()
+        for b, (what, _, geo) in zip(bufs, steps):
+            counts, _ = _check(b, w, h, geo, 6, what)
+            assert counts.min() > 0, what
 
 
 def test_1080p_three_lines_and_noise():
