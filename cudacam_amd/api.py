@@ -75,6 +75,7 @@ ABI_SYMBOLS = [
     "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
     "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
     "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
+    "hc_hough_segments_device", "hc_hough_walk_tables",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -141,6 +142,8 @@ def load_library(legacy=False):
     d, fp = C.c_double, C.POINTER(C.c_float)
     L.hc_hough_lines_device.argtypes = [vp, vp, vp, sz, i, d, d, i, d, d, vp, vp, sz]
     L.hc_hough_tables.argtypes = [i, i, d, d, d, d, C.POINTER(i), C.POINTER(i), fp, fp, fp, sz]
+    L.hc_hough_segments_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, i, d, d, d, d, i, i, vp, vp, sz]
+    L.hc_hough_walk_tables.argtypes = [i, i, d, d, d, d, C.POINTER(i), C.POINTER(C.c_int32), fp, fp, sz]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -238,6 +241,19 @@ def hough_tables(width, height, rho, theta, min_theta=0.0, max_theta=math.pi):
     fp = C.POINTER(C.c_float)
     _ck(L.hc_hough_tables(*args, C.byref(na), C.byref(nr), *[t.ctypes.data_as(fp) for t in tabs], na.value))
     return (na.value, nr.value, *tabs)
+
+
+def hough_walk_tables(width, height, rho, theta, min_theta=0.0, max_theta=math.pi):
+    """The walk tables of hough_segments_device for width x height frames (hc_hough_walk_tables: the host function the device
+    entry itself uses; no context, no GPU).  Returns (numangle, major int32, slope float32, scale float32), [numangle] each."""
+    L = load_library()
+    na = C.c_int(0)
+    args = (int(width), int(height), float(rho), float(theta), float(min_theta), float(max_theta))
+    _ck(L.hc_hough_walk_tables(*args, C.byref(na), None, None, None, 0))
+    major, slope, scale = np.empty(na.value, np.int32), np.empty(na.value, np.float32), np.empty(na.value, np.float32)
+    fp = C.POINTER(C.c_float)
+    _ck(L.hc_hough_walk_tables(*args, C.byref(na), major.ctypes.data_as(C.POINTER(C.c_int32)), slope.ctypes.data_as(fp), scale.ctypes.data_as(fp), na.value))
+    return na.value, major, slope, scale
 
 
 class Context:
@@ -656,8 +672,9 @@ class Context:
                                            float(rho), float(theta), int(threshold), float(min_theta), float(max_theta),
                                            C.c_void_p(d_line_counts), C.c_void_p(d_lines or None), int(line_capacity)))
 
-    def _hough_lines_of(self, d_maps, n, rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity):
-        """(counts, lines) of n tight maps on the device: edge points, then lines, chained on the context stream."""
+    def _lines_on_device(self, d_maps, n, rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity):
+        """Edge points, then lines, of n tight maps on the device, chained on the context stream and not waited for: (uint32
+        line counts as an int32 tensor [n], float32 lines [n, max(capacity, 1), 3], capacity, the point lists)."""
         import torch
         dev, fs = d_maps.device, self.w * self.h
         pcounts = torch.empty((n,), dtype=torch.int32, device=dev)
@@ -678,6 +695,11 @@ class Context:
         lines = torch.empty((n, max(cap, 1), 3), dtype=torch.float32, device=dev)
         self._wait_for_torch()
         self.hough_lines_device(pts.data_ptr(), pcounts.data_ptr(), pcap, n, *geo, lcounts.data_ptr(), lines.data_ptr() if cap else None, cap)
+        return lcounts, lines, cap, (pts, pcounts)   # (the queued kernels read the lists: referenced until the caller has synchronised)
+
+    def _hough_lines_of(self, d_maps, n, rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity):
+        """(counts, lines) of n tight maps on the device: edge points, then lines, chained on the context stream."""
+        lcounts, lines, cap, _lists = self._lines_on_device(d_maps, n, rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity)
         self.sync()
         cnt = lcounts.cpu().numpy().view(np.uint32)
         host = lines.cpu().numpy()
@@ -705,6 +727,65 @@ class Context:
         tail = (rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity)
         counts, lines = self._again_if_continued(lambda: self._hough_lines_of(out, n, *tail))
         return out.cpu().numpy(), counts, lines
+
+    def hough_segments_device(self, d_map, pitch, fs, d_lines, d_line_counts, line_capacity, nframes, rho, theta, min_theta, max_theta,
+                              min_length, max_gap, d_seg_counts, d_segs, seg_capacity):
+        """Line segments per frame on the device (hc_hough_segments_device, either mode): the lines hough_lines_device wrote
+        (d_lines float32 [nframes][line_capacity][3], d_line_counts uint32 [nframes], made with the same rho, theta, min_theta,
+        max_theta) walked over the one-channel u8 maps d_map (any alignment) and cut by max_gap and min_length.  d_seg_counts is
+        uint32 [nframes] (always the full counts), d_segs int32 [nframes][seg_capacity][4] = (x0, y0, x1, y1) by line, then along
+        the line, the first min(count, seg_capacity) of each frame; seg_capacity 0 (d_segs None / 0): counts only.  Asynchronous
+        on the context stream; not a run, but a pipelined run in flight that writes the map is completed first."""
+        _ck(self.lib.hc_hough_segments_device(self.handle, C.c_void_p(d_map), pitch, fs, C.c_void_p(d_lines), C.c_void_p(d_line_counts),
+                                              int(line_capacity), int(nframes), float(rho), float(theta), float(min_theta), float(max_theta),
+                                              int(min_length), int(max_gap), C.c_void_p(d_seg_counts), C.c_void_p(d_segs or None), int(seg_capacity)))
+
+    def _hough_segments_of(self, d_maps, n, rho, theta, threshold, min_length, max_gap, min_theta, max_theta, max_lines, max_segments, point_capacity):
+        """(counts, segments) of n tight maps on the device: edge points, lines, then segments, chained on the context stream."""
+        import torch
+        lcounts, lines, lcap, _lists = self._lines_on_device(d_maps, n, rho, theta, threshold, min_theta, max_theta, max_lines, point_capacity)
+        scounts = torch.zeros((n,), dtype=torch.int32, device=d_maps.device)
+        segs = None
+        cap = 0
+        if lcap:   # (max_lines 0: no line is walked, no segment found)
+            walk = (d_maps.data_ptr(), self.w, self.w * self.h, lines.data_ptr(), lcounts.data_ptr(), lcap, n, float(rho), float(theta), float(min_theta),
+                    float(max_theta), int(min_length), int(max_gap), scounts.data_ptr())
+            self._wait_for_torch()
+            if max_segments is None:     # a counts pass first, as for the lines
+                self.hough_segments_device(*walk, None, 0)
+                max_segments = self._largest_count(scounts)
+            cap = int(max_segments)
+            segs = torch.empty((n, max(cap, 1), 4), dtype=torch.int32, device=d_maps.device)
+            self._wait_for_torch()
+            self.hough_segments_device(*walk, segs.data_ptr() if cap else None, cap)
+        self.sync()
+        cnt = scounts.cpu().numpy().view(np.uint32)
+        host = segs.cpu().numpy() if cap else np.empty((n, 0, 4), np.int32)
+        return cnt, [host[f, :min(int(cnt[f]), cap)].copy() for f in range(n)]
+
+    def hough_segments(self, maps, rho, theta, threshold, min_length, max_gap, min_theta=0.0, max_theta=math.pi, max_lines=None, max_segments=None,
+                       point_capacity=None):
+        """Line segments per map: host or torch u8 maps [n, H, W] (or one map) in; (uint32 counts [n], [int32 (min(count_f,
+        max_segments), 4) = (x0, y0, x1, y1) per frame]) out -- edge_points_device, hough_lines_device (rho, theta, threshold,
+        min_theta, max_theta) and hough_segments_device (min_length, max_gap) on the device.  max_segments=None: a counts pass
+        first, then a buffer sized by the largest count; max_lines and point_capacity likewise, as in hough_lines (smaller ones
+        cut the lists: the segments are then those of the cut lists)."""
+        d = self._maps_on_device(maps, "hough_segments")
+        return self._hough_segments_of(d, d.shape[0], rho, theta, threshold, min_length, max_gap, min_theta, max_theta, max_lines, max_segments, point_capacity)
+
+    def canny_segments(self, frames, low, high, rho, theta, threshold, min_length, max_gap, aperture=3, l2gradient=False, blur=None, min_theta=0.0,
+                       max_theta=math.pi, max_lines=None, max_segments=None, point_capacity=None):
+        """cv::GaussianBlur (blur = (ksize, sigma), optional), cv::Canny, cv::findNonZero, cv::HoughLines and the segment walk
+        chained on the device (mode O), with no host copy of maps, point lists or lines in between.  Returns (uint8 (n,H,W) edge
+        maps, uint32 segment counts, segments as hough_segments gives them)."""
+        raw, n, row, fs = self._device_view(frames, "canny_segments")
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
+        self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        tail = (rho, theta, threshold, min_length, max_gap, min_theta, max_theta, max_lines, max_segments, point_capacity)
+        counts, segs = self._again_if_continued(lambda: self._hough_segments_of(out, n, *tail))
+        return out.cpu().numpy(), counts, segs
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -218,6 +218,27 @@ struct HoughParams {
   float rho;                 // (float)rho of the call: a line's distance is (r - (numrho - 1) * 0.5f) * rho
 };
 
+// k_seg_count / k_seg_scan / k_seg_emit (hough_segments.hip): the lines of k_hough_rank walked over the edge maps and cut into
+// segments by a largest gap and a smallest length (cv::cuda::HoughSegmentDetector's form).  A work item is (frame, line slot)
+// and belongs to one wave; slots at or above min(line_counts[frame], line_capacity) do nothing.
+struct SegParams {
+  const uint8_t *map;        // u8 maps of W x H, one channel, any alignment of base, pitch and frame stride
+  size_t pitch, frame_stride;
+  const float *lines;        // [nframes][line_capacity][3] = (rho, theta, votes): what k_hough_rank wrote
+  const u32 *line_counts;    // [nframes]: frame f walks its first min(count, line_capacity) lines
+  size_t line_capacity;
+  const float *tab_theta;    // [numangle] (hough_fill_tables): a line's angle index is the first entry equal to its theta, bit for bit
+  const int32_t *tab_major;  // [numangle] (hough_walk_tables): 0: one sample per column, 1: one sample per row
+  const float *tab_slope, *tab_scale;  // [numangle]: sample m = rint(t * slope + line_rho * scale)
+  u32 *items;                // scratch [nframes][line_capacity]: kept segments of each line (k_seg_count), then their offsets (k_seg_scan)
+  u32 *seg_counts;           // [nframes]: the full number of kept segments of each frame
+  int32_t *segs;             // [nframes][seg_capacity][4] = (x0, y0, x1, y1), 16-byte aligned; unused when seg_capacity == 0
+  size_t seg_capacity;
+  int W, H, nframes, numangle;  // no byte outside [row, row + W) is read
+  int min_length, max_gap;   // both >= 0
+  int total_items;           // nframes * line_capacity
+};
+
 struct HystParams {
   u32 *sbits;
   const u32 *cbits;

@@ -75,6 +75,28 @@ int upload_hough_tables(hc_ctx *c, const HoughTabKey &key)
   return HC_OK;
 }
 
+// The tables [4][numangle] of hc_hough_segments_device (theta, major, slope, scale) on the device, made from `key`
+// (hough_walk_tables, host_plan.h): as upload_hough_tables
+int upload_seg_tables(hc_ctx *c, const HoughTabKey &key)
+{
+  const size_t na = (size_t)key.numangle;
+  std::vector<float> ftab(3 * na);  // theta, slope, scale
+  std::vector<int32_t> major(na);
+  int a2 = 0;
+  if (hough_walk_tables(c->W, c->H, key.rho, key.theta, key.min_theta, key.max_theta, &a2, major.data(), ftab.data() + na, ftab.data() + 2 * na, na, ftab.data())
+      || a2 != key.numangle)
+    return fail(HC_E_STATE, "hc_hough_segments_device: the tables disagree with the plan");
+  HIPCK(hipStreamSynchronize(c->stream));
+  c->seg_key = HoughTabKey{};  // (nothing valid on the device until the copies are complete)
+  if (int rc = ensure_scratch(c, c->seg_tab, 16 * na)) return rc;
+  char *d = (char *)c->seg_tab.p;  // the order of seg_on_scratch (host_plan.h).  Each copy is complete when it returns
+  HIPCK(hipMemcpy(d, ftab.data(), 4 * na, hipMemcpyHostToDevice));
+  HIPCK(hipMemcpy(d + 4 * na, major.data(), 4 * na, hipMemcpyHostToDevice));
+  HIPCK(hipMemcpy(d + 8 * na, ftab.data() + na, 8 * na, hipMemcpyHostToDevice));
+  c->seg_key = key;
+  return HC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -166,6 +188,31 @@ int hc_hough_lines_device(hc_ctx *c, const void *d_points, const void *d_point_c
     if (int rc = upload_hough_tables(c, key)) return rc;
   if (int rc = ensure_scratch(c, c->hough, P.scratch_bytes)) return rc;
   for (int k = 0; k < P.passes; ++k) HIPCK(launch_hough(hough_pass(P, k, (uintptr_t)c->hough.p, (uintptr_t)c->hough_tab.p), c->stream));
+  return HC_OK;
+}
+
+// k_seg_count, k_seg_scan, k_seg_emit on the context stream (hough_segments.hip).  Not a run, as hc_edge_points_device, and like
+// it a reader of edge maps: a pipelined run in flight whose output the map overlaps is completed first (finish_writers_of).
+// Successive calls share the per-line counts and the walk tables and are ordered by the stream they are queued on.
+int hc_hough_segments_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs, const void *d_lines, const void *d_line_counts, size_t line_capacity, int n,
+                             double rho, double theta, double min_theta, double max_theta, int min_length, int max_gap, void *d_seg_counts, void *d_segs,
+                             size_t seg_capacity)
+{
+  if (!c || !d_map) return fail(HC_E_ARG, "hc_hough_segments_device: null argument");
+  const int max_frames = c->max_batch * (c->per_channel ? 3 : 1);  // (as hc_edge_points_device: the output frames of a max_batch run)
+  if (int rc = check_views(c, "hc_hough_segments_device", n, max_frames, { { "d_map (pitch, fs)", d_map, pitch, fs, (size_t)c->W, 1, true } })) return rc;
+  const View map{ (uintptr_t)d_map, pitch, fs };
+  const SegPlan P = plan_hough_segments(c->W, c->H, max_frames, map, (uintptr_t)d_lines, (uintptr_t)d_line_counts, line_capacity, n, rho, theta, min_theta, max_theta,
+                                        min_length, max_gap, (uintptr_t)d_seg_counts, (uintptr_t)d_segs, seg_capacity);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_hough_segments_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  if (int rc = finish_writers_of(c, map, (size_t)c->W, n)) return rc;
+  // every refusal lies above.  New tables or a larger table of counts: what is queued on the context stream may still read the old ones
+  const HoughTabKey key{ P.sp.numangle, rho, theta, min_theta, max_theta };
+  if (!(c->seg_key == key))
+    if (int rc = upload_seg_tables(c, key)) return rc;
+  if (int rc = ensure_scratch(c, c->seg_items, P.items_bytes)) return rc;
+  HIPCK(launch_hough_segments(seg_on_scratch(P, (uintptr_t)c->seg_items.p, (uintptr_t)c->seg_tab.p), c->stream));
   return HC_OK;
 }
 

@@ -212,6 +212,10 @@ struct hc_ctx {
   hc::HoughTabKey hough_key;
   size_t hough_bound = hc::HOUGH_SCRATCH_BYTES;  // (HC_OPT_TEST_HOUGH_SCRATCH)
   int hough_rows = 0;  // HC_OPT_TEST_HOUGH_ROWS: angles per workgroup of k_hough_vote; 0: by the plan's rule
+  // hc_hough_segments_device: kept segments / offsets per line slot [nframes][line_capacity]; its tables [4][numangle] (theta, major,
+  // slope, scale) on the device and the arguments they were made from
+  hc::DeviceScratch seg_items, seg_tab;
+  hc::HoughTabKey seg_key;
 };
 
 namespace hc {

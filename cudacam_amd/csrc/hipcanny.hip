@@ -615,7 +615,7 @@ void hc_destroy(hc_ctx *c)
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump }) (void)hipFree(q);
-  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab }) (void)hipFree(q->p);
+  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab, &c->seg_items, &c->seg_tab }) (void)hipFree(q->p);
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);
@@ -892,6 +892,15 @@ int hc_hough_tables(int width, int height, double rho, double theta, double min_
 {
   if (const char *e = hough_tables(width, height, rho, theta, min_theta, max_theta, numangle, numrho, tab_cos, tab_sin, tab_theta, table_capacity))
     return fail(HC_E_ARG, std::string("hc_hough_tables: ") + e);
+  return HC_OK;
+}
+
+// host only: the walk tables of hc_hough_segments_device by the rule include/hipcanny.h states (hough_walk_tables, host_plan.h)
+int hc_hough_walk_tables(int width, int height, double rho, double theta, double min_theta, double max_theta, int *numangle, int32_t *major, float *slope,
+                         float *scale, size_t table_capacity)
+{
+  if (const char *e = hough_walk_tables(width, height, rho, theta, min_theta, max_theta, numangle, major, slope, scale, table_capacity))
+    return fail(HC_E_ARG, std::string("hc_hough_walk_tables: ") + e);
   return HC_OK;
 }
 

@@ -2,8 +2,8 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines; the taps rule of hc_gaussian_taps_q8 and the table
-// rule of hc_hough_tables).  No HIP, no hc_ctx: hipcanny.hip fills
+// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments; the taps rule of
+// hc_gaussian_taps_q8 and the table rules of hc_hough_tables and hc_hough_walk_tables).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
 #include "../../include/hipcanny.h"
@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 namespace hc {
 
@@ -897,6 +898,37 @@ inline const char *hough_tables(int W, int H, double rho, double theta, double m
   return nullptr;
 }
 
+// hc_hough_walk_tables: how hc_hough_segments_device walks a line of angle tab_theta[n] (include/hipcanny.h): the axis with one
+// sample per step, and the sample m = rint(t * slope + line_rho * scale) on the other.  libm in double, as the tables above.
+inline void hough_fill_walk_tables(int numangle, const float *tab_theta, int32_t *major, float *slope, float *scale)
+{
+  for (int n = 0; n < numangle; ++n) {
+    const double a = (double)tab_theta[n], c = std::cos(a), s = std::sin(a);
+    if (std::fabs(s) >= std::fabs(c)) { major[n] = 0; slope[n] = (float)(-c / s); scale[n] = (float)(1.0 / s); }
+    else { major[n] = 1; slope[n] = (float)(-s / c); scale[n] = (float)(1.0 / c); }
+  }
+}
+
+// Geometry and, with all three tables given, the walk tables; tab_theta (optional, numangle floats as hc_hough_tables gives them:
+// the device entry uploads it beside the three) needs the tables too.  Refusals write nothing.
+inline const char *hough_walk_tables(int W, int H, double rho, double theta, double min_theta, double max_theta, int *numangle, int32_t *major, float *slope,
+                                     float *scale, size_t table_capacity, float *tab_theta = nullptr)
+{
+  if (!numangle) return "numangle must not be null";
+  const bool tabs = major || slope || scale;
+  if ((tabs || tab_theta) && (!major || !slope || !scale)) return "the three tables are given together or not at all";
+  int a = 0, r = 0;
+  if (const char *e = hough_geometry(W, H, rho, theta, min_theta, max_theta, &a, &r)) return e;
+  if (tabs && table_capacity < (size_t)a) return "table_capacity is smaller than numangle";
+  *numangle = a;
+  if (!tabs) return nullptr;
+  std::vector<float> tmp(3 * (size_t)a);  // the angles by the one rule that makes them (hough_fill_tables; cos and sin are not used)
+  float *th = tab_theta ? tab_theta : tmp.data() + 2 * (size_t)a;
+  hough_fill_tables(a, rho, theta, min_theta, tmp.data(), tmp.data() + a, th);
+  hough_fill_walk_tables(a, th, major, slope, scale);
+  return nullptr;
+}
+
 constexpr size_t HOUGH_MAX_PASS_FRAMES = 65535;  // frames of a pass at most: a frame is a row of k_hough_rank's grid (gridDim.y)
 constexpr size_t HOUGH_SCRATCH_BYTES = (size_t)256 << 20;  // the context's bound by default (HC_OPT_TEST_HOUGH_SCRATCH sets another)
 // Angles per workgroup of k_hough_vote.  More rows load every point less often, but a workgroup's LDS decides how many of them
@@ -988,6 +1020,64 @@ inline HoughParams hough_pass(const HoughPlan &P, int k, uintptr_t scratch, uint
   h.tab_sin = h.tab_cos + h.numangle;
   h.tab_theta = h.tab_sin + h.numangle;
   return h;
+}
+
+// ---- hc_hough_segments_device ---------------------------------------------------------------------
+// Everything the entry refuses and decides, but for the context pointer: sp is complete but for the context's scratch (items,
+// the four tables: seg_on_scratch patches them in).  A refused plan holds nothing but its text.
+struct SegPlan {
+  const char *error = nullptr;
+  SegParams sp{};
+  size_t items_bytes = 0;   // scratch [nframes][line_capacity] u32
+  size_t table_bytes = 0;   // scratch [4][numangle] 4-byte words: theta, major, slope, scale
+  unsigned lines_grid = 0, scan_grid = 0;  // workgroups of four waves: k_seg_count / k_seg_emit (a wave per line slot); k_seg_scan (a wave per frame)
+  bool emit = false;        // k_seg_emit is launched (seg_capacity > 0)
+};
+inline SegPlan plan_hough_segments(int W, int H, int max_frames, const View &map, uintptr_t lines, uintptr_t line_counts, size_t line_capacity, int n, double rho,
+                                   double theta, double min_theta, double max_theta, int min_length, int max_gap, uintptr_t seg_counts, uintptr_t segs,
+                                   size_t seg_capacity)
+{
+  SegPlan P;
+  auto refuse = [](const char *text) { SegPlan R; R.error = text; return R; };
+  if (!map.p || !lines || !line_counts || !seg_counts) return refuse("null argument");
+  if (seg_capacity && !segs) return refuse("d_segs is null with seg_capacity > 0");
+  if ((lines | line_counts | seg_counts) & 3u) return refuse("d_lines, d_line_counts and d_seg_counts must be 4-byte aligned");
+  if (segs & 15u) return refuse("d_segs must be 16-byte aligned");
+  if (min_length < 0 || max_gap < 0) return refuse("min_length and max_gap must not be negative");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  int numangle = 0, numrho = 0;
+  if (const char *e = hough_geometry(W, H, rho, theta, min_theta, max_theta, &numangle, &numrho)) return refuse(e);
+  if (const ViewFault f = check_view(map, (size_t)W, H, n, 1, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  if (!line_capacity) return refuse("line_capacity must be positive");
+  if (line_capacity > SIZE_MAX / 12 / (size_t)n) return refuse("line_capacity * 12 * nframes overflows size_t");
+  if (seg_capacity > SIZE_MAX / 16 / (size_t)n) return refuse("seg_capacity * 16 * nframes overflows size_t");
+  if (line_capacity > (size_t)0x7FFFFFF0 / (size_t)n) return refuse("too many work items (nframes x line_capacity)");
+  // a walk of L steps holds at most ceil(L / 2) segments: a frame's count stays below 2^32
+  if (line_capacity > (size_t)0xFFFFFFFFu / (((size_t)std::max(W, H) + 1) / 2)) return refuse("line_capacity * ceil(max(width, height) / 2) reaches 2^32: a frame's segment count would not fit uint32");
+  SegParams &s = P.sp;
+  s.map = (const uint8_t *)map.p; s.pitch = map.pitch; s.frame_stride = map.fs;
+  s.lines = (const float *)lines; s.line_counts = (const u32 *)line_counts; s.line_capacity = line_capacity;
+  s.seg_counts = (u32 *)seg_counts; s.segs = (int32_t *)segs; s.seg_capacity = seg_capacity;
+  s.W = W; s.H = H; s.nframes = n; s.numangle = numangle; s.min_length = min_length; s.max_gap = max_gap;
+  s.total_items = (int)((size_t)n * line_capacity);
+  P.items_bytes = (size_t)s.total_items * 4;
+  P.table_bytes = (size_t)numangle * 16;
+  P.lines_grid = (unsigned)(((long long)s.total_items + 3) / 4);
+  P.scan_grid = (unsigned)((n + 3) / 4);
+  P.emit = seg_capacity > 0;
+  return P;
+}
+
+// The parameters of a plan that was not refused, on the context's scratch: `items` (items_bytes) and `tables` (table_bytes)
+inline SegParams seg_on_scratch(const SegPlan &P, uintptr_t items, uintptr_t tables)
+{
+  SegParams s = P.sp;
+  s.items = (u32 *)items;
+  s.tab_theta = (const float *)tables;
+  s.tab_major = (const int32_t *)(tables + (size_t)s.numangle * 4);
+  s.tab_slope = (const float *)(tables + (size_t)s.numangle * 8);
+  s.tab_scale = (const float *)(tables + (size_t)s.numangle * 12);
+  return s;
 }
 
 }  // namespace hc

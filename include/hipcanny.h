@@ -310,7 +310,7 @@ int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps);
  * cudacam_amd/csrc/hough.hip).  One call returns per frame the number of lines and the strongest of them as (rho, theta, votes)
  * in cv::HoughLines' order.  The semantics are stated here and restated in tests/hough_ref.py (numpy); like the rest of Mode O
  * they are not pinned against a build of OpenCV.  Out of scope: cv::HoughLines' multi-scale form (srn / stn other than 0),
- * cv::HoughLinesP and cv::HoughCircles.
+ * cv::HoughLinesP's progressive probabilistic transform (segments: hc_hough_segments_device below) and cv::HoughCircles.
  * With W, H the context's frame size and rho, theta, min_theta, max_theta doubles:
  * Geometry.  numangle = floor((max_theta - min_theta) / theta) + 1; if numangle > 1 and |pi - (numangle - 1) * theta| < theta / 2
  *   it is one less.  numrho = rint((2 * (W + H) + 1) / rho), half to even.  (1920 x 1080, rho 1, theta pi / 180, [0, pi]: 180, 6001.)
@@ -367,6 +367,66 @@ int hc_hough_lines_device(hc_ctx *ctx, const void *d_points /* int32 [nframes][p
  * refusals of hc_hough_lines_device; table_capacity < numangle. */
 int hc_hough_tables(int width, int height, double rho, double theta, double min_theta, double max_theta, int *numangle, int *numrho,
                     float *tab_cos, float *tab_sin, float *tab_theta, size_t table_capacity);
+
+/* Line segments from the lines of hc_hough_lines_device: every line is walked across the edge map and the walk is cut into
+ * segments by a largest gap and a smallest length (k_seg_count, k_seg_scan, k_seg_emit: cudacam_amd/csrc/hough_segments.hip).
+ * This is the form of cv::cuda::HoughSegmentDetector, not cv::HoughLinesP: that one is a sequential transform driven by a random
+ * number generator, whose result is no function of its input alone.  The semantics are stated here and restated in
+ * tests/hough_segments_ref.py (numpy); like the rest of Mode O they are not pinned against a build of OpenCV.
+ * With W, H the context's frame size:
+ * Input.  d_map is what hc_edge_points_device reads: one-channel u8 maps of W x H in a pitched view; a pixel is an edge iff its
+ *   byte is non-zero.  d_lines (float32 [nframes][line_capacity][3]) and d_line_counts (uint32 [nframes]) are exactly what
+ *   hc_hough_lines_device wrote: frame f walks its first min(d_line_counts[f], line_capacity) lines.  rho, theta, min_theta and
+ *   max_theta are those of the call that made the lines: they give numangle and tab_theta by the rule of hc_hough_tables.
+ *   Neither the map nor the lines are written.
+ * Angle of a line.  Its index is the smallest n with tab_theta[n] equal to the line's second float bit for bit (the lines carry
+ *   copies of the table's entries).  A line whose theta equals no entry -- a NaN included -- yields no segments.  The device
+ *   computes no trigonometry.
+ * Walk tables, on the host (hc_hough_walk_tables below is the function the device entry itself uses).  For angle n: a =
+ *   (double)tab_theta[n], c = cos(a), s = sin(a) (libm, double).  If fabs(s) >= fabs(c): major[n] = 0 (x-major: one sample per
+ *   column), slope[n] = (float)(-c / s), scale[n] = (float)(1.0 / s).  Otherwise major[n] = 1 (y-major: one sample per row),
+ *   slope[n] = (float)(-s / c), scale[n] = (float)(1.0 / c).  |slope| <= 1 either way.
+ * Samples.  L = W, M = H when x-major; L = H, M = W when y-major.  For step t = 0 .. L - 1: m = rint((float)t * slope[n] + line_rho
+ *   * scale[n]) -- two float32 products, each rounded, and one float32 sum, no fused multiply-add, rint half to even --, line_rho
+ *   being the line's first float, in pixels.  The sample is pixel (t, m) when x-major and (m, t) when y-major.  The range test
+ *   0 <= m <= M - 1 is made on the float, as a comparison of real numbers, before any conversion: a rho of any size, infinities
+ *   and NaNs address nothing.  A sample outside the frame is not an edge.
+ * Segments.  Let t_1 < t_2 < ... be the steps whose sample is an edge.  A new group starts at t_1 and at every t_(k+1) with
+ *   t_(k+1) - t_k - 1 > max_gap.  A group is a candidate segment from its first sample (x0, y0) to its last (x1, y1), and is kept
+ *   iff (x1 - x0)^2 + (y1 - y0)^2 >= min_length^2 in 64-bit integers: a group of one sample only when min_length == 0.
+ * Order.  By line, in the order of d_lines; within a line by ascending t.  A function of the input alone.
+ * Output.  d_seg_counts[f] (uint32) is always the full number of kept segments of frame f.  d_segs is int32 [nframes]
+ *   [seg_capacity][4]: the slot of frame f, at byte f * seg_capacity * 16, receives its first min(count, seg_capacity) segments as
+ *   (x0, y0, x1, y1) -- the memory of the std::vector<cv::Vec4i> cv::HoughLinesP fills.  Nothing else is written.  seg_capacity
+ *   == 0 (d_segs null or not) gives the counts only.
+ * Asynchronous on the context stream (hc_set_stream honoured), in order with everything else queued there: chained behind
+ * hc_canny_device, hc_edge_points_device and hc_hough_lines_device it needs no synchronisation.  Contexts of either mode.  It is
+ * not a run, exactly as hc_edge_points_device is none, and like it completes first a pipelined run still in flight whose output
+ * overlaps d_map.  The view follows hc_edge_points_device: any alignment of base, pitch and frame stride, no byte outside [row,
+ * row + width) of a row is read, rows are addressed with 32-bit offsets.
+ * Scratch, owned by the context, allocated on first use and freed by hc_destroy: a count per line slot (uint32 [nframes]
+ * [line_capacity], allocated again after a synchronisation when a call needs more) and the tables on the device (made again,
+ * after a synchronisation of the context stream, only when rho, theta, min_theta or max_theta differ from the call before).
+ * Successive calls on one context share both and are ordered by the stream they are queued on, as for hc_hough_lines_device.
+ * Cost.  A wave per line slot, 64 steps per trip; a y-major walk reads one cache line per step.
+ * HC_E_ARG: ctx, d_map, d_lines, d_line_counts or d_seg_counts null; d_segs null with seg_capacity > 0; d_lines, d_line_counts
+ * or d_seg_counts not 4-byte, d_segs not 16-byte aligned; min_length < 0 or max_gap < 0; the view and nframes refusals of
+ * hc_edge_points_device; the rho, theta, min_theta, max_theta and accumulator refusals of hc_hough_lines_device; line_capacity
+ * == 0; line_capacity * 12 * nframes, line_capacity * 4 * nframes or seg_capacity * 16 * nframes overflowing size_t; nframes *
+ * line_capacity above 2^31 - 16 line slots; line_capacity * ceil(max(W, H) / 2) >= 2^32 (a frame's count would not fit). */
+int hc_hough_segments_device(hc_ctx *ctx, const void *d_map, size_t pitch, size_t frame_stride,
+                             const void *d_lines /* float32 [nframes][line_capacity][3] */, const void *d_line_counts /* uint32 [nframes] */,
+                             size_t line_capacity, int nframes, double rho, double theta, double min_theta, double max_theta,
+                             int min_length, int max_gap, void *d_seg_counts /* uint32 [nframes] */,
+                             void *d_segs /* int32 [nframes][seg_capacity][4] = (x0, y0, x1, y1); may be NULL when seg_capacity == 0 */, size_t seg_capacity);
+
+/* The walk tables of the entry above, on the host (no context, no GPU), by the rule stated there.  *numangle is always written
+ * on success.  The tables are given together or not at all (all three null: numangle only); each receives numangle values, and
+ * table_capacity, the values each can hold, must be at least numangle.  HC_E_ARG, with nothing written: numangle null; only some
+ * tables given; width or height < 1; the rho / theta / min_theta / max_theta and accumulator refusals of hc_hough_lines_device;
+ * table_capacity < numangle. */
+int hc_hough_walk_tables(int width, int height, double rho, double theta, double min_theta, double max_theta,
+                         int *numangle, int32_t *major, float *slope, float *scale, size_t table_capacity);   /* host, no context, no GPU */
 
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
