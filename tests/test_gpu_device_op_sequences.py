@@ -1,0 +1,185 @@
+"""Chains of device ops and runs on one context (tests/device_op_sequences.py) on the MI355X: the committed seeds, and the cases
+the generator aims at written out as step lists a reader can follow.  Every case runs through the same model and executor: each
+step's expected output is the restatement (or the CPU oracle) applied to the model's expected input, nothing is read back between
+steps, and at the end every buffer -- maps with their padding, counts between guards, lists with the canary behind them -- equals
+the model byte for byte.
+
+The pipelined contexts queue one hysteresis launch per run on 32-row tiles, and their first frames hold a weak chain across the
+tiles: until finish_slot has continued such a run from the host its maps differ from the final ones
+(test_the_neighbour_stays_in_flight reads that difference off the device), so a reader that was not ordered behind its writer
+gives other points, lines and segments, every time."""
+import math
+
+import numpy as np
+import pytest
+
+import device_op_sequences as DS
+from cudacam_amd import api
+
+pytestmark = pytest.mark.gpu
+
+PARTS = 7
+
+
+@pytest.mark.parametrize("part", range(PARTS))
+def test_seeds(oracle, part):
+    for seed in DS.SEEDS[part::PARTS]:
+        DS.run_seed(seed, oracle)
+
+
+def _params(w=130, h=67, ch=1, mode="R", pipeline=True, per_channel=False, **more):
+    P = dict(w=w, h=h, ch=ch, mode=mode, per_channel=per_channel, per_channel_ever=per_channel, pipeline=pipeline, low=10 if mode == "R" else 50,
+             high=40 if mode == "R" else 150, hough_bound=0, pool_kinds=["chain0", "chain1", "natural", "wobble", "natural", "sparse"], pool_seeds=[1, 2, 3, 4, 5, 6])
+    P.update(more)
+    return P
+
+
+def _run(f0, out, n=4, src="frames"):
+    return dict(kind="run", src=src, f0=f0, n=n, out=out)
+
+
+def _points(view, n, slot=0, cap=None, P=None):
+    return dict(kind="points", view=view, n=n, slot=slot, cap=P["w"] * P["h"] if cap is None else cap)
+
+
+def _lines(n, geo, lslot, lcap, P, pslot=0, threshold=6):
+    return dict(kind="lines", pslot=pslot, pcap=P["w"] * P["h"], n=n, geo=geo, threshold=threshold, lslot=lslot, lcap=lcap)
+
+
+def _segs(view, n, lslot, lcap, geo, sslot, scap=DS.SCAP_MAX, lgeo=None):
+    return dict(kind="segs", view=view, n=n, lslot=lslot, lcap=lcap, lgeo=geo if lgeo is None else lgeo, geo=geo, min_length=3, max_gap=2, sslot=sslot, scap=scap)
+
+
+def _blur(src, f0, dst, g0, n):
+    return dict(kind="blur", src=src, f0=f0, dst=dst, g0=g0, n=n, ksize=5, sigma=1.2, border=0)
+
+
+SYNC = dict(kind="sync")
+
+
+@pytest.mark.parametrize("reader", ["points of the last frame", "segments of an ROI inside frame 2", "blur of frame 0", "blur into the buffer a staged run copies to"])
+def test_partial_views_of_a_pending_output(oracle, reader):
+    """Pipelined Mode R, four frames, runs into rotating outputs whose content needs the host continuation; then, with no
+    synchronisation, a reader (or a writer) of PART of a pending output.  Each must complete the run first."""
+    P = _params()
+    staged = reader.startswith("blur into")
+    steps = [_run(0, 0), _points(("whole", 0), 4, P=P), _lines(4, 0, 0, 64, P), SYNC,          # lines of the final maps, for the segment walk
+             _run(0, 0), _run(1, "sout" if staged else 1)]                                  # ... and the same maps again, in flight
+    kind = {"points": "frame", "segmen": "roi", "blur o": "blur_in", "blur i": "blur_out"}[reader[:6]]
+    steps.append({"frame": _points(("frame", 0, 3), 1, slot=1, P=P), "roi": _segs(("roi", 0, 2, 3, 1, 1), 1, 0, 64, 0, 0),
+                  "blur_in": _blur(0, 0, "blur", 0, 1), "blur_out": _blur("frames", 2, "sout", 1, 2)}[kind])
+    with DS.Executor(P, oracle, reader) as e:
+        for st in steps:
+            e.queue(st)
+            if st is SYNC:
+                assert e.ctx.hysteresis_totals(reset=True)[:2] == (1, 1)   # the first run, complete: the count starts again
+        assert e.model.counters[f"overlap_{kind}"] == 1, "the model sees no pending writer under this view"
+        e.check()
+        assert e.ctx.hysteresis_totals()[:2] == (2, 2), "the two runs in flight under the reader were not both continued from the host"
+        if kind == "roi":
+            assert e.model.counters["seg_lists_nonempty"] > 0
+
+
+def test_the_neighbour_stays_in_flight(oracle):
+    """Readers of a buffer that ends exactly where a pending output begins, and of one that begins exactly where it ends: right
+    results, and the run is NOT completed for them.  hc_pipeline_slots_in_use does not say that (it is the size of the ring, 4
+    before and after), and every getter of the last run's hysteresis completes the runs itself.  What shows an unfinished run is
+    its output: once the device is idle it holds what the one queued launch left, which differs from the final map until
+    finish_slot continues the run on the host -- at hc_sync here, not at the readers' calls."""
+    import torch
+    P = _params()
+    L = DS.layout(P)
+    with DS.Executor(P, oracle, "neighbours") as e:
+        for st in (_run(0, 0), _run(1, 1)):
+            e.queue(st)
+        slots = e.ctx.pipeline_slots_in_use()
+        e.queue(_points(("before", 0), 1, slot=0, P=P))
+        e.queue(_points(("behind", 1, 4), 1, slot=1, P=P))
+        assert e.model.counters["adjacent"] == 2 and not any(e.model.counters[f"overlap_{k}"] for k in DS.VIEW_KINDS)
+        assert e.ctx.pipeline_slots_in_use() == slots == 4
+        torch.cuda.synchronize()   # the device, not the context: no run is completed by this
+        got, want = e.d["maps"].cpu().numpy(), e.model.buf["maps"]
+        for k in (0, 1):
+            a = DS.out_start(L, k)
+            assert not np.array_equal(got[a:a + L["oreg"]], want[a:a + L["oreg"]]), f"output {k} already holds its final maps: its run was completed, or its content needs no continuation"
+        e.check()
+        assert e.continued_runs() == 2
+
+
+@pytest.mark.parametrize("other", [1, 2], ids=["rho differs", "min_theta differs"])
+def test_equal_numangle_other_tables(oracle, other):
+    """Lines with geometry A, B, A, then segments with A, B, A, queued with no synchronisation: numangle is 12 for both, the tables
+    are not.  Every result is that of its own geometry."""
+    P = _params(w=250, h=66, mode="O", pipeline=False)
+    steps = [_run(0, 0), _points(("whole", 0), 4, P=P)]
+    steps += [_lines(4, g, s, 64, P) for g, s in ((0, 0), (other, 1), (0, 0))]
+    steps += [_segs(("whole", 0), 4, s, 64, g, s) for g, s in ((0, 0), (other, 1), (0, 0))]
+    assert DS.R.geometry(P["w"], P["h"], *DS.GEOS[0])[0] == DS.R.geometry(P["w"], P["h"], *DS.GEOS[other])[0] == 12
+    model = DS.execute(P, steps, oracle, f"A, B = geometry {other}, A")
+    c = model.counters
+    assert c["hough_tables_equal_numangle"] == 2 and c["line_lists_nonempty"] == 12 and c["seg_lists_nonempty"] >= 8, c
+    assert c["seg_tables_equal_numangle"] == 2
+    assert not np.array_equal(model.buf["lines0"], model.buf["lines1"]), "A and B give the same lines for this input"
+
+
+def _refused(call, entry):
+    with pytest.raises(api.HipCannyError, match="error -1") as err:
+        call()
+    assert entry in str(err.value) and "nframes out of range" in str(err.value), err.value
+
+
+def test_three_channels_and_per_channel(oracle):
+    """A 3-channel Mode R context with HC_OPT_PER_CHANNEL and max_batch 2: points, lines and segments take the 6 maps of a run and
+    refuse 7; without the option they take 2 and refuse 3; switching the option between two chains leaves both right.  Blur,
+    derivatives and automatic thresholds on the same context."""
+    P = _params(w=65, h=64, ch=3, pipeline=True, per_channel=True, max_batch=2)
+    with DS.Executor(P, oracle, "per-channel") as e:
+        def chain(n):
+            for st in (_run(0, 0, n=2), _points(("whole", 0), n, P=P), _lines(n, 3, 0, 64, P), _segs(("whole", 0), n, 0, 64, 3, 0),
+                       _blur("frames", 1, "blur", 0, 2), dict(kind="deriv", f0=2, n=2, ksize=7), dict(kind="autothr", f0=0, n=2, rule=1, param=0.5)):
+                e.queue(st)
+
+        def at_the_limit_and_beyond(n):
+            """Points, lines and segments of n maps into the second slots with capacity 8 each: taken.  The same pointers, pitches
+            and capacities with n + 1: refused for nframes, and nothing is written."""
+            for st in (_points(("whole", 0), n, slot=1, cap=8), dict(kind="lines", pslot=1, pcap=8, n=n, geo=0, threshold=5, lslot=1, lcap=8), _segs(("whole", 0), n, 1, 8, 0, 1, scap=8)):
+                e.queue(st)
+            p, l, s = (e._counts(f"{b}1") for b in ("pts", "lines", "segs"))
+            pl, ll, sl = (e._list(f"{b}1") for b in ("pts", "lines", "segs"))
+            m, geo = e._view(("whole", 0)), DS.GEOS[0]
+            _refused(lambda: e.ctx.edge_points_device(*m, n + 1, p, pl, 8), "hc_edge_points_device")
+            _refused(lambda: e.ctx.hough_lines_device(pl, p, 8, n + 1, geo[0], geo[1], 5, geo[2], geo[3], l, ll, 8), "hc_hough_lines_device")
+            _refused(lambda: e.ctx.hough_segments_device(*m, ll, l, 8, n + 1, *geo, 3, 2, s, sl, 8), "hc_hough_segments_device")
+        chain(6)
+        at_the_limit_and_beyond(6)
+        e.check()
+        assert e.model.counters["n_above_max_batch"] >= 6 and e.model.counters["seg_lists_nonempty"] > 0
+        e.queue(dict(kind="option", option=api.OPT_PER_CHANNEL, value=0))
+        chain(2)
+        at_the_limit_and_beyond(2)
+        e.check()
+        e.queue(dict(kind="option", option=api.OPT_PER_CHANNEL, value=1))
+        chain(6)
+        e.check()
+        assert e.continued_runs() > 0
+
+
+def test_three_channels_mode_o(oracle):
+    """The entries that had not met a 3-channel context: canny_device at every aperture, blur, derivatives chained with the gradient
+    run, automatic thresholds installed as the table of a run -- then points, lines and segments of what they wrote."""
+    P = _params(w=61, h=33, ch=3, mode="O", pipeline=True)
+    steps = [dict(kind="canny", f0=k, n=2, out=k % 3, low=DS.CANNY_THR[ap][0], high=DS.CANNY_THR[ap][1], aperture=ap, l2=int(ap == 5)) for k, ap in enumerate((3, 5, 7, -1))]
+    steps += [_blur("frames", 0, "blur", 0, 4), dict(kind="autothr", f0=1, rule=0, param=0.33), dict(kind="thr_on"), _run(0, 1, src="blur"),
+              dict(kind="deriv", f0=2, n=3, ksize=-1), dict(kind="rungrad", n=3, out=2), dict(kind="thr_off"),
+              _points(("whole", 1), 4, P=P), _lines(4, 3, 0, DS.LCAP_MAX, P), _segs(("frame", 2, 2), 1, 0, DS.LCAP_MAX, 3, 0), _points(("whole", 0), 2, slot=1, cap=5, P=P)]
+    DS.execute(P, steps, oracle, "3 channels, mode O")
+
+
+def test_growth_across_entries(oracle):
+    """One context, six calls queued with no synchronisation, each entry's second call needing more scratch than its first: points
+    of one frame then four, lines at PI / 12 then PI / 180 (tables and accumulators grow), segments of 4 lines then 400 per frame."""
+    P = _params(w=250, h=66, mode="R", pipeline=True)
+    steps = [_run(0, 0), _points(("frame", 0, 1), 1, slot=1, P=P), _points(("whole", 0), 4, slot=0, P=P), _lines(1, 0, 0, 4, P), _lines(4, 3, 1, DS.LCAP_MAX, P),
+             _segs(("whole", 0), 1, 0, 4, 0, 0), _segs(("whole", 0), 4, 1, DS.LCAP_MAX, 3, 1)]
+    model = DS.execute(P, steps, oracle, "growth")
+    assert model.counters["scratch_growths"] == 2 and model.counters["seg_lists_nonempty"] >= 4 and model.counters["lists_cut"] > 0, model.counters
