@@ -75,7 +75,7 @@ ABI_SYMBOLS = [
     "hc_profile_get_front_each", "hc_hysteresis_totals", "hc_last_hysteresis_schedule", "hc_download_begin", "hc_download_end", "hc_run_gradients_device",
     "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
     "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
-    "hc_hough_segments_device", "hc_hough_walk_tables",
+    "hc_hough_segments_device", "hc_hough_walk_tables", "hc_hough_circles_device", "hc_hough_circle_geometry",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -144,6 +144,8 @@ def load_library(legacy=False):
     L.hc_hough_tables.argtypes = [i, i, d, d, d, d, C.POINTER(i), C.POINTER(i), fp, fp, fp, sz]
     L.hc_hough_segments_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, i, d, d, d, d, i, i, vp, vp, sz]
     L.hc_hough_walk_tables.argtypes = [i, i, d, d, d, d, C.POINTER(i), C.POINTER(C.c_int32), fp, fp, sz]
+    L.hc_hough_circles_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, i, d, d, i, i, i, sz, vp, vp, sz]
+    L.hc_hough_circle_geometry.argtypes = [i, i, d, d, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_end.argtypes = [vp]
@@ -254,6 +256,16 @@ def hough_walk_tables(width, height, rho, theta, min_theta=0.0, max_theta=math.p
     fp = C.POINTER(C.c_float)
     _ck(L.hc_hough_walk_tables(*args, C.byref(na), major.ctypes.data_as(C.POINTER(C.c_int32)), slope.ctypes.data_as(fp), scale.ctypes.data_as(fp), na.value))
     return na.value, major, slope, scale
+
+
+def hough_circle_geometry(width, height, dp, min_dist, min_radius, max_radius):
+    """The geometry of hough_circles_device for width x height frames (hc_hough_circle_geometry: the host function the device
+    entry itself uses; no context, no GPU).  Returns (acc_width, acc_height, min_d2): the accumulator's cells and the smallest
+    squared distance of two kept centres, in cells."""
+    L = load_library()
+    aw, ah, d2 = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    _ck(L.hc_hough_circle_geometry(int(width), int(height), float(dp), float(min_dist), int(min_radius), int(max_radius), C.byref(aw), C.byref(ah), C.byref(d2)))
+    return aw.value, ah.value, d2.value
 
 
 class Context:
@@ -786,6 +798,97 @@ class Context:
         tail = (rho, theta, threshold, min_length, max_gap, min_theta, max_theta, max_lines, max_segments, point_capacity)
         counts, segs = self._again_if_continued(lambda: self._hough_segments_of(out, n, *tail))
         return out.cpu().numpy(), counts, segs
+
+    def hough_circles_device(self, d_points, d_point_counts, point_capacity, d_dx, d_dy, pitch, fs, nframes, dp, min_dist, votes_threshold,
+                             min_radius, max_radius, centre_capacity, d_circle_counts, d_circles, circle_capacity):
+        """Circles per frame on the device (hc_hough_circles_device, either mode; the form of cv::cuda::HoughCirclesDetector), from
+        what edge_points_device wrote (d_points int32 [nframes][point_capacity][2], d_point_counts uint32 [nframes]) and the
+        one-channel int16 gradient planes d_dx / d_dy (pitch and frame stride in bytes: derivatives_device on a 1-channel
+        context).  d_circle_counts is uint32 [nframes] (always the full counts), d_circles float32 [nframes][circle_capacity][4] =
+        (x, y, radius, votes) by centre (votes descending), then by radius, the first min(count, circle_capacity) of each frame;
+        circle_capacity 0 (d_circles None / 0): counts only.  Asynchronous on the context stream; not a run."""
+        _ck(self.lib.hc_hough_circles_device(self.handle, C.c_void_p(d_points), C.c_void_p(d_point_counts), int(point_capacity), C.c_void_p(d_dx),
+                                             C.c_void_p(d_dy), pitch, fs, int(nframes), float(dp), float(min_dist), int(votes_threshold), int(min_radius),
+                                             int(max_radius), int(centre_capacity), C.c_void_p(d_circle_counts), C.c_void_p(d_circles or None),
+                                             int(circle_capacity)))
+
+    def _hough_circles_of(self, d_maps, d_dx, d_dy, n, dp, min_dist, votes_threshold, min_radius, max_radius, max_centres, max_circles, point_capacity):
+        """(counts, circles) of n tight maps and tight int16 planes on the device: edge points, then circles, chained on the
+        context stream."""
+        import torch
+        dev, fs = d_maps.device, self.w * self.h
+        pcounts = torch.empty((n,), dtype=torch.int32, device=dev)
+        ccounts = torch.empty((n,), dtype=torch.int32, device=dev)
+        self._wait_for_torch()
+        if point_capacity is None:   # the counts size the list buffer
+            self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, pcounts.data_ptr(), None, 0)
+            point_capacity = self._largest_count(pcounts)
+        pcap = max(int(point_capacity), 1)
+        pts = torch.empty((n, pcap, 2), dtype=torch.int32, device=dev)
+        self._wait_for_torch()
+        self.edge_points_device(d_maps.data_ptr(), self.w, fs, n, pcounts.data_ptr(), pts.data_ptr(), pcap)
+        call = (pts.data_ptr(), pcounts.data_ptr(), pcap, d_dx.data_ptr(), d_dy.data_ptr(), 2 * self.w, 2 * fs, n, dp, min_dist, votes_threshold, min_radius,
+                max_radius, max_centres, ccounts.data_ptr())
+        if max_circles is None:      # likewise: a counts pass first
+            self.hough_circles_device(*call, None, 0)
+            max_circles = self._largest_count(ccounts)
+        cap = int(max_circles)
+        circles = torch.empty((n, max(cap, 1), 4), dtype=torch.float32, device=dev)
+        self._wait_for_torch()
+        self.hough_circles_device(*call, circles.data_ptr() if cap else None, cap)
+        self.sync()
+        cnt = ccounts.cpu().numpy().view(np.uint32)
+        host = circles.cpu().numpy()
+        return cnt, [host[f, :min(int(cnt[f]), cap)].copy() for f in range(n)]
+
+    def _planes_on_device(self, planes, n, who):
+        """Host or torch int16 planes [n, H, W] (or one plane) as a contiguous int16 tensor [n, H, W] on the context's device."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(planes, torch.Tensor):
+            d = planes if planes.ndim == 3 else planes[None]
+            if d.dtype != torch.int16:
+                raise HipCannyError(f"{who}: must be int16 (CV_16SC1), not {d.dtype}")
+            d = d.to(dev).contiguous()
+        else:
+            a = np.ascontiguousarray(planes)
+            if a.dtype != np.int16:
+                raise HipCannyError(f"{who}: must be int16 (CV_16SC1), not {a.dtype}")
+            d = torch.from_numpy(a[None] if a.ndim == 2 else a).to(dev)
+        if tuple(d.shape) != (n, self.h, self.w):
+            raise HipCannyError(f"{who}: planes {tuple(d.shape)} do not match the maps' {(n, self.h, self.w)}")
+        return d
+
+    def hough_circles(self, maps, dx, dy, dp, min_dist, votes_threshold, min_radius, max_radius, max_centres=4096, max_circles=None, point_capacity=None):
+        """Circles per map (the form of cv::cuda::HoughCirclesDetector): host or torch u8 edge maps [n, H, W] (or one map) and the
+        int16 gradient planes dx, dy of the same shape in; (uint32 counts [n], [float32 (min(count_f, max_circles), 4) = (x, y,
+        radius, votes) per frame]) out -- edge_points_device then hough_circles_device on the device.  max_centres: the strongest
+        centres that go on to the smallest-distance rule (1 .. 4096).  max_circles=None: a counts pass first, then a buffer sized
+        by the largest count; point_capacity=None likewise for the point lists (a smaller one cuts them: the circles are then
+        those of the cut lists)."""
+        d = self._maps_on_device(maps, "hough_circles")
+        n = d.shape[0]
+        gx, gy = self._planes_on_device(dx, n, "hough_circles: dx"), self._planes_on_device(dy, n, "hough_circles: dy")
+        return self._hough_circles_of(d, gx, gy, n, dp, min_dist, votes_threshold, min_radius, max_radius, max_centres, max_circles, point_capacity)
+
+    def canny_circles(self, frames, low, high, dp, min_dist, votes_threshold, min_radius, max_radius, aperture=3, l2gradient=False, blur=None,
+                      max_centres=4096, max_circles=None, point_capacity=None):
+        """cv::GaussianBlur (blur = (ksize, sigma), optional), the derivatives of cv::Canny's aperture, cv::Canny, cv::findNonZero
+        and the circle transform chained on the device (mode O, 1-channel contexts), with no host copy of maps, planes or point
+        lists in between.  Returns (uint8 (n,H,W) edge maps, uint32 circle counts, circles as hough_circles gives them)."""
+        import torch
+        if self.c != 1:
+            raise ValueError("canny_circles: a 1-channel context is required (the derivative planes of 3-channel frames are interleaved)")
+        raw, n, row, fs = self._device_view(frames, "canny_circles")
+        out = self._device_maps(n)
+        gx, gy = torch.empty_like(raw, dtype=torch.int16), torch.empty_like(raw, dtype=torch.int16)
+        self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
+        self.derivatives_device(src.data_ptr(), row, fs, gx.data_ptr(), gy.data_ptr(), 2 * row, 2 * fs, n, aperture)
+        self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        tail = (dp, min_dist, votes_threshold, min_radius, max_radius, max_centres, max_circles, point_capacity)
+        counts, circles = self._again_if_continued(lambda: self._hough_circles_of(out, gx, gy, n, *tail))
+        return out.cpu().numpy(), counts, circles
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -126,6 +126,25 @@ static __device__ __forceinline__ u64 uniform64(u64 v)
 }
 static __device__ __forceinline__ u32 mbcnt64(u64 m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
 
+// The comparison loop of k_hough_rank and k_circle_rank, for a workgroup of HOUGH_RANK_THREADS threads that all call it: how many
+// of the np peaks pk[] = (votes, accumulator index) precede `me` in the order (votes descending, index ascending), the list
+// passing through the LDS tile in pieces of HOUGH_RANK_THREADS.  The keys are unique, so the ranks of a list are a permutation.
+static __device__ __forceinline__ u32 peak_rank(const uint2 *pk, u32 np, uint2 me, uint2 *tile)
+{
+  u32 rank = 0;
+  for (u32 t0 = 0; t0 < np; t0 += HOUGH_RANK_THREADS) {
+    __syncthreads();
+    if (t0 + threadIdx.x < np) tile[threadIdx.x] = pk[t0 + threadIdx.x];
+    __syncthreads();
+    const u32 m = min((u32)HOUGH_RANK_THREADS, np - t0);
+    for (u32 j = 0; j < m; ++j) {
+      const uint2 o = tile[j];  // one address for the whole wave: an LDS broadcast
+      rank += (o.x > me.x || (o.x == me.x && o.y < me.y)) ? 1u : 0u;
+    }
+  }
+  return rank;
+}
+
 // Mode O, per-frame thresholds (FrontParams::frame_thr != null): the pair of the work item's frame as the kernel compares
 // it (the normalisation itself is frame_threshold_pair, canny_params.h, which the host can call too).  `frame` is wave-uniform:
 // one scalar load of the pair's 8 bytes and a few scalar instructions per work item, the results in SGPRs.

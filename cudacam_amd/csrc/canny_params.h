@@ -239,6 +239,40 @@ struct SegParams {
   int total_items;           // nframes * line_capacity
 };
 
+// k_circle_vote / k_hough_peaks / k_hough_scan / k_circle_rank / k_circle_sift / k_circle_radii / k_circle_scan
+// (hough_circles.hip): gradient-voted circle centres and per-centre radius histograms from the point lists of k_edge_emit and the
+// int16 planes of k_deriv16 (cv::cuda::HoughCirclesDetector's form).  One block describes one pass, as HoughParams does.
+constexpr int CIRCLE_MAX_CENTRES = 4096;     // centre_capacity at most: k_circle_sift keeps the kept list in LDS, 8 bytes a centre
+constexpr int CIRCLE_MAX_HIST = 4096;        // words of a radius histogram (max_radius - min_radius + 3) at most: one workgroup's LDS table
+constexpr int CIRCLE_THREADS = 256;          // points per workgroup trip of k_circle_vote and k_circle_radii
+constexpr int CIRCLE_VOTE_GROUPS = 256;      // workgroups of k_circle_vote per frame at most: each strides over the frame's list
+struct CircleParams {
+  const int32_t *points;     // [nframes][point_capacity][2] = (x, y), 8-byte aligned: what k_edge_emit wrote
+  const u32 *point_counts;   // [nframes]: frame f uses its first min(count, point_capacity) points
+  size_t point_capacity;
+  const int16_t *dx, *dy;    // int16 planes of W x H, one channel; pitch and frame_stride in BYTES, both even (H * pitch < 2^32)
+  size_t pitch, frame_stride;
+  int32_t *accum;            // scratch [nframes][AH + 2][AW + 2]: zeroed before k_circle_vote
+  u32 *row_items;            // scratch [nframes][AH]: peaks of each accumulator row (k_hough_peaks), then their offsets (k_hough_scan)
+  u32 *peaks;                // scratch [nframes][peak_cap][2] = (votes, accumulator index) in index order
+  u32 *npeaks;               // scratch [nframes]: the peaks of each frame
+  int32_t *ranked;           // scratch [nframes][centre_capacity][4] = (votes, cx, cy, 0): the first min(npeaks, centre_capacity) centres in order
+  int32_t *kept;             // scratch [nframes][centre_capacity][4]: those of them the smallest distance keeps, in order
+  u32 *nkept;                // scratch [nframes]
+  u32 *items;                // scratch [nframes][centre_capacity]: circles of each kept centre (k_circle_radii<false>), then their offsets
+  u32 *circle_counts;        // [nframes]: the full number of circles of each frame
+  float *circles;            // [nframes][circle_capacity][4] = (x, y, radius, votes), 16-byte aligned; unused when circle_capacity == 0
+  size_t circle_capacity, peak_cap;  // peak_cap = AH * ceil(AW / 2): no frame has more peaks
+  long long min_d2;          // two kept centres are at least this far apart, squared, in accumulator cells
+  int W, H, AW, AH, nframes;
+  int centre_capacity;       // 1 .. CIRCLE_MAX_CENTRES
+  int threshold;             // a centre has more votes than this, a circle at least this many (>= 0)
+  int min_radius, max_radius;  // 1 <= min_radius <= max_radius, max_radius - min_radius + 3 <= CIRCLE_MAX_HIST
+  float idp, dp;             // 1.0f / (float)dp and (float)dp of the call
+  unsigned vote_groups;      // workgroups of k_circle_vote per frame (1 .. CIRCLE_VOTE_GROUPS)
+  unsigned rank_groups;      // workgroups of k_circle_rank per frame: ceil(peak_cap / HOUGH_RANK_THREADS)
+};
+
 struct HystParams {
   u32 *sbits;
   const u32 *cbits;

@@ -216,4 +216,28 @@ int hc_hough_segments_device(hc_ctx *c, const void *d_map, size_t pitch, size_t 
   return HC_OK;
 }
 
+// The zeroing of the accumulators, then k_circle_vote, the peaks of hough.hip, k_circle_rank, k_circle_sift, k_circle_radii and
+// k_circle_scan on the context stream (hough_circles.hip), pass after pass.  Not a run, as hc_hough_lines_device; no run writes a
+// point list or a gradient plane, so nothing is completed first.  Successive calls share the scratch and are ordered by the stream
+// they are queued on (include/hipcanny.h).
+int hc_hough_circles_device(hc_ctx *c, const void *d_points, const void *d_point_counts, size_t point_capacity, const void *d_dx, const void *d_dy, size_t pitch,
+                            size_t fs, int n, double dp, double min_dist, int votes_threshold, int min_radius, int max_radius, size_t centre_capacity,
+                            void *d_circle_counts, void *d_circles, size_t circle_capacity)
+{
+  if (!c) return fail(HC_E_ARG, "hc_hough_circles_device: null argument");
+  const CirclePlan P = plan_hough_circles(c->W, c->H, c->max_batch * (c->per_channel ? 3 : 1), (uintptr_t)d_points, (uintptr_t)d_point_counts, point_capacity,
+                                          View{ (uintptr_t)d_dx, pitch, fs }, (uintptr_t)d_dy, n, dp, min_dist, votes_threshold, min_radius, max_radius, centre_capacity,
+                                          (uintptr_t)d_circle_counts, (uintptr_t)d_circles, circle_capacity, c->hough_bound);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_hough_circles_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  // every refusal lies above.  A larger scratch: what is queued on the context stream may still read the old one
+  if (int rc = ensure_scratch(c, c->circles, P.scratch_bytes)) return rc;
+  for (int k = 0; k < P.passes; ++k) {
+    const CircleParams cp = circle_pass(P, k, (uintptr_t)c->circles.p);
+    HIPCK(hipMemsetAsync(cp.accum, 0, (size_t)cp.nframes * P.frame_accum_bytes, c->stream));
+    HIPCK(launch_hough_circles(cp, c->stream));
+  }
+  return HC_OK;
+}
+
 }  // extern "C"

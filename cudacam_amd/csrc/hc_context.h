@@ -216,6 +216,9 @@ struct hc_ctx {
   // slope, scale) on the device and the arguments they were made from
   hc::DeviceScratch seg_items, seg_tab;
   hc::HoughTabKey seg_key;
+  // hc_hough_circles_device: the scratch of one pass [ranked centres | kept centres | peak lists | accumulators | per-row counts |
+  // per-centre counts | peak and kept totals] (circle_pass, host_plan.h), bounded by hough_bound as well
+  hc::DeviceScratch circles;
 };
 
 namespace hc {

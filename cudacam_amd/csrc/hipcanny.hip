@@ -615,7 +615,7 @@ void hc_destroy(hc_ctx *c)
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump }) (void)hipFree(q);
-  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab, &c->seg_items, &c->seg_tab }) (void)hipFree(q->p);
+  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab, &c->seg_items, &c->seg_tab, &c->circles }) (void)hipFree(q->p);
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);
@@ -901,6 +901,14 @@ int hc_hough_walk_tables(int width, int height, double rho, double theta, double
 {
   if (const char *e = hough_walk_tables(width, height, rho, theta, min_theta, max_theta, numangle, major, slope, scale, table_capacity))
     return fail(HC_E_ARG, std::string("hc_hough_walk_tables: ") + e);
+  return HC_OK;
+}
+
+// host only: the accumulator and the smallest squared distance of hc_hough_circles_device (hough_circle_geometry, host_plan.h)
+int hc_hough_circle_geometry(int width, int height, double dp, double min_dist, int min_radius, int max_radius, int *acc_width, int *acc_height, long long *min_d2)
+{
+  if (const char *e = hough_circle_geometry(width, height, dp, min_dist, min_radius, max_radius, acc_width, acc_height, min_d2))
+    return fail(HC_E_ARG, std::string("hc_hough_circle_geometry: ") + e);
   return HC_OK;
 }
 

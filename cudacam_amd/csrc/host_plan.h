@@ -2,8 +2,8 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments; the taps rule of
-// hc_gaussian_taps_q8 and the table rules of hc_hough_tables and hc_hough_walk_tables).  No HIP, no hc_ctx: hipcanny.hip fills
+// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles; the taps rule of
+// hc_gaussian_taps_q8, the table rules of hc_hough_tables and hc_hough_walk_tables and the geometry of hc_hough_circle_geometry).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
 #include "../../include/hipcanny.h"
@@ -1078,6 +1078,119 @@ inline SegParams seg_on_scratch(const SegPlan &P, uintptr_t items, uintptr_t tab
   s.tab_slope = (const float *)(tables + (size_t)s.numangle * 8);
   s.tab_scale = (const float *)(tables + (size_t)s.numangle * 12);
   return s;
+}
+
+// ---- hc_hough_circles_device / hc_hough_circle_geometry -------------------------------------------
+// The accumulator of the centre votes and the smallest squared distance of two kept centres, as include/hipcanny.h states them.
+// nullptr and the three numbers, or the refusal's text and nothing written.
+constexpr int CIRCLE_COORD_LIMIT = 1 << 20;  // width + max_radius and height + max_radius stay below: the Q10 walk stays inside int32
+inline const char *hough_circle_geometry(int W, int H, double dp, double min_dist, int min_radius, int max_radius, int *acc_width, int *acc_height,
+                                         long long *min_d2)
+{
+  if (!acc_width || !acc_height || !min_d2) return "acc_width, acc_height and min_d2 must not be null";
+  if (W < 1 || H < 1) return "width and height must be positive";
+  if (!std::isfinite(dp) || !(dp >= 1)) return "dp must be finite and at least 1";
+  if (!std::isfinite(min_dist) || min_dist < 0) return "min_dist must be finite and not negative";
+  if (min_radius < 1 || max_radius < min_radius) return "1 <= min_radius <= max_radius is required";
+  if ((long long)max_radius - min_radius + 3 > CIRCLE_MAX_HIST) return "a radius histogram, max_radius - min_radius + 3 words, exceeds 4096 words";
+  if ((long long)W + max_radius >= CIRCLE_COORD_LIMIT || (long long)H + max_radius >= CIRCLE_COORD_LIMIT) return "width + max_radius and height + max_radius must stay below 2^20";
+  const float idp = 1.0f / (float)dp;
+  const double aw = std::ceil((double)((float)W * idp)), ah = std::ceil((double)((float)H * idp));  // (at most 2^20: dp >= 1)
+  if (!(aw >= 1) || !(ah >= 1)) return "dp is so large that the accumulator has no cell";  // ((float)dp infinite, or a product that underflows)
+  if (!((aw + 2.0) * (ah + 2.0) < 2147483648.0)) return "the accumulator, (acc_height + 2) * (acc_width + 2) cells, reaches 2^31 cells";
+  const double md = min_dist / dp, v = md * md;  // (no two cells lie 2^62 apart: a larger bound is that one)
+  *acc_width = (int)aw;
+  *acc_height = (int)ah;
+  *min_d2 = v >= 4611686018427387904.0 ? (1ll << 62) : (long long)std::ceil(v);
+  return nullptr;
+}
+
+// Everything hc_hough_circles_device refuses and decides, but for the context pointer.  cp describes the FIRST pass with the
+// scratch pointers null; circle_pass gives pass k with them patched in.  A refused plan holds nothing but its text.
+struct CirclePlan {
+  const char *error = nullptr;
+  CircleParams cp{};
+  int frames = 0, frames_per_pass = 0, passes = 0;
+  // scratch per frame, in the order of the scratch's sections (each section holds frames_per_pass frames)
+  size_t frame_ranked_bytes = 0, frame_kept_bytes = 0, frame_peaks_bytes = 0, frame_accum_bytes = 0, frame_rows_bytes = 0, frame_items_bytes = 0, frame_counts_bytes = 0;
+  size_t scratch_bytes = 0;
+  // The grids: cp.vote_groups and cp.rank_groups are the workgroups per frame of k_circle_vote and k_circle_rank, and the launch
+  // reads them there.  Every other grid is one of cp.nframes, cp.centre_capacity and what launch_hough_peaks derives for its own
+  // kernels (hough_circles.hip, hough.hip): the plan keeps no second copy of them.
+  bool emit = false;  // k_circle_radii<true> is launched (circle_capacity > 0)
+};
+inline CirclePlan plan_hough_circles(int W, int H, int max_frames, uintptr_t points, uintptr_t point_counts, size_t point_capacity, const View &dx, uintptr_t dy,
+                                     int n, double dp, double min_dist, int votes_threshold, int min_radius, int max_radius, size_t centre_capacity,
+                                     uintptr_t circle_counts, uintptr_t circles, size_t circle_capacity, size_t scratch_bound)
+{
+  CirclePlan P;
+  auto refuse = [](const char *text) { CirclePlan R; R.error = text; return R; };
+  if (!points || !point_counts || !dx.p || !dy || !circle_counts) return refuse("null argument");
+  if (circle_capacity && !circles) return refuse("d_circles is null with circle_capacity > 0");
+  if (points & 7u) return refuse("d_points must be 8-byte aligned");
+  if ((point_counts | circle_counts) & 3u) return refuse("d_point_counts and d_circle_counts must be 4-byte aligned");
+  if (circles & 15u) return refuse("d_circles must be 16-byte aligned");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  if (votes_threshold < 0) return refuse("votes_threshold must not be negative");
+  if (centre_capacity < 1 || centre_capacity > (size_t)CIRCLE_MAX_CENTRES) return refuse("centre_capacity must lie in 1 .. 4096");
+  int AW = 0, AH = 0;
+  long long min_d2 = 0;
+  if (const char *e = hough_circle_geometry(W, H, dp, min_dist, min_radius, max_radius, &AW, &AH, &min_d2)) return refuse(e);
+  const View dyv{ dy, dx.pitch, dx.fs };
+  if (const ViewFault f = check_view(dx, 2 * (size_t)W, H, n, 2, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  if (const ViewFault f = check_view(dyv, 2 * (size_t)W, H, n, 2, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  uintptr_t end = 0;
+  if (!view_end(dx, 2 * (size_t)W, H, n, &end) || !view_end(dyv, 2 * (size_t)W, H, n, &end)) return refuse("a view wraps the address space");
+  if (point_capacity > SIZE_MAX / 8 / (size_t)n) return refuse("point_capacity * 8 * nframes overflows size_t");
+  if (circle_capacity > SIZE_MAX / 16 / (size_t)n) return refuse("circle_capacity * 16 * nframes overflows size_t");
+  const size_t cells = (size_t)(AH + 2) * (size_t)(AW + 2), peak_cap = (size_t)AH * (size_t)((AW + 1) / 2);
+  P.frame_ranked_bytes = P.frame_kept_bytes = centre_capacity * 16;
+  P.frame_peaks_bytes = peak_cap * 8; P.frame_accum_bytes = cells * 4; P.frame_rows_bytes = (size_t)AH * 4;
+  P.frame_items_bytes = centre_capacity * 4; P.frame_counts_bytes = 8;
+  const size_t per_frame = P.frame_ranked_bytes + P.frame_kept_bytes + P.frame_peaks_bytes + P.frame_accum_bytes + P.frame_rows_bytes + P.frame_items_bytes
+                           + P.frame_counts_bytes;  // (below 2^33 + 2^33 + a few 2^17)
+  if (scratch_bound < per_frame) return refuse("one frame's accumulator, peak list and centre lists exceed the context's scratch bound: use a larger dp");
+  P.frames = n;
+  P.frames_per_pass = (int)std::min<size_t>(std::min<size_t>((size_t)n, scratch_bound / per_frame), HOUGH_MAX_PASS_FRAMES);
+  P.passes = (n + P.frames_per_pass - 1) / P.frames_per_pass;
+  P.scratch_bytes = (size_t)P.frames_per_pass * per_frame;
+  if ((long long)P.frames_per_pass * AH > 0x7FFFFFF0ll) return refuse("too many work items (frames of a pass x accumulator rows)");
+  CircleParams &c = P.cp;
+  c.points = (const int32_t *)points; c.point_counts = (const u32 *)point_counts; c.point_capacity = point_capacity;
+  c.dx = (const int16_t *)dx.p; c.dy = (const int16_t *)dy; c.pitch = dx.pitch; c.frame_stride = dx.fs;
+  c.circle_counts = (u32 *)circle_counts; c.circles = (float *)circles; c.circle_capacity = circle_capacity; c.peak_cap = peak_cap;
+  c.min_d2 = min_d2; c.W = W; c.H = H; c.AW = AW; c.AH = AH; c.nframes = P.frames_per_pass; c.centre_capacity = (int)centre_capacity;
+  c.threshold = votes_threshold; c.min_radius = min_radius; c.max_radius = max_radius; c.idp = 1.0f / (float)dp; c.dp = (float)dp;
+  c.vote_groups = (unsigned)std::min<size_t>(std::max<size_t>((point_capacity + CIRCLE_THREADS - 1) / CIRCLE_THREADS, 1), CIRCLE_VOTE_GROUPS);
+  c.rank_groups = (unsigned)((peak_cap + HOUGH_RANK_THREADS - 1) / HOUGH_RANK_THREADS);  // (at least 1: AW, AH >= 1; below 2^22: fewer than 2^30 peaks)
+  P.emit = circle_capacity > 0;
+  return P;
+}
+
+// Pass k of a plan that was not refused (0 <= k < passes), on `scratch` (scratch_bytes, 16-byte aligned): the sections lie in the
+// order ranked | kept | peaks | accumulators | per-row counts | per-centre counts | npeaks | nkept, the widest alignment first
+inline CircleParams circle_pass(const CirclePlan &P, int k, uintptr_t scratch)
+{
+  CircleParams c = P.cp;
+  const int f0 = k * P.frames_per_pass;
+  const size_t fpp = (size_t)P.frames_per_pass;
+  c.nframes = std::min(P.frames_per_pass, P.frames - f0);
+  c.points += (size_t)f0 * c.point_capacity * 2;
+  c.point_counts += f0;
+  c.dx = (const int16_t *)((uintptr_t)c.dx + (size_t)f0 * c.frame_stride);
+  c.dy = (const int16_t *)((uintptr_t)c.dy + (size_t)f0 * c.frame_stride);
+  c.circle_counts += f0;
+  if (c.circles) c.circles += (size_t)f0 * c.circle_capacity * 4;
+  uintptr_t q = scratch;
+  c.ranked = (int32_t *)q; q += fpp * P.frame_ranked_bytes;
+  c.kept = (int32_t *)q;   q += fpp * P.frame_kept_bytes;
+  c.peaks = (u32 *)q;      q += fpp * P.frame_peaks_bytes;
+  c.accum = (int32_t *)q;  q += fpp * P.frame_accum_bytes;
+  c.row_items = (u32 *)q;  q += fpp * P.frame_rows_bytes;
+  c.items = (u32 *)q;      q += fpp * P.frame_items_bytes;
+  c.npeaks = (u32 *)q;     q += fpp * 4;
+  c.nkept = (u32 *)q;
+  return c;
 }
 
 }  // namespace hc

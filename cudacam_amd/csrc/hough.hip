@@ -130,17 +130,7 @@ __global__ __launch_bounds__(HOUGH_RANK_THREADS) void k_hough_rank(const HoughPa
   const uint2 *pk = reinterpret_cast<const uint2 *>(p.peaks) + (size_t)frame * p.peak_cap;
   const u32 i = i0 + threadIdx.x;
   const uint2 me = i < np ? pk[i] : make_uint2(0u, 0u);
-  u32 rank = 0;
-  for (u32 t0 = 0; t0 < np; t0 += HOUGH_RANK_THREADS) {
-    __syncthreads();
-    if (t0 + threadIdx.x < np) tile[threadIdx.x] = pk[t0 + threadIdx.x];
-    __syncthreads();
-    const u32 m = min((u32)HOUGH_RANK_THREADS, np - t0);
-    for (u32 j = 0; j < m; ++j) {
-      const uint2 o = tile[j];  // one address for the whole wave: an LDS broadcast
-      rank += (o.x > me.x || (o.x == me.x && o.y < me.y)) ? 1u : 0u;
-    }
-  }
+  const u32 rank = peak_rank(pk, np, me, tile);
   if (i >= np || (size_t)rank >= p.line_capacity) return;
   const int stride = p.numrho + 2;
   const int n = (int)(me.y / (u32)stride) - 1, r = (int)(me.y % (u32)stride) - 1;
@@ -152,31 +142,45 @@ __global__ __launch_bounds__(HOUGH_RANK_THREADS) void k_hough_rank(const HoughPa
 
 }  // namespace
 
+// what k_hough_peaks and k_hough_scan need of a block: the accumulator, the peak list and the per-row counts of one pass
+static bool peaks_ok(const HoughParams &p)
+{
+  const long long stride = (long long)p.numrho + 2, cells = ((long long)p.numangle + 2) * stride;
+  return p.accum && p.items && p.peaks && p.line_counts && !((((uintptr_t)p.line_counts | (uintptr_t)p.accum | (uintptr_t)p.items) & 3u) | ((uintptr_t)p.peaks & 7u))
+         && p.numangle >= 1 && p.numrho >= 0 && p.nframes >= 1 && p.threshold >= 0 && cells < (1ll << 31) && (long long)p.nframes * p.numangle <= 0x7FFFFFF0ll
+         && p.peak_cap == (size_t)p.numangle * (size_t)((p.numrho + 1) / 2);
+}
+
+// The peaks of the padded accumulators p.accum [nframes][numangle + 2][numrho + 2] on stream s: count, scan (the frames' totals ->
+// p.line_counts) and, where a cell can be a peak at all, emit.  Of p it reads accum, items, peaks, peak_cap, line_counts, numangle,
+// numrho, nframes and threshold only: hc_hough_circles_device calls it on its own accumulator (rows = numangle, columns = numrho).
+hipError_t launch_hough_peaks(const HoughParams &p, hipStream_t s)
+{
+  if (!peaks_ok(p)) return hipErrorInvalidValue;
+  const dim3 rows_grid((unsigned)(((long long)p.nframes * p.numangle + 3) / 4)), block(256);
+  hipLaunchKernelGGL(k_hough_peaks<false>, rows_grid, block, 0, s, p);
+  hipLaunchKernelGGL(k_hough_scan, dim3((p.nframes + 3) / 4), block, 0, s, p);
+  if (p.peak_cap) hipLaunchKernelGGL(k_hough_peaks<true>, rows_grid, block, 0, s, p);
+  return hipGetLastError();
+}
+
 // One pass on stream s: the votes, the peaks (count, scan, emit) and, with p.line_capacity > 0, the ranking.
 hipError_t launch_hough(const HoughParams &p, hipStream_t s)
 {
-  const long long stride = (long long)p.numrho + 2, cells = ((long long)p.numangle + 2) * stride;
-  if (!p.points || !p.point_counts || !p.tab_cos || !p.tab_sin || !p.tab_theta || !p.accum || !p.items || !p.peaks || !p.line_counts
-      || (((uintptr_t)p.points & 7u) | (((uintptr_t)p.point_counts | (uintptr_t)p.line_counts | (uintptr_t)p.lines | (uintptr_t)p.accum | (uintptr_t)p.items) & 3u) | ((uintptr_t)p.peaks & 7u))
-      || (p.line_capacity && !p.lines) || p.numangle < 1 || p.numrho < 0 || p.nframes < 1 || p.threshold < 0 || cells >= (1ll << 31)
-      || p.rows < 1 || p.rows > HOUGH_MAX_ROWS || (long long)p.rows * stride * 4 > HOUGH_LDS_BYTES || p.groups != (p.numangle + p.rows - 1) / p.rows
-      || (long long)p.nframes * p.groups > 0x7FFFFFF0ll || (long long)p.nframes * p.numangle > 0x7FFFFFF0ll || p.nframes > 65535
-      || p.peak_cap != (size_t)p.numangle * (size_t)((p.numrho + 1) / 2))
+  const long long stride = (long long)p.numrho + 2;
+  if (!peaks_ok(p) || !p.points || !p.point_counts || !p.tab_cos || !p.tab_sin || !p.tab_theta || (((uintptr_t)p.points & 7u) | (((uintptr_t)p.point_counts | (uintptr_t)p.lines) & 3u))
+      || (p.line_capacity && !p.lines) || p.rows < 1 || p.rows > HOUGH_MAX_ROWS || (long long)p.rows * stride * 4 > HOUGH_LDS_BYTES || p.groups != (p.numangle + p.rows - 1) / p.rows
+      || (long long)p.nframes * p.groups > 0x7FFFFFF0ll || p.nframes > 65535)
     return hipErrorInvalidValue;
   const size_t lds = (size_t)p.rows * (size_t)stride * 4;
   if (lds > 64 * 1024) {  // above the default bound of dynamic LDS the kernel has to be told
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_hough_vote), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  const dim3 rows_grid((unsigned)(((long long)p.nframes * p.numangle + 3) / 4)), block(256);
   hipLaunchKernelGGL(k_hough_vote, dim3((unsigned)(p.nframes * p.groups)), dim3(HOUGH_VOTE_THREADS), lds, s, p);
-  hipLaunchKernelGGL(k_hough_peaks<false>, rows_grid, block, 0, s, p);
-  hipLaunchKernelGGL(k_hough_scan, dim3((p.nframes + 3) / 4), block, 0, s, p);
-  if (p.peak_cap) {
-    hipLaunchKernelGGL(k_hough_peaks<true>, rows_grid, block, 0, s, p);
-    if (p.line_capacity)
-      hipLaunchKernelGGL(k_hough_rank, dim3((unsigned)((p.peak_cap + HOUGH_RANK_THREADS - 1) / HOUGH_RANK_THREADS), (unsigned)p.nframes), dim3(HOUGH_RANK_THREADS), 0, s, p);
-  }
+  if (const hipError_t e = launch_hough_peaks(p, s)) return e;
+  if (p.peak_cap && p.line_capacity)
+    hipLaunchKernelGGL(k_hough_rank, dim3((unsigned)((p.peak_cap + HOUGH_RANK_THREADS - 1) / HOUGH_RANK_THREADS), (unsigned)p.nframes), dim3(HOUGH_RANK_THREADS), 0, s, p);
   return hipGetLastError();
 }
 

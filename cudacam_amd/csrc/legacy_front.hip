@@ -999,7 +999,9 @@ hipError_t launch_nms(const FrontParams &p, hipStream_t s)
 using namespace hc;
 
 extern "C" {
-// the test library (round-1 front kernels) is built without stats.hip, edge_points.hip, blur.hip, hough.hip and hough_segments.hip
+// the test library (round-1 front kernels) is built without stats.hip, edge_points.hip, blur.hip, hough.hip, hough_segments.hip and
+// hough_circles.hip
+int hc_hough_circles_device(hc_ctx *, const void *, const void *, size_t, const void *, const void *, size_t, size_t, int, double, double, int, int, int, size_t, void *, void *, size_t) { return fail(HC_E_ARG, "hc_hough_circles_device: not part of the test library"); }
 int hc_hough_segments_device(hc_ctx *, const void *, size_t, size_t, const void *, const void *, size_t, int, double, double, double, double, int, int, void *, void *, size_t) { return fail(HC_E_ARG, "hc_hough_segments_device: not part of the test library"); }
 int hc_hough_lines_device(hc_ctx *, const void *, const void *, size_t, int, double, double, int, double, double, void *, void *, size_t) { return fail(HC_E_ARG, "hc_hough_lines_device: not part of the test library"); }
 int hc_gaussian_blur_device(hc_ctx *, const void *, size_t, size_t, void *, size_t, size_t, int, int, const uint16_t *, int) { return fail(HC_E_ARG, "hc_gaussian_blur_device: not part of the test library"); }

@@ -310,7 +310,7 @@ int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps);
  * cudacam_amd/csrc/hough.hip).  One call returns per frame the number of lines and the strongest of them as (rho, theta, votes)
  * in cv::HoughLines' order.  The semantics are stated here and restated in tests/hough_ref.py (numpy); like the rest of Mode O
  * they are not pinned against a build of OpenCV.  Out of scope: cv::HoughLines' multi-scale form (srn / stn other than 0),
- * cv::HoughLinesP's progressive probabilistic transform (segments: hc_hough_segments_device below) and cv::HoughCircles.
+ * cv::HoughLinesP's progressive probabilistic transform (segments: hc_hough_segments_device below; circles: hc_hough_circles_device).
  * With W, H the context's frame size and rho, theta, min_theta, max_theta doubles:
  * Geometry.  numangle = floor((max_theta - min_theta) / theta) + 1; if numangle > 1 and |pi - (numangle - 1) * theta| < theta / 2
  *   it is one less.  numrho = rint((2 * (W + H) + 1) / rho), half to even.  (1920 x 1080, rho 1, theta pi / 180, [0, pi]: 180, 6001.)
@@ -427,6 +427,81 @@ int hc_hough_segments_device(hc_ctx *ctx, const void *d_map, size_t pitch, size_
  * table_capacity < numangle. */
 int hc_hough_walk_tables(int width, int height, double rho, double theta, double min_theta, double max_theta,
                          int *numangle, int32_t *major, float *slope, float *scale, size_t table_capacity);   /* host, no context, no GPU */
+
+/* Circles from the edge point lists of hc_edge_points_device and the gradient planes cv::Canny itself uses: centres voted along
+ * the gradient, sifted by a smallest distance, and a radius histogram per kept centre (k_circle_vote, k_hough_peaks, k_hough_scan,
+ * k_circle_rank, k_circle_sift, k_circle_radii, k_circle_scan: cudacam_amd/csrc/hough_circles.hip).  This is the form of
+ * cv::cuda::HoughCirclesDetector, not cv::HoughCircles, which is no fixed function of its input across OpenCV versions.  The
+ * semantics are stated here and restated in tests/hough_circles_ref.py (numpy); like the rest of Mode O they are not pinned
+ * against a build of OpenCV.  Out of scope: HOUGH_GRADIENT_ALT, param1 (the caller runs cv::Canny with its own thresholds),
+ * 3-channel gradient planes, sub-cell refinement of the centres.  With W, H the context's frame size:
+ * Geometry (hc_hough_circle_geometry below is the function the device entry itself uses).  idp = 1.0f / (float)dp.  AW =
+ *   ceil((double)((float)W * idp)), AH likewise from H.  The accumulator is int32 [AH + 2][AW + 2], zero to begin with.  min_d2 is
+ *   the smallest int64 q with (double)q >= md * md, where md = min_dist / dp in double (min_dist 0 gives 0); a bound of 2^62 and
+ *   more is 2^62: no two cells lie that far apart.
+ * Input.  d_points (int32 [nframes][point_capacity][2] = (x, y), 8-byte aligned) and d_point_counts (uint32 [nframes]) are exactly
+ *   what hc_edge_points_device wrote: frame f uses its first min(d_point_counts[f], point_capacity) points.  d_dx / d_dy are
+ *   one-channel int16 planes of W x H with a common pitch and frame stride in bytes: what hc_derivatives_device writes on a
+ *   1-channel context.  A point outside 0 <= x < W, 0 <= y < H takes part in nothing: it reads no gradient, casts no vote and
+ *   counts in no histogram.  No coordinate a caller can pass makes the entry read or write outside its views.  Nothing of the input
+ *   is written.
+ * Centre votes.  For each point with the gradient (vx, vy) read at (x, y), skipped when both are 0: m = (uint32)(vx * vx + vy * vy)
+ *   (exact; at most 2^31), mag = sqrtf((float)m), correctly rounded; x0 = rint(((float)x * idp) * 1024.0f), sx = rint((((float)vx *
+ *   idp) * 1024.0f) / mag), and likewise y0, sy.  Every product, the quotient and the square root are single float32 operations,
+ *   each rounded to nearest, no fused multiply-add; rint rounds half to even.  Both directions d = +1, -1: x1 = x0 + d * min_radius
+ *   * sx, y1 likewise; then for r = min_radius .. max_radius: x2 = x1 >> 10, y2 = y1 >> 10 (arithmetic shifts); the direction ends
+ *   at the first (x2, y2) outside 0 .. AW - 1 x 0 .. AH - 1; otherwise accum[y2 + 1][x2 + 1] += 1, then x1 += d * sx, y1 += d * sy.
+ *   All of this is int32; the refusals below keep it from overflowing (|sx|, |sy| <= 1024).
+ * Centres.  Cell (cx, cy), 0 <= cx < AW, 0 <= cy < AH, with value a = accum[cy + 1][cx + 1] is a centre iff a > votes_threshold, a
+ *   > accum[cy][cx + 1] (up), a >= accum[cy + 2][cx + 1] (down), a > accum[cy + 1][cx] (left) and a >= accum[cy + 1][cx + 2]
+ *   (right); the padding cells take part as neighbours.  The rule of hc_hough_lines_device, with rows = AH and columns = AW.
+ * Centre order.  Votes descending, ties by ascending index (cy + 1) * (AW + 2) + cx + 1.  Only the first centre_capacity centres in
+ *   that order go on.
+ * Smallest distance.  Those centres are gone through in that order: one is kept iff every centre kept before it has (cx - cx')^2
+ *   + (cy - cy')^2 >= min_d2, in int64.
+ * Radii.  For each kept centre, in that order: fx = ((float)cx + 0.5f) * (float)dp, fy likewise.  hist[0 .. max_radius -
+ *   min_radius + 2] is zero to begin with.  For every point of the frame inside the frame: ddx = fx - (float)x, ddy = fy - (float)y,
+ *   rad = sqrtf(ddx * ddx + ddy * ddy) -- two rounded products, one rounded sum, a correctly rounded root, no fused multiply-add
+ *   --; if rad >= (float)min_radius && rad <= (float)max_radius then hist[(int)rint(rad - (float)min_radius) + 1] += 1.  Radius
+ *   index i = 0 .. max_radius - min_radius is a circle iff h = hist[i + 1] has h >= votes_threshold, h > hist[i] and h >= hist[i + 2].
+ * Output.  Circles are ordered by centre, in the order above, and within a centre by ascending radius: a function of the input
+ *   alone.  d_circle_counts[f] (uint32) is always the full number of circles of frame f.  d_circles is float32 [nframes]
+ *   [circle_capacity][4]: the slot of frame f, at byte f * circle_capacity * 16, receives its first min(count, circle_capacity)
+ *   circles as (fx, fy, (float)(i + min_radius), (float)h).  Nothing else is written.  circle_capacity == 0 (d_circles null or
+ *   not) gives the counts only.
+ * Asynchronous on the context stream (hc_set_stream honoured), in order with everything else queued there: chained behind
+ * hc_derivatives_device, hc_canny_device and hc_edge_points_device it needs no synchronisation.  Contexts of either mode.  It is
+ * not a run, exactly as hc_hough_lines_device is none, and since no run writes a point list or a gradient plane, no run in flight
+ * is completed first.
+ * Scratch, owned by the context, allocated on first use and freed by hc_destroy, per frame of a pass: the accumulator (zeroed on
+ * the context stream before the votes), the compacted peak list (at most AH * ceil(AW / 2) peaks), a count per accumulator row,
+ * the ranked and the kept centres (centre_capacity of 16 bytes each), a count per centre.  It is bounded by the bound of
+ * hc_hough_lines_device (256 MiB): a batch is cut into passes of as many frames as fit, 65535 at most, and the scratch is
+ * allocated again, after a synchronisation, when a call needs more than the calls before.  Successive calls on one context share
+ * it and are ordered by the stream they are queued on: a caller who changes the stream between two calls (hc_set_stream,
+ * hc_use_own_stream) must order the two streams itself, or synchronise, as for hc_hough_lines_device.
+ * Cost.  Votes: up to 2 * (max_radius - min_radius + 1) global atomic adds per point.  The ranking is quadratic in the peaks of a
+ * frame, as for hc_hough_lines_device.  The sift is sequential: one wave per frame.  Every kept centre reads the frame's point
+ * list once per radii launch (twice when circles are written).  Measurements: profiles/hough_circles/README.md.
+ * HC_E_ARG: ctx, d_points, d_point_counts, d_dx, d_dy or d_circle_counts null; d_circles null with circle_capacity > 0; d_points
+ * not 8-byte, d_point_counts or d_circle_counts not 4-byte, d_circles not 16-byte aligned; d_dx, d_dy, pitch or frame_stride odd;
+ * pitch < 2 * W; H * pitch >= 2^32; nframes > 1 with frame_stride < H * pitch; a view that wraps the address space; nframes outside
+ * 1..(max_batch, 3 * max_batch with HC_OPT_PER_CHANNEL); dp < 1 or not finite, or so large that AW or AH is 0; min_dist < 0 or not
+ * finite; votes_threshold < 0; min_radius < 1; max_radius < min_radius; max_radius - min_radius + 3 > 4096 histogram words; W +
+ * max_radius >= 2^20 or H + max_radius >= 2^20; centre_capacity outside 1..4096; (AH + 2) * (AW + 2) >= 2^31; one frame's scratch
+ * above the bound; point_capacity * 8 * nframes or circle_capacity * 16 * nframes overflowing size_t. */
+int hc_hough_circles_device(hc_ctx *ctx, const void *d_points /* int32 [nframes][point_capacity][2] */,
+                            const void *d_point_counts /* uint32 [nframes] */, size_t point_capacity, const void *d_dx, const void *d_dy,
+                            size_t pitch, size_t frame_stride /* int16, ONE channel, W x H, bytes */, int nframes, double dp, double min_dist,
+                            int votes_threshold, int min_radius, int max_radius, size_t centre_capacity, void *d_circle_counts /* uint32 [nframes] */,
+                            void *d_circles /* float32 [nframes][circle_capacity][4] = (x, y, radius, votes); may be NULL when circle_capacity == 0 */,
+                            size_t circle_capacity);
+
+/* The geometry of the entry above, on the host (no context, no GPU), by the rule stated there: all three numbers are written on
+ * success.  HC_E_ARG, with nothing written: a null pointer; width or height < 1; the dp, min_dist, min_radius, max_radius, 2^20
+ * and accumulator refusals of hc_hough_circles_device. */
+int hc_hough_circle_geometry(int width, int height, double dp, double min_dist, int min_radius, int max_radius,
+                             int *acc_width, int *acc_height, long long *min_d2);   /* host, no context, no GPU */
 
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
