@@ -4,6 +4,10 @@
 // guards at 2^20 and 2^31; and that a refused plan holds nothing.  Prints "ok <checks>" or the first violations.
 //   hough_circles_plan_driver geometry W H dp min_dist min_radius max_radius     (the doubles as C99 hex floats)
 // prints "AW AH min_d2", or "refused: <text>".
+//   hough_circles_plan_driver plan W H max_frames { nframes point_capacity pitch frame_stride dp min_dist votes_threshold min_radius
+//                                                   max_radius centre_capacity circle_capacity scratch_bound }...
+// prints, for each group of twelve, "scratch_bytes passes frames_per_pass" or "refused: <text>" (tests/test_device_op_sequences_cpu.py:
+// the circles steps of the seeded chains; a scratch_bound of 0 is the context's default, as hc_set_option takes it).
 #include "../../cudacam_amd/csrc/host_plan.h"
 
 #include <cstdio>
@@ -181,9 +185,27 @@ static int print_geometry(char **v)
   return 0;
 }
 
+static int print_plans(int count, char **v)
+{
+  Call c;
+  c.W = std::atoi(v[0]); c.H = std::atoi(v[1]); c.max_frames = std::atoi(v[2]);
+  for (char **g = v + 3; g + 12 <= v + count; g += 12) {
+    c.n = std::atoi(g[0]); c.pcap = std::strtoull(g[1], nullptr, 10); c.dx = View{ DX, (size_t)std::strtoull(g[2], nullptr, 10), (size_t)std::strtoull(g[3], nullptr, 10) };
+    c.dp = std::strtod(g[4], nullptr); c.min_dist = std::strtod(g[5], nullptr); c.thr = std::atoi(g[6]); c.rmin = std::atoi(g[7]); c.rmax = std::atoi(g[8]);
+    c.centres = std::strtoull(g[9], nullptr, 10); c.ccap = std::strtoull(g[10], nullptr, 10);
+    const size_t bound = std::strtoull(g[11], nullptr, 10);
+    c.bound = bound ? bound : HOUGH_SCRATCH_BYTES;
+    const CirclePlan P = c.plan();
+    if (P.error) std::printf("refused: %s\n", P.error);
+    else std::printf("%zu %d %d\n", P.scratch_bytes, P.passes, P.frames_per_pass);
+  }
+  return 0;
+}
+
 int main(int argc, char **argv)
 {
   if (argc == 8 && !std::strcmp(argv[1], "geometry")) return print_geometry(argv + 2);
+  if (argc >= 5 && (argc - 5) % 12 == 0 && !std::strcmp(argv[1], "plan")) return print_plans(argc - 2, argv + 2);
   refusals();
   shapes();
   geometry_refusals();

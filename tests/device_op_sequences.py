@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Seeded CHAINS of device ops and runs on one context: the entries that are not runs (blur, derivatives, automatic thresholds,
-edge points, Hough lines, Hough segments) queued between and behind runs, with no synchronisation but the few the sequence
+edge points, Hough lines, Hough segments, Hough circles) queued between and behind runs, with no synchronisation but the few the sequence
 itself names.  tests/fuzz_sequences.py does this for the runs alone; each entry has a GPU test file of its own for its shapes,
 capacities, views and refusals.  What neither reaches is the state the entries share on one context (cudacam_amd/csrc/
 device_ops.hip: the scratch buffers that grow and never shrink, the Hough and walk tables cached by geometry) and the one place
@@ -8,12 +8,14 @@ where they meet the runs (finish_writers_of: which pipelined runs in flight a re
 
 Three parts, the first two pure (numpy, the CPU oracle, the numpy restatements; no GPU, no clock):
   make_sequence(seed)   context parameters, 12 .. 20 steps (plain dicts; the synchronisation a stream switch needs, the step that
-                        takes a threshold table off again and the final sync are among them) and counters that say what the
-                        sequence exercises
+                        takes a threshold table off again and the final sync are among them), 1 .. 3 circles steps drawn from a
+                        generator of their own and inserted among them (add_circles), and counters that say what the sequence
+                        exercises
   Model                 the expected content of EVERY byte of every device buffer the sequence owns, step after step: inputs in
                         arenas of 255s, edge maps with the padding of their pitch, counts between guard words, lists in slots
                         pre-filled with a canary.  A step reads its inputs from the model and writes its outputs back, so values
-                        propagate (a run's maps -> points -> lines -> segments) and nothing is read from the device in between.
+                        propagate (a run's maps -> points -> lines -> segments; points and gradient planes -> circles) and
+                        nothing is read from the device in between.
   Executor              queues the same steps through api.Context and, at every "sync" step and at the end, compares every buffer
                         with the model byte for byte -- results, canaries, guards and padding alike.
 The per-entry helpers of the GPU test files (_upload / _check) upload a map per call and check one call's buffers; here a buffer
@@ -46,6 +48,7 @@ import deriv_ref as D              # noqa: E402
 import edge_points_ref as EP       # noqa: E402
 import fuzz_sequences as FS        # noqa: E402
 import gauss_blur_ref as G         # noqa: E402
+import hough_circles_ref as HC     # noqa: E402
 import hough_ref as R              # noqa: E402
 import hough_segments_ref as S     # noqa: E402
 import view_arena as VA            # noqa: E402
@@ -64,13 +67,22 @@ SAME_NUMANGLE = {0: (1, 2), 1: (0, 2), 2: (0, 1), 3: ()}   # index -> the others
 CANARY_BYTE = 0xA5   # lists, counts: int32 -0x5A5A5A5B, the canary of the per-entry tests
 GUARD = 64           # int32 words around counts and lists
 NLIST = 12           # count words of a list slot (3 maps per frame of a per-channel context)
-LCAP_MAX, SCAP_MAX = 400, 2000
+LCAP_MAX, SCAP_MAX, CCAP_MAX = 400, 2000, 1024
 CANNY_THR = {3: (50.0, 150.0), 5: (400.0, 1200.0), 7: (3000.0, 9000.0), -1: (160.0, 500.0)}
 KINDS = ("run", "canny", "deriv", "rungrad", "blur", "autothr", "thr_on", "thr_off", "points", "lines", "segs", "sync", "stream")
+# ... and the one kind that make_steps does not draw: add_circles inserts it, from a generator of its own, so that a seed keeps the
+# steps it had before there were circles
+CIRCLES_DP, CIRCLES_MIN_DIST, CIRCLES_THRESHOLD, CIRCLES_CC = (1.0, 1.5, 2.0), (0.0, 3.0, 8.0), (2, 4, 8), (16, 300, 4096)
 VIEW_KINDS = ("whole", "frame", "roi", "before", "behind", "sout")
 COUNTERS = tuple(f"overlap_{k}" for k in ("whole", "frame", "roi", "sout", "before", "behind", "blur_in", "blur_out")) + (
     "adjacent", "hough_tables_equal_numangle", "seg_tables_equal_numangle", "scratch_growths", "n_above_max_batch", "hough_passes_above_one",
-    "line_lists_nonempty", "seg_lists_nonempty", "lists_cut", "staged_runs", "blur_into_pending_copy_dst", "mismatched_geometry", "runs_with_frame_table")
+    "line_lists_nonempty", "seg_lists_nonempty", "lists_cut", "staged_runs", "blur_into_pending_copy_dst", "mismatched_geometry", "runs_with_frame_table",
+    # circles steps: frames with a count above 0 / above a circle capacity that is not 0; calls of more than one pass; calls that
+    # need more scratch than every circles call before them; frames whose stored point count exceeds the point capacity / with
+    # more ranked centres than the centre capacity; centres the smallest distance dropped; calls with no deriv step before them /
+    # with more frames than the last deriv step wrote; calls with a lines call before and behind them and no sync among the three
+    "circle_lists_nonempty", "circle_lists_cut", "circle_passes_above_one", "circle_scratch_growths", "circles_from_cut_points", "circles_centres_cut",
+    "circles_dropped_by_min_dist", "circles_on_unwritten_planes", "circles_on_stale_frames", "circles_between_lines")
 # ... of which the committed seeds together must reach every one but these two: a view beside one output that lies inside its
 # neighbour is a "whole" or "frame" overlap of that neighbour under another name
 REQUIRED = tuple(c for c in COUNTERS if c not in ("overlap_before", "overlap_behind"))
@@ -81,8 +93,10 @@ STAGED_FAMILIES = ("ODDO", "P4_BASE", "ROI_FS")
 # The committed seeds (tests/test_gpu_device_op_sequences.py runs them, tests/test_device_op_sequences_cpu.py checks the conditions):
 # chosen from --scan 0 300 so that together they reach every counter of REQUIRED, every pipelined one has a reader on a view that
 # overlaps a pending writer, every one a segment list that is not empty, and the sizes, modes, channel counts and staged
-# families all occur
-SEEDS = (0, 1, 3, 5, 6, 7, 8, 9, 11, 13, 14, 15, 17, 21, 22, 25, 31, 35, 40, 49, 66, 69, 85, 86, 100, 141, 145, 207)
+# families all occur.  The circles steps came later, from a generator of their own (add_circles), and left those 28 every step they
+# had; of the circle counters of REQUIRED the 28 reach all but two, for which --scan 0 300 gave 58 (circles_on_stale_frames) and
+# 108 (circle_passes_above_one, which takes 61 x 33 frames, a scratch bound and four frames at centre capacity 4096: one seed of the 300)
+SEEDS = (0, 1, 3, 5, 6, 7, 8, 9, 11, 13, 14, 15, 17, 21, 22, 25, 31, 35, 40, 49, 66, 69, 85, 86, 100, 141, 145, 207, 58, 108)
 
 
 def rup(v, m):
@@ -98,18 +112,20 @@ def layout(P):
     w, h, ch = P["w"], P["h"], P["ch"]
     L = dict(w=w, h=h, ch=ch, mb=P.get("max_batch", MAX_BATCH))   # (max_batch: the named cases may ask for another)
     L["nmax"] = L["mb"] * (3 if P["per_channel_ever"] else 1)
+    L["pf"] = max(MAX_BATCH, L["nmax"])   # frames of a gradient plane: a circles step of a per-channel context reads up to nmax
     L["ip"] = rup(w, 8) * ch; L["ifs"] = L["ip"] * h; L["ilead"] = rup(L["ip"] + 64, 512)          # frames / blur: whole 8-pixel groups, in place
     L["op"] = rup(w, 4); L["ofs"] = L["op"] * h; L["oreg"] = L["nmax"] * L["ofs"]; L["olead"] = rup(2 * L["ofs"] + 512, 512)
     sp, sfs, sbase = staged_view(P.get("staged", "ODDO"), w, h)
     L["sp"], L["sfs"], L["soff"] = sp, sfs, rup(sp + 64, 512) + sbase
     L["dp"] = rup(2 * ch * w, 8); L["dfs"] = L["dp"] * h
     L["sizes"] = dict(frames=2 * L["ilead"] + POOL * L["ifs"], blur=2 * L["ilead"] + POOL * L["ifs"], maps=2 * L["olead"] + NOUT * L["oreg"],
-                      sout=L["soff"] + L["nmax"] * sfs + rup(sp + 64, 512), dxdy=1024 + 2 * MAX_BATCH * L["dfs"], thr=4 * (2 * GUARD + 2 * MAX_BATCH))
+                      sout=L["soff"] + L["nmax"] * sfs + rup(sp + 64, 512), dxdy=1024 + 2 * L["pf"] * L["dfs"], thr=4 * (2 * GUARD + 2 * MAX_BATCH))
     words = 3 * GUARD + NLIST
     for k in range(2):
         L["sizes"][f"pts{k}"] = 4 * (words + 2 * NLIST * w * h)
         L["sizes"][f"lines{k}"] = 4 * (words + 3 * NLIST * LCAP_MAX)
         L["sizes"][f"segs{k}"] = 4 * (words + 4 * NLIST * SCAP_MAX)
+        L["sizes"][f"circ{k}"] = 4 * (words + 4 * NLIST * CCAP_MAX)
     L["counts_off"] = 4 * GUARD
     L["list_off"] = 4 * (2 * GUARD + NLIST)
     return L
@@ -170,6 +186,16 @@ def hough_need(w, h, geo, n, bound):
     return fpp * per, (n + fpp - 1) // fpp, per
 
 
+def circle_need(w, h, dp, cc, n, bound):
+    """(scratch bytes, passes, bytes per frame) of hc_hough_circles_device as include/hipcanny.h and plan_hough_circles (host_plan.h)
+    state them: the ranked and the kept centres, the peak list, the accumulator, a count per row and per centre, two counts.
+    (0, 0, bytes per frame) where one frame exceeds the bound: the entry refuses that call."""
+    aw, ah, _ = HC.geometry(w, h, dp, 0.0, 1, 1)
+    per = 2 * 16 * cc + 8 * ah * ((aw + 1) // 2) + 4 * (ah + 2) * (aw + 2) + 4 * ah + 4 * cc + 8
+    fpp = min(n, (bound or (256 << 20)) // per)
+    return (fpp * per, (n + fpp - 1) // fpp, per) if fpp else (0, 0, per)
+
+
 def describe(st):
     return st["kind"] + "(" + ", ".join(f"{k}={v}" for k, v in st.items() if k != "kind") + ")"
 
@@ -209,7 +235,7 @@ class Model:
         self.w, self.h, self.ch = P["w"], P["h"], P["ch"]
         self.buf = {name: np.full(size, 255, np.uint8) for name, size in L["sizes"].items()}
         for name in self.buf:
-            if name[:3] in ("pts", "lin", "seg", "thr"):
+            if name[:3] in ("pts", "lin", "seg", "cir", "thr"):
                 self.buf[name][:] = CANARY_BYTE
         frames = pool_frames(P)
         self.put("frames", L["ilead"], L["ip"], L["ifs"], frames.reshape(POOL, self.h, -1), log=False)
@@ -220,7 +246,10 @@ class Model:
         self.table = False
         self.pending = []          # pipelined runs in flight: (buffer, lo, hi, staged)
         self.hough_key = self.seg_key = None
-        self.hough_bytes = self.seg_bytes = 0
+        self.hough_bytes = self.seg_bytes = self.circle_bytes = 0
+        self.deriv_n = None        # frames the last deriv step wrote (None: the planes still hold the arena's fill)
+        self.lines_queued = False  # a lines step since the last sync ...
+        self.circles_open = 0      # ... and the circles steps behind it that no lines step has followed yet
         self.counters = dict.fromkeys(COUNTERS, 0)
         self.writes = []           # (step, buffer, lo, hi)
         self.step = -1
@@ -315,12 +344,13 @@ class Model:
 
     def _planes(self, n):
         L = self.L
-        return [(512 + p * MAX_BATCH * L["dfs"], L["dp"], L["dfs"]) for p in range(2)]
+        return [(512 + p * L["pf"] * L["dfs"], L["dp"], L["dfs"]) for p in range(2)]
 
     def do_deriv(self, st):
         dx, dy = D.sobel16_frames(self._frames("frames", st["f0"], st["n"]), st["ksize"])
         for (off, pitch, fs), plane in zip(self._planes(st["n"]), (dx, dy)):
             self.put("dxdy", off, pitch, fs, plane.reshape(st["n"], self.h, -1))
+        self.deriv_n = st["n"]
 
     def do_rungrad(self, st):
         shape = (st["n"], self.h, self.w) + ((3,) if self.ch == 3 else ())
@@ -360,9 +390,11 @@ class Model:
 
     def do_sync(self, st):
         self.pending = []
+        self.lines_queued, self.circles_open = False, 0
 
     def do_stream(self, st):
         self.pending = []
+        self.lines_queued, self.circles_open = False, 0
 
     def do_option(self, st):   # (named cases: hc_set_option completes what is in flight)
         self.pending = []
@@ -398,6 +430,8 @@ class Model:
         if self.hough_key is not None and key != self.hough_key and key[0] == self.hough_key[0]:
             self.counters["hough_tables_equal_numangle"] += 1
         self.hough_key = key
+        self.counters["circles_between_lines"] += self.circles_open
+        self.lines_queued, self.circles_open = True, 0
         need, passes, _ = hough_need(self.w, self.h, geo, st["n"], self.P["hough_bound"])
         self.counters["scratch_growths"] += 0 < self.hough_bytes < need
         self.hough_bytes = max(self.hough_bytes, need)
@@ -430,6 +464,36 @@ class Model:
                 self.put_words(name, L["list_off"] + 16 * cap * f, segs)
             self.counters["seg_lists_nonempty"] += c > 0
             self.counters["lists_cut"] += c > cap > 0
+
+    def do_circles(self, st):
+        """hc_hough_circles_device on the point lists of slot pslot and the first W int16 of every row of the gradient planes --
+        whatever they hold: the planes of the last deriv step (on a 3-channel context its interleaved rows, of which the entry
+        reads a defined one-channel view), older planes in the frames behind that step's n, the arena's fill (-1, -1: every ray
+        a diagonal) where no deriv step wrote.  The entry is no reader of edge maps: it completes no run (no _reader call)."""
+        L, n, cap, name, c = self.L, st["n"], st["ccap"], f"circ{st['cslot']}", self.counters
+        need, passes, _ = circle_need(self.w, self.h, st["dp"], st["cc"], n, self.P["hough_bound"])
+        assert passes, f"one frame of {describe(st)} exceeds the scratch bound: the entry refuses it"
+        c["circle_scratch_growths"] += 0 < self.circle_bytes < need
+        self.circle_bytes = max(self.circle_bytes, need)
+        c["circle_passes_above_one"] += passes > 1
+        c["n_above_max_batch"] += n > MAX_BATCH
+        c["circles_on_unwritten_planes"] += self.deriv_n is None
+        c["circles_on_stale_frames"] += self.deriv_n is not None and n > self.deriv_n
+        self.circles_open += self.lines_queued
+        pts = [self._list(f"pts{st['pslot']}", f, st["pcap"], 2, np.int32) for f in range(n)]
+        stored = self.words(f"pts{st['pslot']}", L["counts_off"], n, np.uint32)
+        dx, dy = (self.get("dxdy", off, pitch, fs, n, 2 * self.w).view(np.int16) for off, pitch, fs in self._planes(n))
+        par, stats = (st["dp"], st["min_dist"], st["threshold"], st["rmin"], st["rmax"]), {}
+        counts, circles = HC.circles_batch(pts, dx, dy, self.w, self.h, *par, centre_capacity=st["cc"], capacity=cap, stats=stats)
+        c["circles_dropped_by_min_dist"] += stats.get("dropped", 0)
+        self.put_words(name, L["counts_off"], counts)
+        for f in range(n):
+            if len(circles[f]):
+                self.put_words(name, L["list_off"] + 16 * cap * f, circles[f])
+            c["circle_lists_nonempty"] += int(counts[f]) > 0
+            c["circle_lists_cut"] += int(counts[f]) > cap > 0
+            c["circles_from_cut_points"] += int(stored[f]) > st["pcap"]
+            c["circles_centres_cut"] += len(HC.centres(HC.accumulate(pts[f], dx[f], dy[f], self.w, self.h, par[0], par[3], par[4]), par[2])) > st["cc"]
 
 
 def run_model(P, steps, O=None):
@@ -604,11 +668,39 @@ def make_steps(P, rng):
     return steps
 
 
-def make_sequence(seed, O=None):
-    """(context parameters, steps, counters) of a seed: numpy.random.default_rng(seed) and the host model, nothing else."""
+def add_circles(P, steps, rng):
+    """Inserts 1 .. 3 circles steps into `steps`: each behind the opening's points step, before the final sync and never directly
+    in front of a stream step (the sync there stays adjacent to the switch: include/hipcanny.h on calls that share scratch).  A
+    circles step reads the lists of the points step most recently in front of it, whichever slot and capacity, 0 included.  Every
+    draw comes from `rng`, a generator of the circles' own: the steps make_steps drew stay what they were, in their order."""
+    w, h, bound = P["w"], P["h"], P["hough_bound"]
+    steps = list(steps)
+    first = next(i for i, st in enumerate(steps) if st["kind"] == "points")
+    for _ in range(int(rng.integers(1, 4))):
+        at = int(rng.choice([i for i in range(first + 1, len(steps)) if steps[i]["kind"] != "stream"]))   # the step goes in front of steps[at]
+        pts = next(st for st in reversed(steps[:at]) if st["kind"] == "points")
+        rmin, rmax = ((1, 6), (2, min(w, h) // 2), (3, 66))[int(rng.integers(0, 3))]
+        st = dict(kind="circles", pslot=pts["slot"], pcap=pts["cap"], n=int(rng.integers(1, min(pts["n"], MAX_BATCH) + 1)), dp=float(rng.choice(CIRCLES_DP)),
+                  min_dist=float(rng.choice(CIRCLES_MIN_DIST)), threshold=int(rng.choice(CIRCLES_THRESHOLD)), rmin=rmin, rmax=rmax, cc=int(rng.choice(CIRCLES_CC)),
+                  cslot=int(rng.integers(0, 2)), ccap=int(rng.choice([0, 8, CCAP_MAX])))
+        while bound and circle_need(w, h, st["dp"], st["cc"], 1, 0)[2] > bound and st["cc"] > CIRCLES_CC[0]:   # no committed step is refused: the smaller capacity
+            st["cc"] = CIRCLES_CC[CIRCLES_CC.index(st["cc"]) - 1]
+        steps.insert(at, st)
+    return steps
+
+
+def base_sequence(seed):
+    """(context parameters, steps) of a seed as make_steps draws them from numpy.random.default_rng(seed): no circles step."""
     rng = np.random.default_rng(seed)
     P = make_params(rng)
-    steps = make_steps(P, rng)
+    return P, make_steps(P, rng)
+
+
+def make_sequence(seed, O=None):
+    """(context parameters, steps, counters) of a seed: the steps of numpy.random.default_rng(seed), the circles steps of
+    numpy.random.default_rng([seed, 1]) inserted among them, and the host model; nothing else."""
+    P, steps = base_sequence(seed)
+    steps = add_circles(P, steps, np.random.default_rng([seed, 1]))
     return P, steps, dict(run_model(P, steps, O).counters)
 
 
@@ -702,6 +794,11 @@ class Executor:
             l, s = f"lines{st['lslot']}", f"segs{st['sslot']}"
             ctx.hough_segments_device(*self._view(st["view"]), self._list(l), self._counts(l), st["lcap"], st["n"], *GEOS[st["geo"]], st["min_length"], st["max_gap"],
                                       self._counts(s), self._list(s), st["scap"])
+        elif k == "circles":
+            p, o = f"pts{st['pslot']}", f"circ{st['cslot']}"
+            (xo, pitch, fs), (yo, _, _) = self.model._planes(st["n"])
+            ctx.hough_circles_device(self._list(p), self._counts(p), st["pcap"], self.ptr["dxdy"] + xo, self.ptr["dxdy"] + yo, pitch, fs, st["n"], st["dp"], st["min_dist"],
+                                     st["threshold"], st["rmin"], st["rmax"], st["cc"], self._counts(o), self._list(o), st["ccap"])
         elif k == "sync":
             self.check()
         elif k == "stream":
@@ -759,7 +856,8 @@ def main(argv):
     if len(argv) > 3 and argv[1] == "--scan":
         for seed in range(int(argv[2]), int(argv[3])):
             P, steps, c = make_sequence(seed, O)
-            print(seed, f"{P['w']}x{P['h']} ch{P['ch']} {P['mode']} pc{int(P['per_channel'])} piped{int(P['pipeline'])} bound{int(bool(P['hough_bound']))} {P['staged']}", len(steps),
+            print(seed, f"{P['w']}x{P['h']} ch{P['ch']} {P['mode']} pc{int(P['per_channel'])} piped{int(P['pipeline'])} bound{int(bool(P['hough_bound']))} {P['staged']}",
+                  f"{len(steps)} steps, {sum(st['kind'] == 'circles' for st in steps)} of them circles",
                   " ".join(f"{k}={v}" for k, v in c.items() if v), flush=True)
         return 0
     if len(argv) > 2 and argv[1] == "--seed":

@@ -1,10 +1,14 @@
 """tests/device_op_sequences.py without a GPU: the committed seeds give the same sequence and the same expected buffers every time,
 exercise what they were chosen for (no vacuous sequence), and contain no call an entry would refuse -- by the limits
 include/hipcanny.h documents for each entry, checked here on the steps and the layout of the buffers."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
 import device_op_sequences as DS
+from test_sanitizers import ENV, ROOT, SAN, _cc
 
 
 @pytest.fixture(scope="module")
@@ -16,8 +20,23 @@ def test_make_sequence_is_deterministic(oracle, sequences):
     for seed in DS.SEEDS:
         assert DS.make_sequence(seed, oracle) == sequences[seed], seed
     for seed, (P, steps, _) in sequences.items():
-        assert 12 <= len(steps) <= 20 and steps[-1]["kind"] == "sync", seed
+        assert 12 <= len([st for st in steps if st["kind"] != "circles"]) <= 20 and len(steps) <= 23 and steps[-1]["kind"] == "sync", seed
         assert (P["w"], P["h"]) in DS.SIZES and P["ch"] in (1, 3) and P["staged"] in DS.STAGED_FAMILIES, seed
+
+
+def test_the_circles_steps_leave_every_other_step_where_it_was(sequences):
+    """The circles steps come from a generator of their own: without them a sequence is, step for step, what
+    numpy.random.default_rng(seed) alone gives -- the sequence the seed was chosen for.  Each stands behind the opening's points
+    step, reads the lists of the points step most recently in front of it, and none stands directly in front of a stream switch."""
+    for seed, (P, steps, _) in sequences.items():
+        P0, base = DS.base_sequence(seed)
+        assert P0 == P and [st for st in steps if st["kind"] != "circles"] == base and not any(st["kind"] == "circles" for st in base), seed
+        at = [i for i, st in enumerate(steps) if st["kind"] == "circles"]
+        assert 1 <= len(at) <= 3, seed
+        for i in at:
+            pts = [st for st in steps[:i] if st["kind"] == "points"]
+            assert pts and (steps[i]["pslot"], steps[i]["pcap"]) == (pts[-1]["slot"], pts[-1]["cap"]) and 1 <= steps[i]["n"] <= min(pts[-1]["n"], DS.MAX_BATCH), (seed, i)
+            assert steps[i + 1]["kind"] != "stream", (seed, i)
 
 
 def test_the_model_gives_identical_buffers_twice(oracle, sequences):
@@ -41,6 +60,8 @@ def vacuous(sequences):
             bad.append(f"seed {seed}: every segment list is empty")
         if not c["line_lists_nonempty"]:
             bad.append(f"seed {seed}: every line list is empty")
+    if total["circle_lists_nonempty"] < len(sequences):
+        bad.append(f"{total['circle_lists_nonempty']} circle lists that are not empty in {len(sequences)} sequences")
     bad += [f"no sequence reaches {k}" for k in DS.REQUIRED if not total[k]]
     return bad
 
@@ -51,6 +72,7 @@ def test_no_vacuous_sequences(oracle, sequences):
     kinds = {k: sum(any(st["kind"] == k for st in steps) for _, steps, _ in sequences.values()) for k in DS.KINDS}
     assert all(kinds[k] > len(DS.SEEDS) // 2 for k in ("run", "blur", "points", "lines", "segs", "sync")), kinds
     assert all(kinds[k] > 0 for k in DS.KINDS), kinds
+    assert all(any(st["kind"] == "circles" for st in steps) for _, steps, _ in sequences.values())
     assert sum(P["pipeline"] for P, _, _ in sequences.values()) * 2 >= len(DS.SEEDS)
     assert {(P["w"], P["h"]) for P, _, _ in sequences.values()} == set(DS.SIZES)
     assert any(P["per_channel"] for P, _, _ in sequences.values()) and {P["mode"] for P, _, _ in sequences.values()} == {"R", "O"}
@@ -81,10 +103,43 @@ def test_hough_geometries(oracle):
         assert not any(np.array_equal(tabs[a], tabs[b]) for a, b in ((0, 1), (0, 2), (1, 2)))
 
 
-def test_no_step_would_be_refused(oracle, sequences):
+@pytest.fixture(scope="module")
+def circle_plans(tmp_path_factory):
+    """plan_hough_circles itself (cudacam_amd/csrc/host_plan.h) on circles steps: tests/cpp/hough_circles_plan_driver.cpp, built as
+    tests/test_hough_circles_plan_cpu.py builds it.  Returns plans(P, steps) -> one (scratch bytes, passes, frames per pass) or
+    refusal text per step, for the planes and the frame limit the executor gives the entry."""
+    exe = str(tmp_path_factory.mktemp("circles") / "hough_circles_plan_driver")
+    _cc(["g++", "-std=c++17", "-Wall", "-Werror", *SAN, "-o", exe, os.path.join(ROOT, "tests", "cpp", "hough_circles_plan_driver.cpp")])
+
+    def plans(P, steps):
+        L = DS.layout(P)
+        args = [exe, "plan", str(P["w"]), str(P["h"]), str(L["nmax"] if P["per_channel"] else L["mb"])]
+        for st in steps:
+            args += [str(st["n"]), str(st["pcap"]), str(L["dp"]), str(L["dfs"]), float(st["dp"]).hex(), float(st["min_dist"]).hex(), str(st["threshold"]), str(st["rmin"]), str(st["rmax"]),
+                     str(st["cc"]), str(st["ccap"]), str(P["hough_bound"])]
+        out = subprocess.run(args, capture_output=True, text=True, timeout=600, env=ENV)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        rows = out.stdout.splitlines()
+        assert len(rows) == len(steps)
+        return [r if r.startswith("refused") else tuple(int(v) for v in r.split()) for r in rows]
+    return plans
+
+
+def test_the_plan_driver_refuses_what_the_entry_refuses(circle_plans):
+    """The driver's answers are the plan's: a frame too many, a centre capacity of 0 and a bound below one frame are refused."""
+    P, _ = DS.base_sequence(DS.SEEDS[0])
+    good = dict(kind="circles", pslot=0, pcap=5, n=1, dp=1.0, min_dist=3.0, threshold=2, rmin=1, rmax=6, cc=16, cslot=0, ccap=8)
+    got = circle_plans(dict(P, hough_bound=0), [good, dict(good, n=DS.layout(P)["nmax"] + 1), dict(good, cc=0), dict(good, pcap=0, ccap=0)])
+    assert isinstance(got[0], tuple) and "nframes out of range" in got[1] and "centre_capacity" in got[2] and got[3] == got[0], got
+    assert "scratch bound" in circle_plans(dict(P, hough_bound=DS.circle_need(P["w"], P["h"], 1.0, 16, 1, 0)[2] - 1), [good])[0]
+
+
+def test_no_step_would_be_refused(oracle, sequences, circle_plans):
     """The documented limits of include/hipcanny.h on every step: frame counts, alignments, views inside their buffers, views of a
     blur that do not overlap, lists and tables read only after they were written with the same strides, stream switches behind a
-    synchronisation."""
+    synchronisation.  The circles steps are given to plan_hough_circles itself, which also says how much scratch and how many
+    passes each takes: circle_need, by which the model counts growths and passes, must say the same."""
+    nplans = 0
     for seed, (P, steps, _) in sequences.items():
         L = DS.layout(P)
         size = L["sizes"]
@@ -94,6 +149,8 @@ def test_no_step_would_be_refused(oracle, sequences):
         assert L["ip"] >= DS.rup(P["w"], 8) * P["ch"] and L["ip"] % 4 == 0 and L["ilead"] % 4 == 0
         assert L["counts_off"] % 4 == 0 and L["list_off"] % 16 == 0 and L["dp"] % 2 == 0
         plist, llist, table, table_on, deriv, blur, prev = {}, {}, False, False, 0, 0, None
+        m0 = DS.Model.__new__(DS.Model)
+        m0.L = L
         for i, st in enumerate(steps):
             k, what = st["kind"], f"seed {seed} step {i}: {DS.describe(st)}"
             if k in ("run", "canny", "rungrad", "deriv", "blur", "autothr"):
@@ -144,7 +201,17 @@ def test_no_step_would_be_refused(oracle, sequences):
                 n, cap, geo = llist[st["lslot"]]
                 assert st["n"] <= n and st["lcap"] == cap > 0 and st["lgeo"] == geo and DS.list_fits("segs", st["n"], st["scap"], 4, L), what
                 assert st["geo"] == geo or st["geo"] in DS.SAME_NUMANGLE[geo], what
+            if k == "circles":
+                n, cap = plist[st["pslot"]]
+                assert 1 <= st["n"] <= min(n, limit) and st["pcap"] == cap and DS.list_fits("circ", st["n"], st["ccap"], 4, L) and st["ccap"] <= DS.CCAP_MAX, what
+                assert (512 + L["pf"] * L["dfs"]) % 2 == 0 and DS.view_span(L, DS.Model._planes(m0, st["n"])[1][0], L["dp"], L["dfs"], st["n"], 2 * P["w"])[1] <= size["dxdy"], what
             if k == "stream":
                 assert prev == "sync", what
             prev = k
         assert not table_on, f"seed {seed}: the table is still installed at the end"
+        circles = [st for st in steps if st["kind"] == "circles"]
+        for st, plan in zip(circles, circle_plans(P, circles)):
+            need = DS.circle_need(P["w"], P["h"], st["dp"], st["cc"], st["n"], P["hough_bound"])
+            assert isinstance(plan, tuple) and plan[:2] == need[:2] and plan[1] >= 1 and plan[2] * need[2] == need[0], (seed, DS.describe(st), plan, need)
+            nplans += 1
+    assert nplans >= len(sequences)

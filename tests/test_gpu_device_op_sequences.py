@@ -50,6 +50,19 @@ def _segs(view, n, lslot, lcap, geo, sslot, scap=DS.SCAP_MAX, lgeo=None):
     return dict(kind="segs", view=view, n=n, lslot=lslot, lcap=lcap, lgeo=geo if lgeo is None else lgeo, geo=geo, min_length=3, max_gap=2, sslot=sslot, scap=scap)
 
 
+def _circles(n, P, cslot=0, pslot=0, pcap=None, dp=1.0, min_dist=3.0, threshold=4, rmin=2, rmax=None, cc=4096, ccap=DS.CCAP_MAX):
+    return dict(kind="circles", pslot=pslot, pcap=P["w"] * P["h"] if pcap is None else pcap, n=n, dp=dp, min_dist=min_dist, threshold=threshold, rmin=rmin,
+                rmax=min(P["w"], P["h"]) // 2 if rmax is None else rmax, cc=cc, cslot=cslot, ccap=ccap)
+
+
+def _deriv(n, f0=0, ksize=3):
+    return dict(kind="deriv", f0=f0, n=n, ksize=ksize)
+
+
+def _circle_counts(model, cslot, n):
+    return model.words(f"circ{cslot}", model.L["counts_off"], n, np.uint32).tolist()
+
+
 def _blur(src, f0, dst, g0, n):
     return dict(kind="blur", src=src, f0=f0, dst=dst, g0=g0, n=n, ksize=5, sigma=1.2, border=0)
 
@@ -131,17 +144,18 @@ def _refused(call, entry):
 def test_three_channels_and_per_channel(oracle):
     """A 3-channel Mode R context with HC_OPT_PER_CHANNEL and max_batch 2: points, lines and segments take the 6 maps of a run and
     refuse 7; without the option they take 2 and refuse 3; switching the option between two chains leaves both right.  Blur,
-    derivatives and automatic thresholds on the same context."""
+    derivatives and automatic thresholds on the same context -- and circles, which take as many frames: of the gradient planes
+    the entry reads the first W int16 of each interleaved row, in the frames behind the two that were written whatever is there."""
     P = _params(w=65, h=64, ch=3, pipeline=True, per_channel=True, max_batch=2)
     with DS.Executor(P, oracle, "per-channel") as e:
         def chain(n):
             for st in (_run(0, 0, n=2), _points(("whole", 0), n, P=P), _lines(n, 3, 0, 64, P), _segs(("whole", 0), n, 0, 64, 3, 0),
-                       _blur("frames", 1, "blur", 0, 2), dict(kind="deriv", f0=2, n=2, ksize=7), dict(kind="autothr", f0=0, n=2, rule=1, param=0.5)):
+                       _blur("frames", 1, "blur", 0, 2), dict(kind="deriv", f0=2, n=2, ksize=7), _circles(n, P, threshold=8, cc=300), dict(kind="autothr", f0=0, n=2, rule=1, param=0.5)):
                 e.queue(st)
 
         def at_the_limit_and_beyond(n):
-            """Points, lines and segments of n maps into the second slots with capacity 8 each: taken.  The same pointers, pitches
-            and capacities with n + 1: refused for nframes, and nothing is written."""
+            """Points, lines, segments and circles of n maps into the second slots with capacity 8 each: taken.  The same pointers,
+            pitches and capacities with n + 1: refused for nframes, and nothing is written."""
             for st in (_points(("whole", 0), n, slot=1, cap=8), dict(kind="lines", pslot=1, pcap=8, n=n, geo=0, threshold=5, lslot=1, lcap=8), _segs(("whole", 0), n, 1, 8, 0, 1, scap=8)):
                 e.queue(st)
             p, l, s = (e._counts(f"{b}1") for b in ("pts", "lines", "segs"))
@@ -150,10 +164,15 @@ def test_three_channels_and_per_channel(oracle):
             _refused(lambda: e.ctx.edge_points_device(*m, n + 1, p, pl, 8), "hc_edge_points_device")
             _refused(lambda: e.ctx.hough_lines_device(pl, p, 8, n + 1, geo[0], geo[1], 5, geo[2], geo[3], l, ll, 8), "hc_hough_lines_device")
             _refused(lambda: e.ctx.hough_segments_device(*m, ll, l, 8, n + 1, *geo, 3, 2, s, sl, 8), "hc_hough_segments_device")
+            e.queue(_circles(n, P, cslot=1, pslot=1, pcap=8, threshold=2, rmax=6, cc=300, ccap=8))
+            (xo, pitch, fs), (yo, _, _) = e.model._planes(n)
+            _refused(lambda: e.ctx.hough_circles_device(pl, p, 8, e.ptr["dxdy"] + xo, e.ptr["dxdy"] + yo, pitch, fs, n + 1, 1.0, 3.0, 2, 2, 6, 300, e._counts("circ1"), e._list("circ1"), 8),
+                     "hc_hough_circles_device")
         chain(6)
         at_the_limit_and_beyond(6)
         e.check()
         assert e.model.counters["n_above_max_batch"] >= 6 and e.model.counters["seg_lists_nonempty"] > 0
+        assert e.model.counters["circle_lists_nonempty"] > 0 and e.model.counters["circles_on_stale_frames"] == 2
         e.queue(dict(kind="option", option=api.OPT_PER_CHANNEL, value=0))
         chain(2)
         at_the_limit_and_beyond(2)
@@ -166,13 +185,16 @@ def test_three_channels_and_per_channel(oracle):
 
 def test_three_channels_mode_o(oracle):
     """The entries that had not met a 3-channel context: canny_device at every aperture, blur, derivatives chained with the gradient
-    run, automatic thresholds installed as the table of a run -- then points, lines and segments of what they wrote."""
+    run, automatic thresholds installed as the table of a run -- then points, lines, segments and circles of what they wrote (the
+    circles from a one-channel view of the interleaved Scharr planes, and in frame 3 of what no deriv step wrote)."""
     P = _params(w=61, h=33, ch=3, mode="O", pipeline=True)
     steps = [dict(kind="canny", f0=k, n=2, out=k % 3, low=DS.CANNY_THR[ap][0], high=DS.CANNY_THR[ap][1], aperture=ap, l2=int(ap == 5)) for k, ap in enumerate((3, 5, 7, -1))]
     steps += [_blur("frames", 0, "blur", 0, 4), dict(kind="autothr", f0=1, rule=0, param=0.33), dict(kind="thr_on"), _run(0, 1, src="blur"),
               dict(kind="deriv", f0=2, n=3, ksize=-1), dict(kind="rungrad", n=3, out=2), dict(kind="thr_off"),
-              _points(("whole", 1), 4, P=P), _lines(4, 3, 0, DS.LCAP_MAX, P), _segs(("frame", 2, 2), 1, 0, DS.LCAP_MAX, 3, 0), _points(("whole", 0), 2, slot=1, cap=5, P=P)]
-    DS.execute(P, steps, oracle, "3 channels, mode O")
+              _points(("whole", 1), 4, P=P), _lines(4, 3, 0, DS.LCAP_MAX, P), _segs(("frame", 2, 2), 1, 0, DS.LCAP_MAX, 3, 0), _circles(4, P),
+              _points(("whole", 0), 2, slot=1, cap=5, P=P)]
+    model = DS.execute(P, steps, oracle, "3 channels, mode O")
+    assert model.counters["circle_lists_nonempty"] > 0 and model.counters["circles_on_stale_frames"] == 1
 
 
 def test_growth_across_entries(oracle):
@@ -183,3 +205,103 @@ def test_growth_across_entries(oracle):
              _segs(("whole", 0), 1, 0, 4, 0, 0), _segs(("whole", 0), 4, 1, DS.LCAP_MAX, 3, 1)]
     model = DS.execute(P, steps, oracle, "growth")
     assert model.counters["scratch_growths"] == 2 and model.counters["seg_lists_nonempty"] >= 4 and model.counters["lists_cut"] > 0, model.counters
+
+
+# ---- circles in company: hc_hough_circles_device chained behind the entries that write its inputs, between the Hough-line calls it
+# shares a scratch bound with, and on contexts with runs in flight.  tests/test_gpu_hough_circles.py has the kernels, call by call.
+def test_lines_and_circles_alternate_under_one_bound(oracle):
+    """Five calls queued with no synchronisation under the one bound of both scratches (two frames of the 180-angle line geometry):
+    lines of that geometry take two passes of two frames, circles with 4096 centres two passes of three and one, lines of twelve
+    angles and circles with 16 centres one pass -- each with its own scratch, cut by its own plan."""
+    w, h = 61, 33
+    P = _params(w=w, h=h, mode="O", pipeline=False, hough_bound=2 * DS.hough_need(w, h, DS.GEO_BIG, 1, 0)[2])
+    first, second = _circles(4, P, cslot=0, dp=1.0, cc=4096), _circles(4, P, cslot=1, dp=2.0, cc=16)
+    steps = [_run(0, 0), _points(("whole", 0), 4, P=P), _deriv(4), _lines(4, 3, 0, DS.LCAP_MAX, P), first, _lines(4, 0, 1, 64, P), second, _lines(4, 3, 0, DS.LCAP_MAX, P)]
+    assert DS.hough_need(w, h, DS.GEO_BIG, 4, P["hough_bound"])[1] == 2 and DS.hough_need(w, h, DS.GEO_A, 4, P["hough_bound"])[1] == 1
+    assert [DS.circle_need(w, h, st["dp"], st["cc"], 4, P["hough_bound"])[1] for st in (first, second)] == [2, 1]
+    model = DS.execute(P, steps, oracle, "lines and circles under one bound")
+    c = model.counters
+    assert c["hough_passes_above_one"] == 2 and c["circle_passes_above_one"] == 1 and c["circles_between_lines"] == 2, c
+    assert min(_circle_counts(model, 0, 4)) > 0 and min(_circle_counts(model, 1, 4)) > 0 and c["line_lists_nonempty"] == 12, c
+
+
+def test_the_real_chain_pipelined(oracle):
+    """cv::Canny, its derivatives, the edge points and the circles of four frames, queued with no synchronisation on a pipelined
+    context: the point reader completes the run (its content needs the host continuation), the circles follow on the stream.
+    Then circles of the same lists again while runs into two OTHER outputs are in flight: no run writes a point list or a
+    gradient plane, so the entry completes none of them -- read off the device as test_the_neighbour_stays_in_flight reads it."""
+    import torch
+    P = _params(w=130, h=67, mode="O", pipeline=True)
+    L = DS.layout(P)
+    with DS.Executor(P, oracle, "the real chain") as e:
+        for st in (dict(kind="canny", f0=0, n=4, out=0, low=DS.CANNY_THR[3][0], high=DS.CANNY_THR[3][1], aperture=3, l2=0), _deriv(4), _points(("whole", 0), 4, P=P),
+                   _circles(4, P, cslot=0)):
+            e.queue(st)
+        assert e.model.counters["overlap_whole"] == 1 and not e.model.pending
+        e.check()
+        assert min(_circle_counts(e.model, 0, 4)) > 0 and e.model.counters["circles_on_stale_frames"] == 0
+        before = e.continued_runs()
+        assert before > 0
+        for st in (_run(0, 1), _run(0, 2, n=2)):
+            e.queue(st)
+        e.queue(_circles(4, P, cslot=1, dp=2.0))
+        assert len(e.model.pending) == 2 and e.model.counters["overlap_whole"] == 1
+        torch.cuda.synchronize()   # the device, not the context: no run is completed by this
+        got, want = e.d["maps"].cpu().numpy(), e.model.buf["maps"]
+        for k, n in ((1, 4), (2, 2)):
+            a = DS.out_start(L, k)
+            assert not np.array_equal(got[a:a + n * L["ofs"]], want[a:a + n * L["ofs"]]), f"output {k} already holds its final maps: the circles call completed its run, or its content needs no continuation"
+        e.check()
+        assert min(_circle_counts(e.model, 1, 4)) > 0 and e.continued_runs() == before + 2
+
+
+def test_circles_of_planes_nobody_wrote_and_of_stale_frames(oracle):
+    """The gradient planes are the caller's bytes: before any derivative call they hold what the allocation held (here int16 -1,
+    -1 everywhere: every ray a diagonal), behind the frames of the last call what an earlier one left.  Circles of exactly that."""
+    P = _params(w=65, h=64, mode="R", pipeline=True)
+    steps = [_run(0, 0), _points(("whole", 0), 4, P=P), _circles(4, P, cslot=0), _deriv(2), _circles(4, P, cslot=1), _deriv(4, f0=1, ksize=7), _deriv(1, f0=2, ksize=3),
+             _circles(4, P, cslot=0, dp=1.5)]
+    model = DS.execute(P, steps, oracle, "unwritten and stale planes")
+    c = model.counters
+    assert c["circles_on_unwritten_planes"] == 1 and c["circles_on_stale_frames"] == 2 and c["circle_lists_nonempty"] >= 8, c
+
+
+def test_circle_scratch_grows_while_a_call_is_queued(oracle):
+    """One frame with 16 centres at dp 2, then four frames with 4096 at dp 1 (the scratch is allocated again, behind a
+    synchronisation of the stream the first call is queued on), then the first call again into the other slot: in the larger
+    scratch its sections lie elsewhere, its circles are the same."""
+    P = _params(w=250, h=66, mode="R", pipeline=False)
+    small = dict(dp=2.0, cc=16, threshold=3)
+    steps = [_run(0, 0), _points(("whole", 0), 4, P=P), _deriv(4), _circles(1, P, cslot=0, **small), _circles(4, P, cslot=1, dp=1.0, cc=4096, threshold=3), _circles(1, P, cslot=1, **small)]
+    model = DS.execute(P, steps, oracle, "circle scratch growth")
+    assert model.counters["circle_scratch_growths"] == 1, model.counters
+    (k0,), (k1,) = _circle_counts(model, 0, 1), _circle_counts(model, 1, 1)
+    assert k0 == k1 > 0 and np.array_equal(model.words("circ0", model.L["list_off"], 4 * k0, np.int32), model.words("circ1", model.L["list_off"], 4 * k0, np.int32))
+
+
+def test_circles_of_cut_inputs_and_into_cut_outputs(oracle):
+    """Point lists cut by their capacity (the stored counts stay above it), centres cut by centre_capacity, circles cut by
+    circle_capacity 8, and circle_capacity 0 with a pointer: the counts alone, the lists of the call before untouched."""
+    P = _params(w=130, h=67, mode="R", pipeline=True)
+    steps = [_run(0, 0), _deriv(4), _points(("whole", 0), 4, slot=1, cap=5, P=P), _circles(4, P, cslot=0, pslot=1, pcap=5, threshold=1, min_dist=0.0, rmin=1, rmax=6),
+             _points(("whole", 0), 4, slot=0, P=P), _circles(4, P, cslot=1, cc=16, threshold=2), _circles(4, P, cslot=0, ccap=8, threshold=2), _circles(4, P, cslot=1, ccap=0, threshold=2, dp=1.5)]
+    with DS.Executor(P, oracle, "cut inputs and outputs") as e:
+        seen = []
+        for st in steps:
+            e.queue(st)
+            seen.append(dict(e.model.counters))
+        e.check()
+    assert seen[3]["circles_from_cut_points"] == 4 and seen[3]["lists_cut"] == 4, seen[3]
+    assert seen[5]["circles_centres_cut"] > 0 and seen[5]["circle_lists_nonempty"] > seen[4]["circle_lists_nonempty"], seen[5]
+    assert seen[6]["circle_lists_cut"] > seen[5]["circle_lists_cut"] and seen[7]["circle_lists_cut"] == seen[6]["circle_lists_cut"], seen[7]
+    assert seen[7]["circle_lists_nonempty"] > seen[6]["circle_lists_nonempty"], seen[7]
+
+
+def test_circles_across_a_stream_switch(oracle):
+    """Circles on the context's own stream, on a caller's stream and on its own again, each switch behind a synchronisation as
+    include/hipcanny.h asks of calls that share scratch; the second geometry needs a larger scratch than the first."""
+    P = _params(w=61, h=33, mode="R", pipeline=True)
+    steps = [_run(0, 0), _points(("whole", 0), 4, P=P), _deriv(4), _circles(4, P, cslot=0, dp=2.0, cc=16), SYNC, dict(kind="stream", to="side"),
+             _circles(4, P, cslot=1, dp=1.0, cc=4096, rmin=3, rmax=66), SYNC, dict(kind="stream", to="own"), _circles(2, P, cslot=0, dp=1.5, cc=300)]
+    model = DS.execute(P, steps, oracle, "circles across a stream switch")
+    assert model.counters["circle_lists_nonempty"] >= 6 and model.counters["circle_scratch_growths"] == 1, model.counters

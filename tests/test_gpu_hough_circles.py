@@ -54,20 +54,22 @@ def _scene(w, h, seed, extra_points=0):
 def _upload(points, counts, dx, dy, circle_capacity, point_capacity=None, pitch=None, frame_stride=None, base_off=0):
     """The buffers of one call: per-frame point lists (k_f, 2) padded to [n][pcap][2] with a poison coordinate, their counts, both
     planes [n, h, w] int16 inside arenas of random bytes, the circle counts between two guard words and the circle slots between
-    guards, pre-filled with the canary."""
+    guards, pre-filled with the canary.  point_capacity 0 is taken as given: the lists are [n][0][2], and d_points is a buffer of
+    poison coordinates the entry has no reason to read."""
     import torch
     n, h, w = dx.shape
-    pcap = point_capacity or max(1, max(len(p) for p in points))
+    pcap = max(1, max(len(p) for p in points)) if point_capacity is None else point_capacity
     lists = np.full((n, pcap, 2), 0x7F7F7F7F, np.int32)
     for f, p in enumerate(points):
         lists[f, :min(len(p), pcap)] = p[:pcap]
+    on_device = lists if pcap else np.full((n, 64, 2), 0x7F7F7F7F, np.int32)
     pitch = pitch or 2 * w
     ax, off = VA.make_input(dx, pitch, frame_stride, base_off, fill="random", seed=1)
     ay, _ = VA.make_input(dy, pitch, frame_stride, base_off, fill="random", seed=2)
     g = VA.input_geometry(dx, pitch, frame_stride, base_off)
     counts = np.asarray(counts, np.uint32)
-    return dict(n=n, w=w, h=h, lists=lists, pcounts=counts, pcap=pcap, dx=dx, dy=dy, ax=ax, ay=ay, off=off, g=g, cap=circle_capacity,
-                d_pts=torch.from_numpy(lists).cuda(), d_pc=torch.from_numpy(counts.view(np.int32)).cuda(), d_ax=torch.from_numpy(ax).cuda(), d_ay=torch.from_numpy(ay).cuda(),
+    return dict(n=n, w=w, h=h, lists=lists, on_device=on_device, pcounts=counts, pcap=pcap, dx=dx, dy=dy, ax=ax, ay=ay, off=off, g=g, cap=circle_capacity,
+                d_pts=torch.from_numpy(on_device).cuda(), d_pc=torch.from_numpy(counts.view(np.int32)).cuda(), d_ax=torch.from_numpy(ax).cuda(), d_ay=torch.from_numpy(ay).cuda(),
                 counts=torch.full((n + 2,), CANARY, dtype=torch.int32, device="cuda"),
                 circles=torch.full((2 * GUARD + 4 * n * circle_capacity,), CANARY, dtype=torch.int32, device="cuda"))
 
@@ -87,7 +89,7 @@ def _check(b, par, centre_capacity=4096, what="", want=None):
     """What a call left behind (the context has been synchronised), compared with the restatement.  Returns (counts, circles)."""
     n, cap = b["n"], b["cap"]
     assert np.array_equal(b["d_ax"].cpu().numpy(), b["ax"]) and np.array_equal(b["d_ay"].cpu().numpy(), b["ay"]), f"{what}: a gradient plane or the bytes around it were written"
-    assert np.array_equal(b["d_pts"].cpu().numpy(), b["lists"]) and np.array_equal(b["d_pc"].cpu().numpy().view(np.uint32), b["pcounts"]), f"{what}: the points were written"
+    assert np.array_equal(b["d_pts"].cpu().numpy(), b["on_device"]) and np.array_equal(b["d_pc"].cpu().numpy().view(np.uint32), b["pcounts"]), f"{what}: the points were written"
     c = b["counts"].cpu().numpy()
     assert c[0] == CANARY and c[-1] == CANARY, f"{what}: a word beside d_circle_counts was written"
     got_counts = c[1:-1].view(np.uint32)
@@ -235,6 +237,28 @@ def test_cuts_by_every_capacity():
         for pcap in (1, 64, len(pts[0]) - 1):
             _call(ctx, pts, dx, dy, par, 512, point_capacity=pcap, what=f"point_capacity {pcap}")
         _call(ctx, pts, dx, dy, par, 512, counts=[len(pts[0]), 0xFFFFFFFF, 5, 0], point_capacity=len(pts[1]) + 3, what="counts beyond the capacity")
+
+
+def test_point_capacity_0():
+    """point_capacity 0 with a d_points that is not null: frame f uses its first min(d_point_counts[f], 0) points, whatever the
+    counts say -- no circle, every slot untouched, and the call after it is none the worse."""
+    import torch
+    w, h = 64, 48
+    scenes = [_scene(w, h, 30 + k) for k in range(2)]
+    par = _params(w, h, 1.0)
+    pts, dx, dy = [s[0] for s in scenes], np.stack([s[1] for s in scenes]), np.stack([s[2] for s in scenes])
+    with api.Context(w, h, 1, 2) as ctx:
+        for cap in (256, 0):
+            b = _upload(pts, [len(pts[0]), 0xFFFFFFFF], dx, dy, cap, point_capacity=0)
+            assert b["pcap"] == 0 and b["lists"].shape == (2, 0, 2) and b["d_pts"].data_ptr() % 8 == 0 and b["d_pts"].data_ptr() != 0
+            torch.cuda.synchronize()
+            _queue(ctx, b, par)
+            ctx.sync()
+            counts, circles = _check(b, par, what=f"point_capacity 0, circle_capacity {cap}")
+            assert counts.tolist() == [0, 0] and [len(c) for c in circles] == [0, 0]
+            assert (b["circles"].cpu().numpy() == CANARY).all()
+        counts, _ = _call(ctx, pts, dx, dy, par, 256, what="a valid call after point_capacity 0")
+        assert counts.min() > 0
 
 
 def test_pitched_offset_roi_planes_and_passes():
