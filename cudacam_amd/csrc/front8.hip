@@ -19,10 +19,12 @@
 // that the compiler can overlap the rows' dependency chains -- the kernel is bound by instruction issue and latency, not
 // by HBM:
 //   phase 1   6 input rows -> vertical accumulators -> exact integer quotient floor(S/159) -> 6 blur rows into a
-//             wave-private LDS ring of the last 10 blur rows; pixels whose float result cannot be decided by integers
-//             (S % 159 == 0, 0.6 % of them) are queued
-//   fix-up    the queued pixels get the literal 25-fmaf chain of the reference, read from a wave-private LDS ring of
-//             the last 10 masked input rows, and overwrite their byte of the blur ring
+//             wave-private LDS ring of the last 16 blur rows (mono full-strip instances; the others: 10); pixels whose
+//             float result cannot be decided by integers (S % 159 == 0, 0.6 % of them) are queued
+//   fix-up    the queued pixels get the literal 25-fmaf chain of the reference and overwrite their byte of the blur ring.
+//             The taps are bytes of the caller's frame, still in L1 / L2 (mono full-strip instances), or come from a
+//             wave-private LDS ring of the last 10 masked input rows (BGR, per-channel, half-strip: a tap is no byte of
+//             the frame there)
 //   phase 2   6 blur rows -> Sobel -> sumX^2 + sumY^2, summed over pixel pairs -> low-threshold test (a necessary
 //             condition: the batches decide exactly).  Every byte of the output row is stored as zero at once; the
 //             few half-lanes (4 px) that may hold a candidate only queue their identity (row, lane, half: one dword)
@@ -31,7 +33,9 @@
 //             thresholds, and overwrites its nibble of the planes (and its 4 bytes of the provisional map).  About
 //             6 % of the half-lanes hold a candidate, so redoing their Sobel costs less than carrying three rows of
 //             S2 for everybody in registers -- or parking 96 bytes per candidate in LDS, which is what made the first
-//             form of this kernel LDS-write-bound.
+//             form of this kernel LDS-write-bound.  With the ring of 16 rows an entry stays readable through the
+//             window after its own: only full batches are taken and the rest waits, one window at the most.
+// LDS per wave: 16 blur rows + the two queues = 10,784 B (126 KB for the 12 waves of a CU); with two rings of 10 rows 12,832 B.
 // Only the vertical blur accumulators (16 VGPRs) and the Sobel terms of the two previous blur rows (16 VGPRs) are
 // carried from row to row.  Input rows are requested one window ahead.
 #include "canny_device.h"
@@ -45,16 +49,26 @@
 #define F8_WQ_HIST 0  // measurement build (tools/dense_sweep.py --hist; plain form only): with HC_OPT_DEBUG_TAPS every window leaves its count of half-lanes above the low threshold, and which path it took, in the blur tap instead of the blur rows
 #endif
 
+#ifndef F8_HEAD_RULE
+#define F8_HEAD_RULE 1  // 0 (measurements): a run's first window is held to the threshold of a full window, as it was before the rule
+#endif
+
 namespace hc {
 
 // (F8_STRIP_W, F8_HSTRIP_W, F8_SUB and the strip / run arithmetic: canny_params.h, shared with the host planner)
 constexpr int F8_HALO = 8;                         // one lane each side
-constexpr int F8_RING = F8_SUB + 4;                // rows kept in each LDS ring (masked input rows; blur rows)
+constexpr int F8_RING = 16;                        // mono full-strip instances (CARRY below): blur rows kept in the LDS ring, slot = (blur row - (r0 - 2)) & 15
+constexpr int F8_RING_IN = F8_SUB + 4;             // the other instances: rows kept in each of their two LDS rings (masked input rows; blur rows)
+constexpr int F8O_RING = F8_SUB + 4;               // k_front8o: source rows kept in its LDS ring
 constexpr int F8_FQ = 128;                         // flagged-pixel queue entries per window (expected fill ~20); [F8_FQ] is a dump slot
 constexpr int F8_NQ = 512;                         // NMS queue (ids), circular; [F8_NQ] is a dump slot
 constexpr int F8_ROW_BYTES = 64 * 8;
 constexpr int F8_WPB = 4;                          // waves per workgroup of k_front8 (mono / BGR; one-wave form: 1; per-channel mode: 3, one per channel).  The waves are independent.
-constexpr int F8_WAVE_BYTES = 2 * F8_RING * F8_ROW_BYTES + (F8_FQ + 4) * 4 + (F8_NQ + 4) * 4;  // 12,832 B: 3 workgroups of 4 waves per CU
+constexpr int F8_WAVE_BYTES = F8_RING * F8_ROW_BYTES + (F8_FQ + 4) * 4 + (F8_NQ + 4) * 4;  // 10,784 B: 3 workgroups of 4 waves per CU use 126 KB of its 160
+constexpr int F8_WAVE_BYTES_IN = 2 * F8_RING_IN * F8_ROW_BYTES + (F8_FQ + 4) * 4 + (F8_NQ + 4) * 4;  // 12,832 B (BGR, per-channel and half-strip instances): 154 KB
+// An NMS entry waits one window at the most (k_front8, window): fewer than 64 entries are carried, and between two points
+// where full batches are taken three rows of 62 lanes queue two each
+static_assert(63 + 3 * 2 * 62 <= F8_NQ, "NMS queue: 63 carried entries + 3 rows x 124 queued = 435");
 
 size_t front8_lds_bytes() { return (size_t)4 * F8_WAVE_BYTES; }
 
@@ -74,7 +88,7 @@ static __device__ __forceinline__ u32 f8_chain(const unsigned char *ring, u32 sl
 #pragma unroll
   for (int r = 0; r < 5; ++r) {
     u32 sl = slot0 + (u32)r;
-    sl = min(sl, sl - (u32)F8_RING);  // wrap (unsigned): slot0 < F8_RING
+    sl = min(sl, sl - (u32)F8_RING_IN);  // wrap (unsigned): slot0 < F8_RING_IN
     const unsigned char *q = ring + sl * (u32)F8_ROW_BYTES + colbyte - 2u;
 #pragma unroll
     for (int c = 0; c < 5; ++c) px[r * 5 + c] = q[c];
@@ -83,6 +97,50 @@ static __device__ __forceinline__ u32 f8_chain(const unsigned char *ring, u32 sl
   float f = 0.0f;
 #pragma unroll
   for (int i = 0; i < 25; ++i) f = __builtin_fmaf(GKC.v[i], (float)px[i], f);
+  return (u32)(int)f;
+}
+
+// The same chain on the caller's mono frame (the CARRY instances keep no ring of input rows: the wave loaded these rows a
+// window ago, they sit in L1 / L2).  Blur pixel (row0 + 2, col); taps in the same order.  BORDER: some tap lies outside the
+// image -- a row outside [0, H) is read from the page of zeros, a column outside [0, W) is not read at all (the address is
+// clamped into the row, the value replaced by 0): no byte outside the W x H view is touched, whatever its pitch holds.
+template <bool BORDER>
+static __device__ __forceinline__ u32 f8_chain_g(const uint8_t *frame_base, const uint8_t *zeros, u32 pitch, int row0, int col, int W, int H)
+{
+  float f = 0.0f;
+  if constexpr (!BORDER) {
+    u32 px[25];  // all 25 taps are requested before the first is used: one wait instead of 25 dependent ones
+    const u32 o = (u32)row0 * pitch + (u32)(col - 2);
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+      const uint8_t *q = frame_base + (o + (u32)r * pitch);
+#pragma unroll
+      for (int c = 0; c < 5; ++c) px[r * 5 + c] = q[c];
+    }
+    asm volatile("" ::: "memory");  // keeps the loads above the chain
+#pragma unroll
+    for (int i = 0; i < 25; ++i) f = __builtin_fmaf(GKC.v[i], (float)px[i], f);
+  } else {
+    // (one pass in hundreds, at the frame's edges: a row of taps at a time -- with 25 per-lane 64-bit addresses in flight this
+    // variant alone would set the kernel's register count above three waves per SIMD)
+    u32 cc[5], cm[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      cc[c] = (u32)min(max(col - 2 + c, 0), W - 1);
+      cm[c] = (u32)(col - 2 + c) < (u32)W ? 0xFFu : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+      const int row = row0 + r;
+      u32 px[5];
+      const uint8_t *q = (u32)row < (u32)H ? frame_base + (u32)row * pitch : zeros;
+#pragma unroll
+      for (int c = 0; c < 5; ++c) px[c] = q[cc[c]] & cm[c];
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int c = 0; c < 5; ++c) f = __builtin_fmaf(GKC.v[r * 5 + c], (float)px[c], f);
+    }
+  }
   return (u32)(int)f;
 }
 
@@ -98,15 +156,23 @@ static __device__ __forceinline__ u32 f8_chain(const unsigned char *ring, u32 sl
 // slot on each of the CU's four SIMDs at the same moment -- which gains the front kernel 2-3 % beside the hysteresis and
 // costs the hysteresis 40 % more stream time: the host picks it while that stream has the slack (hipcanny.hip, watch_chain).
 template <int IN, bool PROV, bool HALF, bool ONE = false>
-__global__ __launch_bounds__(256) void k_front8(const FrontParams p)
+// (amdgpu_waves_per_eu: the kernel is sized for three waves per SIMD, 168 VGPRs; the register allocator is held to that)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_front8(const FrontParams p)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
-  unsigned char *ring = smem + wib * F8_WAVE_BYTES;           // masked input rows (fix-up chain)
-  unsigned char *bring = ring + F8_RING * F8_ROW_BYTES;       // blur rows (Sobel stage, NMS batches)
-  u32 *fq = reinterpret_cast<u32 *>(bring + F8_RING * F8_ROW_BYTES);
+  // CARRY: the mono full-strip instances (the ones the flagship workload runs).  A tap of their fix-up chain is a byte of
+  // the caller's frame, so they keep no ring of input rows and spend part of the LDS on a blur ring of 16 rows instead of
+  // 10: a queued NMS entry then stays readable through the window after its own and waits there for a full batch.
+  constexpr bool CARRY = IN == 0 && !HALF;
+  constexpr int RING = CARRY ? F8_RING : F8_RING_IN;
+  unsigned char *ring = smem + wib * (CARRY ? F8_WAVE_BYTES : F8_WAVE_BYTES_IN);  // masked input rows (fix-up chain; not CARRY)
+  unsigned char *bring = ring + (CARRY ? 0 : RING * F8_ROW_BYTES);                // blur rows (Sobel stage, NMS batches)
+  u32 *fq = reinterpret_cast<u32 *>(bring + RING * F8_ROW_BYTES);
   lds_u32 *nq = (lds_u32 *)(fq + F8_FQ + 4);
+  // ring-slot wrap of s < 2 * RING (unsigned)
+  auto wrap = [](u32 s) -> u32 { if constexpr (CARRY) return s & (u32)(F8_RING - 1); else return min(s, s - (u32)F8_RING_IN); };
 
   // Mono / BGR: 4 independent waves per workgroup.  Per-channel mode: a workgroup is the THREE channels of one (frame,
   // strip, run), a wave each, kept within one window of each other by a barrier per window -- so the 24 interleaved bytes
@@ -239,10 +305,10 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
   asm volatile("" : "+s"(magic159));  // (an SGPR operand of the SDWA multiplies, not a literal)
   int qn = 0;                        // flagged-pixel queue fill of the current window (wave-uniform)
   const u32 lane_id2 = (u32)lane << 2;
-  // input row jr (its masked pixels in x) goes to ring slot `islot` and completes blur row jr - 2, which goes to blur-ring
-  // slot `bslot` (warm: a warm-up row, it only feeds the accumulators)
+  // input row jr (its masked pixels in x) goes to ring slot `islot` (not CARRY) and completes blur row jr - 2, which goes
+  // to blur-ring slot `bslot` (warm: a warm-up row, it only feeds the accumulators)
   auto blur_row = [&](auto warm, int jr, int islot, int bslot, const u32 x[2]) {
-    *reinterpret_cast<u32x2 *>(ring + islot * F8_ROW_BYTES + lane * 8) = u32x2{ x[0], x[1] };
+    if constexpr (!CARRY) *reinterpret_cast<u32x2 *>(ring + islot * F8_ROW_BYTES + lane * 8) = u32x2{ x[0], x[1] };
     u32 Sp[4];
     accumulate(x, Sp);
     if constexpr (decltype(warm)::value) return;
@@ -300,6 +366,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
   uint8_t *prov_frame = PROV ? p.prov_out + (size_t)frame * p.prov_fs : nullptr;
 
   int qhead = 0, qcount = 0;  // NMS queue (circular, F8_NQ ids): wave-uniform
+  int old = 0;                // CARRY: entries at the head of the queue that the window before this one left (wave-uniform, < 64)
   int wq = 0;                 // half-lanes that passed the low-threshold test in the window being processed (wave-uniform)
   // blur row k (its 8 bytes per lane in b0, b1) arrives -> Sobel row k-1 -> the row's candidates are queued.  No branch.
   auto step = [&](auto uc, int k, u32 b0, u32 b1) {
@@ -368,7 +435,8 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     wq += (c >= 2 && c < H - 2) ? (int)(n0 + n1) : 0;
   };
 
-  // One dense NMS pass: up to 64 queued half-lanes, an entry per lane.  sbase: blur-ring slot of blur row bw0 - 4.
+  // One dense NMS pass: up to 64 queued half-lanes, an entry per lane.  sbase: blur-ring slot of blur row bw0 - 4 (not
+  // CARRY: there an entry may belong to the window before bw0's, and the slots follow from its own row).
   auto nms_batch = [&](int nwant, int bw0, u32 sbase) {
     wave_lds_sync();
     int nent = nwant;
@@ -384,13 +452,13 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     const int col0 = HALF ? (eB ? sB : strip) * F8_HSTRIP_W - F8_HALO + 8 * (int)(sl & 31u) + 4 * (int)half
                           : strip * F8_STRIP_W - F8_HALO + 8 * (int)sl + 4 * (int)half;  // column of the half's pixel 0
     // blur rows row-2 .. row+2, columns col0-4 .. col0+7 (three aligned dwords; -2 .. +5 are used)
-    const u32 rel = (u32)(row - (bw0 - 2));  // 0..5: the window's output rows are bw0-2 .. bw0+3
+    // not CARRY: 0..5, the window's output rows are bw0-2 .. bw0+3.  CARRY: blur row row - 2 counted from the run's first, r0 - 2
+    const u32 rel = CARRY ? (u32)(row - r0) : (u32)(row - (bw0 - 2));
     const u32 lo = sl * 8u + half * 4u - 4u;
     u32 d[5][3], s[5][3];  // per blur row: d = b[+1]-b[-1], s = b[-1]+2b[0]+b[+1] of the pixel pairs (-1,0), (1,2), (3,4)
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
-      u32 slot = sbase + rel + (u32)r;
-      slot = min(slot, slot - (u32)F8_RING);  // wrap (unsigned): sbase + rel + r < 2 * F8_RING
+      const u32 slot = wrap((CARRY ? 0u : sbase) + rel + (u32)r);  // (not CARRY: sbase + rel + r < 2 * F8_RING_IN)
       const u32 *q = reinterpret_cast<const u32 *>(bring + slot * (u32)F8_ROW_BYTES + lo);
       const u32 D0 = q[0], D1 = q[1], D2 = q[2];
       const u32 Pm = unpack_hi(D0), A = unpack_lo(D1), B = unpack_hi(D1), Cq = unpack_lo(D2);  // (b-2,b-1) (b0,b1) (b2,b3) (b4,b5)
@@ -481,6 +549,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
       *reinterpret_cast<u32 *>(prov_frame + (u32)row * p.prov_pitch + (u32)col0 + ((HALF && eB) ? (u32)(IN == 2 ? 3 * dframe : dframe) * (u32)p.prov_fs : 0u)) = nibble_to_bytes(nib & 0xFu);
     qhead = (qhead + nent) & (F8_NQ - 1);
     qcount -= nent;
+    if constexpr (CARRY) old = max(old - nent, 0);  // FIFO: the carried entries go first
   };
 
 
@@ -522,8 +591,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     int cnt = 0;
 #pragma unroll
     for (int i = WARM ? 4 : 0; i < 10; ++i) {  // blur row bw0 - 4 + i
-      u32 slot = sbase + (u32)i;
-      slot = slot >= (u32)F8_RING ? slot - (u32)F8_RING : slot;
+      const u32 slot = wrap(sbase + (u32)i);
       const u32x2 b = *reinterpret_cast<const u32x2 *>(bring + slot * (u32)F8_ROW_BYTES + lane * 8);
       const u32 A0 = unpack_lo(b.x), B0 = unpack_hi(b.x), A1 = unpack_lo(b.y), B1 = unpack_hi(b.y);
       const u32 Bl = from_lane_below(B1), Ar = from_lane_above(A0);
@@ -617,7 +685,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
 
   // ---- the run -------------------------------------------------------------------------------------------------------
   // input rows r0-4 .. rend+3 -> blur rows r0-2 .. rend+1 -> Sobel / output rows r0 .. rend-1
-  int islot = 0;  // ring slot of the next input row
+  int islot = 0;  // ring slot of the next input row (not CARRY)
   {  // warm-up: input rows r0-4 .. r0-1 only feed the accumulators (and the fix-up ring)
     Raw xw[4];
 #pragma unroll
@@ -627,7 +695,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
       u32 x[2];
       use_raw(r0 - 4 + j, xw[j], x);
       blur_row(std::true_type{}, r0 - 4 + j, islot, 0, x);
-      islot = islot + 1 == F8_RING ? 0 : islot + 1;
+      if constexpr (!CARRY) islot = islot + 1 == RING ? 0 : islot + 1;
     }
   }
   Raw xn[G];
@@ -635,6 +703,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
   for (int j = 0; j < G; ++j) xn[j] = load_raw(r0 + j);
   const int nwin = (rend + 2 - (r0 - 2) + F8_SUB - 1) / F8_SUB;
   int bslot0 = 0;  // blur-ring slot of the window's first blur row (blur row r0 - 2 sits in slot 0)
+  bool dense = p.dense_enter < 0;  // the next window takes the dense path (HC_OPT_FRONT_DENSE = 1: every window, tests)
   // one window; PATH: its phase 2 is 0 the queue path, 1 the dense path's cold form, 2 its warm form.  (A lambda instantiated
   // three times, for the separate loops below.)
   auto window = [&](auto path_c, int w) {
@@ -647,15 +716,25 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
       u32 x[2];
       use_raw(bw0 + 2 + j, xn[j % G], x);
       xn[j % G] = load_raw(bw0 + 2 + j + G);
-      const int bs = bslot0 + j;
-      blur_row(std::false_type{}, bw0 + 2 + j, islot, bs >= F8_RING ? bs - F8_RING : bs, x);
-      islot = islot + 1 == F8_RING ? 0 : islot + 1;
+      blur_row(std::false_type{}, bw0 + 2 + j, islot, (int)wrap((u32)(bslot0 + j)), x);
+      if constexpr (!CARRY) islot = islot + 1 == RING ? 0 : islot + 1;
     }
     // fix-up: the queued pixels get the literal chain, written over their byte of the blur ring.  Queue overflow (flat
     // areas: every pixel of a constant region has S = 159 v): every pixel of the window is recomputed.
     wave_lds_sync();
-    // the ring now holds input rows bw0-2 .. bw0+7 and `islot` is where bw0+8 will go, i.e. where the oldest, bw0-2, sits:
-    // the chain of blur row bw0 + e starts at input row bw0 + e - 2, ring slot (islot + e) mod F8_RING
+    // not CARRY: the ring now holds input rows bw0-2 .. bw0+7 and `islot` is where bw0+8 will go, i.e. where the oldest,
+    // bw0-2, sits: the chain of blur row bw0 + e starts at input row bw0 + e - 2, ring slot (islot + e) mod F8_RING_IN.
+    // CARRY: the chain of blur pixel (row, col) reads the frame (f8_chain_g); in one pass all lanes take the variant
+    // without border handling unless one of them has a tap outside the image (wave-uniform choice, as in the batches)
+    auto chain = [&](u32 s0, u32 colbyte, int row, int col) -> u32 {
+      if constexpr (CARRY) {
+        const bool border = row < 2 || row + 2 >= H || col < 2 || col + 2 >= W;
+        if (__ballot(border) != 0) return f8_chain_g<true>(frame_base, p.zeros, in_pitch32, row - 2, col, W, H);
+        return f8_chain_g<false>(frame_base, p.zeros, in_pitch32, row - 2, col, W, H);
+      } else {
+        return f8_chain(ring, s0, colbyte);
+      }
+    };
     if (F8_ABL & 2) qn = 0;
     if (qn <= F8_FQ) {
 #pragma nounroll
@@ -664,15 +743,13 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
         const u32 ent = e < qn ? fq[e] : 0u;
         u32 fl = ent & 0x03030303u;
         const u32 el = (ent >> 2) & 63u, es = (ent >> 10) & 15u;  // lane, blur-ring slot
-        u32 rel = es + (u32)F8_RING - (u32)bslot0;                // row of the window, 0..5
-        rel = min(rel, rel - (u32)F8_RING);
-        u32 s0 = (u32)islot + rel;
-        s0 = min(s0, s0 - (u32)F8_RING);
+        const u32 rel = wrap(es + (u32)RING - (u32)bslot0);       // row of the window, 0..5
+        const u32 s0 = CARRY ? 0u : wrap((u32)islot + rel);
         while (fl) {
           const u32 b = (u32)__builtin_ctz(fl);
           fl &= fl - 1;
           const u32 k = (b >> 3) + 4u * (b & 1u);  // pixel 0..7 of the lane
-          bring[es * (u32)F8_ROW_BYTES + el * 8u + k] = (unsigned char)f8_chain(ring, s0, el * 8u + k);
+          bring[es * (u32)F8_ROW_BYTES + el * 8u + k] = (unsigned char)chain(s0, el * 8u + k, bw0 + (int)rel, strip * F8_STRIP_W - F8_HALO + (int)(el * 8u + k));
         }
       }
     } else {
@@ -682,12 +759,10 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
         const int row = bw0 + (int)rel;
         const u32 cb = (u32)e % (u32)F8_ROW_BYTES;
         const int col = HALF ? (cb >= 256u ? sB : strip) * F8_HSTRIP_W - F8_HALO + (int)(cb & 255u) : strip * F8_STRIP_W - F8_HALO + (int)cb;
-        u32 es = (u32)bslot0 + rel;
-        es = min(es, es - (u32)F8_RING);
-        u32 s0 = (u32)islot + rel;
-        s0 = min(s0, s0 - (u32)F8_RING);
+        const u32 es = wrap((u32)bslot0 + rel);
+        const u32 s0 = CARRY ? 0u : wrap((u32)islot + rel);
         if (cb >= 2u && cb < (u32)F8_ROW_BYTES - 2u && row >= 0 && row < H && col >= 0 && col < W)
-          bring[es * (u32)F8_ROW_BYTES + cb] = (unsigned char)f8_chain(ring, s0, cb);
+          bring[es * (u32)F8_ROW_BYTES + cb] = (unsigned char)chain(s0, cb, row, col);
       }
     }
     wave_lds_sync();
@@ -696,8 +771,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     u32x2 bq[F8_SUB];
 #pragma unroll
     for (int j = 0; j < F8_SUB; ++j) {
-      int bs = bslot0 + j - 1;
-      bs = bs < 0 ? bs + F8_RING : bs >= F8_RING ? bs - F8_RING : bs;
+      const int bs = (int)wrap((u32)(bslot0 + j - 1 + (j == 0 ? RING : 0)));  // (the argument stays within [0, 2 * RING))
       bq[j] = *reinterpret_cast<const u32x2 *>(bring + bs * F8_ROW_BYTES + lane * 8);
     }
     if (!F8_WQ_HIST && p.dbg_blur && own_lane && c0 < W) {  // diagnostics (HC_OPT_DEBUG_TAPS): the fixed-up blur rows of this run
@@ -707,9 +781,9 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
         if (k >= r0 && k < rend) *reinterpret_cast<g_u32x2 *>(p.dbg_blur + (size_t)(frame + (hB ? (IN == 2 ? 3 * dframe : dframe) : 0)) * p.dbg_fs + (size_t)k * p.dbg_pitch + (u32)c0) = bq[j];
       }
     }
-    int sb = bslot0 - 4;  // blur-ring slot of blur row bw0 - 4
-    if (sb < 0) sb += F8_RING;
+    const int sb = (int)wrap((u32)(bslot0 - 4 + RING));  // blur-ring slot of blur row bw0 - 4
     if constexpr (DENSE) {
+      // (the queue is empty here: the queue-path window that handed over flushed it, see below)
       dense_window(std::integral_constant<bool, PATH == 2>{}, bw0, (u32)sb);
     } else {
       wq = 0;
@@ -723,7 +797,22 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
         step(std::integral_constant<int, 4>{}, bw0 + 3, bq[4].x, bq[4].y);
         step(std::integral_constant<int, 5>{}, bw0 + 4, bq[5].x, bq[5].y);
         if (F8_ABL & 1) { qhead = (qhead + qcount) & (F8_NQ - 1); qcount = 0; }
-        while (qcount > 0) nms_batch(min(qcount, 64), bw0, (u32)sb);
+      }
+      // The window that follows one with more than p.dense_enter queued half-lanes takes the dense path.  A run's first
+      // window owns two output rows of its six (the others belong to the run above): it is judged on those two, scaled.
+      dense = (F8_HEAD_RULE && w == 0 && r0 > 0) ? wq * 3 > p.dense_enter : wq > p.dense_enter;
+      if (!(F8_ABL & 4)) {
+        // not CARRY: the next window's phase 1 overwrites blur rows that the queued entries read -- every window ends with an
+        // empty queue, its last batch as full as it happens to be (75 % on camera-like frames).
+        // CARRY: the ring keeps blur rows bw0-10 .. bw0+5, so after the next window's phase 1 it still holds bw0-4 .. bw0+5,
+        // all that this window's entries (output rows bw0-2 .. bw0+3, each reading row-2 .. row+2) need; after the one
+        // after that it does not.  Only full batches are taken, then, and what is left (< 64) waits -- one window: if
+        // entries of the window before are still there, one batch takes the whole queue.  Nothing may wait where no
+        // queue-path window of this run follows: in a run's last window and in one that hands over to the dense loop.
+        const bool flush = !CARRY || dense || w + 1 == nwin;
+        // (one call site: a batch of fewer than 64 takes the whole queue, so `old` is zero after it)
+        while (qcount >= 64 || (qcount > 0 && (flush || old > 0))) nms_batch(min(qcount, 64), bw0, (u32)sb);
+        if constexpr (CARRY) old = qcount;
       }
     }
     if (F8_WQ_HIST && !HALF && p.dbg_blur && lane == 0) {  // one record per (frame, strip, run, window): row r0 + w of the tap, 8 bytes per strip
@@ -733,7 +822,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
     }
     wave_lds_sync();  // the next window's phase 1 overwrites the oldest ring rows
     if (IN == 2) __syncthreads();  // the three channels of this run stay within a window of each other (see above)
-    bslot0 = bslot0 + F8_SUB >= F8_RING ? bslot0 + F8_SUB - F8_RING : bslot0 + F8_SUB;
+    bslot0 = (int)wrap((u32)(bslot0 + F8_SUB));
   };
   // Two loops, not one loop with a branch in it: the dense path needs more SGPRs than the kernel has (its compare masks),
   // and with the branch inside the window loop the spills it caused were paid by every window of every frame (+2 % on
@@ -742,13 +831,9 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
   // cold form and the rest of the stretch, a loop of its own again, the warm one: what a warm window starts from is live
   // in that loop only, never across a sparse window, a run or a frame.
   int w = 0;
-  bool dense = p.dense_enter < 0;  // HC_OPT_FRONT_DENSE = 1: every window (tests)
   while (w < nwin) {
 #pragma nounroll
-    for (; w < nwin && !dense; ++w) {
-      window(std::integral_constant<int, 0>{}, w);
-      dense = wq > p.dense_enter;
-    }
+    for (; w < nwin && !dense; ++w) window(std::integral_constant<int, 0>{}, w);  // (sets `dense`)
     if (w < nwin) {
       window(std::integral_constant<int, 1>{}, w);
       dense = wq > p.dense_leave;
@@ -778,7 +863,7 @@ __global__ __launch_bounds__(256) void k_front8(const FrontParams p)
 // instructions per pixel pair; the cheaper pair-summed dx^2 + dy^2 >= ceil((low + 1)^2 / 2) queued three times as many
 // half-lanes as pass, and the batches cost more than the test saves); with L2gradient by the necessary condition
 // dx^2 + dy^2 summed over the pair (two v_dot2) >= low + 1.
-constexpr int F8O_WAVE_BYTES = F8_RING * F8_ROW_BYTES + (F8_NQ + 4) * 4;  // 7,184 B per wave
+constexpr int F8O_WAVE_BYTES = F8O_RING * F8_ROW_BYTES + (F8_NQ + 4) * 4;  // 7,184 B per wave
 
 // TAB: per-frame thresholds from p.frame_thr (as k_front_o: the launcher picks the instantiation)
 template <bool L2, bool PROV, bool TAB = false>
@@ -788,7 +873,7 @@ __global__ __launch_bounds__(256) void k_front8o(const FrontParams p)
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
   unsigned char *bring = smem + wib * F8O_WAVE_BYTES;  // source rows (columns outside the image zero)
-  lds_u32 *nq = (lds_u32 *)(bring + F8_RING * F8_ROW_BYTES);
+  lds_u32 *nq = (lds_u32 *)(bring + F8O_RING * F8_ROW_BYTES);
   for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < p.zero_count; i += gridDim.x * blockDim.x) p.zero_words[i] = 0u;  // (as k_front8)
   const int item = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x) * 4 + wib);
   if (item >= p.total_items) return;
@@ -946,7 +1031,7 @@ __global__ __launch_bounds__(256) void k_front8o(const FrontParams p)
 #pragma unroll
       for (int r = 0; r < 5; ++r) {
         u32 slot = sbase + rel + (u32)r;
-        slot = min(slot, slot - (u32)F8_RING);
+        slot = min(slot, slot - (u32)F8O_RING);
         const u32 *q = reinterpret_cast<const u32 *>(bring + slot * (u32)F8_ROW_BYTES + lo);
         const u32 D0 = q[0], D1 = q[1], D2 = q[2];
         u32 Pm, A, B, Cq;  // (b-2,b-1) (b0,b1) (b2,b3) (b4,b5)
@@ -1046,16 +1131,16 @@ __global__ __launch_bounds__(256) void k_front8o(const FrontParams p)
       const u32x2 x = u32x2{ xn[j].x & cmask[0], xn[j].y & cmask[1] };
       xn[j] = load_raw(bw0 + j + F8_SUB);
       const int bs = bslot0 + j;
-      *reinterpret_cast<u32x2 *>(bring + (bs >= F8_RING ? bs - F8_RING : bs) * F8_ROW_BYTES + lane * 8) = x;
+      *reinterpret_cast<u32x2 *>(bring + (bs >= F8O_RING ? bs - F8O_RING : bs) * F8_ROW_BYTES + lane * 8) = x;
     }
     wave_lds_sync();
     int sb = bslot0 - 4;  // ring slot of source row bw0 - 4
-    if (sb < 0) sb += F8_RING;
+    if (sb < 0) sb += F8O_RING;
     u32x2 bq[F8_SUB];  // rows bw0-1 .. bw0+4 (the first one is the previous window's last)
 #pragma unroll
     for (int j = 0; j < F8_SUB; ++j) {
       int bs = bslot0 + j - 1;
-      bs = bs < 0 ? bs + F8_RING : bs >= F8_RING ? bs - F8_RING : bs;
+      bs = bs < 0 ? bs + F8O_RING : bs >= F8O_RING ? bs - F8O_RING : bs;
       bq[j] = *reinterpret_cast<const u32x2 *>(bring + bs * F8_ROW_BYTES + lane * 8);
     }
     if (!(F8_ABL & 4)) {
@@ -1071,7 +1156,7 @@ __global__ __launch_bounds__(256) void k_front8o(const FrontParams p)
       while (qcount > 0) nms_batch(min(qcount, 64), bw0, (u32)sb);
     }
     wave_lds_sync();  // the next window overwrites the oldest ring rows
-    bslot0 = bslot0 + F8_SUB >= F8_RING ? bslot0 + F8_SUB - F8_RING : bslot0 + F8_SUB;
+    bslot0 = bslot0 + F8_SUB >= F8O_RING ? bslot0 + F8_SUB - F8O_RING : bslot0 + F8_SUB;
   }
 }
 
@@ -1084,13 +1169,13 @@ static hipError_t launch_front8_t(const FrontParams &p, hipStream_t s)
     if (p.one_wave) {  // (only beside a hysteresis, i.e. with the provisional map)
       if (!p.prov_out) return hipErrorInvalidValue;
       const dim3 grid1((unsigned)p.total_items), block1(64);
-      if (p.half) hipLaunchKernelGGL((k_front8<IN, true, true, true>), grid1, block1, (size_t)F8_WAVE_BYTES, s, p);
-      else hipLaunchKernelGGL((k_front8<IN, true, false, true>), grid1, block1, (size_t)F8_WAVE_BYTES, s, p);
+      if (p.half) hipLaunchKernelGGL((k_front8<IN, true, true, true>), grid1, block1, (size_t)F8_WAVE_BYTES_IN, s, p);
+      else hipLaunchKernelGGL((k_front8<IN, true, false, true>), grid1, block1, (size_t)(IN == 0 ? F8_WAVE_BYTES : F8_WAVE_BYTES_IN), s, p);
       return hipGetLastError();
     }
   }
   const dim3 grid((unsigned)((p.total_items + WPB - 1) / WPB)), block(64 * WPB);
-  const size_t lds = (size_t)WPB * F8_WAVE_BYTES;
+  const size_t lds = (size_t)WPB * (IN == 0 && !p.half ? F8_WAVE_BYTES : F8_WAVE_BYTES_IN);  // (the kernel's CARRY instances)
   if (p.half) {
     if (p.prov_out) hipLaunchKernelGGL((k_front8<IN, true, true>), grid, block, lds, s, p);
     else hipLaunchKernelGGL((k_front8<IN, false, true>), grid, block, lds, s, p);
