@@ -63,6 +63,8 @@ FORM_O_APERTURE7, FORM_O_SCHARR = 8, 9
 AUTO_MEDIAN, AUTO_OTSU = 0, 1
 # borders of hc_gaussian_blur_device (the header's HC_BORDER_REFLECT_101 / HC_BORDER_REPLICATE)
 BORDER_REFLECT_101, BORDER_REPLICATE = 0, 1
+# words of a statistics row of hc_connected_components_device (the header's HC_CC_STAT_*)
+CC_STAT_LEFT, CC_STAT_TOP, CC_STAT_WIDTH, CC_STAT_HEIGHT, CC_STAT_AREA, CC_STAT_WORDS = 0, 1, 2, 3, 4, 5
 # words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
 SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
@@ -76,6 +78,7 @@ ABI_SYMBOLS = [
     "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
     "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
     "hc_hough_segments_device", "hc_hough_walk_tables", "hc_hough_circles_device", "hc_hough_circle_geometry",
+    "hc_connected_components_device",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -145,6 +148,7 @@ def load_library(legacy=False):
     L.hc_hough_segments_device.argtypes = [vp, vp, sz, sz, vp, vp, sz, i, d, d, d, d, i, i, vp, vp, sz]
     L.hc_hough_walk_tables.argtypes = [i, i, d, d, d, d, C.POINTER(i), C.POINTER(C.c_int32), fp, fp, sz]
     L.hc_hough_circles_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, i, d, d, i, i, i, sz, vp, vp, sz]
+    L.hc_connected_components_device.argtypes = [vp, vp, sz, sz, i, i, vp, sz, sz, vp, vp, vp, sz]
     L.hc_hough_circle_geometry.argtypes = [i, i, d, d, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
@@ -889,6 +893,60 @@ class Context:
         tail = (dp, min_dist, votes_threshold, min_radius, max_radius, max_centres, max_circles, point_capacity)
         counts, circles = self._again_if_continued(lambda: self._hough_circles_of(out, gx, gy, n, *tail))
         return out.cpu().numpy(), counts, circles
+
+    def connected_components_device(self, d_map, pitch, fs, nframes, connectivity, d_labels, label_pitch, label_fs, d_counts, d_stats=None,
+                                    d_centroids=None, capacity=0):
+        """cv::connectedComponentsWithStats per frame on the device (hc_connected_components_device): d_map holds one-channel u8
+        maps (any alignment), d_labels receives int32 [H][W] per frame (pitch and frame stride in bytes, multiples of 4), d_counts
+        uint32 [nframes] = components + 1, d_stats int32 [nframes][capacity][5] and d_centroids float64 [nframes][capacity][2] the
+        rows 0 .. min(N, capacity) - 1 of each frame (row 0: the background).  Components are numbered in raster order of their
+        first pixels.  capacity 0 (d_stats, d_centroids None / 0): labels and counts only.  Asynchronous on the context stream;
+        not a run, but a pipelined run in flight that writes the map or the label plane is completed first."""
+        _ck(self.lib.hc_connected_components_device(self.handle, C.c_void_p(d_map), pitch, fs, int(nframes), int(connectivity), C.c_void_p(d_labels),
+                                                    label_pitch, label_fs, C.c_void_p(d_counts), C.c_void_p(d_stats or None),
+                                                    C.c_void_p(d_centroids or None), int(capacity)))
+
+    def _components_of(self, d_maps, n, connectivity, max_components):
+        """(labels, counts, stats, centroids) of n tight maps on the device (a torch u8 tensor [n, H, W] the context stream may read)."""
+        import torch
+        dev = d_maps.device
+        labels = torch.empty((n, self.h, self.w), dtype=torch.int32, device=dev)
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        fs = self.w * self.h
+        self._wait_for_torch()
+        if max_components is None:   # two passes: the counts size the rows
+            self.connected_components_device(d_maps.data_ptr(), self.w, fs, n, connectivity, labels.data_ptr(), 4 * self.w, 4 * fs, counts.data_ptr())
+            max_components = self._largest_count(counts)
+        cap = int(max_components)
+        stats = torch.empty((n, max(cap, 1), CC_STAT_WORDS), dtype=torch.int32, device=dev)
+        cent = torch.empty((n, max(cap, 1), 2), dtype=torch.float64, device=dev)
+        self._wait_for_torch()
+        self.connected_components_device(d_maps.data_ptr(), self.w, fs, n, connectivity, labels.data_ptr(), 4 * self.w, 4 * fs, counts.data_ptr(),
+                                         stats.data_ptr() if cap else None, cent.data_ptr() if cap else None, cap)
+        self.sync()
+        cnt = counts.cpu().numpy().view(np.uint32)
+        hs, hc = stats.cpu().numpy(), cent.cpu().numpy()
+        rows = [min(int(cnt[f]), cap) for f in range(n)]
+        return labels.cpu().numpy(), cnt, [hs[f, :rows[f]].copy() for f in range(n)], [hc[f, :rows[f]].copy() for f in range(n)]
+
+    def connected_components(self, maps, connectivity=8, max_components=None):
+        """Host or torch u8 maps [n, H, W] (or one map) in; (int32 labels [n, H, W], uint32 counts [n] = components + 1, [int32
+        array (min(N_f, max_components), 5) = (left, top, width, height, area) per frame], [float64 array (.., 2) = centroid (x, y)
+        per frame]) out; row 0 is the background.  max_components=None: two passes, counts first, then rows sized by the largest."""
+        d = self._maps_on_device(maps, "connected_components")
+        return self._components_of(d, d.shape[0], connectivity, max_components)
+
+    def canny_components(self, frames, low, high, connectivity=8, aperture=3, l2gradient=False, blur=None, max_components=None):
+        """cv::Canny followed by cv::connectedComponentsWithStats (mode O): canny_device and connected_components_device chained on
+        the device, with no host copy of the maps in between.  Returns (uint8 (n,H,W) edge maps, labels, counts, stats, centroids as
+        connected_components gives them).  blur = (ksize, sigma): the frames are blurred first (gaussian_blur_device)."""
+        raw, n, row, fs = self._device_view(frames, "canny_components")
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
+        self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        labels, counts, stats, cent = self._again_if_continued(lambda: self._components_of(out, n, connectivity, max_components))
+        return out.cpu().numpy(), labels, counts, stats, cent
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -13,7 +13,7 @@ hipError_t check_gauss_coeffs(const float gk[25]);
 hipError_t launch_front_o(const FrontParams &p, hipStream_t s);
 hipError_t launch_front_o_ext(const FrontExtParams &p, hipStream_t s);  // front_o_ext.hip
 hipError_t launch_deriv16(const DerivParams &p, hipStream_t s);  // deriv.hip: Sobel 3 / 5 / 7 and Scharr derivatives, u8 -> int16 dx / dy
-// stats.hip (the product library only, as the launchers down to launch_hough_circles: the test library defines none of them): frame
+// stats.hip (the product library only, as the launchers down to launch_connected_components: the test library defines none of them): frame
 // histograms and the automatic thresholds of Mode O
 hipError_t launch_hist256(const HistParams &p, hipStream_t s);  // p.hist must be zero when the kernel starts
 hipError_t launch_auto_thr(const u32 *hist, int nframes, int rule, double param, int32_t *thr, hipStream_t s);  // hist [nframes][256] -> thr [nframes][2]
@@ -31,6 +31,9 @@ hipError_t launch_hough_segments(const SegParams &p, hipStream_t s);
 // (launch_hough_peaks), k_circle_rank, k_circle_sift, k_circle_radii (count), k_circle_scan and, with p.circle_capacity > 0,
 // k_circle_radii (emit)
 hipError_t launch_hough_circles(const CircleParams &p, hipStream_t s);
+// ccl.hip (the product library only): one pass of k_ccl_local, k_ccl_merge, k_ccl_flatten, k_ccl_scan, k_ccl_roots, k_ccl_number
+// and, with p.capacity > 0, k_ccl_rows, k_ccl_stats and k_ccl_finish
+hipError_t launch_connected_components(const CclParams &p, hipStream_t s);
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

@@ -273,6 +273,34 @@ struct CircleParams {
   unsigned rank_groups;      // workgroups of k_circle_rank per frame: ceil(peak_cap / HOUGH_RANK_THREADS)
 };
 
+// k_ccl_local / k_ccl_merge / k_ccl_flatten / k_ccl_scan / k_ccl_roots / k_ccl_number / k_ccl_rows / k_ccl_stats / k_ccl_finish
+// (ccl.hip): the connected components of u8 maps -- labels, number, and per component bounding box, area and centroid
+// (cv::connectedComponentsWithStats).  The only per-pixel storage is the caller's label plane.  While the kernels run, a
+// foreground pixel's label is 1 + the WORD index of a pixel of its component that lies before it in raster order, the word index
+// of pixel (x, y) being y * (label_pitch / 4) + x: its place in the frame's label plane, which orders pixels as y * W + x does
+// and needs no division to become an address (H * label_pitch < 2^32: below 2^30).  One block describes one pass, as
+// HoughParams does: `nframes` frames whose per-chunk root counts lie in the context's table together.
+constexpr int CCL_TILE_W = 64, CCL_TILE_H = 32;  // a workgroup of k_ccl_local: a row of the tile is one wave's ballot, 8 KiB of LDS labels
+constexpr int CCL_THREADS = 256;
+constexpr unsigned CCL_ROW_GROUPS = 1024;        // workgroups per frame of k_ccl_rows / k_ccl_finish at most: each strides over the rows
+struct CclParams {
+  const uint8_t *map;      // u8 maps of W x H, one channel, any alignment of base, pitch and frame stride
+  size_t pitch, frame_stride;
+  int32_t *labels;         // int32 [H][W] per frame; label_pitch and label_frame_stride in BYTES, multiples of 4, H * label_pitch < 2^32
+  size_t label_pitch, label_frame_stride;
+  u32 *items;              // scratch [nframes][nchunks]: the roots of a chunk of rows (k_ccl_flatten), then the roots before it (k_ccl_scan)
+  u32 *counts;             // [nframes]: components + 1
+  int32_t *stats;          // [nframes][capacity][5], 4-byte aligned; unused when capacity == 0
+  unsigned long long *sums;  // the centroids [nframes][capacity][2], 8-byte aligned: the int64 sums of x and y until k_ccl_finish divides them
+  size_t capacity;
+  int W, H, nframes;
+  int connectivity;        // 4 or 8
+  int tiles_x, tiles_y;    // ceil(W / CCL_TILE_W), ceil(H / CCL_TILE_H)
+  unsigned border_items;   // per frame: (tiles_y - 1) * W pixels below a horizontal tile border + (tiles_x - 1) * H right of a vertical one
+  int chunk_rows, nchunks, total_items;  // hist_chunk_rows of the call; ceil(H / chunk_rows); nframes * nchunks
+  unsigned row_groups;     // workgroups per frame of k_ccl_rows / k_ccl_finish: ceil(min(capacity, W * H + 1) / CCL_THREADS), at most CCL_ROW_GROUPS
+};
+
 struct HystParams {
   u32 *sbits;
   const u32 *cbits;

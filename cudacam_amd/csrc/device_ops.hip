@@ -240,4 +240,27 @@ int hc_hough_circles_device(hc_ctx *c, const void *d_points, const void *d_point
   return HC_OK;
 }
 
+// The kernels of ccl.hip on the context stream, pass after pass.  Not a run, as hc_edge_points_device; like hc_gaussian_blur_device
+// it completes first a pipelined run in flight whose output overlaps either view: the map it reads or the label plane it writes.
+// Successive calls share the table of per-chunk counts and are ordered by the stream they are queued on (include/hipcanny.h).
+int hc_connected_components_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs, int n, int connectivity, void *d_labels, size_t label_pitch,
+                                   size_t label_fs, void *d_counts, void *d_stats, void *d_centroids, size_t capacity)
+{
+  if (!c || !d_map || !d_labels || !d_counts) return fail(HC_E_ARG, "hc_connected_components_device: null argument");
+  const int max_frames = c->max_batch * (c->per_channel ? 3 : 1);  // (as hc_edge_points_device: the output frames of a max_batch run)
+  const size_t row = (size_t)c->W, label_row = 4 * (size_t)c->W;
+  if (int rc = check_views(c, "hc_connected_components_device", n, max_frames, { { "d_map (pitch, frame_stride)", d_map, pitch, fs, row, 1, true }, { "d_labels (label_pitch, label_frame_stride)", d_labels, label_pitch, label_fs, label_row, 4, true } })) return rc;
+  const View map{ (uintptr_t)d_map, pitch, fs }, labels{ (uintptr_t)d_labels, label_pitch, label_fs };
+  const CclPlan P = plan_connected_components(c->W, c->H, max_frames, map, labels, n, connectivity, (uintptr_t)d_counts, (uintptr_t)d_stats, (uintptr_t)d_centroids,
+                                              capacity, c->hough_bound);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_connected_components_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  if (int rc = finish_writers_of(c, map, row, n)) return rc;
+  if (int rc = finish_writers_of(c, labels, label_row, n)) return rc;
+  // every refusal lies above.  A larger table: what is queued on the context stream may still read the old one
+  if (int rc = ensure_scratch(c, c->ccl_items, P.scratch_bytes)) return rc;
+  for (int k = 0; k < P.passes; ++k) HIPCK(launch_connected_components(ccl_pass(P, k, (uintptr_t)c->ccl_items.p), c->stream));
+  return HC_OK;
+}
+
 }  // extern "C"

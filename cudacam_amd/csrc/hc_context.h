@@ -219,6 +219,8 @@ struct hc_ctx {
   // hc_hough_circles_device: the scratch of one pass [ranked centres | kept centres | peak lists | accumulators | per-row counts |
   // per-centre counts | peak and kept totals] (circle_pass, host_plan.h), bounded by hough_bound as well
   hc::DeviceScratch circles;
+  // hc_connected_components_device: the roots / offsets per chunk of rows of one pass (ccl_pass, host_plan.h), bounded by hough_bound as well
+  hc::DeviceScratch ccl_items;
 };
 
 namespace hc {

@@ -1193,4 +1193,76 @@ inline CircleParams circle_pass(const CirclePlan &P, int k, uintptr_t scratch)
   return c;
 }
 
+// ---- hc_connected_components_device ---------------------------------------------------------------
+// Everything the entry refuses and decides, but for the context pointer.  cp describes the FIRST pass with the table pointer
+// null; ccl_pass gives pass k with it patched in.  A refused plan holds nothing but its text.  The scratch is the table of
+// per-chunk root counts alone ([frames_per_pass][nchunks] words: it grows with the frame's height, so it falls under the
+// context's scratch bound and a batch is cut into passes of as many frames as fit); the sums of the statistics live in the
+// caller's own rows until the last kernel turns them into the result.
+struct CclPlan {
+  const char *error = nullptr;
+  CclParams cp{};
+  int frames = 0, frames_per_pass = 0, passes = 0;
+  size_t frame_items_bytes = 0, scratch_bytes = 0;
+  bool stats = false;  // k_ccl_rows, k_ccl_stats and k_ccl_finish are launched (capacity > 0)
+};
+inline CclPlan plan_connected_components(int W, int H, int max_frames, const View &map, const View &labels, int n, int connectivity, uintptr_t counts,
+                                         uintptr_t stats, uintptr_t centroids, size_t capacity, size_t scratch_bound)
+{
+  CclPlan P;
+  auto refuse = [](const char *text) { CclPlan R; R.error = text; return R; };
+  if (!map.p || !labels.p || !counts) return refuse("null argument");
+  if (capacity && (!stats || !centroids)) return refuse("d_stats or d_centroids is null with capacity > 0");
+  if (connectivity != 4 && connectivity != 8) return refuse("connectivity must be 4 or 8");
+  if ((counts | stats) & 3u) return refuse("d_counts and d_stats must be 4-byte aligned");
+  if (centroids & 7u) return refuse("d_centroids must be 8-byte aligned");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  if (W < 1 || H < 1) return refuse("width and height must be positive");
+  if ((long long)W * H >= 0x7FFFFFFFll) return refuse("width * height reaches 2^31 - 1 pixels");
+  if (const ViewFault f = check_view(map, (size_t)W, H, n, 1, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  if (const ViewFault f = check_view(labels, 4 * (size_t)W, H, n, 4, true))
+    return refuse(f == VIEW_ALIGN ? "d_labels, label_pitch and label_frame_stride must be multiples of 4" : f == VIEW_PITCH ? "label_pitch smaller than a row of int32 labels" : VIEW_FAULT_TEXT[f]);
+  uintptr_t end[2];
+  if (!view_end(map, (size_t)W, H, n, &end[0]) || !view_end(labels, 4 * (size_t)W, H, n, &end[1])) return refuse("a view wraps the address space");
+  if (map.p < end[1] && labels.p < end[0]) return refuse("the map and the label plane overlap");
+  if (capacity > SIZE_MAX / 20 / (size_t)n) return refuse("capacity * 20 * nframes overflows size_t");
+  if (capacity > SIZE_MAX / 16 / (size_t)n) return refuse("capacity * 16 * nframes overflows size_t");
+  CclParams &c = P.cp;
+  c.chunk_rows = hist_chunk_rows(H, n); c.nchunks = (H + c.chunk_rows - 1) / c.chunk_rows;
+  P.frame_items_bytes = 4 * (size_t)c.nchunks;
+  if (scratch_bound < P.frame_items_bytes) return refuse("one frame's table of per-chunk counts exceeds the context's scratch bound");
+  P.frames = n;
+  P.frames_per_pass = (int)std::min<size_t>(std::min<size_t>((size_t)n, scratch_bound / P.frame_items_bytes), HOUGH_MAX_PASS_FRAMES);
+  P.passes = (n + P.frames_per_pass - 1) / P.frames_per_pass;
+  P.scratch_bytes = (size_t)P.frames_per_pass * P.frame_items_bytes;
+  c.tiles_x = (W + CCL_TILE_W - 1) / CCL_TILE_W; c.tiles_y = (H + CCL_TILE_H - 1) / CCL_TILE_H;
+  const long long tiles = (long long)c.tiles_x * c.tiles_y, border = (long long)(c.tiles_y - 1) * W + (long long)(c.tiles_x - 1) * H;
+  if (tiles > (1ll << 23) || border > 0x7FFFFFF0ll || (long long)P.frames_per_pass * c.nchunks > 0x7FFFFFF0ll)
+    return refuse("too many work items (tiles, border pixels or frames of a pass x row chunks)");
+  c.map = (const uint8_t *)map.p; c.pitch = map.pitch; c.frame_stride = map.fs;
+  c.labels = (int32_t *)labels.p; c.label_pitch = labels.pitch; c.label_frame_stride = labels.fs;
+  c.counts = (u32 *)counts; c.stats = (int32_t *)stats; c.sums = (unsigned long long *)centroids; c.capacity = capacity;
+  c.W = W; c.H = H; c.nframes = P.frames_per_pass; c.connectivity = connectivity;
+  c.border_items = (unsigned)border; c.total_items = c.nframes * c.nchunks;
+  const size_t rows = std::min<size_t>(capacity, (size_t)W * (size_t)H + 1);  // (no frame has more components than pixels)
+  c.row_groups = (unsigned)std::min<size_t>((rows + CCL_THREADS - 1) / CCL_THREADS, CCL_ROW_GROUPS);
+  P.stats = capacity > 0;
+  return P;
+}
+
+// Pass k of a plan that was not refused (0 <= k < passes), on the table `items` (scratch_bytes, 4-byte aligned)
+inline CclParams ccl_pass(const CclPlan &P, int k, uintptr_t items)
+{
+  CclParams c = P.cp;
+  const int f0 = k * P.frames_per_pass;
+  c.nframes = std::min(P.frames_per_pass, P.frames - f0);
+  c.total_items = c.nframes * c.nchunks;
+  c.map += (size_t)f0 * c.frame_stride;
+  c.labels = (int32_t *)((uintptr_t)c.labels + (size_t)f0 * c.label_frame_stride);
+  c.counts += f0;
+  if (c.capacity) { c.stats += (size_t)f0 * c.capacity * 5; c.sums += (size_t)f0 * c.capacity * 2; }
+  c.items = (u32 *)items;
+  return c;
+}
+
 }  // namespace hc

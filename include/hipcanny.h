@@ -503,6 +503,62 @@ int hc_hough_circles_device(hc_ctx *ctx, const void *d_points /* int32 [nframes]
 int hc_hough_circle_geometry(int width, int height, double dp, double min_dist, int min_radius, int max_radius,
                              int *acc_width, int *acc_height, long long *min_d2);   /* host, no context, no GPU */
 
+/* The connected components of u8 maps on the device: a number per pixel, the number of components and, per component, bounding
+ * box, area and centroid -- cv::connectedComponents / cv::connectedComponentsWithStats per frame, the form OpenCV's GPU module
+ * offers as cv::cuda::connectedComponents (k_ccl_local, k_ccl_merge, k_ccl_flatten, k_ccl_scan, k_ccl_roots, k_ccl_number,
+ * k_ccl_rows, k_ccl_stats, k_ccl_finish: cudacam_amd/csrc/ccl.hip).  The semantics are stated here and restated in
+ * tests/ccl_ref.py (numpy and a flood fill); like the rest of Mode O they are not pinned against a build of OpenCV.  With W, H the
+ * context's frame size:
+ * Input.  d_map is what hc_edge_points_device reads: one-channel u8 maps of W x H in a pitched view, whatever `channels` the
+ *   context has; any alignment of base, pitch and frame stride; no byte outside [row, row + W) of a row is read.  A pixel is
+ *   foreground iff its byte is non-zero: the 255 of a final map, the 128 / 255 of an HC_STAGE_THRESH map alike.  The map is never
+ *   written.
+ * Connectivity.  8: neighbours share an edge or a corner (OpenCV's default); 4: an edge only.  A component is a maximal set of
+ *   foreground pixels connected through such neighbours inside the frame.  Frames are independent.
+ * Numbering.  The first pixel of a component is its pixel with the smallest y * W + x; components are numbered 1, 2, ... in
+ *   ascending order of their first pixels; background is 0.  This is the order a raster scan meets them in, and the order
+ *   scipy.ndimage.label gives.  cv::connectedComponents promises no order: a caller who compares with it compares partitions.
+ * Labels.  d_labels receives int32 [H][W] per frame, label_pitch and label_frame_stride in bytes -- the memory of a CV_32S
+ *   cv::Mat.  Exactly the bytes [row, row + 4 * W) of every row are written, so it may be an ROI of a larger plane; base, pitch
+ *   and frame stride are multiples of 4 (nothing is staged).  Required; CV_16U labels are not offered.  Every pixel gets its final
+ *   number, also the pixels of components numbered `capacity` and above.  While the call runs the plane holds intermediate links.
+ * Counts.  d_counts[f] = N = components + 1, the value cv::connectedComponents returns (background included) -- always the full
+ *   number, also above `capacity`.
+ * Stats and centroids.  The slots of frame f start at bytes f * capacity * 20 and f * capacity * 16 and receive the rows
+ *   0 .. min(N, capacity) - 1; row 0 is the background, row k component k -- the memory of the CV_32S N x 5 and CV_64F N x 2
+ *   matrices of cv::connectedComponentsWithStats.  HC_CC_STAT_LEFT / TOP: the smallest x / y; WIDTH / HEIGHT: largest minus
+ *   smallest plus 1; AREA: the pixel count.  Centroid = ((double)sx / (double)area, (double)sy / (double)area) with sx, sy the
+ *   exact int64 sums of the pixels' x and y: one correctly rounded float64 division each.  A background without a pixel (a full
+ *   frame) gets five zeros and the centroid (0.0, 0.0); OpenCV leaves its initial values (INT_MAX / INT_MIN boxes, a 0 / 0
+ *   centroid) there.  Nothing else is written: not the rows behind a slot's written rows, not other slots.  The written rows hold
+ *   intermediate sums while the call runs.  capacity == 0 (pointers null or not) gives labels and counts only:
+ *   cv::connectedComponents.  d_stats is 4-byte, d_centroids 8-byte aligned; both are required when capacity > 0.
+ * Asynchronous on the context stream (hc_set_stream honoured).  Chained behind hc_canny_device it needs no synchronisation.
+ * Contexts of either mode.  It is not a run, exactly as hc_edge_points_device is none (hc_last_run_info, the stage timers, the
+ * hysteresis schedule / history and the pipeline slots stay as they were), and as hc_gaussian_blur_device does for both of its
+ * views it completes first a pipelined run still in flight whose output overlaps d_map or the label view.
+ * The result is a function of the map alone although the kernels merge with global atomics: the fixed point of a min-label
+ * union-find is unique (every component ends rooted at its first pixel), the numbering is a total order, and integer sums, minima
+ * and maxima do not depend on arrival order.
+ * Scratch: one table of per-row-chunk counts the context owns (allocated on first use, grown when a call needs more, freed by
+ * hc_destroy; 4 bytes per 8 to 64 rows of a frame), under the bound of hc_hough_lines_device's scratch (256 MiB; a batch whose
+ * tables exceed it runs in passes of as many frames as fit).  The only per-pixel storage is the label plane.  Successive calls
+ * share the table and are ordered by the stream they are queued on, as for hc_edge_points_device.
+ * HC_E_ARG: ctx, d_map, d_labels or d_counts null; d_stats or d_centroids null with capacity > 0; connectivity not 4 or 8;
+ * d_counts or d_stats not 4-byte, d_centroids not 8-byte aligned; d_labels, label_pitch or label_frame_stride no multiple of 4;
+ * pitch < W; label_pitch < 4 * W; H * pitch >= 2^32 or H * label_pitch >= 2^32; nframes outside 1..(max_batch, 3 * max_batch with
+ * HC_OPT_PER_CHANNEL); nframes > 1 with a frame stride below H * pitch on either side; a view that wraps the address space;
+ * W * H >= 2^31 - 1; overlapping byte ranges of the two views (views that merely touch are fine); capacity * 20 * nframes or
+ * capacity * 16 * nframes overflowing size_t; one frame's table above the scratch bound.  Every refusal lies above the first
+ * allocation or launch.  Measurements: profiles/ccl/README.md. */
+enum { HC_CC_STAT_LEFT = 0, HC_CC_STAT_TOP, HC_CC_STAT_WIDTH, HC_CC_STAT_HEIGHT, HC_CC_STAT_AREA, HC_CC_STAT_WORDS };
+int hc_connected_components_device(hc_ctx *ctx, const void *d_map, size_t pitch, size_t frame_stride, int nframes, int connectivity,
+                                   void *d_labels, size_t label_pitch, size_t label_frame_stride,
+                                   void *d_counts    /* uint32  [nframes] */,
+                                   void *d_stats     /* int32   [nframes][capacity][5]; may be NULL when capacity == 0 */,
+                                   void *d_centroids /* float64 [nframes][capacity][2]; may be NULL when capacity == 0 */,
+                                   size_t capacity);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
