@@ -75,6 +75,50 @@ def stats_fast(lab, n):
     return st, cen
 
 
+def _pixels_row(x, y):
+    """(statistics row, centroid) of a set of pixels given by its coordinates: the sums are Python ints until the two divisions."""
+    x, y = np.asarray(x, np.int64), np.asarray(y, np.int64)
+    area = int(x.size)
+    if area == 0:
+        return (0, 0, 0, 0, 0), (0.0, 0.0)
+    left, top = int(x.min()), int(y.min())
+    return (left, top, int(x.max()) - left + 1, int(y.max()) - top + 1, area), (np.float64(int(x.sum())) / np.float64(area), np.float64(int(y.sum())) / np.float64(area))
+
+
+def checkerboard4(w, h):
+    """(labels, N, statistics, centroids) of the map (x + y) % 2 == 0 at connectivity 4, in closed form, no fill: no two foreground
+    pixels share an edge, so each is a component of its own, numbered in raster order -- row k is (x, y, 1, 1, 1) with the
+    centroid (x, y); row 0 is the other colour of the board."""
+    yy, xx = np.mgrid[0:h, 0:w]
+    fg = (xx + yy) % 2 == 0
+    n = int(fg.sum()) + 1
+    labels = np.zeros((h, w), np.int32)
+    labels[fg] = np.arange(1, n, dtype=np.int32)
+    st = np.ones((n, STAT_WORDS), np.int32)
+    cen = np.zeros((n, 2), np.float64)
+    st[1:, 0], st[1:, 1] = xx[fg], yy[fg]
+    cen[1:, 0], cen[1:, 1] = xx[fg], yy[fg]
+    st[0], cen[0] = _pixels_row(xx[~fg], yy[~fg])
+    return labels, n, st, cen
+
+
+def columns(w, h, x1):
+    """(labels, N, statistics, centroids) of the map whose columns [0, x1) are foreground, at either connectivity, in closed form:
+    x1 = w is the full frame, x1 = 0 the empty one.  One rectangle and the rectangle behind it; a rectangle of the columns
+    [a, b) has the sums (b - a) * h * (a + b - 1) / 2 of x and (b - a) * h * (h - 1) / 2 of y, exact as Python ints."""
+    def rect(a, b):
+        area = (b - a) * h
+        if area == 0:
+            return (0, 0, 0, 0, 0), (0.0, 0.0)
+        sx, sy = (b - a) * h * (a + b - 1) // 2, (b - a) * h * (h - 1) // 2
+        return (a, 0, b - a, h, area), (np.float64(sx) / np.float64(area), np.float64(sy) / np.float64(area))
+    n = 2 if x1 > 0 else 1
+    labels = np.zeros((h, w), np.int32)
+    labels[:, :x1] = 1
+    rows = [rect(x1, w), rect(0, x1)][:n]
+    return labels, n, np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.float64)
+
+
 def connected_components(maps, connectivity=8, capacity=None):
     """maps (n, H, W) -> (int32 labels (n, H, W), uint32 counts (n), [int32 (min(N, capacity), 5)], [float64 (min(N, capacity), 2)]);
     capacity None: every row."""

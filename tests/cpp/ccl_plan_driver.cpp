@@ -2,6 +2,12 @@
 // (tests/test_ccl_plan_cpu.py builds this with g++ under ASan + UBSan): every refusal hc_connected_components_device documents, by
 // its message; tiles, grids, passes and scratch bytes under the default bound and small ones; the guards at 2^31 - 1 pixels and
 // 2^32 row bytes; and that a refused plan holds nothing.  Prints "ok <checks>" or the first violations.
+//   ccl_plan_driver plan W H max_frames { nframes connectivity map pitch frame_stride labels label_pitch label_frame_stride rows
+//                                         capacity scratch_bound }...
+// prints, for each group of eleven, "scratch_bytes passes frames_per_pass chunk_rows" or "refused: <text>" (tests/
+// test_device_op_sequences_cpu.py: the components steps of the seeded chains).  map and labels are addresses, so that the plan
+// sees how the two views lie to each other; rows 0 gives null statistics and centroid pointers; a scratch_bound of 0 is the
+// context's default, as hc_set_option takes it.
 #include "../../cudacam_amd/csrc/host_plan.h"
 
 #include <cstdio>
@@ -149,8 +155,30 @@ static void passes()
     if (!P.error) { const CclParams q = ccl_pass(P, 2, 0x70000000u); VCHECK(q.stats == nullptr && q.sums == nullptr && q.nframes == 1, "null rows stay null"); } }
 }
 
-int main()
+static int print_plans(int count, char **v)
 {
+  Call c;
+  c.W = std::atoi(v[0]); c.H = std::atoi(v[1]); c.max_frames = std::atoi(v[2]);
+  auto num = [](const char *t) { return (size_t)std::strtoull(t, nullptr, 10); };
+  for (char **g = v + 3; g + 11 <= v + count; g += 11) {
+    c.n = std::atoi(g[0]); c.conn = std::atoi(g[1]);
+    c.map = View{ (uintptr_t)num(g[2]), num(g[3]), num(g[4]) };
+    c.labels = View{ (uintptr_t)num(g[5]), num(g[6]), num(g[7]) };
+    const bool rows = std::atoi(g[8]) != 0;
+    c.stats = rows ? ST : 0; c.cents = rows ? CE : 0;
+    c.cap = num(g[9]);
+    const size_t bound = num(g[10]);
+    c.bound = bound ? bound : HOUGH_SCRATCH_BYTES;
+    const CclPlan P = c.plan();
+    if (P.error) std::printf("refused: %s\n", P.error);
+    else std::printf("%zu %d %d %d\n", P.scratch_bytes, P.passes, P.frames_per_pass, P.cp.chunk_rows);
+  }
+  return 0;
+}
+
+int main(int argc, char **argv)
+{
+  if (argc >= 5 && (argc - 5) % 11 == 0 && !std::strcmp(argv[1], "plan")) return print_plans(argc - 2, argv + 2);
   refusals();
   geometry();
   passes();

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Seeded CHAINS of device ops and runs on one context: the entries that are not runs (blur, derivatives, automatic thresholds,
-edge points, Hough lines, Hough segments, Hough circles) queued between and behind runs, with no synchronisation but the few the sequence
+edge points, Hough lines, Hough segments, Hough circles, connected components) queued between and behind runs, with no synchronisation but the few the sequence
 itself names.  tests/fuzz_sequences.py does this for the runs alone; each entry has a GPU test file of its own for its shapes,
 capacities, views and refusals.  What neither reaches is the state the entries share on one context (cudacam_amd/csrc/
 device_ops.hip: the scratch buffers that grow and never shrink, the Hough and walk tables cached by geometry) and the one place
@@ -9,13 +9,14 @@ where they meet the runs (finish_writers_of: which pipelined runs in flight a re
 Three parts, the first two pure (numpy, the CPU oracle, the numpy restatements; no GPU, no clock):
   make_sequence(seed)   context parameters, 12 .. 20 steps (plain dicts; the synchronisation a stream switch needs, the step that
                         takes a threshold table off again and the final sync are among them), 1 .. 3 circles steps drawn from a
-                        generator of their own and inserted among them (add_circles), and counters that say what the sequence
-                        exercises
+                        generator of their own and inserted among them (add_circles), 1 .. 3 components steps from a third
+                        generator inserted among those (add_components), and counters that say what the sequence exercises
   Model                 the expected content of EVERY byte of every device buffer the sequence owns, step after step: inputs in
                         arenas of 255s, edge maps with the padding of their pitch, counts between guard words, lists in slots
                         pre-filled with a canary.  A step reads its inputs from the model and writes its outputs back, so values
-                        propagate (a run's maps -> points -> lines -> segments; points and gradient planes -> circles) and
-                        nothing is read from the device in between.
+                        propagate (a run's maps -> points -> lines -> segments; points and gradient planes -> circles; maps ->
+                        labels, which a later reader of the same bytes takes for a map) and nothing is read from the device in
+                        between.
   Executor              queues the same steps through api.Context and, at every "sync" step and at the end, compares every buffer
                         with the model byte for byte -- results, canaries, guards and padding alike.
 The per-entry helpers of the GPU test files (_upload / _check) upload a map per call and check one call's buffers; here a buffer
@@ -43,6 +44,7 @@ for p in (os.path.dirname(HERE), HERE):
         sys.path.insert(0, p)
 
 import auto_thr_ref as AT          # noqa: E402
+import ccl_ref as CC               # noqa: E402
 import canny_o_ext_ref as X        # noqa: E402
 import deriv_ref as D              # noqa: E402
 import edge_points_ref as EP       # noqa: E402
@@ -73,6 +75,11 @@ KINDS = ("run", "canny", "deriv", "rungrad", "blur", "autothr", "thr_on", "thr_o
 # ... and the one kind that make_steps does not draw: add_circles inserts it, from a generator of its own, so that a seed keeps the
 # steps it had before there were circles
 CIRCLES_DP, CIRCLES_MIN_DIST, CIRCLES_THRESHOLD, CIRCLES_CC = (1.0, 1.5, 2.0), (0.0, 3.0, 8.0), (2, 4, 8), (16, 300, 4096)
+# ... nor the other: add_components inserts `components` steps behind the circles, from a third generator, for the same reason.
+# Capacities: 0 with null rows, 0 with row pointers, the background row alone, a few rows (which cuts most frames), every row.
+# Label planes of their own (lab0 / lab1) begin 4 * loff bytes into the arena, with lpad bytes behind each row and lgap between frames
+COMP_CAPS, COMP_CUTS = ("null", "zero", "one", "cut", "all"), (2, 3, 9)
+LAB_LEAD, LAB_OFFS, LAB_PADS, LAB_GAPS = 512, (0, 1, 2, 3), (0, 4, 20), (0, 8, 132)
 VIEW_KINDS = ("whole", "frame", "roi", "before", "behind", "sout")
 COUNTERS = tuple(f"overlap_{k}" for k in ("whole", "frame", "roi", "sout", "before", "behind", "blur_in", "blur_out")) + (
     "adjacent", "hough_tables_equal_numangle", "seg_tables_equal_numangle", "scratch_growths", "n_above_max_batch", "hough_passes_above_one",
@@ -82,10 +89,20 @@ COUNTERS = tuple(f"overlap_{k}" for k in ("whole", "frame", "roi", "sout", "befo
     # more ranked centres than the centre capacity; centres the smallest distance dropped; calls with no deriv step before them /
     # with more frames than the last deriv step wrote; calls with a lines call before and behind them and no sync among the three
     "circle_lists_nonempty", "circle_lists_cut", "circle_passes_above_one", "circle_scratch_growths", "circles_from_cut_points", "circles_centres_cut",
-    "circles_dropped_by_min_dist", "circles_on_unwritten_planes", "circles_on_stale_frames", "circles_between_lines")
-# ... of which the committed seeds together must reach every one but these two: a view beside one output that lies inside its
-# neighbour is a "whole" or "frame" overlap of that neighbour under another name
-REQUIRED = tuple(c for c in COUNTERS if c not in ("overlap_before", "overlap_behind"))
+    "circles_dropped_by_min_dist", "circles_on_unwritten_planes", "circles_on_stale_frames", "circles_between_lines",
+    # components steps: calls whose map view / whose label plane overlapped the output of a run in flight; frames with more
+    # components than a capacity that is not 0; calls with capacity 0; calls of more frames than max_batch; calls whose map view
+    # overlaps bytes that an earlier step wrote as labels over an output and no write has covered since; calls that need a
+    # larger table than every components call before them; calls of more than one pass
+    "components_overlap_map", "components_labels_over_pending", "components_rows_cut", "components_capacity_0", "components_n_above_max_batch",
+    "components_of_label_bytes", "ccl_scratch_growths", "ccl_passes_above_one")
+# ... of which the committed seeds together must reach every one but these four.  A view beside one output that lies inside its
+# neighbour is a "whole" or "frame" overlap of that neighbour under another name.  The table of a components call has a word per
+# chunk of 8 rows: at most 36 bytes per frame here, while a seeded context's bound, if it has one, is two frames of the largest
+# Hough geometry -- so no seeded call can take a second pass: test_components_in_passes_under_a_bound (tests/
+# test_gpu_device_op_sequences.py) covers that as a named case.  A table grows where a call of more frames follows one of fewer,
+# which five of the committed seeds happen to do; test_the_component_table_grows_while_a_call_is_queued is the case that must
+REQUIRED = tuple(c for c in COUNTERS if c not in ("overlap_before", "overlap_behind", "ccl_scratch_growths", "ccl_passes_above_one"))
 # Output views that force the staged path (copy_dst), from the families of tests/test_gpu_views.py.  Of those only the odd one
 # stages an output (P4, GM and ROI are multiples of 4 throughout); the other two here are its P4 and ROI with the one thing made
 # odd that hc_run_device names beside the pitch: the base pointer alone, the frame stride alone.
@@ -95,8 +112,13 @@ STAGED_FAMILIES = ("ODDO", "P4_BASE", "ROI_FS")
 # overlaps a pending writer, every one a segment list that is not empty, and the sizes, modes, channel counts and staged
 # families all occur.  The circles steps came later, from a generator of their own (add_circles), and left those 28 every step they
 # had; of the circle counters of REQUIRED the 28 reach all but two, for which --scan 0 300 gave 58 (circles_on_stale_frames) and
-# 108 (circle_passes_above_one, which takes 61 x 33 frames, a scratch bound and four frames at centre capacity 4096: one seed of the 300)
-SEEDS = (0, 1, 3, 5, 6, 7, 8, 9, 11, 13, 14, 15, 17, 21, 22, 25, 31, 35, 40, 49, 66, 69, 85, 86, 100, 141, 145, 207, 58, 108)
+# 108 (circle_passes_above_one, which takes 61 x 33 frames, a scratch bound and four frames at centre capacity 4096: one seed of the 300).
+# The components steps came last, from a third generator (add_components), and left those 30 every step they had, circles
+# included.  The 30 reach every components counter of REQUIRED (--scan: labels over a pending output in 3, 15 and 207, label bytes
+# read as a map in 15, 22 and 207, more than max_batch frames in 25, the others in a dozen each), so no seed was added for a
+# counter.  One was added for a view: in none of the 30 does a components step read the buffer a staged run copies to, the one map
+# view at an odd pitch; --scan 0 300 gave 229 (components of `sout` at every row's capacity, the labels over a pending output)
+SEEDS = (0, 1, 3, 5, 6, 7, 8, 9, 11, 13, 14, 15, 17, 21, 22, 25, 31, 35, 40, 49, 66, 69, 85, 86, 100, 141, 145, 207, 58, 108, 229)
 
 
 def rup(v, m):
@@ -126,6 +148,14 @@ def layout(P):
         L["sizes"][f"lines{k}"] = 4 * (words + 3 * NLIST * LCAP_MAX)
         L["sizes"][f"segs{k}"] = 4 * (words + 4 * NLIST * SCAP_MAX)
         L["sizes"][f"circ{k}"] = 4 * (words + 4 * NLIST * CCAP_MAX)
+    # components: label planes of their own (nmax frames at the largest pad and gap, behind the largest offset), and per output slot
+    # the counts between guard words, nmax x (W * H + 1) statistics rows, a guard, as many centroid rows at an 8-byte offset, a guard
+    L["cmax"] = w * h + 1
+    L["stats_off"] = 4 * (2 * GUARD + NLIST)
+    L["cent_off"] = rup(L["stats_off"] + 20 * L["nmax"] * L["cmax"] + 4 * GUARD, 8)
+    for k in range(2):
+        L["sizes"][f"lab{k}"] = 2 * LAB_LEAD + 4 * LAB_OFFS[-1] + L["nmax"] * ((4 * w + LAB_PADS[-1]) * h + LAB_GAPS[-1])
+        L["sizes"][f"comp{k}"] = L["cent_off"] + 16 * L["nmax"] * L["cmax"] + 4 * GUARD
     L["counts_off"] = 4 * GUARD
     L["list_off"] = 4 * (2 * GUARD + NLIST)
     return L
@@ -169,6 +199,15 @@ def resolve_view(L, v):
     raise ValueError(v)
 
 
+def label_view(L, st):
+    """(buffer, offset, pitch, frame stride) of the label plane of a components step: in an arena of its own, or -- one frame --
+    laid over output region lslot of `maps`, four bytes for each byte of the region's first frames."""
+    if st["dest"] == "over":
+        return "maps", out_start(L, st["lslot"]), 4 * L["op"], 4 * L["ofs"]
+    pitch = 4 * L["w"] + st["lpad"]
+    return f"lab{st['lslot']}", LAB_LEAD + 4 * st["loff"], pitch, pitch * L["h"] + st["lgap"]
+
+
 def list_fits(kind, n, cap, width, L):
     """n slots of `cap` entries of `width` words lie inside a list buffer, behind its counts and before its last guard."""
     return n <= NLIST and L["list_off"] + 4 * width * cap * n <= L["sizes"][kind + "0"] - 4 * GUARD
@@ -193,6 +232,17 @@ def circle_need(w, h, dp, cc, n, bound):
     aw, ah, _ = HC.geometry(w, h, dp, 0.0, 1, 1)
     per = 2 * 16 * cc + 8 * ah * ((aw + 1) // 2) + 4 * (ah + 2) * (aw + 2) + 4 * ah + 4 * cc + 8
     fpp = min(n, (bound or (256 << 20)) // per)
+    return (fpp * per, (n + fpp - 1) // fpp, per) if fpp else (0, 0, per)
+
+
+def ccl_need(h, n, bound):
+    """(scratch bytes, passes, bytes per frame) of hc_connected_components_device as include/hipcanny.h and plan_connected_components
+    (host_plan.h) state them: a word per chunk of rows and frame of a pass, the rows of a chunk by hist_chunk_rows (canny_params.h)
+    from the rows of the whole call -- 8, or all of a lower frame, until H x nframes passes 65,536; then a 8192nd of them, 64 at
+    most.  (0, 0, bytes per frame) where one frame exceeds the bound: the entry refuses that call."""
+    rows = min(max((h * n + 8191) // 8192, 8), 64, h)
+    per = 4 * ((h + rows - 1) // rows)
+    fpp = min(n, (bound or (256 << 20)) // per, 65535)
     return (fpp * per, (n + fpp - 1) // fpp, per) if fpp else (0, 0, per)
 
 
@@ -230,12 +280,12 @@ class Model:
         if O is None:
             from oracle import oracle as O
             O.build()
-        self.O, self.P = O, P
+        self.O, self.P = O, dict(P)   # (a copy: an option step of a named case changes the scratch bound)
         self.L = L = layout(P)
         self.w, self.h, self.ch = P["w"], P["h"], P["ch"]
         self.buf = {name: np.full(size, 255, np.uint8) for name, size in L["sizes"].items()}
         for name in self.buf:
-            if name[:3] in ("pts", "lin", "seg", "cir", "thr"):
+            if name[:3] in ("pts", "lin", "seg", "cir", "thr", "com"):
                 self.buf[name][:] = CANARY_BYTE
         frames = pool_frames(P)
         self.put("frames", L["ilead"], L["ip"], L["ifs"], frames.reshape(POOL, self.h, -1), log=False)
@@ -246,7 +296,8 @@ class Model:
         self.table = False
         self.pending = []          # pipelined runs in flight: (buffer, lo, hi, staged)
         self.hough_key = self.seg_key = None
-        self.hough_bytes = self.seg_bytes = self.circle_bytes = 0
+        self.hough_bytes = self.seg_bytes = self.circle_bytes = self.ccl_bytes = 0
+        self.label_spans = []      # (buffer, lo, hi) that components steps wrote as labels over outputs and no later write has covered
         self.deriv_n = None        # frames the last deriv step wrote (None: the planes still hold the arena's fill)
         self.lines_queued = False  # a lines step since the last sync ...
         self.circles_open = 0      # ... and the circles steps behind it that no lines step has followed yet
@@ -266,7 +317,9 @@ class Model:
         n, rows, rb = rows3.shape
         self.buf[name][self._index(off, pitch, fs, n, rows, rb)] = rows3
         if log:
-            self.writes.append((self.step, name, off, off + (n - 1) * fs + (rows - 1) * pitch + rb))
+            hi = off + (n - 1) * fs + (rows - 1) * pitch + rb
+            self.writes.append((self.step, name, off, hi))
+            self.label_spans = [s for s in self.label_spans if not (s[0] == name and off <= s[1] and s[2] <= hi)]   # (a counter's bookkeeping, by byte range)
 
     def put_words(self, name, off, words):
         b = np.ascontiguousarray(words).view(np.uint8).reshape(-1)
@@ -283,10 +336,10 @@ class Model:
     def _finish(self, hit):
         self.pending = [p for p in self.pending if p not in hit]
 
-    def _reader(self, name, lo, hi, kind):
+    def _reader(self, name, lo, hi, kind, counter=None):
         hit = self._overlapping(name, lo, hi)
         if hit:
-            self.counters[f"overlap_{kind}"] += 1
+            self.counters[counter or f"overlap_{kind}"] += 1
             self._finish(hit)
         elif any(p[0] == name and (p[1] == hi or p[2] == lo) for p in self.pending):
             self.counters["adjacent"] += 1
@@ -400,6 +453,8 @@ class Model:
         self.pending = []
         if st["option"] == api.OPT_PER_CHANNEL:
             self.per_channel = bool(st["value"])
+        if st["option"] == api.OPT_TEST_HOUGH_SCRATCH:
+            self.P["hough_bound"] = st["value"]
 
     def _maps(self, st):
         name, off, pitch, fs, _ = resolve_view(self.L, st["view"])
@@ -494,6 +549,40 @@ class Model:
             c["circle_lists_cut"] += int(counts[f]) > cap > 0
             c["circles_from_cut_points"] += int(stored[f]) > st["pcap"]
             c["circles_centres_cut"] += len(HC.centres(HC.accumulate(pts[f], dx[f], dy[f], self.w, self.h, par[0], par[3], par[4]), par[2])) > st["cc"]
+
+    def do_components(self, st):
+        """hc_connected_components_device on a view of maps -- whatever bytes it holds: a run's maps, a blur's output, the labels an
+        earlier step laid over the region, of which every non-zero byte is foreground.  The entry reads the maps and writes the
+        label plane, and completes the runs in flight that write either (as do_blur books its output).  It writes [row, row + 4 W)
+        of each label row, the n counts and min(N, capacity) rows per frame, the centroids as float64 bits; nothing behind them."""
+        L, n, cap, c = self.L, st["n"], st["cap"], self.counters
+        name, off, pitch, fs, _ = resolve_view(L, st["view"])
+        mspan = view_span(L, off, pitch, fs, n, self.w)
+        c["components_overlap_map"] += bool(self._overlapping(name, *mspan))
+        c["components_of_label_bytes"] += any(b == name and lo < mspan[1] and mspan[0] < hi for b, lo, hi in self.label_spans)
+        maps = self._maps(st)
+        c["components_n_above_max_batch"] += n > MAX_BATCH
+        lname, loff, lpitch, lfs = label_view(L, st)
+        lspan = view_span(L, loff, lpitch, lfs, n, 4 * self.w)
+        assert lname != name or lspan[1] <= mspan[0] or mspan[1] <= lspan[0], f"the label plane of {describe(st)} overlaps its map: the entry refuses it"
+        self._reader(lname, *lspan, "labels", counter="components_labels_over_pending")
+        need, passes, _ = ccl_need(self.h, n, self.P["hough_bound"])
+        assert passes, f"one frame of {describe(st)} exceeds the scratch bound: the entry refuses it"
+        c["ccl_scratch_growths"] += 0 < self.ccl_bytes < need
+        self.ccl_bytes = max(self.ccl_bytes, need)
+        c["ccl_passes_above_one"] += passes > 1
+        c["components_capacity_0"] += cap == 0
+        labels, counts, stats, cents = CC.connected_components(maps, st["conn"], cap)
+        self.put(lname, loff, lpitch, lfs, labels)
+        if st["dest"] == "over":
+            self.label_spans.append((lname,) + lspan)
+        out = f"comp{st['cslot']}"
+        self.put_words(out, L["counts_off"], counts)
+        for f in range(n):
+            c["components_rows_cut"] += int(counts[f]) > cap > 0
+            if cap and len(stats[f]):   # (rows: the pointers are null only with capacity 0)
+                self.put_words(out, L["stats_off"] + 20 * cap * f, stats[f])
+                self.put_words(out, L["cent_off"] + 16 * cap * f, cents[f])
 
 
 def run_model(P, steps, O=None):
@@ -689,6 +778,46 @@ def add_circles(P, steps, rng):
     return steps
 
 
+def written_before(P, steps):
+    """What make_steps calls `written` once it has drawn `steps`: output -> frames of it that a step has written."""
+    per, written = 3 if P["per_channel"] else 1, {}
+    for st in steps:
+        if st["kind"] == "run":
+            written[st["out"]] = st["n"] * per
+        elif st["kind"] in ("canny", "rungrad"):
+            written[st["out"]] = st["n"]
+        elif st["kind"] == "blur" and st["dst"] != "blur":
+            written[st["dst"]] = max(written.get(st["dst"], 0), st["g0"] + st["n"])
+    return written
+
+
+def add_components(P, steps, rng):
+    """Inserts 1 .. 3 components steps into `steps`, by the rules of add_circles: behind the opening's points step, before the
+    final sync, never directly in front of a stream step, every draw from `rng`, a generator of the components' own.  A step reads
+    a view as a points step draws it (draw_view: all six kinds, up to nmax frames) and writes its labels into an arena of their
+    own -- or, one frame of them, OVER an output region of `maps` that its map view does not touch: the one place where the entry
+    completes a run for the plane it writes.  What later steps read from that region are those label bytes."""
+    L = layout(P)
+    w, h = P["w"], P["h"]
+    steps = list(steps)
+    first = next(i for i, st in enumerate(steps) if st["kind"] == "points")
+    for _ in range(int(rng.integers(1, 4))):
+        at = int(rng.choice([i for i in range(first + 1, len(steps)) if steps[i]["kind"] != "stream"]))   # the step goes in front of steps[at]
+        view, n = draw_view(rng, L, written_before(P, steps[:at]), L["nmax"])
+        kind = COMP_CAPS[int(rng.integers(0, len(COMP_CAPS)))]
+        cap = {"null": 0, "zero": 0, "one": 1, "cut": int(rng.choice(COMP_CUTS)), "all": w * h + 1}[kind]
+        st = dict(kind="components", view=view, n=n, conn=int(rng.choice([4, 8])), cap=cap, rows=kind != "null", cslot=int(rng.integers(0, 2)), dest="own",
+                  lslot=int(rng.integers(0, 2)), loff=int(rng.choice(LAB_OFFS)), lpad=int(rng.choice(LAB_PADS)), lgap=int(rng.choice(LAB_GAPS)))
+        over, k0 = rng.random() < 0.45, int(rng.integers(0, NOUT))
+        if over:   # one frame, over the first region from k0 on (cyclically) that the map view stays clear of: it touches two at most
+            name, off, pitch, fs, _ = resolve_view(L, view)
+            lo, hi = view_span(L, off, pitch, fs, 1, w)
+            free = [k for k in ((k0 + j) % NOUT for j in range(NOUT)) if name != "maps" or hi <= out_start(L, k) or out_start(L, k) + 4 * L["ofs"] <= lo]
+            st.update(n=1, dest="over", lslot=free[0], loff=0, lpad=4 * (L["op"] - w), lgap=0)
+        steps.insert(at, st)
+    return steps
+
+
 def base_sequence(seed):
     """(context parameters, steps) of a seed as make_steps draws them from numpy.random.default_rng(seed): no circles step."""
     rng = np.random.default_rng(seed)
@@ -698,9 +827,11 @@ def base_sequence(seed):
 
 def make_sequence(seed, O=None):
     """(context parameters, steps, counters) of a seed: the steps of numpy.random.default_rng(seed), the circles steps of
-    numpy.random.default_rng([seed, 1]) inserted among them, and the host model; nothing else."""
+    numpy.random.default_rng([seed, 1]) inserted among them, the components steps of numpy.random.default_rng([seed, 2]) inserted
+    among those, and the host model; nothing else."""
     P, steps = base_sequence(seed)
     steps = add_circles(P, steps, np.random.default_rng([seed, 1]))
+    steps = add_components(P, steps, np.random.default_rng([seed, 2]))
     return P, steps, dict(run_model(P, steps, O).counters)
 
 
@@ -799,6 +930,10 @@ class Executor:
             (xo, pitch, fs), (yo, _, _) = self.model._planes(st["n"])
             ctx.hough_circles_device(self._list(p), self._counts(p), st["pcap"], self.ptr["dxdy"] + xo, self.ptr["dxdy"] + yo, pitch, fs, st["n"], st["dp"], st["min_dist"],
                                      st["threshold"], st["rmin"], st["rmax"], st["cc"], self._counts(o), self._list(o), st["ccap"])
+        elif k == "components":
+            o, (lname, loff, lpitch, lfs) = f"comp{st['cslot']}", label_view(L, st)
+            ctx.connected_components_device(*self._view(st["view"]), st["n"], st["conn"], self.ptr[lname] + loff, lpitch, lfs, self._counts(o),
+                                            self.ptr[o] + L["stats_off"] if st["rows"] else None, self.ptr[o] + L["cent_off"] if st["rows"] else None, st["cap"])
         elif k == "sync":
             self.check()
         elif k == "stream":
@@ -857,7 +992,7 @@ def main(argv):
         for seed in range(int(argv[2]), int(argv[3])):
             P, steps, c = make_sequence(seed, O)
             print(seed, f"{P['w']}x{P['h']} ch{P['ch']} {P['mode']} pc{int(P['per_channel'])} piped{int(P['pipeline'])} bound{int(bool(P['hough_bound']))} {P['staged']}",
-                  f"{len(steps)} steps, {sum(st['kind'] == 'circles' for st in steps)} of them circles",
+                  f"{len(steps)} steps, {sum(st['kind'] == 'circles' for st in steps)} of them circles, {sum(st['kind'] == 'components' for st in steps)} components",
                   " ".join(f"{k}={v}" for k, v in c.items() if v), flush=True)
         return 0
     if len(argv) > 2 and argv[1] == "--seed":

@@ -118,3 +118,33 @@ def test_stats_against_bincount(conn):
             for k in range(n):
                 sel = np.argwhere(lab == k)
                 assert st[k, :4].tolist() == [sel[:, 1].min(), sel[:, 0].min(), np.ptp(sel[:, 1]) + 1, np.ptp(sel[:, 0]) + 1]
+
+
+@pytest.mark.parametrize("size", [(9, 7), (65, 64), (130, 67)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_closed_forms_equal_the_fill(size):
+    """checkerboard4 and columns, the references of the large GPU cases (a fill of 4.4 M pixels is not a test's business), against
+    the flood fill at sizes it takes in its stride: labels, N, statistics, and the centroids in their bits."""
+    w, h = size
+    yy, xx = np.mgrid[0:h, 0:w]
+
+    def same(got, m, conn):
+        lab, n, st, cen = _one(m, conn)
+        assert got[1] == n and got[0].dtype == np.int32 and np.array_equal(got[0], lab)
+        assert got[2].dtype == np.int32 and got[2].shape == (n, 5) and np.array_equal(got[2], st)
+        assert got[3].dtype == np.float64 and got[3].shape == (n, 2) and np.array_equal(got[3].view(np.int64), cen.view(np.int64))
+    same(R.checkerboard4(w, h), ((xx + yy) % 2 == 0).astype(np.uint8) * 255, 4)
+    for x1 in (0, 1, w // 2, w - 1, w):
+        for conn in (4, 8):
+            same(R.columns(w, h, x1), (xx < x1).astype(np.uint8) * 255, conn)
+
+
+def test_the_closed_forms_beyond_32_bits():
+    """At 2100 x 2100 the sums of x and of y pass 2^32; the centroid of a rectangle is still its middle, exactly."""
+    w = h = 2100
+    assert w * h * (h - 1) // 2 > 1 << 32
+    _, n, st, cen = R.columns(w, h, w)
+    assert n == 2 and st.tolist() == [[0, 0, 0, 0, 0], [0, 0, w, h, w * h]] and cen.tolist() == [[0.0, 0.0], [1049.5, 1049.5]]
+    _, n, st, cen = R.columns(w, h, 0)
+    assert n == 1 and st.tolist() == [[0, 0, w, h, w * h]] and cen.tolist() == [[1049.5, 1049.5]]
+    _, n, st, cen = R.columns(w, h, w // 2)
+    assert st.tolist() == [[1050, 0, 1050, h, 1050 * h], [0, 0, 1050, h, 1050 * h]] and cen.tolist() == [[1574.5, 1049.5], [524.5, 1049.5]]

@@ -20,7 +20,7 @@ def test_make_sequence_is_deterministic(oracle, sequences):
     for seed in DS.SEEDS:
         assert DS.make_sequence(seed, oracle) == sequences[seed], seed
     for seed, (P, steps, _) in sequences.items():
-        assert 12 <= len([st for st in steps if st["kind"] != "circles"]) <= 20 and len(steps) <= 23 and steps[-1]["kind"] == "sync", seed
+        assert 12 <= len([st for st in steps if st["kind"] not in ("circles", "components")]) <= 20 and len(steps) <= 26 and steps[-1]["kind"] == "sync", seed
         assert (P["w"], P["h"]) in DS.SIZES and P["ch"] in (1, 3) and P["staged"] in DS.STAGED_FAMILIES, seed
 
 
@@ -29,6 +29,7 @@ def test_the_circles_steps_leave_every_other_step_where_it_was(sequences):
     numpy.random.default_rng(seed) alone gives -- the sequence the seed was chosen for.  Each stands behind the opening's points
     step, reads the lists of the points step most recently in front of it, and none stands directly in front of a stream switch."""
     for seed, (P, steps, _) in sequences.items():
+        steps = [st for st in steps if st["kind"] != "components"]   # (the next test: what is left is exactly this)
         P0, base = DS.base_sequence(seed)
         assert P0 == P and [st for st in steps if st["kind"] != "circles"] == base and not any(st["kind"] == "circles" for st in base), seed
         at = [i for i, st in enumerate(steps) if st["kind"] == "circles"]
@@ -37,6 +38,38 @@ def test_the_circles_steps_leave_every_other_step_where_it_was(sequences):
             pts = [st for st in steps[:i] if st["kind"] == "points"]
             assert pts and (steps[i]["pslot"], steps[i]["pcap"]) == (pts[-1]["slot"], pts[-1]["cap"]) and 1 <= steps[i]["n"] <= min(pts[-1]["n"], DS.MAX_BATCH), (seed, i)
             assert steps[i + 1]["kind"] != "stream", (seed, i)
+
+
+def test_the_components_steps_leave_every_other_step_where_it_was(sequences):
+    """One level up: the components steps come from a third generator, and without them a sequence is exactly what add_circles
+    makes of the seed's base steps -- the sequence the seed was chosen for, circles included.  None stands directly in front of a
+    stream switch.  A label plane laid over an output region is one frame at four times the region's pitch, and its bytes are
+    disjoint from those of the map view; a plane of its own lies in its arena."""
+    dests = set()
+    for seed, (P, steps, _) in sequences.items():
+        P0, base = DS.base_sequence(seed)
+        with_circles = DS.add_circles(P0, base, np.random.default_rng([seed, 1]))
+        assert [st for st in steps if st["kind"] != "components"] == with_circles and not any(st["kind"] == "components" for st in with_circles), seed
+        at = [i for i, st in enumerate(steps) if st["kind"] == "components"]
+        first = next(i for i, st in enumerate(steps) if st["kind"] == "points")
+        assert 1 <= len(at) <= 3 and first < at[0], seed
+        L = DS.layout(P)
+        for i in at:
+            st = steps[i]
+            assert steps[i + 1]["kind"] != "stream" and st["view"][0] in DS.VIEW_KINDS and st["conn"] in (4, 8), (seed, i)
+            assert (st["cap"], st["rows"]) in [(0, False), (0, True), (1, True), (P["w"] * P["h"] + 1, True)] + [(c, True) for c in DS.COMP_CUTS], (seed, i)
+            name, off, pitch, fs, _ = DS.resolve_view(L, st["view"])
+            lname, loff, lpitch, lfs = DS.label_view(L, st)
+            mspan, lspan = DS.view_span(L, off, pitch, fs, st["n"], P["w"]), DS.view_span(L, loff, lpitch, lfs, st["n"], 4 * P["w"])
+            if st["dest"] == "over":
+                assert st["n"] == 1 and lname == "maps" and lpitch == 4 * L["op"] and loff == DS.out_start(L, st["lslot"]) and 0 <= st["lslot"] < DS.NOUT, (seed, i)
+                assert lspan[1] <= DS.out_start(L, st["lslot"]) + L["oreg"] and L["nmax"] >= 4, (seed, i)
+                assert name != "maps" or lspan[1] <= mspan[0] or mspan[1] <= lspan[0], (seed, i, mspan, lspan)
+            else:
+                assert st["dest"] == "own" and lname in ("lab0", "lab1") and loff % 4 == 0 and lpitch % 4 == 0 and lfs % 4 == 0 and lfs >= lpitch * P["h"], (seed, i)
+                assert DS.LAB_LEAD <= lspan[0] and lspan[1] + DS.LAB_LEAD <= L["sizes"][lname], (seed, i)
+            dests.add((st["dest"], st["view"][0]))
+    assert {d for d, _ in dests} == {"own", "over"} and {v for _, v in dests} == set(DS.VIEW_KINDS), dests
 
 
 def test_the_model_gives_identical_buffers_twice(oracle, sequences):
@@ -84,7 +117,7 @@ def test_the_check_notices_a_vacuous_seed(oracle, sequences):
     keep = {s: v for s, v in sequences.items() if not v[2]["hough_tables_equal_numangle"]}
     assert keep and any("hough_tables_equal_numangle" in t for t in vacuous(keep))
     P, steps, c = next(v for v in sequences.values() if v[0]["pipeline"])
-    cut = [st for st in steps if st["kind"] not in ("points", "segs", "blur")]   # no reader left: nothing overlaps a pending writer
+    cut = [st for st in steps if st["kind"] not in ("points", "segs", "blur", "components")]   # no reader left: nothing overlaps a pending writer
     assert any("overlaps a pending writer" in t for t in vacuous({-1: (P, cut, dict(DS.run_model(P, [st for st in cut if st["kind"] != "lines"], oracle).counters))}))
 
 
@@ -134,11 +167,59 @@ def test_the_plan_driver_refuses_what_the_entry_refuses(circle_plans):
     assert "scratch bound" in circle_plans(dict(P, hough_bound=DS.circle_need(P["w"], P["h"], 1.0, 16, 1, 0)[2] - 1), [good])[0]
 
 
-def test_no_step_would_be_refused(oracle, sequences, circle_plans):
+@pytest.fixture(scope="module")
+def ccl_plans(tmp_path_factory):
+    """plan_connected_components itself on components steps: tests/cpp/ccl_plan_driver.cpp, built as tests/test_ccl_plan_cpu.py
+    builds it, a stand-alone program under ASan + UBSan.  Returns plans(P, steps) -> one (scratch bytes, passes, frames per pass,
+    rows per chunk) or refusal text per step, for the views and the frame limit the executor gives the entry: every buffer gets an
+    address of its own, 256 MiB apart, so the plan sees a map and a label plane inside `maps` as they lie to each other."""
+    exe = str(tmp_path_factory.mktemp("ccl") / "ccl_plan_driver")
+    _cc(["g++", "-std=c++17", "-Wall", "-Werror", *SAN, "-o", exe, os.path.join(ROOT, "tests", "cpp", "ccl_plan_driver.cpp")])
+    base = {name: (k + 1) << 28 for k, name in enumerate(("maps", "sout", "lab0", "lab1"))}
+
+    def plans(P, steps):
+        L = DS.layout(P)
+        args = [exe, "plan", str(P["w"]), str(P["h"]), str(L["nmax"] if P["per_channel"] else L["mb"])]
+        for st in steps:
+            name, off, pitch, fs, _ = DS.resolve_view(L, st["view"])
+            lname, loff, lpitch, lfs = DS.label_view(L, st)
+            args += [str(v) for v in (st["n"], st["conn"], base[name] + off, pitch, fs, base[lname] + loff, lpitch, lfs, int(st["rows"]), st["cap"], P["hough_bound"])]
+        out = subprocess.run(args, capture_output=True, text=True, timeout=600, env=ENV)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        rows = out.stdout.splitlines()
+        assert len(rows) == len(steps)
+        return [r if r.startswith("refused") else tuple(int(v) for v in r.split()) for r in rows]
+    return plans
+
+
+def test_the_ccl_plan_driver_refuses_what_the_entry_refuses(ccl_plans):
+    """The driver's answers are the plan's: a frame too many, a connectivity of 6, a label plane over its own map, rows asked for
+    with null pointers and a bound below one frame are refused; ccl_need says what the plan says where the rows of a chunk change."""
+    P, _ = DS.base_sequence(DS.SEEDS[0])
+    P = dict(P, hough_bound=0)
+    L = DS.layout(P)
+    good = dict(kind="components", view=("whole", 1), n=1, conn=8, cap=5, rows=True, cslot=0, dest="over", lslot=0, loff=0, lpad=0, lgap=0)
+    got = ccl_plans(P, [good, dict(good, n=L["nmax"] + 1, dest="own"), dict(good, conn=6), dict(good, view=("whole", 0)), dict(good, rows=False), dict(good, rows=False, cap=0),
+                        dict(good, view=("frame", 0, 3)), dict(good, view=("behind", 0, 4))])   # the plane covers four frames of the region: the last of them; the bytes behind them
+    assert got[0] == DS.ccl_need(P["h"], 1, 0)[:2] + (1, min(P["h"], 8)) and got[5] == got[0] and got[7] == got[0], got
+    assert "nframes out of range" in got[1] and "connectivity" in got[2] and "overlap" in got[3] and "null with capacity" in got[4] and "overlap" in got[6], got
+    per = DS.ccl_need(P["h"], 1, 0)[2]
+    assert "scratch bound" in ccl_plans(dict(P, hough_bound=per - 1), [good])[0] and ccl_plans(dict(P, hough_bound=per), [good])[0][:2] == (per, 1)
+    for h, n in ((5, 1), (8, 3), (9, 1), (67, 4), (513, 1), (1030, 1), (1030, 63), (1030, 64), (1080, 600), (1080, 1024)):   # hist_chunk_rows: 8, then 9 .. 64
+        for bound in (0, 3 * DS.ccl_need(h, n, 0)[2] + 3):
+            Q = dict(P, w=5, h=h, per_channel=False, per_channel_ever=False, max_batch=1024, hough_bound=bound)   # (narrow: 1024 frames stay inside the 256 MiB between two buffers)
+            (plan,) = ccl_plans(Q, [dict(good, n=n, dest="own")])
+            need = DS.ccl_need(h, n, bound)
+            assert plan[:2] == need[:2] and plan[2] * need[2] == need[0] and need[2] == 4 * ((h + plan[3] - 1) // plan[3]), (h, n, bound, plan, need)
+    assert DS.ccl_need(1030, 64, 0)[2] == 4 * 115 and DS.ccl_need(1030, 63, 0)[2] == 4 * 129 and DS.ccl_need(67, 5, 80) == (72, 3, 36)
+
+
+def test_no_step_would_be_refused(oracle, sequences, circle_plans, ccl_plans):
     """The documented limits of include/hipcanny.h on every step: frame counts, alignments, views inside their buffers, views of a
     blur that do not overlap, lists and tables read only after they were written with the same strides, stream switches behind a
     synchronisation.  The circles steps are given to plan_hough_circles itself, which also says how much scratch and how many
-    passes each takes: circle_need, by which the model counts growths and passes, must say the same."""
+    passes each takes: circle_need, by which the model counts growths and passes, must say the same.  Likewise the components
+    steps, plan_connected_components and ccl_need; the plan is also what says that no label plane overlaps its map."""
     nplans = 0
     for seed, (P, steps, _) in sequences.items():
         L = DS.layout(P)
@@ -185,7 +266,7 @@ def test_no_step_would_be_refused(oracle, sequences, circle_plans):
                 assert st["ksize"] in (3, 5, 7) and (P["ch"] == 1 or (a, b) == ("frames", "blur")), what
                 if st["dst"] == "blur":
                     blur = st["n"]
-            if k in ("points", "segs"):
+            if k in ("points", "segs", "components"):
                 name, off, pitch, fs, maxn = DS.resolve_view(L, st["view"])
                 lo, hi = DS.view_span(L, off, pitch, fs, st["n"], P["w"])
                 assert 1 <= st["n"] <= min(limit, maxn) and 0 <= lo and hi <= size[name] and pitch >= P["w"] and (st["n"] == 1 or fs >= pitch * P["h"]), what
@@ -205,6 +286,11 @@ def test_no_step_would_be_refused(oracle, sequences, circle_plans):
                 n, cap = plist[st["pslot"]]
                 assert 1 <= st["n"] <= min(n, limit) and st["pcap"] == cap and DS.list_fits("circ", st["n"], st["ccap"], 4, L) and st["ccap"] <= DS.CCAP_MAX, what
                 assert (512 + L["pf"] * L["dfs"]) % 2 == 0 and DS.view_span(L, DS.Model._planes(m0, st["n"])[1][0], L["dp"], L["dfs"], st["n"], 2 * P["w"])[1] <= size["dxdy"], what
+            if k == "components":
+                lname, loff, lpitch, lfs = DS.label_view(L, st)
+                assert 0 <= loff and DS.view_span(L, loff, lpitch, lfs, st["n"], 4 * P["w"])[1] <= size[lname] and lpitch >= 4 * P["w"], what
+                assert L["stats_off"] % 4 == 0 and L["cent_off"] % 8 == 0 and L["cent_off"] >= L["stats_off"] + 20 * st["n"] * st["cap"] + 4 * DS.GUARD, what
+                assert L["cent_off"] + 16 * st["n"] * st["cap"] + 4 * DS.GUARD <= size[f"comp{st['cslot']}"] and st["n"] <= DS.NLIST, what
             if k == "stream":
                 assert prev == "sync", what
             prev = k
@@ -214,4 +300,9 @@ def test_no_step_would_be_refused(oracle, sequences, circle_plans):
             need = DS.circle_need(P["w"], P["h"], st["dp"], st["cc"], st["n"], P["hough_bound"])
             assert isinstance(plan, tuple) and plan[:2] == need[:2] and plan[1] >= 1 and plan[2] * need[2] == need[0], (seed, DS.describe(st), plan, need)
             nplans += 1
-    assert nplans >= len(sequences)
+        comps = [st for st in steps if st["kind"] == "components"]
+        for st, plan in zip(comps, ccl_plans(P, comps)):
+            need = DS.ccl_need(P["h"], st["n"], P["hough_bound"])
+            assert isinstance(plan, tuple) and plan[:2] == need[:2] and plan[1] == 1 and plan[2] * need[2] == need[0] and plan[3] == min(P["h"], 8), (seed, DS.describe(st), plan, need)
+            nplans += 1
+    assert nplans >= 2 * len(sequences)

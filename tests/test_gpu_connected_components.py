@@ -98,8 +98,9 @@ def _content(kind, w, h, seed=0):
     raise ValueError(kind)
 
 
-def _call(ctx, maps, conn, capacity, pitch=None, frame_stride=None, base_off=0, label_pad=0, label_gap=0, label_off=0, fill="ff", null_rows=False, what=""):
-    """One call on `maps` (n, H, W) in a guarded arena; everything is compared with the restatement.  Returns (labels, counts)."""
+def _call(ctx, maps, conn, capacity, pitch=None, frame_stride=None, base_off=0, label_pad=0, label_gap=0, label_off=0, fill="ff", null_rows=False, what="", want=None):
+    """One call on `maps` (n, H, W) in a guarded arena; everything is compared with the restatement -- or with `want`, the same four
+    values from a closed form (ccl_ref.checkerboard4, ccl_ref.columns) where a flood fill would take too long.  Returns (labels, counts)."""
     import torch
     n, h, w = maps.shape
     pitch = w if pitch is None else pitch
@@ -116,7 +117,7 @@ def _call(ctx, maps, conn, capacity, pitch=None, frame_stride=None, base_off=0, 
     ctx.connected_components_device(d.data_ptr() + off, pitch, g.frame_stride, n, conn, dl.data_ptr() + lg.offset, lpitch, lg.frame_stride, counts.data_ptr() + 4,
                                     None if null_rows else stats.data_ptr() + 4 * GUARD, None if null_rows else cents.data_ptr() + 8 * GUARD, capacity)
     ctx.sync()
-    want_labels, want_counts, want_stats, want_cents = _ref(maps, conn)
+    want_labels, want_counts, want_stats, want_cents = _ref(maps, conn) if want is None else want
     assert np.array_equal(d.cpu().numpy(), arena), f"{what}: the map arena was written"
     c = counts.cpu().numpy()
     assert c[0] == CANARY and c[-1] == CANARY, f"{what}: a word beside d_counts was written"
@@ -390,3 +391,69 @@ def test_argument_errors():
         assert counts.cpu().numpy()[:3].tolist() == [2, 2, 2] and (lab3.cpu().numpy() == 1).all()
         with pytest.raises(api.HipCannyError, match="error -1"):
             ctx.connected_components_device(three.data_ptr(), w, fs, 4, 8, lab3.data_ptr(), lp, lfs, c)
+
+
+# ---- the tall and large paths: the thresholds follow from the constants of ccl.hip and canny_params.h.  k_ccl_scan takes a frame's
+# chunks 64 at a time (a carry from 513 rows of 8 up), hist_chunk_rows leaves 8 rows per chunk once H x nframes passes 65,536,
+# k_ccl_rows and k_ccl_finish stride over the rows from CCL_ROW_GROUPS x CCL_THREADS = 262,144 up, and a sum of coordinates passes
+# 2^32 once W * H * (H - 1) / 2 does.  Each shape is narrow or short in the other direction, so that it stays small.
+ROW_THREADS = 1024 * 256
+
+
+@pytest.mark.parametrize("kind", ["random0.3", "comb", "spiral"])
+def test_the_scan_carries_across_64_chunks(kind):
+    """65 x 520, two frames: 65 chunks of 8 rows, one carry in k_ccl_scan, and k_ccl_roots numbers across it.  9 x 1030: 129
+    chunks, two carries.  A carry that is dropped, or added twice, shifts every number behind chunk 64."""
+    for w, h, n in ((65, 520, 2), (9, 1030, 1)):
+        assert (h + 7) // 8 > 64 * (2 if h > 1024 else 1) and h * n <= 65536
+        maps = np.stack([_content(kind, w, h, 20 + k) for k in range(n)])
+        if n == 2:
+            maps[1] = maps[1, ::-1]   # (comb and spiral take no seed: the second frame upside down)
+        with api.Context(w, h, 1, n) as ctx:
+            for conn in (4, 8):
+                _, got = _call(ctx, maps, conn, w * h + 1, w + 3, base_off=1, label_pad=8, what=f"{kind} {w}x{h} n={n} c={conn}")
+                assert kind == "random0.3" or (int(got[0]) == 2 and (h > 1000 or int(got[1]) == 2))
+                assert kind != "random0.3" or int(got.min()) > 500   # (604 .. 4431: roots in every chunk, behind the carries too)
+
+
+def test_chunks_of_nine_rows_straddle_the_tiles():
+    """5 x 1030, 64 frames: 65,920 rows in the call, so hist_chunk_rows gives 9 and a frame has 115 chunks whose borders fall on
+    no multiple of the 32 rows of a tile but 288, 576 and 864; k_ccl_scan carries once per frame."""
+    w, h, n = 5, 1030, 64
+    assert (h * n + 8191) // 8192 == 9 and (h + 8) // 9 == 115
+    maps = np.stack([_content("random0.5", w, h, 300 + k) for k in range(n)])
+    with api.Context(w, h, 1, n) as ctx:
+        for conn in (4, 8):
+            _, got = _call(ctx, maps, conn, 1200, w + 3, (w + 3) * h + 5, base_off=2, label_pad=4, label_gap=12, what=f"chunk_rows 9, c={conn}")
+            assert 100 < int(got.min()) and int(got.max()) < 1200   # nothing is cut
+
+
+def test_more_rows_of_statistics_than_threads():
+    """A 1024 x 514 checkerboard at connectivity 4: N = 263,169 rows of statistics, 1,025 more than the 262,144 threads k_ccl_rows
+    and k_ccl_finish have per frame, so the last rows are the second trip of their stride.  Capacity N: the whole trip; 262,144 +
+    77: a capacity that cuts inside it; 262,144: no second trip.  _call checks that each slot's tail stays canary."""
+    w, h = 1024, 514
+    want = R.checkerboard4(w, h)
+    n = want[1]
+    assert n == 263169 > ROW_THREADS
+    maps = _content("checkerboard", w, h)[None]
+    want = (want[0][None], np.array([n], np.uint32), [want[2]], [want[3]])
+    with api.Context(w, h, 1, 1) as ctx:
+        for cap in (n, ROW_THREADS + 77, ROW_THREADS):
+            _call(ctx, maps, 4, cap, what=f"checkerboard, capacity {cap}", want=want)
+
+
+@pytest.mark.parametrize("kind", ["full", "empty", "left half"])
+def test_coordinate_sums_beyond_32_bits(kind):
+    """2100 x 2100: the sums of x and of y of the full frame's component, and of the empty frame's background, are 4,628,295,000 >
+    2^32 -- through the atomicAdd on 64 bits in the one case, through the registers and shfl_xor64 in the other.  A sum narrowed to
+    32 bits anywhere gives another centroid; the centroids are compared in their bits."""
+    w = h = 2100
+    assert w * h * (h - 1) // 2 == 4628295000 > 1 << 32
+    x1 = {"full": w, "empty": 0, "left half": w // 2}[kind]
+    want = R.columns(w, h, x1)
+    maps = np.zeros((1, h, w), np.uint8)
+    maps[0, :, :x1] = 255
+    conn = 4 if kind == "empty" else 8
+    with api.Context(w, h, 1, 1) as ctx:
+        _call(ctx, maps, conn, 3, what=f"2100 x 2100 {kind}", want=(want[0][None], np.array([want[1]], np.uint32), [want[2]], [want[3]]))

@@ -63,6 +63,20 @@ def _circle_counts(model, cslot, n):
     return model.words(f"circ{cslot}", model.L["counts_off"], n, np.uint32).tolist()
 
 
+def _components(view, n, P, conn=8, cap=None, rows=True, cslot=0, over=None, lslot=0, loff=1, lpad=4, lgap=8):
+    """A components step with a label plane of its own (padded rows, a gap between frames, 4 * loff bytes into its arena) -- or, with
+    over=k, one frame of labels laid over output region k."""
+    st = dict(kind="components", view=view, n=n, conn=conn, cap=P["w"] * P["h"] + 1 if cap is None else cap, rows=rows, cslot=cslot, dest="own", lslot=lslot, loff=loff, lpad=lpad, lgap=lgap)
+    if over is not None:
+        assert n == 1
+        st.update(dest="over", lslot=over, loff=0, lpad=4 * (DS.layout(P)["op"] - P["w"]), lgap=0)
+    return st
+
+
+def _component_counts(model, cslot, n):
+    return model.words(f"comp{cslot}", model.L["counts_off"], n, np.uint32).tolist()
+
+
 def _blur(src, f0, dst, g0, n):
     return dict(kind="blur", src=src, f0=f0, dst=dst, g0=g0, n=n, ksize=5, sigma=1.2, border=0)
 
@@ -305,3 +319,126 @@ def test_circles_across_a_stream_switch(oracle):
              _circles(4, P, cslot=1, dp=1.0, cc=4096, rmin=3, rmax=66), SYNC, dict(kind="stream", to="own"), _circles(2, P, cslot=0, dp=1.5, cc=300)]
     model = DS.execute(P, steps, oracle, "circles across a stream switch")
     assert model.counters["circle_lists_nonempty"] >= 6 and model.counters["circle_scratch_growths"] == 1, model.counters
+
+
+# ---- components in company: hc_connected_components_device reads edge maps AND writes a plane the caller chooses, so it completes
+# the runs in flight under either; its table of per-chunk counts is the third scratch under the context's one bound.
+# tests/test_gpu_connected_components.py has the kernels, call by call.
+def test_labels_over_a_pending_output(oracle):
+    """Two pipelined runs into outputs 0 and 1 whose content needs the host continuation; then, with no synchronisation, the
+    components of frame 1 of output 1 with the label plane laid OVER output 0, then the points of output 0 -- of the label bytes.
+    The entry must continue run 0 before its kernels write there: continued later (by the points call, or at the sync), the run
+    rewrites its whole maps over the labels."""
+    P = _params()
+    with DS.Executor(P, oracle, "labels over a pending output") as e:
+        for st in (_run(0, 0), _run(1, 1), _components(("frame", 1, 1), 1, P, over=0), _points(("whole", 0), 4, P=P)):
+            e.queue(st)
+        c = e.model.counters
+        assert c["components_labels_over_pending"] == 1 and c["components_overlap_map"] == 1 and c["overlap_frame"] == 1 and c["overlap_whole"] == 0 and not e.model.pending, c
+        e.check()
+        assert e.continued_runs() == 2 and _component_counts(e.model, 0, 1)[0] > 9
+        (n0,) = e.model.words("pts0", e.model.L["counts_off"], 1, np.uint32).tolist()
+        assert n0 > P["w"]   # the points of frame 0 are the non-zero bytes of the labels' first rows
+
+
+def test_components_behind_runs_left_in_flight(oracle):
+    """Three pipelined runs into the three outputs, then the components of the LAST frame of output 1 into a plane of their own:
+    run 1 is completed, its neighbours are not -- read off the device as test_the_neighbour_stays_in_flight reads it."""
+    import torch
+    P = _params()
+    L = DS.layout(P)
+    with DS.Executor(P, oracle, "components behind runs in flight") as e:
+        for st in (_run(0, 0), _run(0, 1), _run(0, 2), _components(("frame", 1, 3), 1, P, conn=4)):
+            e.queue(st)
+        c = e.model.counters
+        assert c["overlap_frame"] == 1 and c["components_overlap_map"] == 1 and c["components_labels_over_pending"] == 0 and len(e.model.pending) == 2, c
+        torch.cuda.synchronize()   # the device, not the context: no run is completed by this
+        got, want = e.d["maps"].cpu().numpy(), e.model.buf["maps"]
+        for k in (0, 2):
+            a = DS.out_start(L, k)
+            assert not np.array_equal(got[a:a + L["oreg"]], want[a:a + L["oreg"]]), f"output {k} already holds its final maps: the components call completed its run, or its content needs no continuation"
+        a = DS.out_start(L, 1)
+        assert np.array_equal(got[a:a + L["oreg"]], want[a:a + L["oreg"]]), "output 1 does not hold its final maps behind the call that read it"
+        e.check()
+        assert e.continued_runs() == 3 and _component_counts(e.model, 0, 1)[0] > 2
+
+
+def test_components_in_passes_under_a_bound(oracle):
+    """67 rows are 9 chunks of 8: 36 bytes of table per frame.  Under a bound of 39 bytes four frames take four passes, under 75
+    two; then, with the default bound again, lines, circles and components follow one another with no synchronisation -- the
+    accumulators, the circle scratch and the table are three buffers under one bound -- and the components are the same."""
+    P = _params(pipeline=False)
+    per = DS.ccl_need(P["h"], 4, 0)[2]
+    assert per == 36 and [DS.ccl_need(P["h"], 4, b)[1] for b in (per + 3, 2 * per + 3, 0)] == [4, 2, 1]
+    bound = lambda v: dict(kind="option", option=api.OPT_TEST_HOUGH_SCRATCH, value=v)
+    steps = [_run(0, 0), bound(per + 3), _components(("whole", 0), 4, P, cslot=0, lslot=0), bound(2 * per + 3), _components(("whole", 0), 4, P, conn=4, cap=5, cslot=0, lslot=0),
+             bound(0), _points(("whole", 0), 4, P=P), _deriv(4), _lines(4, 3, 0, DS.LCAP_MAX, P), _circles(4, P, cc=300), _components(("whole", 0), 4, P, cslot=1, lslot=1, loff=0, lpad=0),
+             _lines(4, 0, 1, 64, P)]
+    with DS.Executor(P, oracle, "components in passes") as e:
+        for i, st in enumerate(steps):
+            e.queue(st)
+            if i == 2:   # what four passes left, before the second call writes into the same slots
+                e.check()
+                first = {k: e.model.buf[k].copy() for k in ("comp0", "lab0")}
+        e.check()
+        c, L = e.model.counters, e.model.L
+        assert c["ccl_passes_above_one"] == 2 and c["components_rows_cut"] == 4 and c["circle_lists_nonempty"] == 4 and c["line_lists_nonempty"] == 8, c
+        assert np.array_equal(first["comp0"], e.model.buf["comp1"]), "one pass gives other rows than four"
+        lab = lambda b, st: b[e.model._index(*DS.label_view(L, st)[1:], 4, P["h"], 4 * P["w"])]
+        assert np.array_equal(lab(first["lab0"], steps[2]), lab(e.model.buf["lab1"], steps[10])), "one pass gives other labels than four"
+        assert min(_component_counts(e.model, 1, 4)) > 1 and max(_component_counts(e.model, 1, 4)) > 9
+
+
+def test_the_component_table_grows_while_a_call_is_queued(oracle):
+    """One frame (the third of the output, a natural one), then four (the table is allocated again, behind a synchronisation of the stream the first call is queued on),
+    then a lines call, then the first call again into the other slot: the same rows."""
+    P = _params(w=250, h=66, pipeline=False)
+    steps = [_run(0, 0), _points(("whole", 0), 4, P=P), _components(("frame", 0, 2), 1, P, cslot=0, lslot=0), _components(("whole", 0), 4, P, conn=4, cslot=1, lslot=1),
+             _lines(4, 3, 0, DS.LCAP_MAX, P), _components(("frame", 0, 2), 1, P, cslot=1, lslot=1)]
+    with DS.Executor(P, oracle, "component table growth") as e:
+        for st in steps[:-1]:
+            e.queue(st)
+        four = _component_counts(e.model, 1, 4)
+        e.queue(steps[-1])
+        e.check()
+        m = e.model
+        assert m.counters["ccl_scratch_growths"] == 1 and m.counters["line_lists_nonempty"] == 4, m.counters
+        (k0,), now = _component_counts(m, 0, 1), _component_counts(m, 1, 4)
+        assert now[0] == k0 > 9 and now[1:] == four[1:] and min(four) > 2
+        assert np.array_equal(m.words("comp0", m.L["stats_off"], 5 * k0, np.int32), m.words("comp1", m.L["stats_off"], 5 * k0, np.int32))
+
+
+def test_components_per_channel(oracle):
+    """A 3-channel Mode R context with HC_OPT_PER_CHANNEL and max_batch 2: the components of the 6 maps of a run, 7 refused; with
+    the option off 2 are taken and 3 refused, and nothing is written by a refused call."""
+    P = _params(w=65, h=64, ch=3, pipeline=True, per_channel=True, max_batch=2)
+    with DS.Executor(P, oracle, "components per channel") as e:
+        def at_the_limit_and_beyond(n):
+            e.queue(_components(("whole", 0), n, P, conn=4, cap=5, cslot=1, lslot=1))
+            (lname, loff, lpitch, lfs), o = DS.label_view(e.L, e.steps[-1]), "comp1"
+            _refused(lambda: e.ctx.connected_components_device(*e._view(("whole", 0)), n + 1, 8, e.ptr[lname] + loff, lpitch, lfs, e._counts(o), e.ptr[o] + e.L["stats_off"],
+                                                               e.ptr[o] + e.L["cent_off"], 5), "hc_connected_components_device")
+        e.queue(_run(0, 0, n=2))
+        e.queue(_components(("whole", 0), 6, P, conn=4, cslot=0, lslot=0))
+        at_the_limit_and_beyond(6)
+        e.check()
+        c = e.model.counters
+        assert c["components_n_above_max_batch"] == 2 and c["components_overlap_map"] == 1 and c["components_rows_cut"] == 6 and min(_component_counts(e.model, 0, 6)) > 5, c
+        e.queue(dict(kind="option", option=api.OPT_PER_CHANNEL, value=0))
+        e.queue(_run(1, 1, n=2))
+        e.queue(_components(("whole", 1), 2, P, conn=4, cslot=0, lslot=0))
+        at_the_limit_and_beyond(2)
+        e.check()
+        assert e.continued_runs() > 0
+
+
+def test_components_across_a_stream_switch(oracle):
+    """Components on the context's own stream, on a caller's stream and on its own again, each switch behind a synchronisation as
+    include/hipcanny.h asks of calls that share scratch; the second call needs a larger table than the first, and lays its labels
+    over an output."""
+    P = _params(w=61, h=33, pipeline=True)
+    steps = [_run(0, 0), _run(1, 1), _components(("whole", 0), 2, P, cslot=0), SYNC, dict(kind="stream", to="side"), _components(("whole", 1), 4, P, conn=4, cslot=1, lslot=1), SYNC,
+             dict(kind="stream", to="own"), _components(("frame", 0, 2), 1, P, cap=3, over=2), _points(("whole", 2), 1, P=P)]
+    model = DS.execute(P, steps, oracle, "components across a stream switch")
+    c = model.counters
+    assert c["ccl_scratch_growths"] == 1 and c["components_overlap_map"] == 1 and c["components_rows_cut"] == 1 and min(_component_counts(model, 1, 4)) > 2, c
