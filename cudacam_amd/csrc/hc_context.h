@@ -182,6 +182,7 @@ struct hc_ctx {
   // HC_OPT_COPY_STREAMS: uploads / downloads on the device's shared copy streams, tied to the context stream by events
   bool copy_streams = false;
   hipEvent_t ev_up = nullptr, ev_ready = nullptr, ev_ready2 = nullptr, ev_down = nullptr;
+  hipEvent_t ev_switch = nullptr;  // hc_set_stream / hc_use_own_stream: the end of the outgoing stream, which the incoming one waits for (created by the first switch)
   struct {  // HC_OPT_DEBUG_TAPS: copies of the bit planes as the front kernels left them, and (fused kernel) a plain blur plane
     hc::u32 *s = nullptr, *c = nullptr;
     uint8_t *blur = nullptr;

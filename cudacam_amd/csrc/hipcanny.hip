@@ -619,7 +619,7 @@ void hc_destroy(hc_ctx *c)
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : { c->ev_up, c->ev_ready, c->ev_ready2, c->ev_down }) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : { c->ev_up, c->ev_ready, c->ev_ready2, c->ev_down, c->ev_switch }) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ring.f) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ring.d) if (e) (void)hipEventDestroy(e);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -657,20 +657,37 @@ int hc_get_thresholds(const hc_ctx *c, int *low, int *high)
   return HC_OK;
 }
 
+namespace {
+// The context stream changes: everything queued on the outgoing stream up to now -- an hc_upload above all, whose frames the
+// next hc_run reads on the incoming stream, but the caller's own work there as well: an event cannot tell them apart -- comes
+// first on the incoming one.  With the copy streams the upload itself sits on g_h2d, behind ev_ready and ahead of ev_up: the
+// incoming stream waits for ev_up as the outgoing one does.  Events only: the host waits for nothing, and a stream with
+// nothing queued is passed at once.  ev_switch is this function's alone (ev_ready belongs to hc_upload).
+int switch_stream(hc_ctx *c, hipStream_t to)
+{
+  if (to == c->stream) return HC_OK;
+  HIPCK(hipSetDevice(c->device));
+  if (!c->ev_switch) HIPCK(hipEventCreateWithFlags(&c->ev_switch, hipEventDisableTiming));
+  if (hipEventRecord(c->ev_switch, c->stream) == hipSuccess) HIPCK(hipStreamWaitEvent(to, c->ev_switch, 0));
+  else (void)hipGetLastError();  // a caller's stream that no longer exists: there is nothing left to order against
+  if (c->ev_up) HIPCK(hipStreamWaitEvent(to, c->ev_up, 0));  // (never recorded: no upload went through g_h2d, nothing to wait for)
+  c->stream = to;
+  return HC_OK;
+}
+}  // namespace
+
 int hc_set_stream(hc_ctx *c, void *s)
 {
   if (!c) return fail(HC_E_ARG, "null context");
   if (int rc = finish_all(c)) return rc;
-  c->stream = (hipStream_t)s;  // 0 = the null stream itself (ordered with everything the caller queued on it)
-  return HC_OK;
+  return switch_stream(c, (hipStream_t)s);  // 0 = the null stream itself (ordered with everything the caller queued on it)
 }
 
 int hc_use_own_stream(hc_ctx *c)
 {
   if (!c) return fail(HC_E_ARG, "null context");
   if (int rc = finish_all(c)) return rc;
-  c->stream = c->own_stream;
-  return HC_OK;
+  return switch_stream(c, c->own_stream);
 }
 
 int hc_set_tuning(hc_ctx *c, int chunk_rows, int hyst_launches)
@@ -964,6 +981,9 @@ int queue_download(hc_ctx *c)
     HIPCK(hipEventRecord(c->ev_ready2, c->stream));
     HIPCK(hipStreamWaitEvent(cs, c->ev_ready2, 0));
     Slot &s = c->slot[c->last.slot];
+    // Redundant, kept as a second line of defence: hc_download_begin has already made the context stream wait for this
+    // ev_done, ahead of the ev_ready2 recorded above, and on the repeated copy (hc_download_end) finish_all has completed
+    // the run.  Removing it alone changes no result; tests/test_gpu_host_fed.py pins hc_download_begin's wait.
     if (s.pending && s.stream != c->stream) HIPCK(hipStreamWaitEvent(cs, s.ev_done, 0));
   }
   if (int rc = copy_out_d2h(c, c->dl.host, c->dl.row, c->dl.fs, c->dl.n, cs)) return rc;

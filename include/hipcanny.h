@@ -217,9 +217,10 @@ int hc_histogram_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t i
  * derivatives of aperture 7 or Scharr (hc_derivatives_device chained with hc_run_gradients_device) the pairs mean what that
  * entry says about units; nothing is rescaled here.  Asynchronous on the context stream, not a run (as hc_histogram_device):
  * chained with hc_frame_thresholds_device and a run on the same context, no synchronisation is needed in between.
- * Successive calls on one context share that table and are ordered by the stream they are queued on: a caller who changes
- * the stream between two calls (hc_set_stream, hc_use_own_stream) must order the two streams itself, or synchronise, as for any
- * other memory that work on both streams touches; hc_histogram_device, which writes caller memory only, has no such state.
+ * Successive calls on one context share that table and are ordered by the stream they are queued on; a change of the stream
+ * between two calls (hc_set_stream, hc_use_own_stream) keeps that order, since the switch queues the incoming stream behind
+ * the outgoing one.  Work the caller queues itself on a third stream it orders itself, as for any other memory that two
+ * streams touch; hc_histogram_device, which writes caller memory only, has no such state.
  * HC_E_ARG: an unknown rule; param outside [0, 1] or not finite; width * height * channels > 2^27 (up to there the integer
  * sums above are exact); d_thr null or not 4-byte aligned; otherwise what hc_histogram_device refuses. */
 enum { HC_AUTO_MEDIAN = 0, HC_AUTO_OTSU = 1 };
@@ -250,8 +251,8 @@ int hc_auto_thresholds_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, si
  * neither finished nor waited for.  In plain mode the order of the context stream suffices (as for any reader of a plain run's
  * output on that stream: a run that had to be continued from the host, hc_last_hysteresis_info, is complete after hc_sync).
  * Scratch: one table of per-work-item counts the context owns (allocated on first use, freed by hc_destroy).  Successive calls
- * on one context share it and are ordered by the stream they are queued on: a caller who changes the stream between two calls
- * (hc_set_stream, hc_use_own_stream) must order the two streams itself, or synchronise, as for hc_auto_thresholds_device.
+ * on one context share it and are ordered by the stream they are queued on, across a change of the stream (hc_set_stream,
+ * hc_use_own_stream) too, as for hc_auto_thresholds_device.
  * HC_E_ARG: ctx, d_map or d_counts null; d_points null with capacity > 0; d_counts not 4-byte / d_points not 8-byte aligned;
  * pitch < width; nframes outside 1..(output frames of a max_batch run: max_batch, 3 * max_batch with HC_OPT_PER_CHANNEL);
  * nframes > 1 with a frame stride smaller than height * pitch; height * pitch >= 2^32; capacity * 8 * nframes overflowing
@@ -344,8 +345,7 @@ int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps);
  * neighbours never being both peaks) and a count per angle row.  The scratch is bounded at 256 MiB: a batch is cut into passes
  * of as many frames as fit, 65535 at most (a 1080p accumulator is 4.4 MB) and is allocated again, after a synchronisation, when a call needs more
  * than the calls before.  Successive calls on one context share scratch and tables and are ordered by the stream they are
- * queued on: a caller who changes the stream between two calls (hc_set_stream, hc_use_own_stream) must order the two streams
- * itself, or synchronise, as for hc_auto_thresholds_device.
+ * queued on, across a change of the stream (hc_set_stream, hc_use_own_stream) too, as for hc_auto_thresholds_device.
  * Cost.  Votes: points x numangle LDS atomics per frame; an accumulator row lives in one workgroup's LDS.  The ranking compares
  * every peak of a frame with every other: quadratic in the peaks -- a few hundred at any threshold in use, a few 10^5 only at threshold 0
  * on large noisy frames (measured on an MI355X: 0.4 ms per frame at 56 k peaks, profiles/hough/README.md; extrapolated by the
@@ -478,8 +478,8 @@ int hc_hough_walk_tables(int width, int height, double rho, double theta, double
  * the ranked and the kept centres (centre_capacity of 16 bytes each), a count per centre.  It is bounded by the bound of
  * hc_hough_lines_device (256 MiB): a batch is cut into passes of as many frames as fit, 65535 at most, and the scratch is
  * allocated again, after a synchronisation, when a call needs more than the calls before.  Successive calls on one context share
- * it and are ordered by the stream they are queued on: a caller who changes the stream between two calls (hc_set_stream,
- * hc_use_own_stream) must order the two streams itself, or synchronise, as for hc_hough_lines_device.
+ * it and are ordered by the stream they are queued on, across a change of the stream (hc_set_stream, hc_use_own_stream) too,
+ * as for hc_hough_lines_device.
  * Cost.  Votes: up to 2 * (max_radius - min_radius + 1) global atomic adds per point.  The ranking is quadratic in the peaks of a
  * frame, as for hc_hough_lines_device.  The sift is sequential: one wave per frame.  Every kept centre reads the frame's point
  * list once per radii launch (twice when circles are written).  Measurements: profiles/hough_circles/README.md.
@@ -585,7 +585,10 @@ int hc_sync(hc_ctx *ctx);
  * torch.cuda.current_stream().cuda_stream is unless the caller switched streams.  Front kernels, uploads and
  * (outside pipelined mode) the hysteresis are then queued on that stream, in order with the caller's own work on
  * it: a run sees everything queued before it.  The context's own stream is created non-blocking, i.e. it does NOT
- * synchronise with the null stream; hc_use_own_stream() goes back to it. */
+ * synchronise with the null stream; hc_use_own_stream() goes back to it.  Either switch orders the incoming stream behind
+ * everything queued on the outgoing one at the time of the switch -- the context's work and the caller's own alike -- by an
+ * event, without waiting on the host: a run after the switch sees the frames of an hc_upload made before it, with and
+ * without HC_OPT_COPY_STREAMS, and device-op entries that share a context's scratch stay in order across it. */
 int hc_set_stream(hc_ctx *ctx, void *hip_stream);
 int hc_use_own_stream(hc_ctx *ctx);
 
