@@ -65,6 +65,9 @@ AUTO_MEDIAN, AUTO_OTSU = 0, 1
 BORDER_REFLECT_101, BORDER_REPLICATE = 0, 1
 # words of a statistics row of hc_connected_components_device (the header's HC_CC_STAT_*)
 CC_STAT_LEFT, CC_STAT_TOP, CC_STAT_WIDTH, CC_STAT_HEIGHT, CC_STAT_AREA, CC_STAT_WORDS = 0, 1, 2, 3, 4, 5
+# operations and element shapes of hc_morphology_device / hc_structuring_element (the header's HC_MORPH_*)
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
+MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2
 # words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
 SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
@@ -78,7 +81,7 @@ ABI_SYMBOLS = [
     "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
     "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
     "hc_hough_segments_device", "hc_hough_walk_tables", "hc_hough_circles_device", "hc_hough_circle_geometry",
-    "hc_connected_components_device",
+    "hc_connected_components_device", "hc_morphology_device", "hc_structuring_element",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -149,6 +152,8 @@ def load_library(legacy=False):
     L.hc_hough_walk_tables.argtypes = [i, i, d, d, d, d, C.POINTER(i), C.POINTER(C.c_int32), fp, fp, sz]
     L.hc_hough_circles_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, i, d, d, i, i, i, sz, vp, vp, sz]
     L.hc_connected_components_device.argtypes = [vp, vp, sz, sz, i, i, vp, sz, sz, vp, vp, vp, sz]
+    L.hc_morphology_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, C.POINTER(C.c_int8)]
+    L.hc_structuring_element.argtypes = [i, i, C.POINTER(C.c_int8)]
     L.hc_hough_circle_geometry.argtypes = [i, i, d, d, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
@@ -234,6 +239,15 @@ def gaussian_taps_q8(ksize, sigma=0.0):
     if min(taps) < 0 or max(taps) > 256:
         raise HipCannyError("gaussian_taps_q8: sigma gives taps outside 0 .. 256")
     return taps
+
+
+def structuring_element(shape, ksize):
+    """The ksize half-widths of cv::getStructuringElement(shape, Size(ksize, ksize)) for morphology_device (hc_structuring_element:
+    the host function; no context, no GPU): shape MORPH_RECT, MORPH_CROSS or MORPH_ELLIPSE, ksize 3, 5 or 7.  Row j of the element
+    covers the columns -spans[j] .. +spans[j] around the anchor."""
+    spans = (C.c_int8 * 8)()
+    _ck(load_library().hc_structuring_element(int(shape), int(ksize), spans))
+    return [int(v) for v in spans[:int(ksize)]]
 
 
 def hough_tables(width, height, rho, theta, min_theta=0.0, max_theta=math.pi):
@@ -936,17 +950,104 @@ class Context:
         d = self._maps_on_device(maps, "connected_components")
         return self._components_of(d, d.shape[0], connectivity, max_components)
 
-    def canny_components(self, frames, low, high, connectivity=8, aperture=3, l2gradient=False, blur=None, max_components=None):
+    def morphology_device(self, d_in, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes, channels, op, ksize, spans):
+        """cv::erode / cv::dilate / cv::morphologyEx (open, close, gradient) for u8 frames on device memory (hc_morphology_device,
+        either mode): op MORPH_ERODE .. MORPH_GRADIENT, ksize 3, 5 or 7, `spans` the ksize half-widths of the element's rows (-1: an
+        empty row; structuring_element gives OpenCV's shapes), channels 1 or 3 (3: a 3-channel context).  Constant border that never
+        takes part.  Pitches and frame strides in bytes, any alignment; the views must not overlap.  Asynchronous on the context
+        stream; not a run, but a pipelined run in flight that writes either view is completed first."""
+        vals = [int(v) for v in spans]
+        if any(v < -128 or v > 127 for v in vals) or (int(ksize) in _FIXED_TAPS_Q8 and len(vals) != int(ksize)):
+            raise HipCannyError(f"hc_morphology_device: `spans` must hold ksize = {int(ksize)} int8 values, not {vals}")
+        t = (C.c_int8 * max(len(vals), 1))(*vals)
+        _ck(self.lib.hc_morphology_device(self.handle, C.c_void_p(d_in), in_pitch, in_fs, C.c_void_p(d_out), out_pitch, out_fs, int(nframes),
+                                          int(channels), int(op), int(ksize), t))
+
+    def _morphed(self, src, op, ksize, spans, iterations=1):
+        """Queues `op` on a contiguous u8 device tensor (n,H,W) / (n,H,W,3) on the context stream, `iterations` times as
+        cv::morphologyEx counts them, and returns the result tensor.  Every tensor the queued kernels touch is appended to
+        self._morph_keep, which the caller clears once it has synchronised.  The caller has waited for torch's stream."""
+        import torch
+        n = src.shape[0]
+        ch = 3 if src.ndim == 4 else 1
+        row = ch * self.w
+        fs = row * self.h
+        if int(iterations) < 1:
+            raise HipCannyError("morphology: iterations must be at least 1")
+        if int(iterations) == 1:
+            chain = [op]
+        elif op in (MORPH_ERODE, MORPH_DILATE):
+            chain = [op] * int(iterations)
+        elif op == MORPH_OPEN:
+            chain = [MORPH_ERODE] * int(iterations) + [MORPH_DILATE] * int(iterations)
+        elif op == MORPH_CLOSE:
+            chain = [MORPH_DILATE] * int(iterations) + [MORPH_ERODE] * int(iterations)
+        elif op == MORPH_GRADIENT:   # dilate^n - erode^n: both chains, then the difference on torch's stream
+            bufs = [self._morphed(src, o, ksize, spans, iterations) for o in (MORPH_DILATE, MORPH_ERODE)]
+            self.sync()
+            return (bufs[0].to(torch.int16) - bufs[1].to(torch.int16)).clamp_(min=0).to(torch.uint8)   # (saturated, as cv::subtract)
+        else:
+            raise HipCannyError("hc_morphology_device: op must be one of HC_MORPH_ERODE .. HC_MORPH_GRADIENT")
+        keep = getattr(self, "_morph_keep", None)
+        if keep is None:
+            keep = self._morph_keep = []
+        keep.append(src)
+        cur = src
+        for o in chain:
+            dst = torch.empty_like(src)
+            self._wait_for_torch()
+            self.morphology_device(cur.data_ptr(), row, fs, dst.data_ptr(), row, fs, n, ch, o, ksize, spans)
+            keep.append(dst)
+            cur = dst
+        return cur
+
+    def morphology(self, frames_or_maps, op, shape=MORPH_RECT, ksize=3, iterations=1, spans=None):
+        """numpy or torch u8 (n,H,W) / (n,H,W,3) -- or one frame -- in, the result of the same shape out (numpy), through device
+        tensors (either mode).  spans: ksize half-widths instead of structuring_element(shape, ksize).  iterations > 1 chains the
+        primitive calls on the device with no synchronisation in between, as cv::morphologyEx does: OPEN is `iterations` erosions
+        then as many dilations, CLOSE the reverse, GRADIENT the difference of the iterated dilation and erosion."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(frames_or_maps, torch.Tensor):
+            d = frames_or_maps.to(device=dev, dtype=torch.uint8)
+        else:
+            d = torch.from_numpy(np.ascontiguousarray(frames_or_maps, dtype=np.uint8)).to(dev)
+        if d.ndim == 2 or (d.ndim == 3 and tuple(d.shape) == (self.h, self.w, 3)):
+            d = d[None]
+        d = d.contiguous()
+        if d.ndim not in (3, 4) or tuple(d.shape[1:3]) != (self.h, self.w) or (d.ndim == 4 and d.shape[3] != 3):
+            raise HipCannyError(f"morphology: frames {tuple(d.shape)} do not match the context's {(self.h, self.w)}")
+        sp = structuring_element(shape, ksize) if spans is None else spans
+        self._wait_for_torch()
+        out = self._morphed(d, int(op), ksize, sp, iterations)
+        self.sync()
+        res = out.cpu().numpy()
+        self._morph_keep = None
+        return res
+
+    def canny_components(self, frames, low, high, connectivity=8, aperture=3, l2gradient=False, blur=None, max_components=None, close=None):
         """cv::Canny followed by cv::connectedComponentsWithStats (mode O): canny_device and connected_components_device chained on
         the device, with no host copy of the maps in between.  Returns (uint8 (n,H,W) edge maps, labels, counts, stats, centroids as
-        connected_components gives them).  blur = (ksize, sigma): the frames are blurred first (gaussian_blur_device)."""
+        connected_components gives them).  blur = (ksize, sigma): the frames are blurred first (gaussian_blur_device).
+        close = (shape, ksize): cv::morphologyEx(MORPH_CLOSE) with that element runs between the two on the device
+        (morphology_device), the components are those of the closed maps, and the closed maps are what the call returns."""
         raw, n, row, fs = self._device_view(frames, "canny_components")
         out = self._device_maps(n)
         self._wait_for_torch()
         src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
         self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
-        labels, counts, stats, cent = self._again_if_continued(lambda: self._components_of(out, n, connectivity, max_components))
-        return out.cpu().numpy(), labels, counts, stats, cent
+        if close is None:
+            labels, counts, stats, cent = self._again_if_continued(lambda: self._components_of(out, n, connectivity, max_components))
+            return out.cpu().numpy(), labels, counts, stats, cent
+        spans = structuring_element(*close)
+        closed = self._device_maps(n)
+
+        def closed_components():
+            self._wait_for_torch()
+            self.morphology_device(out.data_ptr(), self.w, self.w * self.h, closed.data_ptr(), self.w, self.w * self.h, n, 1, MORPH_CLOSE, close[1], spans)
+            return self._components_of(closed, n, connectivity, max_components)
+        labels, counts, stats, cent = self._again_if_continued(closed_components)
+        return closed.cpu().numpy(), labels, counts, stats, cent
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -155,6 +155,28 @@ struct BlurParams {
   uint16_t taps[BLUR_MAX_TAPS + 1];  // Q8 (256 = 1.0), each <= 256, sum 256; [ksize ..]: 0
 };
 
+// k_morph8 (morph.hip): one launch of a K x K maximum (dilate) or, on complemented bytes, minimum (erode) filter, u8 frames -> u8
+// frames of the same interleave (hc_morphology_device, where the operation is stated).  Strips, lanes and chunks as k_gauss8.
+// The element is K half-widths per row; the kernel keeps one horizontal maximum per DISTINCT half-width (a "level") of each of the
+// last K rows, so the plan hands it the levels (ascending) and, per element row, the index of its level.
+constexpr int MORPH_MAX_K = 7, MORPH_MAX_LEVELS = 4;  // (half-widths 0 .. 3)
+constexpr int MORPH_ERODE = 0, MORPH_DILATE = 1, MORPH_OPEN = 2, MORPH_CLOSE = 3, MORPH_GRADIENT = 4;  // HC_MORPH_* (host_plan.h asserts the match)
+struct MorphParams {
+  const uint8_t *in;       // u8 frames, `channels` interleaved; any alignment (in_aligned: base, pitch and frame stride are multiples of 4)
+  size_t in_pitch, in_frame_stride;
+  uint8_t *out;            // u8 frames of the same shape; any alignment (out_aligned as in_aligned); no byte shared with the input view
+  size_t out_pitch, out_frame_stride;
+  int W, H, nframes, channels;
+  int ksize;               // 3, 5 or 7
+  int complement;          // 1: bytes are complemented after the load and before the store -- the maximum filter erodes
+  int subtract;            // 1: out = (what out holds) - result, bytewise (the second launch of GRADIENT; the result never exceeds it)
+  int in_aligned, out_aligned;  // as BlurParams
+  int nstrips, nchunks, total_items;
+  int nlevels;                      // 1 .. ksize / 2 + 1 distinct half-widths
+  int8_t level[MORPH_MAX_LEVELS];   // ... ascending; [nlevels ..]: 0
+  int8_t row_level[MORPH_MAX_K + 1];  // per element row: the index of its half-width in level[], -1: an empty row; [ksize ..]: -1
+};
+
 // k_hist256 (stats.hip): 256-bin histograms of u8 frames, all channels pooled.  A work item is (frame, chunk of rows); a wave
 // counts its rows into a wave-private LDS histogram and adds the non-zero bins to hist[frame] with global atomics.
 constexpr int HIST_MAX_CHUNK_ROWS = 64, HIST_MIN_CHUNK_ROWS = 8;

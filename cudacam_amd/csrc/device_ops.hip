@@ -263,4 +263,29 @@ int hc_connected_components_device(hc_ctx *c, const void *d_map, size_t pitch, s
   return HC_OK;
 }
 
+// One or two launches of k_morph8 per pass on the context stream (morph.hip).  Not a run, as hc_gaussian_blur_device, and like it
+// it completes first a pipelined run in flight whose output overlaps either view.  `channels` is the caller's: edge maps have one
+// channel on every context.  OPEN and CLOSE keep their intermediate frames in the context's scratch; successive calls share it and
+// are ordered by the stream they are queued on (include/hipcanny.h).
+int hc_morphology_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in_fs, void *d_out, size_t out_pitch, size_t out_fs, int n, int channels, int op,
+                         int ksize, const int8_t *spans)
+{
+  if (!c || !d_in || !d_out || !spans) return fail(HC_E_ARG, "hc_morphology_device: null argument");
+  const View in{ (uintptr_t)d_in, in_pitch, in_fs }, out{ (uintptr_t)d_out, out_pitch, out_fs };
+  const MorphPlan P = plan_morphology(c->W, c->H, c->C, c->per_channel != 0, c->max_batch, in, out, n, channels, op, ksize, spans, c->hough_bound);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_morphology_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  const size_t row = (size_t)channels * c->W;
+  if (int rc = finish_writers_of(c, in, row, n)) return rc;
+  if (int rc = finish_writers_of(c, out, row, n)) return rc;
+  // every refusal lies above.  A larger scratch: what is queued on the context stream may still read the old one
+  if (P.scratch_bytes)
+    if (int rc = ensure_scratch(c, c->morph_mid, P.scratch_bytes)) return rc;
+  for (int k = 0; k < P.passes; ++k) {
+    const MorphPass mp = morph_pass(P, k, (uintptr_t)c->morph_mid.p);
+    for (int s = 0; s < mp.stages; ++s) HIPCK(launch_morph8(mp.st[s], c->stream));
+  }
+  return HC_OK;
+}
+
 }  // extern "C"

@@ -222,6 +222,9 @@ struct hc_ctx {
   hc::DeviceScratch circles;
   // hc_connected_components_device: the roots / offsets per chunk of rows of one pass (ccl_pass, host_plan.h), bounded by hough_bound as well
   hc::DeviceScratch ccl_items;
+  // hc_morphology_device: the frames between the two stages of HC_MORPH_OPEN / HC_MORPH_CLOSE of one pass (morph_pass, host_plan.h),
+  // bounded by hough_bound as well
+  hc::DeviceScratch morph_mid;
 };
 
 namespace hc {

@@ -615,7 +615,7 @@ void hc_destroy(hc_ctx *c)
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump }) (void)hipFree(q);
-  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab, &c->seg_items, &c->seg_tab, &c->circles, &c->ccl_items }) (void)hipFree(q->p);
+  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab, &c->seg_items, &c->seg_tab, &c->circles, &c->ccl_items, &c->morph_mid }) (void)hipFree(q->p);
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);
@@ -900,6 +900,15 @@ int hc_gaussian_taps_q8(int ksize, double sigma, uint16_t *taps)
   if (!taps) return fail(HC_E_ARG, "hc_gaussian_taps_q8: null argument");
   if (!blur_ksize_ok(ksize)) return fail(HC_E_ARG, "hc_gaussian_taps_q8: ksize 3, 5 or 7");
   if (!gaussian_taps_q8(ksize, sigma, taps)) return fail(HC_E_ARG, "hc_gaussian_taps_q8: sigma must be finite and give taps of 0 .. 256");
+  return HC_OK;
+}
+
+// host only: the rule is stated in include/hipcanny.h, the arithmetic is structuring_spans (host_plan.h)
+int hc_structuring_element(int shape, int ksize, int8_t *spans)
+{
+  if (!spans) return fail(HC_E_ARG, "hc_structuring_element: null argument");
+  if (!blur_ksize_ok(ksize)) return fail(HC_E_ARG, "hc_structuring_element: ksize 3, 5 or 7");
+  if (!structuring_spans(shape, ksize, spans)) return fail(HC_E_ARG, "hc_structuring_element: shape must be HC_MORPH_RECT, HC_MORPH_CROSS or HC_MORPH_ELLIPSE");
   return HC_OK;
 }
 

@@ -2,7 +2,7 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles; the taps rule of
+// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology; the taps rule of
 // hc_gaussian_taps_q8, the table rules of hc_hough_tables and hc_hough_walk_tables and the geometry of hc_hough_circle_geometry).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
@@ -1263,6 +1263,123 @@ inline CclParams ccl_pass(const CclPlan &P, int k, uintptr_t items)
   if (c.capacity) { c.stats += (size_t)f0 * c.capacity * 5; c.sums += (size_t)f0 * c.capacity * 2; }
   c.items = (u32 *)items;
   return c;
+}
+
+// ---- hc_morphology_device -------------------------------------------------------------------------
+static_assert(MORPH_ERODE == HC_MORPH_ERODE && MORPH_DILATE == HC_MORPH_DILATE && MORPH_OPEN == HC_MORPH_OPEN && MORPH_CLOSE == HC_MORPH_CLOSE
+              && MORPH_GRADIENT == HC_MORPH_GRADIENT, "canny_params.h names the header's operations");
+// hc_structuring_element: the half-widths of cv::getStructuringElement's three shapes as include/hipcanny.h states the rule.
+// false: a shape outside the enum, ksize not 3 / 5 / 7 or spans null (nothing is written then)
+inline bool structuring_spans(int shape, int ksize, int8_t *spans)
+{
+  if (!blur_ksize_ok(ksize) || !spans || (shape != HC_MORPH_RECT && shape != HC_MORPH_CROSS && shape != HC_MORPH_ELLIPSE)) return false;
+  const int r = ksize / 2;
+  for (int j = 0; j < ksize; ++j) {
+    const double dy = (double)(j - r);
+    spans[j] = shape == HC_MORPH_RECT ? (int8_t)r : shape == HC_MORPH_CROSS ? (int8_t)(j == r ? r : 0)
+                                      : (int8_t)std::nearbyint((double)r * std::sqrt(((double)(r * r) - dy * dy) / (double)(r * r)));
+  }
+  return true;
+}
+
+// Everything the entry refuses and decides, but for the context pointer.  A call is one or two launches of k_morph8 per pass:
+// ERODE / DILATE one; GRADIENT two with no scratch (dilate into the output, then erode subtracted from it in place); OPEN / CLOSE
+// two through the context's scratch, which holds the intermediate frames of one pass as tight u8 frames of scratch_pitch =
+// channels * W rounded up to a multiple of 4 bytes per row (so that the 256-byte aligned scratch always takes the dword path), H
+// rows per frame with no gap between the frames.  The scratch falls under the context's scratch bound: a batch is cut into passes
+// of as many whole frames as fit.  mp describes the FIRST launch of the first pass as if it went from the input to the output
+// view; morph_pass gives the launches of pass k.  A refused plan holds nothing but its text.
+struct MorphPlan {
+  const char *error = nullptr;
+  MorphParams mp{};
+  int op = 0, stages = 0;  // launches per pass
+  int frames = 0, frames_per_pass = 0, passes = 0;
+  size_t scratch_pitch = 0, scratch_frame_bytes = 0, scratch_bytes = 0;  // 0: the operation needs none
+};
+inline MorphPlan plan_morphology(int W, int H, int ctxC, bool per_channel, int max_batch, const View &in, const View &out, int n, int channels, int op, int ksize,
+                                 const int8_t *spans, size_t scratch_bound)
+{
+  MorphPlan P;
+  auto refuse = [](const char *text) { MorphPlan R; R.error = text; return R; };
+  if (!in.p || !out.p || !spans) return refuse("null argument");
+  if (channels != 1 && channels != 3) return refuse("channels must be 1 or 3");
+  if (channels == 3 && ctxC != 3) return refuse("channels = 3 needs a 3-channel context");
+  if (op != MORPH_ERODE && op != MORPH_DILATE && op != MORPH_OPEN && op != MORPH_CLOSE && op != MORPH_GRADIENT) return refuse("op must be one of HC_MORPH_ERODE .. HC_MORPH_GRADIENT");
+  if (!blur_ksize_ok(ksize)) return refuse("ksize 3, 5 or 7");
+  bool any = false;
+  for (int j = 0; j < ksize; ++j) {
+    if (spans[j] < -1 || spans[j] > ksize / 2) return refuse("a span outside -1 .. ksize / 2");
+    any = any || spans[j] >= 0;
+  }
+  if (!any) return refuse("every row of the element is empty");
+  if (W < 1 || H < 1) return refuse("width and height must be positive");
+  const int max_frames = channels == 1 ? max_batch * (per_channel ? 3 : 1) : max_batch;
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  const size_t row = (size_t)channels * W;
+  for (const View *v : { &in, &out })
+    if (const ViewFault f = check_view(*v, row, H, n, 1, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  uintptr_t end[2];
+  if (!view_end(in, row, H, n, &end[0]) || !view_end(out, row, H, n, &end[1])) return refuse("a view wraps the address space");
+  if (in.p < end[1] && out.p < end[0]) return refuse("the input and output views overlap (in-place operation is not supported)");
+  MorphParams &m = P.mp;
+  m.nstrips = blur_strips(W); m.nchunks = blur_chunks(H);
+  P.op = op; P.frames = n; P.frames_per_pass = n; P.passes = 1;
+  P.stages = op == MORPH_ERODE || op == MORPH_DILATE ? 1 : 2;
+  if (op == MORPH_OPEN || op == MORPH_CLOSE) {
+    P.scratch_pitch = round_up(row, 4);
+    if (reaches_4g(H, P.scratch_pitch)) return refuse(VIEW_FAULT_TEXT[VIEW_4G]);
+    P.scratch_frame_bytes = (size_t)H * P.scratch_pitch;
+    if (scratch_bound < P.scratch_frame_bytes) return refuse("one frame of intermediate results exceeds the context's scratch bound");
+    P.frames_per_pass = (int)std::min<size_t>((size_t)n, scratch_bound / P.scratch_frame_bytes);
+    P.passes = (n + P.frames_per_pass - 1) / P.frames_per_pass;
+    P.scratch_bytes = (size_t)P.frames_per_pass * P.scratch_frame_bytes;
+  }
+  if ((long long)P.frames_per_pass * m.nstrips * m.nchunks > 0x7FFFFFF0ll) return refuse("too many work items (frames of a pass x strips x row chunks)");
+  m.in = (const uint8_t *)in.p; m.in_pitch = in.pitch; m.in_frame_stride = in.fs;
+  m.out = (uint8_t *)out.p; m.out_pitch = out.pitch; m.out_frame_stride = out.fs;
+  m.W = W; m.H = H; m.nframes = P.frames_per_pass; m.channels = channels; m.ksize = ksize;
+  m.in_aligned = aligned4(in.p, in.pitch, in.fs); m.out_aligned = aligned4(out.p, out.pitch, out.fs);
+  m.total_items = m.nframes * m.nstrips * m.nchunks;
+  // the levels: the distinct half-widths, ascending
+  for (int a = 0; a <= ksize / 2; ++a) {
+    bool used = false;
+    for (int j = 0; j < ksize; ++j) used = used || spans[j] == a;
+    if (used) m.level[m.nlevels++] = (int8_t)a;
+  }
+  for (int j = 0; j <= MORPH_MAX_K; ++j) {
+    m.row_level[j] = -1;
+    for (int l = 0; j < ksize && l < m.nlevels; ++l)
+      if (spans[j] == m.level[l]) m.row_level[j] = (int8_t)l;
+  }
+  return P;
+}
+
+// The launches of pass k of a plan that was not refused (0 <= k < passes), in order; scratch: scratch_bytes, 4-byte aligned (not
+// read when the plan needs none)
+struct MorphPass { int stages = 0; MorphParams st[2]; };
+inline MorphPass morph_pass(const MorphPlan &P, int k, uintptr_t scratch)
+{
+  MorphPass R;
+  R.stages = P.stages;
+  const int f0 = k * P.frames_per_pass;
+  MorphParams m = P.mp;
+  m.nframes = std::min(P.frames_per_pass, P.frames - f0);
+  m.total_items = m.nframes * m.nstrips * m.nchunks;
+  m.in += (size_t)f0 * m.in_frame_stride;
+  m.out += (size_t)f0 * m.out_frame_stride;
+  R.st[0] = R.st[1] = m;
+  MorphParams &a = R.st[0], &b = R.st[1];
+  switch (P.op) {
+  case MORPH_ERODE: a.complement = 1; break;
+  case MORPH_DILATE: break;
+  case MORPH_GRADIENT: b.complement = 1; b.subtract = 1; break;  // dilate into the output, then out -= erode
+  default:  // OPEN: erode then dilate; CLOSE: dilate then erode -- through the scratch
+    a.complement = P.op == MORPH_OPEN; b.complement = P.op == MORPH_CLOSE;
+    a.out = (uint8_t *)scratch; a.out_pitch = P.scratch_pitch; a.out_frame_stride = P.scratch_frame_bytes; a.out_aligned = 1;
+    b.in = (const uint8_t *)scratch; b.in_pitch = P.scratch_pitch; b.in_frame_stride = P.scratch_frame_bytes; b.in_aligned = 1;
+    break;
+  }
+  return R;
 }
 
 }  // namespace hc

@@ -559,6 +559,58 @@ int hc_connected_components_device(hc_ctx *ctx, const void *d_map, size_t pitch,
                                    void *d_centroids /* float64 [nframes][capacity][2]; may be NULL when capacity == 0 */,
                                    size_t capacity);
 
+/* cv::erode, cv::dilate and cv::morphologyEx(MORPH_OPEN / MORPH_CLOSE / MORPH_GRADIENT) for CV_8U frames on the device -- the step
+ * between cv::Canny and a labelling or outlining of its map: Canny contours are one pixel wide and break at junctions, so callers
+ * close the map first (k_morph8: cudacam_amd/csrc/morph.hip).  The semantics are stated here and restated in tests/morph_ref.py
+ * (numpy); like the rest of Mode O they are not pinned against a build of OpenCV.
+ * Element: K x K with K = ksize in {3, 5, 7}, anchored at its centre.  `spans` points to K int8 half-widths in HOST memory (read
+ *   before the call returns): row j (0 .. K-1) of the element covers the columns -spans[j] .. +spans[j] around the anchor, and
+ *   spans[j] = -1 is an empty row.  Every span lies in -1 .. K/2 and at least one row is not empty.  That covers the three shapes
+ *   of cv::getStructuringElement (the host function below) and every other element whose rows are convex and symmetric in x; the
+ *   rows need not be symmetric in y.  Arbitrary masks are not offered.
+ * Operation, per pixel and channel (the channels of 3-channel frames are independent and stay interleaved):
+ *     dilate: out(y, x) = max over the rows j and dx in -spans[j] .. spans[j] of src(y + j - K/2, x + dx)
+ *     erode:  the same with min
+ *   The element is not reflected: that is cv::dilate / cv::erode.  HC_MORPH_OPEN = dilate(erode(src)), HC_MORPH_CLOSE =
+ *   erode(dilate(src)), HC_MORPH_GRADIENT = dilate(src) - erode(src), saturated at 0 as cv::morphologyEx subtracts (the difference is
+ *   negative only where the window holds no position of the frame, see the border rule: 0 there); each stage is an operation on
+ *   whole frames under the border rule below, as cv::morphologyEx runs them.
+ * Border: cv::erode / cv::dilate's default, BORDER_CONSTANT with morphologyDefaultBorderValue: positions outside the frame never
+ *   take part.  A window with no position inside the frame gives 0 (dilate) or 255 (erode).  There is no other border mode.
+ * Channels: `channels` is 1 or 3 (interleaved) and is the caller's, not the context's: edge maps have one channel on every context.
+ *   channels = 3 needs a 3-channel context.  With channels = 1, nframes may reach the output frames of a max_batch run (max_batch,
+ *   3 * max_batch with HC_OPT_PER_CHANNEL), as for hc_edge_points_device; with channels = 3 it is at most max_batch.
+ * Views, as hc_gaussian_blur_device: u8 rows of channels * width bytes with any alignment of base, pitch and frame stride; no
+ *   byte outside [row, row + channels * width) of a row is read or written on either side; height * pitch >= 2^32 on either side
+ *   is HC_E_ARG; byte ranges that overlap are refused, ranges that merely touch are fine.
+ * Asynchronous on the context stream (hc_set_stream honoured), in order with everything else queued there: behind hc_canny_device
+ *   and ahead of hc_connected_components_device it needs no synchronisation.  It is not a run, exactly as hc_gaussian_blur_device
+ *   is none (hc_last_run_info, the stage timers, the hysteresis schedule / history and the pipeline slots stay as they were), and
+ *   like that entry it completes first a pipelined run still in flight whose output overlaps either view.
+ * Scratch: HC_MORPH_ERODE, HC_MORPH_DILATE and HC_MORPH_GRADIENT use none (the gradient is two launches, the second subtracting
+ *   in place).  HC_MORPH_OPEN and HC_MORPH_CLOSE keep the frames between their two stages in one buffer the context owns
+ *   (allocated on first use, grown when a call needs more, freed by hc_destroy; rows padded to a multiple of 4 bytes), under the
+ *   bound of hc_hough_lines_device's scratch (256 MiB): a batch that does not fit runs in passes of as many whole frames as do, and
+ *   a single frame above the bound is HC_E_ARG.  Successive calls share it and are ordered by the stream they are queued on, as for
+ *   hc_edge_points_device.
+ * HC_E_ARG: a null pointer; channels not 1 or 3, or 3 on a one-channel context; op outside the enum; ksize not in {3, 5, 7}; a
+ * span outside -1 .. K/2, or all rows empty; a pitch < channels * width; nframes out of range; nframes > 1 with a frame stride
+ * smaller than height * pitch; height * pitch >= 2^32; overlapping views; a frame of intermediate results above the scratch bound.
+ * Every refusal lies above the first allocation or launch.  Measurements: profiles/morph/README.md. */
+enum { HC_MORPH_ERODE = 0, HC_MORPH_DILATE = 1, HC_MORPH_OPEN = 2, HC_MORPH_CLOSE = 3, HC_MORPH_GRADIENT = 4 };
+enum { HC_MORPH_RECT = 0, HC_MORPH_CROSS = 1, HC_MORPH_ELLIPSE = 2 };
+int hc_morphology_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
+                         size_t out_frame_stride, int nframes, int channels, int op, int ksize, const int8_t *spans /* host, ksize values */);
+
+/* The half-widths of cv::getStructuringElement(shape, Size(ksize, ksize)) for the entry above, on the host (no context, no GPU),
+ * restated; not pinned against a build of OpenCV.  With K = ksize (3, 5, 7) and r = K / 2:
+ *   HC_MORPH_RECT:    every span is r.
+ *   HC_MORPH_CROSS:   r in the centre row, 0 in the others.
+ *   HC_MORPH_ELLIPSE: spans[j] = nearbyint(r * sqrt((r * r - (j - r) * (j - r)) / (r * r))) in double: [0 1 0] (the cross),
+ *                     [0 2 2 2 0] and [0 2 3 3 3 2 0].
+ * HC_E_ARG: spans null; a shape outside the enum; ksize not in {3, 5, 7}.  A refusal writes nothing. */
+int hc_structuring_element(int shape, int ksize, int8_t *spans);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
