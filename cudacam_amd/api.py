@@ -68,6 +68,11 @@ CC_STAT_LEFT, CC_STAT_TOP, CC_STAT_WIDTH, CC_STAT_HEIGHT, CC_STAT_AREA, CC_STAT_
 # operations and element shapes of hc_morphology_device / hc_structuring_element (the header's HC_MORPH_*)
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
 MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2
+# targets and distance types of hc_distance_transform_device, and the squared distance of a frame without a feature pixel (the
+# header's HC_DT_*)
+DT_TO_NONZERO, DT_TO_ZERO = 0, 1
+DT_SQUARED_I32, DT_F32 = 0, 1
+DT_NONE = 2147483647
 # words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
 SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
@@ -81,7 +86,7 @@ ABI_SYMBOLS = [
     "hc_derivatives_device", "hc_canny_device", "hc_frame_thresholds_device", "hc_histogram_device", "hc_auto_thresholds_device",
     "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
     "hc_hough_segments_device", "hc_hough_walk_tables", "hc_hough_circles_device", "hc_hough_circle_geometry",
-    "hc_connected_components_device", "hc_morphology_device", "hc_structuring_element",
+    "hc_connected_components_device", "hc_morphology_device", "hc_structuring_element", "hc_distance_transform_device",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -154,6 +159,7 @@ def load_library(legacy=False):
     L.hc_connected_components_device.argtypes = [vp, vp, sz, sz, i, i, vp, sz, sz, vp, vp, vp, sz]
     L.hc_morphology_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, C.POINTER(C.c_int8)]
     L.hc_structuring_element.argtypes = [i, i, C.POINTER(C.c_int8)]
+    L.hc_distance_transform_device.argtypes = [vp, vp, sz, sz, i, i, i, vp, sz, sz, vp, sz, sz]
     L.hc_hough_circle_geometry.argtypes = [i, i, d, d, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
@@ -1048,6 +1054,49 @@ class Context:
             return self._components_of(closed, n, connectivity, max_components)
         labels, counts, stats, cent = self._again_if_continued(closed_components)
         return closed.cpu().numpy(), labels, counts, stats, cent
+
+    def distance_transform_device(self, d_map, pitch, fs, nframes, target, dist_type, d_dist, dist_pitch, dist_fs, d_nearest=None, nearest_pitch=0,
+                                  nearest_fs=0):
+        """The exact Euclidean distance transform per frame on the device (hc_distance_transform_device): d_map holds one-channel
+        u8 maps (any alignment); the feature pixels are its non-zero bytes (target DT_TO_NONZERO) or its zero bytes (DT_TO_ZERO).
+        d_dist receives [H][W] per frame, the squared distance to the nearest feature pixel as int32 (dist_type DT_SQUARED_I32;
+        DT_NONE in a frame without one) or its float32 root (DT_F32; +inf); d_nearest, when given, int32 [H][W] = y' * W + x' of
+        that pixel (-1 in a frame without one), ties to the smallest x', then the smallest y'.  Output pitches and frame strides
+        in bytes, multiples of 4.  Asynchronous on the context stream; not a run, but a pipelined run in flight that writes any
+        of the views is completed first."""
+        _ck(self.lib.hc_distance_transform_device(self.handle, C.c_void_p(d_map), pitch, fs, int(nframes), int(target), int(dist_type), C.c_void_p(d_dist),
+                                                  dist_pitch, dist_fs, C.c_void_p(d_nearest or None), nearest_pitch, nearest_fs))
+
+    def _distances_of(self, d_maps, n, target, squared, nearest):
+        """(dist[, nearest]) of n tight maps on the device (a torch u8 tensor [n, H, W] the context stream may read), as numpy."""
+        import torch
+        dist = torch.empty((n, self.h, self.w), dtype=torch.int32 if squared else torch.float32, device=d_maps.device)
+        near = torch.empty((n, self.h, self.w), dtype=torch.int32, device=d_maps.device) if nearest else None
+        fs = self.w * self.h
+        self._wait_for_torch()
+        self.distance_transform_device(d_maps.data_ptr(), self.w, fs, n, target, DT_SQUARED_I32 if squared else DT_F32, dist.data_ptr(), 4 * self.w, 4 * fs,
+                                       near.data_ptr() if nearest else None, 4 * self.w if nearest else 0, 4 * fs if nearest else 0)
+        self.sync()
+        return (dist.cpu().numpy(), near.cpu().numpy()) if nearest else dist.cpu().numpy()
+
+    def distance_transform(self, maps, target=DT_TO_NONZERO, squared=False, nearest=False):
+        """Host or torch u8 maps [n, H, W] (or one map) in; float32 distances [n, H, W] out (squared=True: the exact int32 squared
+        distances), with nearest=True the pair (distances, int32 [n, H, W] indices y' * W + x' of the nearest feature pixel)."""
+        d = self._maps_on_device(maps, "distance_transform")
+        return self._distances_of(d, d.shape[0], target, squared, nearest)
+
+    def canny_distance(self, frames, low, high, aperture=3, l2gradient=False, blur=None, squared=False, nearest=False):
+        """cv::Canny followed by the distance of every pixel to the nearest edge pixel (mode O): canny_device and
+        distance_transform_device chained on the device, with no host copy of the maps and no synchronisation in between.
+        blur = (ksize, sigma): the frames are blurred first (gaussian_blur_device).  Returns (uint8 (n,H,W) edge maps, distances
+        [, nearest]) as distance_transform gives them."""
+        raw, n, row, fs = self._device_view(frames, "canny_distance")
+        out = self._device_maps(n)
+        self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
+        self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
+        res = self._again_if_continued(lambda: self._distances_of(out, n, DT_TO_NONZERO, squared, nearest))
+        return (out.cpu().numpy(),) + (res if nearest else (res,))
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

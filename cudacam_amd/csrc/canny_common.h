@@ -35,6 +35,7 @@ hipError_t launch_hough_circles(const CircleParams &p, hipStream_t s);
 // and, with p.capacity > 0, k_ccl_rows, k_ccl_stats and k_ccl_finish
 hipError_t launch_connected_components(const CclParams &p, hipStream_t s);
 hipError_t launch_morph8(const MorphParams &p, hipStream_t s);  // morph.hip (the product library only): one maximum / minimum filter launch, u8 -> u8
+hipError_t launch_distance_transform(const DistParams &p, hipStream_t s);  // dist.hip (the product library only): k_dt_cols, then k_dt_rows
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

@@ -323,6 +323,33 @@ struct CclParams {
   unsigned row_groups;     // workgroups per frame of k_ccl_rows / k_ccl_finish: ceil(min(capacity, W * H + 1) / CCL_THREADS), at most CCL_ROW_GROUPS
 };
 
+// k_dt_cols / k_dt_rows (dist.hip): the exact squared Euclidean distance of every pixel of u8 maps to the nearest feature pixel,
+// and that pixel (hc_distance_transform_device, where the result is stated).  The only per-pixel storage is the caller's distance
+// plane: between the two kernels word (x, y) holds dy = y' - y of the nearest feature pixel (x, y') of column x, a tie between
+// above and below going to the one above, or DT_NO_DY in a column without one.  |dy| <= H - 1 < DT_NO_DY, and nothing squares or
+// compares DT_NO_DY: a word that holds it is skipped.
+constexpr int DT_COL_THREADS = 64;   // a workgroup of k_dt_cols: one wave, one column per lane (a small batch spreads over more CUs)
+constexpr int DT_COLS_PER_LANE = 1;  // as k_ccl_local: one byte, one word per lane whatever the views' alignment
+constexpr int DT_LOOKAHEAD = 8;      // rows k_dt_cols loads before it walks them: the loads do not depend on the carried state
+constexpr int DT_ROW_THREADS = 256;  // a workgroup of k_dt_rows: lane t owns the columns t, t + 256, ... of its row
+constexpr int DT_ROWS = 4;           // rows a workgroup of k_dt_rows takes, one after the other, through the same LDS row
+constexpr int DT_MAX_W = 16384;      // the LDS row of k_dt_rows: W int32, 64 KiB at most
+constexpr int DT_NO_DY = 0x7FFFFFFF, DT_NONE = 0x7FFFFFFF;  // DT_NONE: HC_DT_NONE (host_plan.h asserts the match)
+constexpr int DT_TO_NONZERO = 0, DT_TO_ZERO = 1, DT_SQUARED_I32 = 0, DT_F32 = 1;  // HC_DT_* (likewise)
+struct DistParams {
+  const uint8_t *map;      // u8 maps of W x H, one channel, any alignment of base, pitch and frame stride
+  size_t pitch, frame_stride;
+  int32_t *dist;           // int32 / float32 [H][W] per frame; pitch and frame stride in BYTES, multiples of 4, H * dist_pitch < 2^32
+  size_t dist_pitch, dist_frame_stride;
+  int32_t *nearest;        // int32 [H][W] per frame, likewise; null: not wanted
+  size_t nearest_pitch, nearest_frame_stride;
+  int W, H, nframes;       // (W - 1)^2 + (H - 1)^2 < 2^31 - 1, W * H < 2^31 - 1, W <= DT_MAX_W
+  int target, dist_type;   // DT_TO_NONZERO / DT_TO_ZERO; DT_SQUARED_I32 / DT_F32
+  unsigned col_groups;     // workgroups of k_dt_cols per frame: ceil(W / (DT_COL_THREADS * DT_COLS_PER_LANE))
+  unsigned row_groups;     // workgroups of k_dt_rows per frame: ceil(H / DT_ROWS)
+  unsigned lds_bytes;      // dynamic LDS of k_dt_rows: 4 * W
+};
+
 struct HystParams {
   u32 *sbits;
   const u32 *cbits;

@@ -288,4 +288,30 @@ int hc_morphology_device(hc_ctx *c, const void *d_in, size_t in_pitch, size_t in
   return HC_OK;
 }
 
+// k_dt_cols, then k_dt_rows on the context stream (dist.hip).  Not a run, as hc_connected_components_device, and like it it
+// completes first a pipelined run in flight whose output overlaps any of its views: the map it reads, the distance plane or the
+// nearest plane it writes.  No scratch: the dy of the column pass live in the caller's distance plane between the two kernels.
+int hc_distance_transform_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs, int n, int target, int dist_type, void *d_dist, size_t dist_pitch,
+                                 size_t dist_fs, void *d_nearest, size_t nearest_pitch, size_t nearest_fs)
+{
+  if (!c || !d_map || !d_dist) return fail(HC_E_ARG, "hc_distance_transform_device: null argument");
+  const int max_frames = c->max_batch * (c->per_channel ? 3 : 1);  // (as hc_edge_points_device: the output frames of a max_batch run)
+  const size_t row = (size_t)c->W, word_row = 4 * (size_t)c->W;
+  const View map{ (uintptr_t)d_map, pitch, fs }, dist{ (uintptr_t)d_dist, dist_pitch, dist_fs };
+  const View nearest = d_nearest ? View{ (uintptr_t)d_nearest, nearest_pitch, nearest_fs } : View{ 0, 0, 0 };
+  if (int rc = check_views(c, "hc_distance_transform_device", n, max_frames, { { "d_map (pitch, frame_stride)", d_map, pitch, fs, row, 1, true }, { "d_dist (dist_pitch, dist_frame_stride)", d_dist, dist_pitch, dist_fs, word_row, 4, true } })) return rc;
+  if (d_nearest)
+    if (int rc = check_views(c, "hc_distance_transform_device", n, max_frames, { { "d_nearest (nearest_pitch, nearest_frame_stride)", d_nearest, nearest_pitch, nearest_fs, word_row, 4, true } })) return rc;
+  const DistPlan P = plan_distance_transform(c->W, c->H, max_frames, map, dist, nearest, n, target, dist_type);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_distance_transform_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  if (int rc = finish_writers_of(c, map, row, n)) return rc;
+  if (int rc = finish_writers_of(c, dist, word_row, n)) return rc;
+  if (d_nearest)
+    if (int rc = finish_writers_of(c, nearest, word_row, n)) return rc;
+  // every refusal lies above
+  HIPCK(launch_distance_transform(P.dp, c->stream));
+  return HC_OK;
+}
+
 }  // extern "C"

@@ -2,7 +2,7 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology; the taps rule of
+// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology, plan_distance_transform; the taps rule of
 // hc_gaussian_taps_q8, the table rules of hc_hough_tables and hc_hough_walk_tables and the geometry of hc_hough_circle_geometry).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
@@ -1380,6 +1380,55 @@ inline MorphPass morph_pass(const MorphPlan &P, int k, uintptr_t scratch)
     break;
   }
   return R;
+}
+
+// ---- hc_distance_transform_device -----------------------------------------------------------------
+static_assert(DT_TO_NONZERO == HC_DT_TO_NONZERO && DT_TO_ZERO == HC_DT_TO_ZERO && DT_SQUARED_I32 == HC_DT_SQUARED_I32 && DT_F32 == HC_DT_F32 && DT_NONE == HC_DT_NONE,
+              "canny_params.h names the header's targets, types and HC_DT_NONE");
+// Everything the entry refuses and decides, but for the context pointer.  dp is the parameter block of both kernels (k_dt_cols
+// on a grid of col_groups x nframes workgroups, k_dt_rows on row_groups x nframes with lds_bytes of LDS); there is no scratch and
+// there are no passes.  nearest.p == 0: the call wants no nearest plane (its pitch and stride are not looked at then).  A refused
+// plan holds nothing but its text.
+struct DistPlan { const char *error = nullptr; DistParams dp{}; };
+inline DistPlan plan_distance_transform(int W, int H, int max_frames, const View &map, const View &dist, const View &nearest, int n, int target, int dist_type)
+{
+  DistPlan P;
+  auto refuse = [](const char *text) { DistPlan R; R.error = text; return R; };
+  if (!map.p || !dist.p) return refuse("null argument");
+  if (target != DT_TO_NONZERO && target != DT_TO_ZERO) return refuse("target must be HC_DT_TO_NONZERO or HC_DT_TO_ZERO");
+  if (dist_type != DT_SQUARED_I32 && dist_type != DT_F32) return refuse("dist_type must be HC_DT_SQUARED_I32 or HC_DT_F32");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  if (n > 65535) return refuse("more than 65535 frames in one call");
+  if (W < 1 || H < 1) return refuse("width and height must be positive");
+  if ((long long)W * H >= 0x7FFFFFFFll) return refuse("width * height reaches 2^31 - 1 pixels");
+  if ((long long)(W - 1) * (W - 1) + (long long)(H - 1) * (H - 1) >= 0x7FFFFFFFll) return refuse("the squared diagonal (W - 1)^2 + (H - 1)^2 reaches 2^31 - 1");
+  if (W > DT_MAX_W) return refuse("width above the 16384 columns of the row k_dt_rows keeps in LDS");
+  if (const ViewFault f = check_view(map, (size_t)W, H, n, 1, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  if (const ViewFault f = check_view(dist, 4 * (size_t)W, H, n, 4, true))
+    return refuse(f == VIEW_ALIGN ? "d_dist, dist_pitch and dist_frame_stride must be multiples of 4" : f == VIEW_PITCH ? "dist_pitch smaller than a row of 4-byte distances" : VIEW_FAULT_TEXT[f]);
+  if (nearest.p)
+    if (const ViewFault f = check_view(nearest, 4 * (size_t)W, H, n, 4, true))
+      return refuse(f == VIEW_ALIGN ? "d_nearest, nearest_pitch and nearest_frame_stride must be multiples of 4" : f == VIEW_PITCH ? "nearest_pitch smaller than a row of int32 indices" : VIEW_FAULT_TEXT[f]);
+  uintptr_t end[3] = { 0, 0, 0 };
+  if (!view_end(map, (size_t)W, H, n, &end[0]) || !view_end(dist, 4 * (size_t)W, H, n, &end[1]) || (nearest.p && !view_end(nearest, 4 * (size_t)W, H, n, &end[2])))
+    return refuse("a view wraps the address space");
+  if (map.p < end[1] && dist.p < end[0]) return refuse("the map and the distance plane overlap");
+  if (nearest.p && map.p < end[2] && nearest.p < end[0]) return refuse("the map and the nearest plane overlap");
+  // The two outputs may be ROIs of one plane side by side: the same pitch and frame stride, bases in one row of that plane, rows
+  // that do not meet.  Their byte ranges interleave then, but they share no byte (rows r and r' of frames f and f' lie in different
+  // rows of the plane unless r = r' and f = f': a frame stride holds a frame).
+  const size_t word_row = 4 * (size_t)W, apart = (size_t)(dist.p < nearest.p ? nearest.p - dist.p : dist.p - nearest.p);
+  const bool side_by_side = nearest.p && dist.pitch == nearest.pitch && (n == 1 || dist.fs == nearest.fs) && apart >= word_row && apart <= dist.pitch - word_row;
+  if (nearest.p && !side_by_side && dist.p < end[2] && nearest.p < end[1]) return refuse("the distance plane and the nearest plane overlap");
+  DistParams &d = P.dp;
+  d.map = (const uint8_t *)map.p; d.pitch = map.pitch; d.frame_stride = map.fs;
+  d.dist = (int32_t *)dist.p; d.dist_pitch = dist.pitch; d.dist_frame_stride = dist.fs;
+  if (nearest.p) { d.nearest = (int32_t *)nearest.p; d.nearest_pitch = nearest.pitch; d.nearest_frame_stride = nearest.fs; }
+  d.W = W; d.H = H; d.nframes = n; d.target = target; d.dist_type = dist_type;
+  d.col_groups = (unsigned)((W + DT_COL_THREADS * DT_COLS_PER_LANE - 1) / (DT_COL_THREADS * DT_COLS_PER_LANE));
+  d.row_groups = (unsigned)((H + DT_ROWS - 1) / DT_ROWS);
+  d.lds_bytes = 4u * (unsigned)W;
+  return P;
 }
 
 }  // namespace hc

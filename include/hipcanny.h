@@ -611,6 +611,55 @@ int hc_morphology_device(hc_ctx *ctx, const void *d_in, size_t in_pitch, size_t 
  * HC_E_ARG: spans null; a shape outside the enum; ksize not in {3, 5, 7}.  A refusal writes nothing. */
 int hc_structuring_element(int shape, int ksize, int8_t *spans);
 
+/* The exact Euclidean distance transform of u8 maps on the device: for every pixel the distance to the nearest feature pixel,
+ * and which pixel that is -- cv::distanceTransform(255 - edges, DIST_L2, DIST_MASK_PRECISE) with DIST_LABEL_PIXEL labels, the
+ * per-pixel product callers take from an edge map: chamfer matching, watershed markers, snapping to the nearest contour
+ * (k_dt_cols, k_dt_rows: cudacam_amd/csrc/dist.hip).  The semantics are stated here and restated in tests/dist_ref.py (numpy: a
+ * brute force over all feature pixels, and a separable form); like the rest of Mode O they are not pinned against a build of
+ * OpenCV.  DIST_L2 only.  With W, H the context's frame size:
+ * Map.  d_map is what hc_connected_components_device reads: one-channel u8 maps of W x H in a pitched view, whatever `channels`
+ *   the context has; any alignment of base, pitch and frame stride; pitch >= W; no byte outside [row, row + W) of a row is read.
+ *   The map is never written.  target = HC_DT_TO_NONZERO: the feature pixels are the non-zero bytes -- "distance to the nearest
+ *   edge": the 255 of a final map, the 128 / 255 of an HC_STAGE_THRESH map and a 1 alike.  target = HC_DT_TO_ZERO: the feature
+ *   pixels are the zero bytes, cv::distanceTransform's own convention, which saves the caller an inversion pass.
+ * Distance.  For pixel (x, y), d2 = the minimum over the frame's feature pixels (x', y') of (x - x')^2 + (y - y')^2, an exact
+ *   integer: 0 on a feature pixel, HC_DT_NONE in every pixel of a frame without a feature pixel.  Frames are independent.
+ *   dist_type = HC_DT_SQUARED_I32: d_dist receives d2 as int32 [H][W].  dist_type = HC_DT_F32: d_dist receives float32
+ *   sqrtf((float)d2) -- one conversion of the int32 to float32, round to nearest even, then one correctly rounded IEEE square
+ *   root -- and +inf where d2 == HC_DT_NONE.  (From d2 > 2^24 on, which frames of 4100 columns reach, the conversion rounds, and
+ *   the result is not always the float nearest to the square root taken in double: d2 = 6145^2 + 2^2 = 37,761,029 is the first
+ *   example a single feature pixel at a corner gives, d2 = 77,632,802 another.)
+ * Nearest.  When d_nearest is not null it receives, as int32 [H][W], the index y' * W + x' of a nearest feature pixel, and -1 in
+ *   every pixel of a frame without one.  Among the feature pixels at distance d2 it is the one with the smallest x', and among
+ *   those the one with the smallest y'.  That is the information of cv::distanceTransform's `labels` with DIST_LABEL_PIXEL, as
+ *   coordinates instead of OpenCV's running numbers.
+ * Output views, as the label plane of hc_connected_components_device: dist_pitch, dist_frame_stride, nearest_pitch and
+ *   nearest_frame_stride in bytes; base, pitch and frame stride multiples of 4; pitch >= 4 * W.  Exactly the bytes
+ *   [row, row + 4 * W) of every row are written, so either may be an ROI of a larger plane.  While the call runs the planes hold
+ *   intermediate values.  nearest_pitch and nearest_frame_stride are not looked at when d_nearest is null.  No two of the three
+ *   views may overlap, by the rule of the other entries: the byte ranges from a view's first to its last byte must not meet
+ *   (ranges that merely touch are fine).  One exception: d_dist and d_nearest may be ROIs of one plane side by side -- equal
+ *   pitches, equal frame strides (nframes > 1), bases at least 4 * W and at most pitch - 4 * W bytes apart -- whose ranges
+ *   interleave without sharing a byte.
+ * Asynchronous on the context stream (hc_set_stream honoured); chained behind hc_canny_device or hc_morphology_device it needs no
+ * synchronisation.  Contexts of either mode.  It is not a run, exactly as hc_connected_components_device is none
+ * (hc_last_run_info, the stage timers, the hysteresis schedule / history and the pipeline slots stay as they were), and like
+ * that entry it completes first a pipelined run still in flight whose output overlaps any of the three views.
+ * No scratch, no allocation, no passes, no atomics: between the two kernels the distance plane itself holds, per pixel, the
+ * vertical offset to the nearest feature pixel of its column.  The result is a function of the map alone.
+ * HC_E_ARG: ctx, d_map or d_dist null; target or dist_type outside its enum; pitch < W; an output base, pitch or frame stride
+ * that is no multiple of 4; an output pitch < 4 * W; H * pitch >= 2^32 on any side; nframes outside 1..(max_batch, 3 * max_batch
+ * with HC_OPT_PER_CHANNEL) or above 65535; nframes > 1 with a frame stride below H * pitch on any side; a view that wraps the
+ * address space; any two of the views overlapping (views that merely touch are fine); W * H >= 2^31 - 1; (W - 1)^2 + (H - 1)^2
+ * >= 2^31 - 1; W > 16384 (k_dt_rows keeps a row of W int32 in LDS).  Every refusal lies above the first launch, and a refused call
+ * writes nothing.  Measurements: DESIGN.md 3.7k (tools/dist_bench.py). */
+enum { HC_DT_TO_NONZERO = 0, HC_DT_TO_ZERO = 1 };          /* which pixels are the features */
+enum { HC_DT_SQUARED_I32 = 0, HC_DT_F32 = 1 };             /* what d_dist receives */
+#define HC_DT_NONE 2147483647                               /* squared distance of a frame without a feature pixel */
+int hc_distance_transform_device(hc_ctx *ctx, const void *d_map, size_t pitch, size_t frame_stride, int nframes, int target, int dist_type,
+                                 void *d_dist, size_t dist_pitch, size_t dist_frame_stride,
+                                 void *d_nearest /* may be NULL */, size_t nearest_pitch, size_t nearest_frame_stride);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
