@@ -2,9 +2,15 @@
 // (tests/test_dist_plan_cpu.py builds this with g++ under ASan + UBSan): every refusal hc_distance_transform_device documents, by
 // its message; the grids of both kernels at the workgroup and wave boundaries; the LDS row at its limit; views that touch; and that
 // a refused plan holds nothing to launch.  Prints "ok <checks>" or the first violations.
+//   dist_plan_driver plan W H max_frames { nframes target dist_type map pitch frame_stride dist dist_pitch dist_frame_stride nearest
+//                                          nearest_pitch nearest_frame_stride }...
+// prints, for each group of twelve, "col_groups row_groups lds_bytes" or "refused: <text>" (tests/test_device_op_sequences_cpu.py:
+// the dist steps of the seeded chains).  map, dist and nearest are addresses, so that the plan sees how the views lie to each
+// other -- side by side among them; a nearest of 0 is a call without that plane.
 #include "../../cudacam_amd/csrc/host_plan.h"
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 using namespace hc;
@@ -162,8 +168,26 @@ static void geometry()
     }
 }
 
-int main()
+static int print_plans(int count, char **v)
 {
+  Call c;
+  c.W = std::atoi(v[0]); c.H = std::atoi(v[1]); c.max_frames = std::atoi(v[2]);
+  auto num = [](const char *t) { return (size_t)std::strtoull(t, nullptr, 10); };
+  for (char **g = v + 3; g + 12 <= v + count; g += 12) {
+    c.n = std::atoi(g[0]); c.target = std::atoi(g[1]); c.type = std::atoi(g[2]);
+    c.map = View{ (uintptr_t)num(g[3]), num(g[4]), num(g[5]) };
+    c.dist = View{ (uintptr_t)num(g[6]), num(g[7]), num(g[8]) };
+    c.nearest = View{ (uintptr_t)num(g[9]), num(g[10]), num(g[11]) };
+    const DistPlan P = c.plan();
+    if (P.error) std::printf("refused: %s\n", P.error);
+    else std::printf("%u %u %u\n", P.dp.col_groups, P.dp.row_groups, P.dp.lds_bytes);
+  }
+  return 0;
+}
+
+int main(int argc, char **argv)
+{
+  if (argc >= 5 && (argc - 5) % 12 == 0 && !std::strcmp(argv[1], "plan")) return print_plans(argc - 2, argv + 2);
   refusals();
   geometry();
   if (g_fail) { std::printf("%ld of %ld checks failed\n", g_fail, g_checks); return 1; }

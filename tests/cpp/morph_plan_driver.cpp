@@ -4,9 +4,16 @@
 // per_channel, overlapping and touching views, the launches of every operation, and the passes of OPEN / CLOSE at scratch bounds
 // of exactly k frames, one byte less, and below one frame.
 // Prints "ok <checks>" or the first violations.
+//   morph_plan_driver plan W H context_channels per_channel max_batch { nframes channels op ksize span0 .. span6 in in_pitch
+//                                                                       in_frame_stride out out_pitch out_frame_stride scratch_bound }...
+// prints, for each group of eighteen, "scratch_bytes passes frames_per_pass" or "refused: <text>" (tests/
+// test_device_op_sequences_cpu.py: the morph steps of the seeded chains).  in and out are addresses, so that the plan sees how the
+// two views lie to each other; of the seven spans the first ksize count; a scratch_bound of 0 is the context's default, as
+// hc_set_option takes it.
 #include "../../cudacam_amd/csrc/host_plan.h"
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 using namespace hc;
@@ -190,8 +197,26 @@ static void passes()
   }
 }
 
-int main()
+static int print_plans(int count, char **v)
 {
+  const int W = std::atoi(v[0]), H = std::atoi(v[1]), ctxC = std::atoi(v[2]), mb = std::atoi(v[4]);
+  const bool pc = std::atoi(v[3]) != 0;
+  auto num = [](const char *t) { return (size_t)std::strtoull(t, nullptr, 10); };
+  for (char **g = v + 5; g + 18 <= v + count; g += 18) {
+    int8_t spans[7];
+    for (int j = 0; j < 7; ++j) spans[j] = (int8_t)std::atoi(g[4 + j]);
+    const View in{ (uintptr_t)num(g[11]), num(g[12]), num(g[13]) }, out{ (uintptr_t)num(g[14]), num(g[15]), num(g[16]) };
+    const size_t bound = num(g[17]);
+    const MorphPlan P = plan_morphology(W, H, ctxC, pc, mb, in, out, std::atoi(g[0]), std::atoi(g[1]), std::atoi(g[2]), std::atoi(g[3]), spans, bound ? bound : HOUGH_SCRATCH_BYTES);
+    if (P.error) std::printf("refused: %s\n", P.error);
+    else std::printf("%zu %d %d\n", P.scratch_bytes, P.passes, P.frames_per_pass);
+  }
+  return 0;
+}
+
+int main(int argc, char **argv)
+{
+  if (argc >= 7 && (argc - 7) % 18 == 0 && !std::strcmp(argv[1], "plan")) return print_plans(argc - 2, argv + 2);
   counts_and_flags();
   levels();
   refusals();

@@ -1,22 +1,25 @@
 #!/usr/bin/env python3
 """Seeded CHAINS of device ops and runs on one context: the entries that are not runs (blur, derivatives, automatic thresholds,
-edge points, Hough lines, Hough segments, Hough circles, connected components) queued between and behind runs, with no synchronisation but the few the sequence
+edge points, Hough lines, Hough segments, Hough circles, connected components, morphology, distance transform) queued between and behind runs, with no synchronisation but the few the sequence
 itself names.  tests/fuzz_sequences.py does this for the runs alone; each entry has a GPU test file of its own for its shapes,
 capacities, views and refusals.  What neither reaches is the state the entries share on one context (cudacam_amd/csrc/
 device_ops.hip: the scratch buffers that grow and never shrink, the Hough and walk tables cached by geometry) and the one place
-where they meet the runs (finish_writers_of: which pipelined runs in flight a reader of edge maps completes first).
+where they meet the runs (finish_writers_of: which pipelined runs in flight a reader of edge maps completes first -- and a writer
+of a view the caller chooses: blur, the label plane, the morphed frames, the distance and the nearest plane).
 
 Three parts, the first two pure (numpy, the CPU oracle, the numpy restatements; no GPU, no clock):
   make_sequence(seed)   context parameters, 12 .. 20 steps (plain dicts; the synchronisation a stream switch needs, the step that
                         takes a threshold table off again and the final sync are among them), 1 .. 3 circles steps drawn from a
                         generator of their own and inserted among them (add_circles), 1 .. 3 components steps from a third
-                        generator inserted among those (add_components), and counters that say what the sequence exercises
+                        generator inserted among those (add_components), 1 .. 3 morph steps from a fourth (add_morphology) and
+                        1 .. 3 dist steps from a fifth (add_distance), and counters that say what the sequence exercises
   Model                 the expected content of EVERY byte of every device buffer the sequence owns, step after step: inputs in
                         arenas of 255s, edge maps with the padding of their pitch, counts between guard words, lists in slots
                         pre-filled with a canary.  A step reads its inputs from the model and writes its outputs back, so values
                         propagate (a run's maps -> points -> lines -> segments; points and gradient planes -> circles; maps ->
-                        labels, which a later reader of the same bytes takes for a map) and nothing is read from the device in
-                        between.
+                        labels, which a later reader of the same bytes takes for a map; maps -> morphed maps in another output ->
+                        whoever reads that output next; maps -> a distance plane over an output, read as a map likewise) and
+                        nothing is read from the device in between.
   Executor              queues the same steps through api.Context and, at every "sync" step and at the end, compares every buffer
                         with the model byte for byte -- results, canaries, guards and padding alike.
 The per-entry helpers of the GPU test files (_upload / _check) upload a map per call and check one call's buffers; here a buffer
@@ -47,12 +50,14 @@ import auto_thr_ref as AT          # noqa: E402
 import ccl_ref as CC               # noqa: E402
 import canny_o_ext_ref as X        # noqa: E402
 import deriv_ref as D              # noqa: E402
+import dist_ref as DR              # noqa: E402
 import edge_points_ref as EP       # noqa: E402
 import fuzz_sequences as FS        # noqa: E402
 import gauss_blur_ref as G         # noqa: E402
 import hough_circles_ref as HC     # noqa: E402
 import hough_ref as R              # noqa: E402
 import hough_segments_ref as S     # noqa: E402
+import morph_ref as MR             # noqa: E402
 import view_arena as VA            # noqa: E402
 from cudacam_amd import api  # noqa: E402
 
@@ -80,6 +85,14 @@ CIRCLES_DP, CIRCLES_MIN_DIST, CIRCLES_THRESHOLD, CIRCLES_CC = (1.0, 1.5, 2.0), (
 # Label planes of their own (lab0 / lab1) begin 4 * loff bytes into the arena, with lpad bytes behind each row and lgap between frames
 COMP_CAPS, COMP_CUTS = ("null", "zero", "one", "cut", "all"), (2, 3, 9)
 LAB_LEAD, LAB_OFFS, LAB_PADS, LAB_GAPS = 512, (0, 1, 2, 3), (0, 4, 20), (0, 8, 132)
+# ... nor the two newest.  add_morphology inserts `morph` steps behind the components, from a fourth generator: an output arena of
+# their own (mor0 / mor1) begins moff bytes into it, with mpad bytes behind each row and mgap between frames -- any alignment, so
+# pads and gaps that are no multiples of 4.  The elements: the three shapes at 3 / 5 / 7, and three that are asymmetric in y with an
+# empty row.  add_distance inserts `dist` steps behind those, from a fifth: planes of their own (dtp0 / dtp1) are laid out as label
+# planes are (LAB_*); side by side, the two ROIs of one plane lie 4 W + 4 * swords bytes apart
+MOR_LEAD, MOR_OFFS, MOR_PADS, MOR_GAPS = 512, (0, 1, 2, 3), (0, 1, 7), (0, 3, 129)
+MORPH_ASYM = ((1, 0, -1), (2, 1, 0, -1, 1), (-1, 0, 3, 1, 2, 0, 3))
+MORPH_DSTS, DIST_NEARS, DT_SIDE_WORDS = ("own", "maps", "sout", "blur"), ("none", "own", "side"), (0, 1, 3)
 VIEW_KINDS = ("whole", "frame", "roi", "before", "behind", "sout")
 COUNTERS = tuple(f"overlap_{k}" for k in ("whole", "frame", "roi", "sout", "before", "behind", "blur_in", "blur_out")) + (
     "adjacent", "hough_tables_equal_numangle", "seg_tables_equal_numangle", "scratch_growths", "n_above_max_batch", "hough_passes_above_one",
@@ -95,14 +108,31 @@ COUNTERS = tuple(f"overlap_{k}" for k in ("whole", "frame", "roi", "sout", "befo
     # overlaps bytes that an earlier step wrote as labels over an output and no write has covered since; calls that need a
     # larger table than every components call before them; calls of more than one pass
     "components_overlap_map", "components_labels_over_pending", "components_rows_cut", "components_capacity_0", "components_n_above_max_batch",
-    "components_of_label_bytes", "ccl_scratch_growths", "ccl_passes_above_one")
+    "components_of_label_bytes", "ccl_scratch_growths", "ccl_passes_above_one",
+    # morph steps: calls whose input / whose output overlapped the output of a run in flight; calls of 3-channel frames; of more
+    # frames than max_batch; whose input overlaps label bytes (as components_of_label_bytes); OPEN / CLOSE calls that need more
+    # scratch than every one before them / of more than one pass; calls whose output differs from their input; steps that read
+    # bytes a morph step wrote into `maps` or `sout` and no write has covered since
+    "morph_overlap_in", "morph_out_over_pending", "morph_three_channel", "morph_n_above_max_batch", "morph_of_label_bytes", "morph_scratch_growths",
+    "morph_passes_above_one", "morph_output_differs", "morph_read_by_a_later_step",
+    # dist steps: calls whose map view / whose distance plane overlapped the output of a run in flight; calls with the two planes
+    # side by side; FRAMES without a feature pixel; calls whose map overlaps bytes a morph step wrote; calls of more frames than
+    # max_batch; calls with a frame that has a feature pixel and another; steps that read, as a map, bytes a dist step wrote as a
+    # distance plane over an output and no write has covered since
+    "dist_overlap_map", "dist_plane_over_pending", "dist_side_by_side", "dist_without_features", "dist_of_morph_output", "dist_n_above_max_batch",
+    "dist_maps_mixed", "dist_plane_read_as_map")
 # ... of which the committed seeds together must reach every one but these four.  A view beside one output that lies inside its
 # neighbour is a "whole" or "frame" overlap of that neighbour under another name.  The table of a components call has a word per
 # chunk of 8 rows: at most 36 bytes per frame here, while a seeded context's bound, if it has one, is two frames of the largest
 # Hough geometry -- so no seeded call can take a second pass: test_components_in_passes_under_a_bound (tests/
 # test_gpu_device_op_sequences.py) covers that as a named case.  A table grows where a call of more frames follows one of fewer,
-# which five of the committed seeds happen to do; test_the_component_table_grows_while_a_call_is_queued is the case that must
-REQUIRED = tuple(c for c in COUNTERS if c not in ("overlap_before", "overlap_behind", "ccl_scratch_growths", "ccl_passes_above_one"))
+# which five of the committed seeds happen to do; test_the_component_table_grows_while_a_call_is_queued is the case that must.
+# The same holds for the intermediate frames of OPEN / CLOSE: one is W x H bytes (3 W x H of 3-channel frames, rows rounded up to 4:
+# at most 49,632 bytes here), the seeded bound several hundred KiB, so the twelve frames a seeded call can have fit into one pass:
+# test_morphology_in_passes_under_a_bound covers passes, test_the_morphology_scratch_grows_while_a_call_is_queued the growth that
+# seeds reach only where a call of more frames happens to follow one of fewer
+NOT_REQUIRED = ("overlap_before", "overlap_behind", "ccl_scratch_growths", "ccl_passes_above_one", "morph_scratch_growths", "morph_passes_above_one")
+REQUIRED = tuple(c for c in COUNTERS if c not in NOT_REQUIRED)
 # Output views that force the staged path (copy_dst), from the families of tests/test_gpu_views.py.  Of those only the odd one
 # stages an output (P4, GM and ROI are multiples of 4 throughout); the other two here are its P4 and ROI with the one thing made
 # odd that hc_run_device names beside the pitch: the base pointer alone, the frame stride alone.
@@ -117,8 +147,17 @@ STAGED_FAMILIES = ("ODDO", "P4_BASE", "ROI_FS")
 # included.  The 30 reach every components counter of REQUIRED (--scan: labels over a pending output in 3, 15 and 207, label bytes
 # read as a map in 15, 22 and 207, more than max_batch frames in 25, the others in a dozen each), so no seed was added for a
 # counter.  One was added for a view: in none of the 30 does a components step read the buffer a staged run copies to, the one map
-# view at an odd pitch; --scan 0 300 gave 229 (components of `sout` at every row's capacity, the labels over a pending output)
-SEEDS = (0, 1, 3, 5, 6, 7, 8, 9, 11, 13, 14, 15, 17, 21, 22, 25, 31, 35, 40, 49, 66, 69, 85, 86, 100, 141, 145, 207, 58, 108, 229)
+# view at an odd pitch; --scan 0 300 gave 229 (components of `sout` at every row's capacity, the labels over a pending output).
+# The morph and dist steps came after that, from a fourth and a fifth generator (add_morphology, add_distance), and left those 31
+# every step they had.  Every one of the 31 keeps what the CPU test demands of each sequence (segment, line and circle lists that
+# are not empty, a reader over a pending writer) and has a morph step that changes its input and a dist step on a map with feature
+# and other pixels, so none was replaced.  Together they reach every new counter of REQUIRED but one (--scan: a morph input over a
+# pending output in 6, a distance plane over one in 40 and 141, frames without a feature pixel in 69, 85 and 100, more than
+# max_batch frames in 0 and 25, morphed bytes read again in 10, a distance plane read as a map in 10): in none does a morph step
+# WRITE over the output of a run in flight, which takes a run directly in front of the step and a free region that is that
+# run's.  21 of --scan 0 300 do; 38 is the one among them with the smallest frames (61 x 33, three channels, mode O), and it also
+# lays a distance plane over a pending output
+SEEDS = (0, 1, 3, 5, 6, 7, 8, 9, 11, 13, 14, 15, 17, 21, 22, 25, 31, 35, 40, 49, 66, 69, 85, 86, 100, 141, 145, 207, 58, 108, 229, 38)
 
 
 def rup(v, m):
@@ -156,6 +195,11 @@ def layout(P):
     for k in range(2):
         L["sizes"][f"lab{k}"] = 2 * LAB_LEAD + 4 * LAB_OFFS[-1] + L["nmax"] * ((4 * w + LAB_PADS[-1]) * h + LAB_GAPS[-1])
         L["sizes"][f"comp{k}"] = L["cent_off"] + 16 * L["nmax"] * L["cmax"] + 4 * GUARD
+    # morphology: output arenas for nmax one-channel frames or max_batch frames of the context's channels, at the largest pad and
+    # gap behind the largest offset.  Distances: planes for nmax frames of two ROIs side by side, at the largest of everything
+    for k in range(2):
+        L["sizes"][f"mor{k}"] = 2 * MOR_LEAD + MOR_OFFS[-1] + max(L["nmax"] * ((w + MOR_PADS[-1]) * h + MOR_GAPS[-1]), L["mb"] * ((ch * w + MOR_PADS[-1]) * h + MOR_GAPS[-1]))
+        L["sizes"][f"dtp{k}"] = 2 * LAB_LEAD + 4 * LAB_OFFS[-1] + L["nmax"] * ((8 * w + 4 * DT_SIDE_WORDS[-1] + LAB_PADS[-1]) * h + LAB_GAPS[-1])
     L["counts_off"] = 4 * GUARD
     L["list_off"] = 4 * (2 * GUARD + NLIST)
     return L
@@ -208,6 +252,42 @@ def label_view(L, st):
     return f"lab{st['lslot']}", LAB_LEAD + 4 * st["loff"], pitch, pitch * L["h"] + st["lgap"]
 
 
+def morph_views(L, st):
+    """((buffer, offset, pitch, frame stride) of the input, the same of the output) of a morph step.  The input: a view of maps, or
+    3-channel frames of the pool from f0 on.  The output: an arena of its own, frames g0 .. of output region mslot of `maps`, of
+    `sout`, or -- 3-channel frames -- of the `blur` buffer."""
+    w, h = L["w"], L["h"]
+    a = ("frames", L["ilead"] + st["f0"] * L["ifs"], L["ip"], L["ifs"]) if st["src"] == "frames" else resolve_view(L, st["view"])[:4]
+    if st["dst"] == "own":
+        pitch = st["channels"] * w + st["mpad"]
+        return a, (f"mor{st['mslot']}", MOR_LEAD + st["moff"], pitch, pitch * h + st["mgap"])
+    if st["dst"] == "blur":
+        return a, ("blur", L["ilead"] + st["g0"] * L["ifs"], L["ip"], L["ifs"])
+    if st["dst"] == "sout":
+        return a, ("sout", L["soff"] + st["g0"] * L["sfs"], L["sp"], L["sfs"])
+    return a, ("maps", out_start(L, st["mslot"]) + st["g0"] * L["ofs"], L["op"], L["ofs"])
+
+
+def dist_views(L, st):
+    """((buffer, offset, pitch, frame stride) of the distance plane, the same of the nearest plane or None) of a dist step.  The
+    distance plane: in an arena of its own or -- one frame -- over output region dslot of `maps`, as label_view lays labels.  The
+    nearest plane: none, a view of an arena of its own, or the other ROI of the plane the distances lie in, side by side: equal
+    pitch and frame stride, 4 W + 4 * swords bytes to the right of the distances (nleft: to their left)."""
+    w, h = L["w"], L["h"]
+    if st["dest"] == "over":
+        d = ("maps", out_start(L, st["dslot"]), 4 * L["op"], 4 * L["ofs"])
+    else:
+        apart = 4 * w + 4 * st["swords"] if st["near"] == "side" else 0
+        pitch, base = 4 * w + apart + st["dpad"], LAB_LEAD + 4 * st["doff"]
+        d = (f"dtp{st['dslot']}", base + (apart if st["nleft"] else 0), pitch, pitch * h + st["dgap"])
+        if st["near"] == "side":
+            return d, (d[0], base + (0 if st["nleft"] else apart), d[2], d[3])
+    if st["near"] == "none":
+        return d, None
+    pitch = 4 * w + st["npad"]
+    return d, (f"dtp{st['nslot']}", LAB_LEAD + 4 * st["noff"], pitch, pitch * h + st["ngap"])
+
+
 def list_fits(kind, n, cap, width, L):
     """n slots of `cap` entries of `width` words lie inside a list buffer, behind its counts and before its last guard."""
     return n <= NLIST and L["list_off"] + 4 * width * cap * n <= L["sizes"][kind + "0"] - 4 * GUARD
@@ -243,6 +323,18 @@ def ccl_need(h, n, bound):
     rows = min(max((h * n + 8191) // 8192, 8), 64, h)
     per = 4 * ((h + rows - 1) // rows)
     fpp = min(n, (bound or (256 << 20)) // per, 65535)
+    return (fpp * per, (n + fpp - 1) // fpp, per) if fpp else (0, 0, per)
+
+
+def morph_need(w, h, channels, op, n, bound):
+    """(scratch bytes, passes, bytes per frame) of hc_morphology_device as include/hipcanny.h and plan_morphology (host_plan.h)
+    state them: OPEN and CLOSE keep the intermediate frames of a pass as tight frames whose rows of channels * W bytes are rounded
+    up to a multiple of 4; the other operations need none and take one pass under any bound.  (0, 0, bytes per frame) where one
+    frame exceeds the bound: the entry refuses that call."""
+    if op not in (MR.OPEN, MR.CLOSE):
+        return 0, 1, 0
+    per = rup(channels * w, 4) * h
+    fpp = min(n, (bound or (256 << 20)) // per)
     return (fpp * per, (n + fpp - 1) // fpp, per) if fpp else (0, 0, per)
 
 
@@ -296,8 +388,10 @@ class Model:
         self.table = False
         self.pending = []          # pipelined runs in flight: (buffer, lo, hi, staged)
         self.hough_key = self.seg_key = None
-        self.hough_bytes = self.seg_bytes = self.circle_bytes = self.ccl_bytes = 0
+        self.hough_bytes = self.seg_bytes = self.circle_bytes = self.ccl_bytes = self.morph_bytes = 0
         self.label_spans = []      # (buffer, lo, hi) that components steps wrote as labels over outputs and no later write has covered
+        self.morph_spans = []      # ... that morph steps wrote into `maps` or `sout`
+        self.dist_spans = []       # ... that dist steps wrote as distance planes over outputs
         self.deriv_n = None        # frames the last deriv step wrote (None: the planes still hold the arena's fill)
         self.lines_queued = False  # a lines step since the last sync ...
         self.circles_open = 0      # ... and the circles steps behind it that no lines step has followed yet
@@ -319,7 +413,8 @@ class Model:
         if log:
             hi = off + (n - 1) * fs + (rows - 1) * pitch + rb
             self.writes.append((self.step, name, off, hi))
-            self.label_spans = [s for s in self.label_spans if not (s[0] == name and off <= s[1] and s[2] <= hi)]   # (a counter's bookkeeping, by byte range)
+            for spans in (self.label_spans, self.morph_spans, self.dist_spans):   # (the counters' bookkeeping, by byte range)
+                spans[:] = [s for s in spans if not (s[0] == name and off <= s[1] and s[2] <= hi)]
 
     def put_words(self, name, off, words):
         b = np.ascontiguousarray(words).view(np.uint8).reshape(-1)
@@ -343,6 +438,15 @@ class Model:
             self._finish(hit)
         elif any(p[0] == name and (p[1] == hi or p[2] == lo) for p in self.pending):
             self.counters["adjacent"] += 1
+
+    @staticmethod
+    def _touches(spans, name, lo, hi):
+        return any(b == name and s0 < hi and lo < s1 for b, s0, s1 in spans)
+
+    def _reads(self, name, lo, hi):
+        """Books a read of [lo, hi) of a buffer for the two counters of propagation."""
+        self.counters["morph_read_by_a_later_step"] += self._touches(self.morph_spans, name, lo, hi)
+        self.counters["dist_plane_read_as_map"] += self._touches(self.dist_spans, name, lo, hi)
 
     def _run_output(self, out, maps):
         """Writes a run's maps into output `out` (0 .. NOUT - 1 in place, "sout" staged) and books the run as in flight: with
@@ -425,7 +529,8 @@ class Model:
         (a, aoff, ap, afs), (b, boff, bp, bfs) = self.blur_views(st)
         rb, n = self.w * self.ch, st["n"]
         self._reader(a, *view_span(self.L, aoff, ap, afs, n, rb), "blur_in")
-        span = view_span(self.L, boff, bp, bfs, n, rb)
+        self._reads(a, *view_span(self.L, aoff, ap, afs, n, rb))
+        span =view_span(self.L, boff, bp, bfs, n, rb)
         self.counters["blur_into_pending_copy_dst"] += any(p[3] for p in self._overlapping(b, *span))
         self._reader(b, *span, "blur_out")
         src = self.get(a, aoff, ap, afs, n, rb).reshape((n, self.h, self.w) + ((3,) if self.ch == 3 else ()))
@@ -459,6 +564,7 @@ class Model:
     def _maps(self, st):
         name, off, pitch, fs, _ = resolve_view(self.L, st["view"])
         self._reader(name, *view_span(self.L, off, pitch, fs, st["n"], self.w), st["view"][0])
+        self._reads(name, *view_span(self.L, off, pitch, fs, st["n"], self.w))
         if st["n"] > MAX_BATCH:
             self.counters["n_above_max_batch"] += 1
         return self.get(name, off, pitch, fs, st["n"], self.w)
@@ -583,6 +689,63 @@ class Model:
             if cap and len(stats[f]):   # (rows: the pointers are null only with capacity 0)
                 self.put_words(out, L["stats_off"] + 20 * cap * f, stats[f])
                 self.put_words(out, L["cent_off"] + 16 * cap * f, cents[f])
+
+    def do_morph(self, st):
+        """hc_morphology_device on a one-channel view of maps (whatever bytes it holds, as do_components) or on 3-channel frames of
+        the pool, into a view the step names.  The entry completes the runs in flight that write either view (as do_blur books
+        them) and writes exactly [row, row + channels * W) of each output row.  Morphed bytes in `maps` or `sout` are what later
+        steps read there."""
+        L, n, cn, c = self.L, st["n"], st["channels"], self.counters
+        (a, aoff, ap, afs), (b, boff, bp, bfs) = morph_views(L, st)
+        rb = cn * self.w
+        ispan, ospan = view_span(L, aoff, ap, afs, n, rb), view_span(L, boff, bp, bfs, n, rb)
+        assert a != b or ispan[1] <= ospan[0] or ospan[1] <= ispan[0], f"the output of {describe(st)} overlaps its input: the entry refuses it"
+        c["morph_overlap_in"] += bool(self._overlapping(a, *ispan))
+        c["morph_of_label_bytes"] += self._touches(self.label_spans, a, *ispan)
+        if st["src"] == "frames":
+            src = self._frames("frames", st["f0"], n)
+        else:
+            src = self._maps(st)
+        self._reader(b, *ospan, "morph_out", counter="morph_out_over_pending")
+        c["morph_three_channel"] += cn == 3
+        c["morph_n_above_max_batch"] += n > MAX_BATCH
+        need, passes, _ = morph_need(self.w, self.h, cn, st["op"], n, self.P["hough_bound"])
+        assert passes, f"one intermediate frame of {describe(st)} exceeds the scratch bound: the entry refuses it"
+        c["morph_scratch_growths"] += 0 < self.morph_bytes < need
+        self.morph_bytes = max(self.morph_bytes, need)
+        c["morph_passes_above_one"] += passes > 1
+        out = MR.morph(src, st["op"], list(st["spans"]), cn)
+        c["morph_output_differs"] += not np.array_equal(out, src)
+        self.put(b, boff, bp, bfs, out.reshape(n, self.h, rb))
+        if b in ("maps", "sout"):
+            self.morph_spans.append((b,) + ospan)
+
+    def do_dist(self, st):
+        """hc_distance_transform_device on a view of maps -- whatever bytes it holds -- into a distance plane (squared int32, or the
+        float32 root) and, where the step has one, a nearest plane.  The entry completes the runs in flight that write any of the
+        three views and writes exactly [row, row + 4 W) of each row of either plane: side by side in one plane, the words between
+        and around the two ROIs stay what they were.  A frame without a feature pixel gives HC_DT_NONE / +inf and -1."""
+        L, n, c = self.L, st["n"], self.counters
+        name, off, pitch, fs, _ = resolve_view(L, st["view"])
+        mspan = view_span(L, off, pitch, fs, n, self.w)
+        c["dist_overlap_map"] += bool(self._overlapping(name, *mspan))
+        c["dist_of_morph_output"] += self._touches(self.morph_spans, name, *mspan)
+        maps = self._maps(st)
+        c["dist_n_above_max_batch"] += n > MAX_BATCH
+        (dn, doff, dpitch, dfs), near = dist_views(L, st)
+        dspan = view_span(L, doff, dpitch, dfs, n, 4 * self.w)
+        assert dn != name or dspan[1] <= mspan[0] or mspan[1] <= dspan[0], f"the distance plane of {describe(st)} overlaps its map: the entry refuses it"
+        self._reader(dn, *dspan, "dist", counter="dist_plane_over_pending")
+        c["dist_side_by_side"] += st["near"] == "side"
+        feat = DR.features(maps, st["target"])
+        c["dist_without_features"] += sum(not f.any() for f in feat)
+        c["dist_maps_mixed"] += any(f.any() and not f.all() for f in feat)
+        d2, nearest = DR.distance_transform(maps, st["target"], DR.vectorised)
+        self.put(dn, doff, dpitch, dfs, DR.root_f32(d2) if st["dtype"] == api.DT_F32 else d2)
+        if near is not None:
+            self.put(*near, nearest)
+        if st["dest"] == "over":
+            self.dist_spans.append((dn,) + dspan)
 
 
 def run_model(P, steps, O=None):
@@ -788,6 +951,9 @@ def written_before(P, steps):
             written[st["out"]] = st["n"]
         elif st["kind"] == "blur" and st["dst"] != "blur":
             written[st["dst"]] = max(written.get(st["dst"], 0), st["g0"] + st["n"])
+        elif st["kind"] == "morph" and st["dst"] in ("maps", "sout"):   # (only add_distance meets these)
+            out = st["mslot"] if st["dst"] == "maps" else "sout"
+            written[out] = max(written.get(out, 0), st["g0"] + st["n"])
     return written
 
 
@@ -818,6 +984,89 @@ def add_components(P, steps, rng):
     return steps
 
 
+def draw_element(rng):
+    """ksize half-widths: one of the three shapes at 3, 5 or 7 -- or, one time in four, an element asymmetric in y with an empty row."""
+    if rng.random() < 0.25:
+        return list(MORPH_ASYM[int(rng.integers(0, len(MORPH_ASYM)))])
+    return [int(v) for v in MR.structuring_spans(int(rng.choice(MR.SHAPES)), int(rng.choice(MR.KSIZES)))]
+
+
+def draw_map_view(rng, L, written, first):
+    """draw_view; the first step a generator inserts takes no view beside an output (those mostly hold one value throughout)."""
+    view, n = draw_view(rng, L, written, L["nmax"])
+    while first and view[0] in ("before", "behind"):
+        view, n = draw_view(rng, L, written, L["nmax"])
+    return view, n
+
+
+def add_morphology(P, steps, rng):
+    """Inserts 1 .. 3 morph steps into `steps`, by the rules of add_components: behind the opening's points step, before the final
+    sync, never directly in front of a stream step, every draw from `rng`, a generator of the morphology's own.  A step reads a
+    one-channel view as a points step draws it (all six kinds, up to nmax frames) -- or, on a 3-channel context, sometimes 3-channel
+    frames of the pool -- and writes an arena of its own at any alignment, or frames g0 .. of ANOTHER output region of `maps` or of
+    `sout` that its input does not touch (for 3-channel frames: of the `blur` buffer): there the entry completes a run for the
+    view it writes, and what later steps read from that region are the morphed bytes."""
+    L = layout(P)
+    w, ch = P["w"], P["ch"]
+    steps = list(steps)
+    first = next(i for i, st in enumerate(steps) if st["kind"] == "points")
+    for j in range(int(rng.integers(1, 4))):
+        at = int(rng.choice([i for i in range(first + 1, len(steps)) if steps[i]["kind"] != "stream"]))   # the step goes in front of steps[at]
+        st = dict(kind="morph", src="view", view=None, f0=0, n=1, channels=1, op=int(rng.choice(MR.OPS)), spans=draw_element(rng), dst="own", mslot=int(rng.integers(0, 2)),
+                  moff=int(rng.choice(MOR_OFFS)), mpad=int(rng.choice(MOR_PADS)), mgap=int(rng.choice(MOR_GAPS)), g0=0)
+        c, elsewhere = rng.random(), dict(moff=0, mpad=0, mgap=0)
+        if ch == 3 and rng.random() < 0.4:
+            n = int(rng.integers(1, MAX_BATCH + 1))
+            st.update(src="frames", channels=3, n=n, f0=int(rng.integers(0, POOL - n + 1)))
+            if c < 0.4:
+                st.update(elsewhere, dst="blur", mslot=0, g0=int(rng.integers(0, POOL - n + 1)))
+        else:
+            view, n = draw_map_view(rng, L, written_before(P, steps[:at]), j == 0)
+            st.update(view=view, n=n)
+            name, off, pitch, fs, _ = resolve_view(L, view)
+            lo, hi = view_span(L, off, pitch, fs, n, w)
+            g0, k0 = int(rng.integers(0, L["nmax"] - n + 1)) if rng.random() < 0.5 else 0, int(rng.integers(0, NOUT))
+            # frames g0 .. g0 + n of the first region from k0 on (cyclically) that the input stays clear of
+            free = [k for k in ((k0 + i) % NOUT for i in range(NOUT)) if name != "maps" or hi <= out_start(L, k) + g0 * L["ofs"] or out_start(L, k) + (g0 + n) * L["ofs"] <= lo]
+            if c >= 0.85 and name != "sout":
+                st.update(elsewhere, dst="sout", mslot=0, g0=g0)
+            elif c >= 0.4 and free:
+                st.update(elsewhere, dst="maps", mslot=free[0], g0=g0)
+        steps.insert(at, st)
+    return steps
+
+
+def add_distance(P, steps, rng):
+    """Inserts 1 .. 3 dist steps into `steps`, by the same rules, every draw from `rng`, a generator of the distances' own.  A step
+    reads a view as a points step draws it and writes its distances into an arena of their own -- or, one frame of them, OVER an
+    output region of `maps` that its map view does not touch, exactly as a components step lays its labels.  The nearest plane:
+    none, a view of the other arena, or -- with the distances in an arena -- the second ROI of the same plane, side by side."""
+    L = layout(P)
+    w = P["w"]
+    steps = list(steps)
+    first = next(i for i, st in enumerate(steps) if st["kind"] == "points")
+    for j in range(int(rng.integers(1, 4))):
+        at = int(rng.choice([i for i in range(first + 1, len(steps)) if steps[i]["kind"] != "stream"]))   # the step goes in front of steps[at]
+        view, n = draw_map_view(rng, L, written_before(P, steps[:at]), j == 0)
+        st = dict(kind="dist", view=view, n=n, target=int(rng.integers(0, 2)), dtype=int(rng.integers(0, 2)), dest="own", dslot=int(rng.integers(0, 2)), doff=int(rng.choice(LAB_OFFS)),
+                  dpad=int(rng.choice(LAB_PADS)), dgap=int(rng.choice(LAB_GAPS)), near=DIST_NEARS[int(rng.integers(0, len(DIST_NEARS)))], nslot=int(rng.integers(0, 2)),
+                  noff=int(rng.choice(LAB_OFFS)), npad=int(rng.choice(LAB_PADS)), ngap=int(rng.choice(LAB_GAPS)), swords=int(rng.choice(DT_SIDE_WORDS)), nleft=bool(rng.random() < 0.3))
+        over, k0 = rng.random() < 0.4, int(rng.integers(0, NOUT))
+        if over:   # one frame, over the first region from k0 on (cyclically) that the map view stays clear of: it touches two at most
+            name, off, pitch, fs, _ = resolve_view(L, view)
+            lo, hi = view_span(L, off, pitch, fs, 1, w)
+            free = [k for k in ((k0 + i) % NOUT for i in range(NOUT)) if name != "maps" or hi <= out_start(L, k) or out_start(L, k) + 4 * L["ofs"] <= lo]
+            st.update(n=1, dest="over", dslot=free[0], doff=0, dpad=4 * (L["op"] - w), dgap=0, near="own" if st["near"] == "side" else st["near"])
+        elif st["near"] == "own":
+            st["nslot"] = 1 - st["dslot"]   # two planes of their own: one arena each
+        if st["near"] != "side":
+            st.update(swords=0, nleft=False)
+        if st["near"] != "own":
+            st.update(nslot=0, noff=0, npad=0, ngap=0)
+        steps.insert(at, st)
+    return steps
+
+
 def base_sequence(seed):
     """(context parameters, steps) of a seed as make_steps draws them from numpy.random.default_rng(seed): no circles step."""
     rng = np.random.default_rng(seed)
@@ -828,10 +1077,13 @@ def base_sequence(seed):
 def make_sequence(seed, O=None):
     """(context parameters, steps, counters) of a seed: the steps of numpy.random.default_rng(seed), the circles steps of
     numpy.random.default_rng([seed, 1]) inserted among them, the components steps of numpy.random.default_rng([seed, 2]) inserted
-    among those, and the host model; nothing else."""
+    among those, the morph steps of default_rng([seed, 3]) among those, the dist steps of default_rng([seed, 4]) among those, and
+    the host model; nothing else."""
     P, steps = base_sequence(seed)
     steps = add_circles(P, steps, np.random.default_rng([seed, 1]))
     steps = add_components(P, steps, np.random.default_rng([seed, 2]))
+    steps = add_morphology(P, steps, np.random.default_rng([seed, 3]))
+    steps = add_distance(P, steps, np.random.default_rng([seed, 4]))
     return P, steps, dict(run_model(P, steps, O).counters)
 
 
@@ -934,6 +1186,13 @@ class Executor:
             o, (lname, loff, lpitch, lfs) = f"comp{st['cslot']}", label_view(L, st)
             ctx.connected_components_device(*self._view(st["view"]), st["n"], st["conn"], self.ptr[lname] + loff, lpitch, lfs, self._counts(o),
                                             self.ptr[o] + L["stats_off"] if st["rows"] else None, self.ptr[o] + L["cent_off"] if st["rows"] else None, st["cap"])
+        elif k == "morph":
+            (a, aoff, ap, afs), (b, boff, bp, bfs) = morph_views(L, st)
+            ctx.morphology_device(self.ptr[a] + aoff, ap, afs, self.ptr[b] + boff, bp, bfs, st["n"], st["channels"], st["op"], len(st["spans"]), st["spans"])
+        elif k == "dist":
+            (dn, doff, dpitch, dfs), near = dist_views(L, st)
+            nn, noff, npitch, nfs = near or (dn, 0, 0, 0)
+            ctx.distance_transform_device(*self._view(st["view"]), st["n"], st["target"], st["dtype"], self.ptr[dn] + doff, dpitch, dfs, self.ptr[nn] + noff if near else None, npitch, nfs)
         elif k == "sync":
             self.check()
         elif k == "stream":
@@ -992,7 +1251,7 @@ def main(argv):
         for seed in range(int(argv[2]), int(argv[3])):
             P, steps, c = make_sequence(seed, O)
             print(seed, f"{P['w']}x{P['h']} ch{P['ch']} {P['mode']} pc{int(P['per_channel'])} piped{int(P['pipeline'])} bound{int(bool(P['hough_bound']))} {P['staged']}",
-                  f"{len(steps)} steps, {sum(st['kind'] == 'circles' for st in steps)} of them circles, {sum(st['kind'] == 'components' for st in steps)} components",
+                  f"{len(steps)} steps, " + ", ".join(f"{sum(st['kind'] == k for st in steps)} {k}" for k in ("circles", "components", "morph", "dist")),
                   " ".join(f"{k}={v}" for k, v in c.items() if v), flush=True)
         return 0
     if len(argv) > 2 and argv[1] == "--seed":

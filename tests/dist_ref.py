@@ -2,7 +2,7 @@
 every pixel to the nearest feature pixel, its float32 root, and the index y' * W + x' of that pixel, ties to the smallest x', then
 the smallest y'.
 
-Two independent forms:
+Two independent forms, and a third, `vectorised`, as exact as they are and fast on dense maps (tests/device_op_sequences.py):
 
 * brute_force: all feature pixels sorted by (x', y'), the squared distances of a chunk of pixels to every one of them, argmin
   (numpy's takes the first minimum: the smallest (x', y') in that order).  Nothing of the kernels' structure is in it.
@@ -89,6 +89,39 @@ def separable(m, target=TO_NONZERO):
     return d2, near
 
 
+def vectorised(m, target=TO_NONZERO, budget=1 << 22):
+    """The same pair, exactly, in O(H W^2) numpy: per column the nearest feature pixel of every row (a tie to the one above, the
+    smaller y'), then per pixel the minimum over all columns x' of (x - x')^2 + dy(y, x')^2, argmin taking the first, the smallest
+    x'.  The nearest feature pixel overall lies in some column, and there it is that column's nearest: nothing is approximated.
+    For the dense maps of the seeded chains, where brute_force is quadratic in the pixels; tests/test_dist_ref_cpu.py holds the
+    two equal.  `budget`: pixel x column pairs held at a time."""
+    feat = features(m, target)
+    h, w = feat.shape
+    if not feat.any():
+        return np.full((h, w), NONE, np.int32), np.full((h, w), -1, np.int32)
+    assert (w - 1) ** 2 + (h - 1) ** 2 < NONE and w * h < NONE
+    far = 1 << 20                                         # (rows apart: above every H the squared diagonal admits)
+    ys = np.arange(h, dtype=np.int64)[:, None]
+    up = np.maximum.accumulate(np.where(feat, ys, -far), axis=0)                  # the last feature row at or above y
+    down = np.minimum.accumulate(np.where(feat, ys, 2 * far)[::-1], axis=0)[::-1]   # the first at or below
+    above = ys - up <= down - ys
+    ny = np.where(above, up, down)                        # (a column without a feature pixel: -far, dy^2 beyond every distance)
+    dy2 = (ny - ys) ** 2
+    xs = np.arange(w, dtype=np.int64)
+    dx2 = (xs[:, None] - xs[None, :]) ** 2                # [x, x']
+    d2 = np.empty((h, w), np.int32)
+    near = np.empty((h, w), np.int32)
+    step = max(1, budget // (w * w))
+    for y0 in range(0, h, step):
+        y1 = min(y0 + step, h)
+        cost = dx2[None, :, :] + dy2[y0:y1, None, :]      # [y, x, x']
+        k = np.argmin(cost, axis=2)
+        rows = np.arange(y0, y1)[:, None]
+        d2[y0:y1] = np.take_along_axis(cost, k[:, :, None], axis=2)[:, :, 0]
+        near[y0:y1] = ny[rows, k] * w + k
+    return d2, near
+
+
 def root_f32(d2):
     """HC_DT_F32 of squared distances: int32 -> float32 (round to nearest even), then the correctly rounded float32 square root;
     +inf where d2 == NONE."""
@@ -96,7 +129,7 @@ def root_f32(d2):
     return np.where(d2 == NONE, np.float32(np.inf), np.sqrt(d2.astype(np.float32))).astype(np.float32)
 
 
-def distance_transform(maps, target=TO_NONZERO):
-    """(d2 int32 [n, H, W], nearest int32 [n, H, W]) of a batch, frame by frame, by brute force."""
-    pairs = [brute_force(m, target) for m in maps]
+def distance_transform(maps, target=TO_NONZERO, form=brute_force):
+    """(d2 int32 [n, H, W], nearest int32 [n, H, W]) of a batch, frame by frame, by brute force (or form=vectorised)."""
+    pairs = [form(m, target) for m in maps]
     return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])

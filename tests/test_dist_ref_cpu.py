@@ -21,8 +21,9 @@ ARGS = (None, 16, 64, 64 * 48, 1, 0, 0, 4096, 256, 256 * 48, 8192, 256, 256 * 48
 
 
 def _both(m, target=R.TO_NONZERO):
-    a, b = R.brute_force(m, target), R.separable(m, target)
+    a, b, c = R.brute_force(m, target), R.separable(m, target), R.vectorised(m, target)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    assert np.array_equal(a[0], c[0]) and np.array_equal(a[1], c[1]) and c[0].dtype == c[1].dtype == np.int32
     return a
 
 

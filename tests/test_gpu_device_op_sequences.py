@@ -77,6 +77,43 @@ def _component_counts(model, cslot, n):
     return model.words(f"comp{cslot}", model.L["counts_off"], n, np.uint32).tolist()
 
 
+RECT3 = (1, 1, 1)
+
+
+def _morph(view, n, op=DS.MR.CLOSE, spans=RECT3, into=None, g0=0, mslot=0, moff=1, mpad=1, mgap=3, frames=None):
+    """A morph step of a one-channel view (frames=f0: of 3-channel frames of the pool from f0 on) into arena mslot at an odd
+    offset, pitch and frame stride -- or, with into=k, into frames g0 .. of output region k; into="sout" / "blur": of that buffer."""
+    st = dict(kind="morph", src="view", view=view, f0=0, n=n, channels=1, op=op, spans=list(spans), dst="own", mslot=mslot, moff=moff, mpad=mpad, mgap=mgap, g0=0)
+    if frames is not None:
+        st.update(src="frames", view=None, f0=frames, channels=3)
+    if into is not None:
+        st.update(dst=into if isinstance(into, str) else "maps", mslot=0 if isinstance(into, str) else into, moff=0, mpad=0, mgap=0, g0=g0)
+    return st
+
+
+def _dist(view, n, P, target=api.DT_TO_NONZERO, dtype=api.DT_F32, over=None, dslot=0, near="none", swords=1, nleft=False, doff=1, dpad=4, dgap=8):
+    """A dist step with the distance plane in arena dslot (padded rows, a gap between frames, 4 * doff bytes in) -- or, with over=k,
+    one frame of it laid over output region k.  near: "none", "own" (the other arena, or with over=k arena dslot) or "side" (the
+    second ROI of the distances' plane, 4 W + 4 * swords bytes to their right; nleft: to their left)."""
+    own = near == "own"
+    st = dict(kind="dist", view=view, n=n, target=target, dtype=dtype, dest="own", dslot=dslot, doff=doff, dpad=dpad, dgap=dgap, near=near, nslot=1 - dslot if own else 0,
+              noff=2 if own else 0, npad=20 if own else 0, ngap=132 if own else 0, swords=swords if near == "side" else 0, nleft=nleft and near == "side")
+    if over is not None:
+        assert n == 1 and near != "side"
+        st.update(dest="over", dslot=over, doff=0, dpad=4 * (DS.layout(P)["op"] - P["w"]), dgap=0, nslot=dslot if own else 0)
+    return st
+
+
+def _region(model, k, n):
+    """The first n frames of output region k as the model holds them: (n, H, W) bytes."""
+    L = model.L
+    return model.get("maps", DS.out_start(L, k), L["op"], L["ofs"], n, model.w)
+
+
+def _point_counts(model, slot, n):
+    return model.words(f"pts{slot}", model.L["counts_off"], n, np.uint32).tolist()
+
+
 def _blur(src, f0, dst, g0, n):
     return dict(kind="blur", src=src, f0=f0, dst=dst, g0=g0, n=n, ksize=5, sigma=1.2, border=0)
 
@@ -149,10 +186,10 @@ def test_equal_numangle_other_tables(oracle, other):
     assert not np.array_equal(model.buf["lines0"], model.buf["lines1"]), "A and B give the same lines for this input"
 
 
-def _refused(call, entry):
+def _refused(call, entry, text="nframes out of range"):
     with pytest.raises(api.HipCannyError, match="error -1") as err:
         call()
-    assert entry in str(err.value) and "nframes out of range" in str(err.value), err.value
+    assert entry in str(err.value) and text in str(err.value), err.value
 
 
 def test_three_channels_and_per_channel(oracle):
@@ -442,3 +479,200 @@ def test_components_across_a_stream_switch(oracle):
     model = DS.execute(P, steps, oracle, "components across a stream switch")
     c = model.counters
     assert c["ccl_scratch_growths"] == 1 and c["components_overlap_map"] == 1 and c["components_rows_cut"] == 1 and min(_component_counts(model, 1, 4)) > 2, c
+
+
+# ---- morphology and distances in company: hc_morphology_device and hc_distance_transform_device read edge maps AND write views the
+# caller chooses, so each completes the runs in flight under all of its views; OPEN / CLOSE keep their intermediate frames in the
+# fourth scratch under the context's one bound; the distance transform keeps its intermediate values in the caller's own plane.
+# tests/test_gpu_morphology.py and tests/test_gpu_distance_transform.py have the kernels, call by call.
+def test_morphology_and_distances_over_pending_outputs(oracle):
+    """Three pipelined runs into the three outputs whose content needs the host continuation; then, with no synchronisation, CLOSE
+    of output 0 INTO output 1, the distances of frame 1 of output 1 with the plane laid OVER output 2 (the nearest plane in an
+    arena), and the points of outputs 1 and 2.  Each entry must continue the run under the view it writes before its kernels write
+    there: continued later (by the points calls, or at the sync), the run rewrites its whole maps over the result."""
+    P = _params()
+    with DS.Executor(P, oracle, "morphology and distances over pending outputs") as e:
+        for st in (_run(0, 0), _run(0, 1), _run(0, 2)):
+            e.queue(st)
+        runs = [_region(e.model, k, 4).copy() for k in range(3)]
+        e.queue(_morph(("whole", 0), 4, into=1))
+        c = e.model.counters
+        assert c["morph_overlap_in"] == 1 and c["morph_out_over_pending"] == 1 and len(e.model.pending) == 1, c
+        e.queue(_dist(("frame", 1, 1), 1, P, over=2, near="own"))
+        assert c["dist_plane_over_pending"] == 1 and c["dist_overlap_map"] == 0 and c["dist_of_morph_output"] == 1 and not e.model.pending, c
+        for st in (_points(("whole", 1), 4, slot=0, P=P), _points(("whole", 2), 4, slot=1, P=P)):
+            e.queue(st)
+        assert c["morph_read_by_a_later_step"] == 2 and c["dist_plane_read_as_map"] == 1 and c["overlap_whole"] == 1, c   # (the one: the CLOSE, of output 0)
+        e.check()
+        assert e.continued_runs() == 3
+        closed = DS.MR.morph(runs[0], DS.MR.CLOSE, list(RECT3))
+        plane = DS.DR.root_f32(DS.DR.brute_force(closed[1])[0])   # one frame of float32 over the region's four frames of bytes
+        a, L = DS.out_start(e.L, 2), e.L
+        over = np.full(4 * L["ofs"], 255, np.uint8).reshape(4, P["h"], L["op"])   # the region as run 2 left it inside its padding ...
+        over[:, :, :P["w"]] = runs[2]
+        over.reshape(P["h"], -1)[:, :4 * P["w"]] = plane.view(np.uint8)          # ... and the plane's rows, 4 W bytes at four times the pitch
+        assert np.array_equal(over.reshape(-1), e.model.buf["maps"][a:a + 4 * L["ofs"]])
+        want = [[int(np.count_nonzero(m)) for m in closed], [int(np.count_nonzero(f[:, :P["w"]])) for f in over]]
+        assert [_point_counts(e.model, 0, 4), _point_counts(e.model, 1, 4)] == want, want
+        for k, counts in ((1, want[0]), (2, want[1])):   # a run continued after the entry wrote would leave its own maps, with other counts
+            assert [int(np.count_nonzero(m)) for m in runs[k]] != counts, k
+
+
+def test_morphology_and_distances_leave_other_runs_in_flight(oracle):
+    """Three pipelined runs into the three outputs, then the GRADIENT of the LAST frame of output 1 into an arena and the distances
+    of an ROI of output 1: run 1 is completed, its neighbours are not -- read off the device as test_the_neighbour_stays_in_flight
+    reads it."""
+    import torch
+    P = _params()
+    L = DS.layout(P)
+    with DS.Executor(P, oracle, "morphology and distances behind runs in flight") as e:
+        for st in (_run(0, 0), _run(0, 1), _run(0, 2), _morph(("frame", 1, 3), 1, op=DS.MR.GRADIENT, spans=DS.MORPH_ASYM[1]), _dist(("roi", 1, 0, 3, 1, 1), 1, P, near="side")):
+            e.queue(st)
+        c = e.model.counters
+        assert c["morph_overlap_in"] == 1 and c["overlap_frame"] == 1 and c["morph_out_over_pending"] == 0 and c["dist_overlap_map"] == 0 and c["dist_plane_over_pending"] == 0, c
+        assert len(e.model.pending) == 2
+        torch.cuda.synchronize()   # the device, not the context: no run is completed by this
+        got, want = e.d["maps"].cpu().numpy(), e.model.buf["maps"]
+        for k in (0, 2):
+            a = DS.out_start(L, k)
+            assert not np.array_equal(got[a:a + L["oreg"]], want[a:a + L["oreg"]]), f"output {k} already holds its final maps: one of the calls completed its run, or its content needs no continuation"
+        a = DS.out_start(L, 1)
+        assert np.array_equal(got[a:a + L["oreg"]], want[a:a + L["oreg"]]), "output 1 does not hold its final maps behind the calls that read it"
+        e.check()
+        assert e.continued_runs() == 3 and c["morph_output_differs"] == 1 and c["dist_maps_mixed"] == 1, c
+
+
+def test_morphology_in_passes_under_a_bound(oracle):
+    """An intermediate frame of 130 x 67 is 132 x 67 = 8844 bytes.  OPEN and CLOSE of four maps under bounds of one, two and four
+    such frames and a few bytes (four, two and one pass) give the same bytes; then, with the default bound again, lines, circles,
+    components, CLOSE and lines follow one another with no synchronisation -- four buffers under one bound.  A bound one byte below
+    a frame is refused, and the refused call writes nothing."""
+    P = _params(pipeline=False)
+    per = DS.morph_need(P["w"], P["h"], 1, DS.MR.OPEN, 4, 0)[2]
+    assert per == 8844 and [DS.morph_need(P["w"], P["h"], 1, DS.MR.CLOSE, 4, b)[1] for b in (per + 3, 2 * per + 3, 4 * per + 3, 0, per - 1)] == [4, 2, 1, 1, 0]
+    bound = lambda v: dict(kind="option", option=api.OPT_TEST_HOUGH_SCRATCH, value=v)
+    open4, close4 = _morph(("whole", 0), 4, op=DS.MR.OPEN, spans=DS.MORPH_ASYM[0], mslot=0), _morph(("whole", 0), 4, op=DS.MR.CLOSE, spans=DS.MR.structuring_spans(DS.MR.ELLIPSE, 5), mslot=1)
+    with DS.Executor(P, oracle, "morphology in passes") as e:
+        e.queue(_run(0, 0))
+        seen = []
+        for b in (per + 3, 2 * per + 3, 4 * per + 3):
+            for st in (bound(b), open4, close4):
+                e.queue(st)
+            e.check()
+            seen.append({k: e.d[k].cpu().numpy() for k in ("mor0", "mor1")})   # (equal to the model's: the check has passed)
+            for k in ("mor0", "mor1"):   # ... and the next bound starts from the arena's fill
+                e.model.buf[k][:] = 255
+                e.d[k].fill_(255)
+            e.torch.cuda.synchronize()
+        assert e.model.counters["morph_passes_above_one"] == 4 and e.model.counters["morph_output_differs"] == 6, e.model.counters
+        assert all(np.array_equal(seen[0][k], s[k]) for s in seen[1:] for k in ("mor0", "mor1")), "the passes give other bytes than one pass"
+        assert not np.array_equal(seen[0]["mor0"], seen[0]["mor1"]) and (seen[0]["mor0"] != 255).any()
+        for st in (bound(0), _points(("whole", 0), 4, P=P), _deriv(4), _lines(4, 3, 0, DS.LCAP_MAX, P), _circles(4, P, cc=300), _components(("whole", 0), 4, P), close4, _lines(4, 0, 1, 64, P)):
+            e.queue(st)
+        e.check()
+        assert np.array_equal(e.model.buf["mor1"], seen[0]["mor1"]) and e.model.counters["circle_lists_nonempty"] == 4 and e.model.counters["line_lists_nonempty"] == 8, e.model.counters
+        e.queue(bound(per - 1))
+        (a, aoff, ap, afs), (b, boff, bp, bfs) = DS.morph_views(e.L, open4)
+        for op in (DS.MR.OPEN, DS.MR.CLOSE):
+            _refused(lambda: e.ctx.morphology_device(e.ptr[a] + aoff, ap, afs, e.ptr[b] + boff, bp, bfs, 1, 1, op, 3, list(RECT3)), "hc_morphology_device", "scratch bound")
+        e.queue(_morph(("whole", 0), 4, op=DS.MR.GRADIENT, mslot=0))   # (no intermediate frames: any bound)
+        e.check()
+
+
+def test_the_morphology_scratch_grows_while_a_call_is_queued(oracle):
+    """CLOSE of one frame (the third of the output, a natural one), then of four (the scratch is allocated again, behind a
+    synchronisation of the stream the first call is queued on), then a lines call, then the first call again into the other arena:
+    the same bytes."""
+    P = _params(w=250, h=66, pipeline=False)
+    one = lambda mslot: _morph(("frame", 0, 2), 1, spans=DS.MR.structuring_spans(DS.MR.CROSS, 5), mslot=mslot)
+    steps = [_run(0, 0), _points(("whole", 0), 4, P=P), one(0), _morph(("whole", 0), 4, spans=DS.MR.structuring_spans(DS.MR.RECT, 7), mslot=1), _lines(4, 3, 0, DS.LCAP_MAX, P), one(1)]
+    model = DS.execute(P, steps, oracle, "morphology scratch growth")
+    assert model.counters["morph_scratch_growths"] == 1 and model.counters["line_lists_nonempty"] == 4 and model.counters["morph_output_differs"] == 3, model.counters
+    first, again = (model.get(*DS.morph_views(model.L, one(k))[1], 1, P["w"]) for k in (0, 1))
+    assert np.array_equal(first, again) and first.any() and not np.array_equal(first, _region(model, 0, 3)[2:])
+
+
+def test_morphology_and_distances_per_channel(oracle):
+    """A 3-channel Mode R context with HC_OPT_PER_CHANNEL and max_batch 2: both entries take the 6 maps of a run and refuse 7, the
+    morphology takes 2 3-channel frames and refuses 3; with the option off 2 maps are taken and 3 refused.  Nothing is written by a
+    refused call."""
+    P = _params(w=65, h=64, ch=3, pipeline=True, per_channel=True, max_batch=2)
+    with DS.Executor(P, oracle, "morphology and distances per channel") as e:
+        def at_the_limit_and_beyond(n, k):
+            taken = (_morph(("whole", k), n, op=DS.MR.OPEN, spans=DS.MORPH_ASYM[2], mslot=0), _dist(("whole", k), n, P, dtype=api.DT_SQUARED_I32, near="own"))
+            for st in taken:
+                e.queue(st)
+            (a, aoff, ap, afs), (b, boff, bp, bfs) = DS.morph_views(e.L, taken[0])
+            _refused(lambda: e.ctx.morphology_device(e.ptr[a] + aoff, ap, afs, e.ptr[b] + boff, bp, bfs, n + 1, 1, DS.MR.DILATE, 3, list(RECT3)), "hc_morphology_device")
+            (dn, doff, dp, dfs), (nn, noff, npitch, nfs) = DS.dist_views(e.L, taken[1])
+            _refused(lambda: e.ctx.distance_transform_device(*e._view(("whole", k)), n + 1, 0, 0, e.ptr[dn] + doff, dp, dfs, e.ptr[nn] + noff, npitch, nfs), "hc_distance_transform_device")
+            three = _morph(None, 2, op=DS.MR.GRADIENT, spans=DS.MR.structuring_spans(DS.MR.ELLIPSE, 7), mslot=1, frames=1)
+            e.queue(three)
+            (a, aoff, ap, afs), (b, boff, bp, bfs) = DS.morph_views(e.L, three)
+            _refused(lambda: e.ctx.morphology_device(e.ptr[a] + aoff, ap, afs, e.ptr[b] + boff, bp, bfs, 3, 3, DS.MR.DILATE, 3, list(RECT3)), "hc_morphology_device")
+        e.queue(_run(0, 0, n=2))
+        at_the_limit_and_beyond(6, 0)
+        e.check()
+        c = e.model.counters
+        assert c["morph_n_above_max_batch"] == 1 and c["dist_n_above_max_batch"] == 1 and c["morph_three_channel"] == 1 and c["morph_overlap_in"] == 1 and c["dist_maps_mixed"] == 1, c
+        e.queue(dict(kind="option", option=api.OPT_PER_CHANNEL, value=0))
+        e.queue(_run(1, 1, n=2))
+        at_the_limit_and_beyond(2, 1)
+        e.check()
+        assert c["morph_overlap_in"] == 2 and c["morph_three_channel"] == 2 and e.continued_runs() > 0, c
+
+
+def test_morphology_and_distances_across_a_stream_switch(oracle):
+    """Both entries on the context's own stream, on a caller's stream and on its own again, each switch behind a synchronisation as
+    include/hipcanny.h asks of calls that share scratch; the second CLOSE needs a larger scratch than the first, and the distances
+    on the caller's stream lay their plane over an output, which the calls behind the second switch read as a map."""
+    P = _params(w=61, h=33, pipeline=True)
+    steps = [_run(0, 0), _run(1, 1), _morph(("whole", 0), 1, mslot=0), _dist(("whole", 0), 2, P, near="side", nleft=True), SYNC, dict(kind="stream", to="side"),
+             _morph(("whole", 1), 4, spans=DS.MORPH_ASYM[1], mslot=1), _dist(("frame", 0, 2), 1, P, target=api.DT_TO_ZERO, dtype=api.DT_SQUARED_I32, over=2, near="own"), SYNC,
+             dict(kind="stream", to="own"), _morph(("whole", 2), 2, op=DS.MR.OPEN, mslot=0), _points(("whole", 2), 1, P=P), _dist(("whole", 2), 1, P, dslot=1)]
+    model = DS.execute(P, steps, oracle, "morphology and distances across a stream switch")
+    c = model.counters
+    assert c["morph_scratch_growths"] == 1 and c["morph_overlap_in"] == 1 and c["dist_plane_read_as_map"] == 3 and c["dist_side_by_side"] == 1 and c["dist_maps_mixed"] == 3, c
+
+
+def test_the_real_chain_closed_labelled_and_measured(oracle):
+    """cv::Canny, cv::morphologyEx(MORPH_CLOSE) with a 3 x 3 rectangle into another region, the components of the closed maps, the
+    distances to the nearest edge as float32 with the nearest pixel beside them in one plane, and the edge points, of four frames,
+    queued with no synchronisation on a pipelined context: the chains include/hipcanny.h documents as needing none.  Closing joins
+    edges: fewer components behind it than before."""
+    P = _params(w=130, h=67, mode="O", pipeline=True)
+    with DS.Executor(P, oracle, "the real chain, closed") as e:
+        e.queue(dict(kind="canny", f0=0, n=4, out=0, low=DS.CANNY_THR[3][0], high=DS.CANNY_THR[3][1], aperture=3, l2=0))
+        edges = _region(e.model, 0, 4).copy()
+        for st in (_morph(("whole", 0), 4, into=1), _components(("whole", 1), 4, P), _dist(("whole", 1), 4, P, near="side", swords=3), _points(("whole", 1), 4, P=P)):
+            e.queue(st)
+        c = e.model.counters
+        assert c["morph_overlap_in"] == 1 and c["morph_read_by_a_later_step"] == 3 and c["dist_of_morph_output"] == 1 and c["dist_side_by_side"] == 1 and not e.model.pending, c
+        e.check()
+        assert e.continued_runs() == 1
+        before, after = DS.CC.connected_components(edges, 8, 0)[1].tolist(), _component_counts(e.model, 0, 4)
+        assert all(b >= a > 1 for b, a in zip(before, after)) and sum(before) > sum(after), (before, after)
+        assert _point_counts(e.model, 0, 4) == [int(np.count_nonzero(m)) for m in _region(e.model, 1, 4)] and c["dist_without_features"] == 0, c
+
+
+def test_distances_without_features_then_with(oracle):
+    """HC_DT_TO_ZERO on a view of the arena's fill (no zero byte: HC_DT_NONE / +inf and -1), checked; then the same calls again, each
+    followed at once by HC_DT_TO_NONZERO of a pending run's maps into the same planes, whose first frame still holds what the
+    call before left there."""
+    P = _params()
+    none = lambda dtype, dslot: _dist(("before", 0), 1, P, target=api.DT_TO_ZERO, dtype=dtype, dslot=dslot, near="side")
+    some = lambda dtype, dslot: _dist(("whole", 0), 4, P, dtype=dtype, dslot=dslot, near="side")
+    with DS.Executor(P, oracle, "distances without features, then with") as e:
+        for st in (_run(0, 0), none(api.DT_SQUARED_I32, 0), none(api.DT_F32, 1)):
+            e.queue(st)
+        e.check()
+        c, L = e.model.counters, e.L
+        assert c["dist_without_features"] == 2 and c["dist_maps_mixed"] == 0 and c["adjacent"] == 2, c   # (both views end where the pending output begins: its run stays in flight)
+        for dtype, dslot, want in ((np.int32, 0, api.DT_NONE), (np.float32, 1, np.inf)):
+            (dn, doff, dp, dfs), near = DS.dist_views(L, none(0, dslot))
+            assert (e.model.get(dn, doff, dp, dfs, 1, 4 * P["w"]).view(dtype) == want).all() and (e.model.get(*near, 1, 4 * P["w"]).view(np.int32) == -1).all()
+        for st in (_run(0, 0), none(api.DT_SQUARED_I32, 0), some(api.DT_SQUARED_I32, 0), none(api.DT_F32, 1), some(api.DT_F32, 1)):
+            e.queue(st)
+        assert c["dist_overlap_map"] == 1 and c["dist_without_features"] == 4 and c["dist_maps_mixed"] == 2, c
+        e.check()
+        assert e.continued_runs() == 2
