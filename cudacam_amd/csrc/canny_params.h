@@ -421,6 +421,13 @@ constexpr bool is_hyst_shape(int tile_rows, int waves)
 // ... and the two that also have the looping kernel (k_hyst_loop)
 constexpr bool hyst_shape_loops(int tile_rows, int waves) { return (tile_rows == 16 && waves == 8) || (tile_rows == 32 && waves == 2); }
 static_assert(is_hyst_shape(16, 8) && is_hyst_shape(32, 2), "the looping shapes are shapes");
+// Rounds of a tile's loop per launch (hyst_tile: between two rounds the waves of a workgroup exchange their boundary rows).  A
+// path costs one round each time it passes from one wave's rows to another's; natural frames need a handful.  It is a budget,
+// not a bound: content can need up to 2 * (waves - 1) * 2048 + 1 rounds (every round but the last sets a bit of a row another
+// wave looks at) -- a 1-px path up and down the columns of a tile comes close -- and a tile that runs out of rounds flags the
+// launch and leaves itself the reason that reopens its rows in the next one.  The budget keeps a launch short (4096 rounds are
+// 27 ms of an 8-wave workgroup, 57 ms of a 16-wave one) for whoever waits for it: the other workgroups at k_hyst_loop's barrier, the next run's chain.
+constexpr int HYST_ROUND_CAP = 4096;
 // 8 waves x 32 rows (256-row tiles) when the hysteresis has the chip to itself: fewer tile boundaries, fewer
 // launches.  4 waves x 32 rows (one wave per SIMD) when it runs beside the next run's front kernels (pipelined mode):
 // a 4-wave workgroup finds a place as soon as one wave slot per SIMD frees up, an 8-wave one has to wait for two --

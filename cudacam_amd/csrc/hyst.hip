@@ -369,7 +369,9 @@ static __device__ __forceinline__ void hyst_tile(const HystParams &p, int gtile,
     dirty = uniform64(act);
     unfilled = dirty;  // (only) the active rows may still need their first in-row fill: in every other row no open candidate touches a strong bit of the row
   }
-  for (int round = 0; round < 4096; ++round) {
+  // (HYST_ROUND_CAP, canny_params.h: a budget; a tile that uses it up says so below and goes on in the next launch)
+  int round;
+  for (round = 0; round < HYST_ROUND_CAP; ++round) {
     u64 round_changed = 0;
     while (dirty) {
       const int r = __builtin_ctzll(dirty);
@@ -450,6 +452,10 @@ static __device__ __forceinline__ void hyst_tile(const HystParams &p, int gtile,
     if (threadIdx.x == 0) bchg[18 + ((round + 1) & 1)] = 0;
     if (!more) break;
   }
+  // Out of rounds with rows still open: the tile is not at its fixpoint, and nobody else may know -- its boundary rows and
+  // columns need not have changed.  It flags the launch and leaves ITSELF the reason that reopens all its rows (`side`) for
+  // the next launch, as a neighbour would (below); what it reached so far goes to the plane and the map as usual.
+  const bool capped = round == HYST_ROUND_CAP;  // uniform for the workgroup: every wave saw the same `more`
 
   // Rows that changed go back to the plane, and the 0/255 map is written (removeCandidates + output copy,
   // cannyEdgeD.cu:379-395: strong bits -> 255, rest 0; 16 px per lane per store).  When the output already shows
@@ -585,36 +591,37 @@ static __device__ __forceinline__ void hyst_tile(const HystParams &p, int gtile,
   __syncthreads();
   if (MODE == HYST_PER_TILE) {
     // the tiles that look at what changed get their reason (no list: every launch starts a workgroup per tile, and a tile
-    // without a reason leaves after one load).  One lane per neighbour, as below.
+    // without a reason leaves after one load).  One lane per neighbour, as below; lane 8: the tile itself, out of rounds.
     if (wib == 0) {
-      const u32 vis = bchg[16];
+      const u32 vis = bchg[16] | (capped ? 16u : 0u);  // bit 4: out of rounds (lane 8 below)
       if (vis != 0) {
         if (lane == 0) atomicOr(&p.flags[p.iter], 1u);
         u32 *reason = p.wl_reason + (size_t)((p.iter + 1) & 1) * p.wl_stride;
         const int k = lane;
         const int t = k < 3 ? bt + 1 : k < 6 ? bt - 1 : bt;
-        const int q = k < 6 ? pn + (k % 3) - 1 : (k == 6 ? pn - 1 : pn + 1);
-        const u32 need = k < 3 ? 2u : k < 6 ? 1u : k == 6 ? 4u : 8u;
+        const int q = k < 6 ? pn + (k % 3) - 1 : (k == 6 ? pn - 1 : k == 7 ? pn + 1 : pn);
+        const u32 need = k < 3 ? 2u : k < 6 ? 1u : k == 6 ? 4u : k == 7 ? 8u : 16u;
         const u32 why = k < 3 ? 1u : k < 6 ? 2u : 4u;
-        if (k < 8 && (vis & need) != 0 && t >= 0 && t < p.nrtiles && q >= 0 && q < NP) atomicOr(&reason[frame * ntile + t * NP + q], why);
+        if (k < 9 && (vis & need) != 0 && t >= 0 && t < p.nrtiles && q >= 0 && q < NP) atomicOr(&reason[frame * ntile + t * NP + q], why);
       }
     }
   } else if (wib == 0) {
     // The neighbours that look at what changed go on the next launch's worklist -- once each: the first reason to arrive
     // appends the tile, later ones only add their bit.  One lane per neighbour, so that the atomics' round trips overlap.
-    const u32 vis = bchg[16];
+    const u32 vis = bchg[16] | (capped ? 16u : 0u);  // bit 4: out of rounds (lane 8 below)
     if (vis != 0) {
       if (lane == 0) atomicOr(&p.flags[p.iter], 1u);
       const int nxt = (p.iter + 1) & 1;
       u32 *reason = p.wl_reason + (size_t)nxt * p.wl_stride, *list = p.wl_list + (size_t)nxt * p.wl_stride;
       // lanes 0-2: the tiles below (my last row changed: their `top`), 3-5: above (my first row: their `bot`), 6 / 7: the
-      // panel left / right (my first / last column: their `side`)
+      // panel left / right (my first / last column: their `side`), 8: this tile itself when it ran out of rounds (its own
+      // `side`: every row open again)
       const int k = lane;
       const int t = k < 3 ? bt + 1 : k < 6 ? bt - 1 : bt;
-      const int q = k < 6 ? pn + (k % 3) - 1 : (k == 6 ? pn - 1 : pn + 1);
-      const u32 need = k < 3 ? 2u : k < 6 ? 1u : k == 6 ? 4u : 8u;
+      const int q = k < 6 ? pn + (k % 3) - 1 : (k == 6 ? pn - 1 : k == 7 ? pn + 1 : pn);
+      const u32 need = k < 3 ? 2u : k < 6 ? 1u : k == 6 ? 4u : k == 7 ? 8u : 16u;
       const u32 why = k < 3 ? 1u : k < 6 ? 2u : 4u;
-      if (k < 8 && (vis & need) != 0 && t >= 0 && t < p.nrtiles && q >= 0 && q < NP) {
+      if (k < 9 && (vis & need) != 0 && t >= 0 && t < p.nrtiles && q >= 0 && q < NP) {
         const u32 g = (u32)(frame * ntile + t * NP + q);
         if (atomicOr(&reason[g], why) == 0) list[atomicAdd(&p.wl_count[p.iter + 1], 1u)] = g;
       }
