@@ -73,6 +73,9 @@ MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2
 DT_TO_NONZERO, DT_TO_ZERO = 0, 1
 DT_SQUARED_I32, DT_F32 = 0, 1
 DT_NONE = 2147483647
+# methods of hc_thinning_device (the header's HC_THIN_*) and the names Context.thinning takes for them
+THIN_ZHANGSUEN, THIN_GUOHALL = 0, 1
+THIN_METHODS = {"zhangsuen": THIN_ZHANGSUEN, "guohall": THIN_GUOHALL}
 # words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
 SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
@@ -87,6 +90,7 @@ ABI_SYMBOLS = [
     "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
     "hc_hough_segments_device", "hc_hough_walk_tables", "hc_hough_circles_device", "hc_hough_circle_geometry",
     "hc_connected_components_device", "hc_morphology_device", "hc_structuring_element", "hc_distance_transform_device",
+    "hc_thinning_device",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -160,6 +164,7 @@ def load_library(legacy=False):
     L.hc_morphology_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, i, C.POINTER(C.c_int8)]
     L.hc_structuring_element.argtypes = [i, i, C.POINTER(C.c_int8)]
     L.hc_distance_transform_device.argtypes = [vp, vp, sz, sz, i, i, i, vp, sz, sz, vp, sz, sz]
+    L.hc_thinning_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, vp]
     L.hc_hough_circle_geometry.argtypes = [i, i, d, d, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
@@ -1031,29 +1036,36 @@ class Context:
         self._morph_keep = None
         return res
 
-    def canny_components(self, frames, low, high, connectivity=8, aperture=3, l2gradient=False, blur=None, max_components=None, close=None):
+    def canny_components(self, frames, low, high, connectivity=8, aperture=3, l2gradient=False, blur=None, max_components=None, close=None, thin=None):
         """cv::Canny followed by cv::connectedComponentsWithStats (mode O): canny_device and connected_components_device chained on
         the device, with no host copy of the maps in between.  Returns (uint8 (n,H,W) edge maps, labels, counts, stats, centroids as
         connected_components gives them).  blur = (ksize, sigma): the frames are blurred first (gaussian_blur_device).
         close = (shape, ksize): cv::morphologyEx(MORPH_CLOSE) with that element runs between the two on the device
-        (morphology_device), the components are those of the closed maps, and the closed maps are what the call returns."""
+        (morphology_device), the components are those of the closed maps, and the closed maps are what the call returns.
+        thin = a method name of thinning ("zhangsuen" / "guohall"): thinning_device (16 iterations at most) runs after the closing,
+        and the components and the returned maps are those of the skeletons."""
         raw, n, row, fs = self._device_view(frames, "canny_components")
         out = self._device_maps(n)
         self._wait_for_torch()
         src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
         self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
-        if close is None:
+        if close is None and thin is None:
             labels, counts, stats, cent = self._again_if_continued(lambda: self._components_of(out, n, connectivity, max_components))
             return out.cpu().numpy(), labels, counts, stats, cent
-        spans = structuring_element(*close)
-        closed = self._device_maps(n)
+        spans = structuring_element(*close) if close is not None else None
+        method = self._thin_method(thin) if thin is not None else None
+        closed = self._device_maps(n) if close is not None else out
+        last = self._device_maps(n) if thin is not None else closed
 
-        def closed_components():
+        def later_components():
             self._wait_for_torch()
-            self.morphology_device(out.data_ptr(), self.w, self.w * self.h, closed.data_ptr(), self.w, self.w * self.h, n, 1, MORPH_CLOSE, close[1], spans)
-            return self._components_of(closed, n, connectivity, max_components)
-        labels, counts, stats, cent = self._again_if_continued(closed_components)
-        return closed.cpu().numpy(), labels, counts, stats, cent
+            if close is not None:
+                self.morphology_device(out.data_ptr(), self.w, self.w * self.h, closed.data_ptr(), self.w, self.w * self.h, n, 1, MORPH_CLOSE, close[1], spans)
+            if thin is not None:
+                self.thinning_device(closed.data_ptr(), self.w, self.w * self.h, last.data_ptr(), self.w, self.w * self.h, n, method, 16)
+            return self._components_of(last, n, connectivity, max_components)
+        labels, counts, stats, cent = self._again_if_continued(later_components)
+        return last.cpu().numpy(), labels, counts, stats, cent
 
     def distance_transform_device(self, d_map, pitch, fs, nframes, target, dist_type, d_dist, dist_pitch, dist_fs, d_nearest=None, nearest_pitch=0,
                                   nearest_fs=0):
@@ -1097,6 +1109,75 @@ class Context:
         self.canny_device(src.data_ptr(), row, fs, out.data_ptr(), self.w, self.w * self.h, n, low, high, aperture, l2gradient)
         res = self._again_if_continued(lambda: self._distances_of(out, n, DT_TO_NONZERO, squared, nearest))
         return (out.cpu().numpy(),) + (res if nearest else (res,))
+
+    def thinning_device(self, d_map, pitch, fs, d_out, out_pitch, out_fs, nframes, method=THIN_ZHANGSUEN, max_iterations=16, d_status=None):
+        """Zhang-Suen / Guo-Hall thinning of one-channel u8 maps on device memory (hc_thinning_device, either mode): a pixel is
+        foreground iff its byte is non-zero, the output is 0 / 255; method THIN_ZHANGSUEN or THIN_GUOHALL; at most max_iterations
+        (1..1024) iterations, every one of which is queued -- a cost, 16 suits closed Canny maps.  d_status, when given, receives
+        uint32 [nframes][2] = (iterations that removed a pixel, 1 iff the output is known to be the fixed point).  Pitches and frame
+        strides in bytes, any alignment; the views must not overlap.  Asynchronous on the context stream; not a run, but a
+        pipelined run in flight that writes either view is completed first."""
+        _ck(self.lib.hc_thinning_device(self.handle, C.c_void_p(d_map), pitch, fs, C.c_void_p(d_out), out_pitch, out_fs, int(nframes), int(method),
+                                        int(max_iterations), C.c_void_p(d_status or None)))
+
+    @staticmethod
+    def _thin_method(method):
+        if isinstance(method, str):
+            if method.lower() not in THIN_METHODS:
+                raise HipCannyError(f"thinning: method must be one of {sorted(THIN_METHODS)}, not {method!r}")
+            return THIN_METHODS[method.lower()]
+        return int(method)
+
+    def thinning(self, maps, method="zhangsuen", max_iterations=16):
+        """Host or torch u8 maps [n, H, W] (or one map) in; (uint8 0 / 255 skeleton maps [n, H, W], uint32 iterations [n], uint32
+        converged [n]) out, as hc_thinning_device states them.  max_iterations=None: the call is repeated in chunks of 16
+        iterations between two device buffers until every frame reports convergence -- one host synchronisation per chunk;
+        `iterations` is then the sum over the chunks.  Every chunk is a whole call on the whole batch: frames that converged in
+        an earlier chunk are packed and unpacked again (their step launches exit at once), so a batch pays a pack and an unpack
+        per chunk of its slowest frame."""
+        import torch
+        d = self._maps_on_device(maps, "thinning")
+        n, fs = d.shape[0], self.w * self.h
+        m = self._thin_method(method)
+        bufs = [self._device_maps(n), self._device_maps(n)]   # (the caller's tensor is never written)
+        status = torch.empty((n, 2), dtype=torch.int32, device=d.device)
+        total = np.zeros(n, np.uint32)
+        src, k = d, 0
+        while True:
+            dst = bufs[k & 1]
+            self._wait_for_torch()
+            self.thinning_device(src.data_ptr(), self.w, fs, dst.data_ptr(), self.w, fs, n, m, 16 if max_iterations is None else max_iterations, status.data_ptr())
+            self.sync()
+            st = status.cpu().numpy().view(np.uint32)
+            total += st[:, 0]
+            if max_iterations is not None or st[:, 1].all():
+                return dst.cpu().numpy(), total, st[:, 1].copy()
+            src, k = dst, k + 1
+
+    def canny_skeleton(self, frames, low, high, close=(MORPH_RECT, 3), method="zhangsuen", max_iterations=16, aperture=3, l2gradient=False, blur=None):
+        """cv::Canny, cv::morphologyEx(MORPH_CLOSE) with the element close = (shape, ksize) and the thinning of the closed maps
+        (mode O): canny_device, morphology_device and thinning_device chained on the device with no host copy and no
+        synchronisation in between.  blur = (ksize, sigma): the frames are blurred first (gaussian_blur_device).  Returns (uint8
+        (n,H,W) skeleton maps, uint32 iterations [n], uint32 converged [n]) as thinning gives them."""
+        import torch
+        raw, n, row, fs = self._device_view(frames, "canny_skeleton")
+        m = self._thin_method(method)
+        spans = structuring_element(*close)
+        edges, closed, skel = self._device_maps(n), self._device_maps(n), self._device_maps(n)
+        status = torch.empty((n, 2), dtype=torch.int32, device=edges.device)
+        mfs = self.w * self.h
+        self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
+        self.canny_device(src.data_ptr(), row, fs, edges.data_ptr(), self.w, mfs, n, low, high, aperture, l2gradient)
+
+        def skeleton():
+            self._wait_for_torch()
+            self.morphology_device(edges.data_ptr(), self.w, mfs, closed.data_ptr(), self.w, mfs, n, 1, MORPH_CLOSE, close[1], spans)
+            self.thinning_device(closed.data_ptr(), self.w, mfs, skel.data_ptr(), self.w, mfs, n, m, max_iterations, status.data_ptr())
+            self.sync()
+            return skel.cpu().numpy(), status.cpu().numpy().view(np.uint32)
+        maps, st = self._again_if_continued(skeleton)
+        return maps, st[:, 0].copy(), st[:, 1].copy()
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -36,6 +36,12 @@ hipError_t launch_hough_circles(const CircleParams &p, hipStream_t s);
 hipError_t launch_connected_components(const CclParams &p, hipStream_t s);
 hipError_t launch_morph8(const MorphParams &p, hipStream_t s);  // morph.hip (the product library only): one maximum / minimum filter launch, u8 -> u8
 hipError_t launch_distance_transform(const DistParams &p, hipStream_t s);  // dist.hip (the product library only): k_dt_cols, then k_dt_rows
+// thin.hip (the product library only): the map -> bit plane A; sub-iteration `sub` (0: A -> B, 1: B -> A) of iteration `iteration`
+// (1 ..; its removals are added to word `iteration` of each frame's table, and frames whose word iteration - 1 is zero are left
+// alone); plane A -> the 0 / 255 output view and the status pairs
+hipError_t launch_thin_pack(const ThinPackParams &p, hipStream_t s);
+hipError_t launch_thin_step(const ThinStepParams &p, int sub, int iteration, hipStream_t s);
+hipError_t launch_thin_unpack(const ThinUnpackParams &p, hipStream_t s);
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

@@ -177,6 +177,94 @@ struct MorphParams {
   int8_t row_level[MORPH_MAX_K + 1];  // per element row: the index of its half-width in level[], -1: an empty row; [ksize ..]: -1
 };
 
+// k_thin_pack / k_thin_step / k_thin_unpack (thin.hip): Zhang-Suen and Guo-Hall thinning of binary maps on bit planes
+// (hc_thinning_device, where the rules are stated).  A plane holds a frame as H rows of thin_row_words(W) dwords, bit i of word j =
+// column 32 j + i; the bits beyond W are zero.  A lane of k_thin_step holds one dword of a row, so a wave spans a panel of
+// THIN_PANEL_WORDS words (2048 columns); a work item is (frame, panel, tile of THIN_TILE_ROWS rows), one per wave, four to a
+// workgroup.  16 rows: 1080p x 64 frames are 4352 waves, four to a SIMD, for one halo row in eight read twice.
+constexpr int THIN_ZHANGSUEN = 0, THIN_GUOHALL = 1;  // HC_THIN_* (host_plan.h asserts the match)
+constexpr int THIN_MAX_ITERATIONS = 1024;
+constexpr int THIN_TILE_ROWS = 16;
+constexpr int THIN_PANEL_WORDS = 64;
+constexpr int THIN_SEG_PX = 256;  // columns a wave of k_thin_pack / k_thin_unpack covers: 4 per lane, 8 words
+inline int thin_row_words(int W) { return (W + 31) / 32; }
+inline int thin_panels(int W) { return (thin_row_words(W) + THIN_PANEL_WORDS - 1) / THIN_PANEL_WORDS; }
+inline int thin_tiles(int H) { return (H + THIN_TILE_ROWS - 1) / THIN_TILE_ROWS; }
+inline int thin_segs(int W) { return (W + THIN_SEG_PX - 1) / THIN_SEG_PX; }
+// The scratch of a pass of F frames: [plane A x F][plane B x F][removal table x F].  A frame's table holds table_words =
+// max_iterations + 1 words: word k (1 ..) is the number of pixels iteration k removed, word 0 is not used.
+struct ThinPackParams {
+  const uint8_t *map;      // u8 maps of W x H, one channel, any alignment (in_aligned: base, pitch and frame stride are multiples of 4)
+  size_t pitch, frame_stride;
+  u32 *plane_a;            // [nframes][H][row_words]
+  size_t plane_words;      // H * row_words
+  int W, H, nframes, row_words, segs;
+  int in_aligned;          // rows may be read as dwords (whole 4-pixel groups inside the row only)
+};
+struct ThinStepParams {
+  u32 *plane_a, *plane_b;  // sub-iteration 0 reads A and writes B, sub-iteration 1 reads B and writes A
+  u32 *removed;            // [nframes][table_words]; zero when the first step starts
+  size_t plane_words;
+  int H, nframes, row_words, npanels, ntiles, total_items;  // total_items = nframes * npanels * ntiles
+  int table_words;
+  int method;              // THIN_ZHANGSUEN / THIN_GUOHALL
+};
+struct ThinUnpackParams {
+  const u32 *plane_a;
+  const u32 *removed;
+  u32 *status;             // [nframes][2] = (iterations that removed a pixel, 1: the fixed point was reached), or null
+  uint8_t *out;            // u8 maps 0 / 255; any alignment (out_aligned as in_aligned); exactly [row, row + W) is written
+  size_t out_pitch, out_frame_stride;
+  size_t plane_words;
+  int W, H, nframes, row_words, segs;
+  int out_aligned;
+  int table_words, max_iterations;
+};
+// The bit-sliced decision of k_thin_step, plain C++ on dwords so that the CPU test can run the kernel's own text against the
+// per-pixel formulas (tests/cpp/thin_plan_driver.cpp).  A row as three planes: the row, its west-neighbour plane (pixel x - 1 at
+// bit x) and its east-neighbour plane.
+struct ThinRow { u32 c, w, e; };
+// exactly-one accumulator over planes: `one` = at least one seen, `more` = at least two
+struct ThinOneOf {
+  u32 one = 0, more = 0;
+  HC_HOST_DEVICE inline void add(u32 t) { more |= one & t; one |= t; }
+  HC_HOST_DEVICE inline u32 exactly_one() const { return one & ~more; }
+};
+// the pixels of row C that sub-iteration S of METHOD removes (N, S_: the rows above and below): include/hipcanny.h states the rules
+template <int METHOD, int S>
+HC_HOST_DEVICE inline u32 thin_removed(const ThinRow &N, const ThinRow &C, const ThinRow &S_)
+{
+  const u32 p2 = N.c, p3 = N.e, p4 = C.e, p5 = S_.e, p6 = S_.c, p7 = S_.w, p8 = C.w, p9 = N.w;
+  if constexpr (METHOD == THIN_ZHANGSUEN) {
+    // B = p2 + .. + p9 as a carry-save count: bits b0 .. b3
+    const u32 s1 = p2 ^ p3 ^ p4, c1 = (p2 & p3) | (p4 & (p2 ^ p3));
+    const u32 s2 = p5 ^ p6 ^ p7, c2 = (p5 & p6) | (p7 & (p5 ^ p6));
+    const u32 s3 = p8 ^ p9, c3 = p8 & p9;
+    const u32 b0 = s1 ^ s2 ^ s3, c4 = (s1 & s2) | (s3 & (s1 ^ s2));
+    const u32 s5 = c1 ^ c2 ^ c3, c5 = (c1 & c2) | (c3 & (c1 ^ c2));
+    const u32 b1 = s5 ^ c4, c6 = s5 & c4;
+    const u32 b2 = c5 ^ c6, b3 = c5 & c6;
+    const u32 b_ok = (b1 | b2) & ~b3 & ~(b2 & b1 & b0);  // 2 <= B <= 6
+    ThinOneOf a;  // A: the 0 -> 1 steps of the cyclic sequence p2, p3, .., p9, p2
+    a.add(~p2 & p3); a.add(~p3 & p4); a.add(~p4 & p5); a.add(~p5 & p6);
+    a.add(~p6 & p7); a.add(~p7 & p8); a.add(~p8 & p9); a.add(~p9 & p2);
+    const u32 cond = S == 0 ? ~(p2 & p4 & p6) & ~(p4 & p6 & p8) : ~(p2 & p4 & p8) & ~(p2 & p6 & p8);
+    return C.c & b_ok & a.exactly_one() & cond;
+  } else {
+    ThinOneOf c;
+    c.add(~p2 & (p3 | p4)); c.add(~p4 & (p5 | p6)); c.add(~p6 & (p7 | p8)); c.add(~p8 & (p9 | p2));
+    const u32 a1 = p9 | p2, a2 = p3 | p4, a3 = p5 | p6, a4 = p7 | p8;  // N1 = a1 + a2 + a3 + a4
+    const u32 d1 = p2 | p3, d2 = p4 | p5, d3 = p6 | p7, d4 = p8 | p9;  // N2 likewise
+    ThinOneOf n1, n2;
+    n1.add(a1); n1.add(a2); n1.add(a3); n1.add(a4);
+    n2.add(d1); n2.add(d2); n2.add(d3); n2.add(d4);
+    // 2 <= min(N1, N2) <= 3: both counts reach 2, and not both are 4
+    const u32 n_ok = n1.more & n2.more & ~(a1 & a2 & a3 & a4 & d1 & d2 & d3 & d4);
+    const u32 m = S == 0 ? (p6 | p7 | ~p9) & p8 : (p2 | p3 | ~p5) & p4;
+    return C.c & c.exactly_one() & n_ok & ~m;
+  }
+}
+
 // k_hist256 (stats.hip): 256-bin histograms of u8 frames, all channels pooled.  A work item is (frame, chunk of rows); a wave
 // counts its rows into a wave-private LDS histogram and adds the non-zero bins to hist[frame] with global atomics.
 constexpr int HIST_MAX_CHUNK_ROWS = 64, HIST_MIN_CHUNK_ROWS = 8;

@@ -314,4 +314,32 @@ int hc_distance_transform_device(hc_ctx *c, const void *d_map, size_t pitch, siz
   return HC_OK;
 }
 
+// Per pass the zeroing of the removal tables, k_thin_pack, 2 * max_iterations launches of k_thin_step and k_thin_unpack on the
+// context stream (thin.hip).  Not a run, as hc_morphology_device, and like it it completes first a pipelined run in flight whose
+// output overlaps either view.  The bit planes and the tables live in the context's scratch; successive calls share it and are
+// ordered by the stream they are queued on (include/hipcanny.h).
+int hc_thinning_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs, void *d_out, size_t out_pitch, size_t out_fs, int n, int method, int max_iterations,
+                       void *d_status)
+{
+  if (!c || !d_map || !d_out) return fail(HC_E_ARG, "hc_thinning_device: null argument");
+  const View map{ (uintptr_t)d_map, pitch, fs }, out{ (uintptr_t)d_out, out_pitch, out_fs };
+  const ThinPlan P = plan_thinning(c->W, c->H, c->per_channel != 0, c->max_batch, map, out, n, method, max_iterations, (uintptr_t)d_status, c->hough_bound);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_thinning_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  const size_t row = (size_t)c->W;
+  if (int rc = finish_writers_of(c, map, row, n)) return rc;
+  if (int rc = finish_writers_of(c, out, row, n)) return rc;
+  // every refusal lies above.  A larger scratch: what is queued on the context stream may still read the old one
+  if (int rc = ensure_scratch(c, c->thin, P.scratch_bytes)) return rc;
+  for (int k = 0; k < P.passes; ++k) {
+    const ThinPass tp = thin_pass(P, k, (uintptr_t)c->thin.p);
+    HIPCK(hipMemsetAsync((void *)tp.tables, 0, tp.tables_bytes, c->stream));
+    HIPCK(launch_thin_pack(tp.pack, c->stream));
+    for (int it = 1; it <= P.max_iterations; ++it)
+      for (int s = 0; s < 2; ++s) HIPCK(launch_thin_step(tp.step, s, it, c->stream));
+    HIPCK(launch_thin_unpack(tp.unpack, c->stream));
+  }
+  return HC_OK;
+}
+
 }  // extern "C"

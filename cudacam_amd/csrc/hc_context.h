@@ -225,6 +225,9 @@ struct hc_ctx {
   // hc_morphology_device: the frames between the two stages of HC_MORPH_OPEN / HC_MORPH_CLOSE of one pass (morph_pass, host_plan.h),
   // bounded by hough_bound as well
   hc::DeviceScratch morph_mid;
+  // hc_thinning_device: the two bit planes and the removal table of every frame of one pass (thin_pass, host_plan.h), bounded by
+  // hough_bound as well
+  hc::DeviceScratch thin;
 };
 
 namespace hc {

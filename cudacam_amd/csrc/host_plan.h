@@ -2,7 +2,7 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology, plan_distance_transform; the taps rule of
+// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology, plan_distance_transform, plan_thinning; the taps rule of
 // hc_gaussian_taps_q8, the table rules of hc_hough_tables and hc_hough_walk_tables and the geometry of hc_hough_circle_geometry).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
@@ -1429,6 +1429,94 @@ inline DistPlan plan_distance_transform(int W, int H, int max_frames, const View
   d.row_groups = (unsigned)((H + DT_ROWS - 1) / DT_ROWS);
   d.lds_bytes = 4u * (unsigned)W;
   return P;
+}
+
+// ---- hc_thinning_device ---------------------------------------------------------------------------
+static_assert(THIN_ZHANGSUEN == HC_THIN_ZHANGSUEN && THIN_GUOHALL == HC_THIN_GUOHALL, "canny_params.h names the header's methods");
+// Everything the entry refuses and decides, but for the context pointer.  A call is, per pass, the zeroing of the removal tables,
+// k_thin_pack, 2 * max_iterations launches of k_thin_step and k_thin_unpack.  The context's scratch holds, per frame of a pass,
+// two bit planes of H rows of row_words dwords and a table of max_iterations + 1 removal words (frame_bytes in all), laid out
+// [plane A x frames_per_pass][plane B x frames_per_pass][tables x frames_per_pass].  It falls under the context's scratch bound: a
+// batch is cut into passes of as many whole frames as fit.  pack / step / unpack describe the first pass with null scratch
+// pointers; thin_pass gives the blocks of pass k.  A refused plan holds nothing but its text.
+struct ThinPlan {
+  const char *error = nullptr;
+  ThinPackParams pack{};
+  ThinStepParams step{};
+  ThinUnpackParams unpack{};
+  int method = 0, max_iterations = 0;
+  int row_words = 0, tile_rows = 0, tiles = 0, panels = 0;
+  int frames = 0, frames_per_pass = 0, passes = 0;
+  size_t plane_bytes = 0, table_bytes = 0, frame_bytes = 0, scratch_bytes = 0;
+};
+inline ThinPlan plan_thinning(int W, int H, bool per_channel, int max_batch, const View &in, const View &out, int n, int method, int max_iterations, uintptr_t status,
+                              size_t scratch_bound)
+{
+  ThinPlan P;
+  auto refuse = [](const char *text) { ThinPlan R; R.error = text; return R; };
+  if (!in.p || !out.p) return refuse("null argument");
+  if (method != THIN_ZHANGSUEN && method != THIN_GUOHALL) return refuse("method must be HC_THIN_ZHANGSUEN or HC_THIN_GUOHALL");
+  if (max_iterations < 1 || max_iterations > THIN_MAX_ITERATIONS) return refuse("max_iterations outside 1..1024");
+  if (status & 3u) return refuse("d_status must be 4-byte aligned");
+  if (W < 1 || H < 1) return refuse("width and height must be positive");
+  if (n < 1 || n > max_batch * (per_channel ? 3 : 1)) return refuse("nframes out of range");
+  const size_t row = (size_t)W;
+  for (const View *v : { &in, &out })
+    if (const ViewFault f = check_view(*v, row, H, n, 1, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  uintptr_t end[2];
+  if (!view_end(in, row, H, n, &end[0]) || !view_end(out, row, H, n, &end[1])) return refuse("a view wraps the address space");
+  if (in.p < end[1] && out.p < end[0]) return refuse("the map and the output view overlap (in-place operation is not supported)");
+  P.method = method; P.max_iterations = max_iterations;
+  P.row_words = thin_row_words(W); P.tile_rows = THIN_TILE_ROWS; P.tiles = thin_tiles(H); P.panels = thin_panels(W);
+  // (H * pitch < 2^32 and pitch >= W: a plane is below 2^29 + 4 H bytes, so the sums below do not wrap)
+  P.plane_bytes = (size_t)H * P.row_words * 4;
+  P.table_bytes = 4 * ((size_t)max_iterations + 1);
+  P.frame_bytes = 2 * P.plane_bytes + P.table_bytes;
+  if (scratch_bound < P.frame_bytes) return refuse("one frame of bit planes exceeds the context's scratch bound");
+  P.frames = n;
+  P.frames_per_pass = (int)std::min<size_t>((size_t)n, scratch_bound / P.frame_bytes);
+  P.passes = (n + P.frames_per_pass - 1) / P.frames_per_pass;
+  P.scratch_bytes = (size_t)P.frames_per_pass * P.frame_bytes;
+  if ((long long)P.frames_per_pass * P.panels * P.tiles > 0x7FFFFFF0ll || P.plane_bytes > 0xFFFFFFFCull) return refuse("too many work items (frames of a pass x panels x row tiles)");
+  ThinPackParams &a = P.pack;
+  a.map = (const uint8_t *)in.p; a.pitch = in.pitch; a.frame_stride = in.fs;
+  a.plane_words = P.plane_bytes / 4;
+  a.W = W; a.H = H; a.nframes = P.frames_per_pass; a.row_words = P.row_words; a.segs = thin_segs(W);
+  a.in_aligned = aligned4(in.p, in.pitch, in.fs);
+  ThinStepParams &s = P.step;
+  s.plane_words = a.plane_words;
+  s.H = H; s.nframes = P.frames_per_pass; s.row_words = P.row_words; s.npanels = P.panels; s.ntiles = P.tiles;
+  s.total_items = s.nframes * s.npanels * s.ntiles;
+  s.table_words = max_iterations + 1; s.method = method;
+  ThinUnpackParams &u = P.unpack;
+  u.status = (u32 *)status;
+  u.out = (uint8_t *)out.p; u.out_pitch = out.pitch; u.out_frame_stride = out.fs;
+  u.plane_words = a.plane_words;
+  u.W = W; u.H = H; u.nframes = P.frames_per_pass; u.row_words = P.row_words; u.segs = a.segs;
+  u.out_aligned = aligned4(out.p, out.pitch, out.fs);
+  u.table_words = s.table_words; u.max_iterations = max_iterations;
+  return P;
+}
+
+// The launches of pass k of a plan that was not refused (0 <= k < passes): the blocks of k_thin_pack, k_thin_step (every
+// sub-iteration and iteration takes the same) and k_thin_unpack, and the tables the pass zeroes first; scratch: scratch_bytes,
+// 4-byte aligned
+struct ThinPass { ThinPackParams pack; ThinStepParams step; ThinUnpackParams unpack; uintptr_t tables; size_t tables_bytes; };
+inline ThinPass thin_pass(const ThinPlan &P, int k, uintptr_t scratch)
+{
+  ThinPass R{ P.pack, P.step, P.unpack, 0, 0 };
+  const int f0 = k * P.frames_per_pass, nf = std::min(P.frames_per_pass, P.frames - f0);
+  const size_t planes = (size_t)P.frames_per_pass * P.plane_bytes;
+  u32 *const A = (u32 *)scratch, *const B = (u32 *)(scratch + planes), *const T = (u32 *)(scratch + 2 * planes);
+  R.tables = (uintptr_t)T; R.tables_bytes = (size_t)nf * P.table_bytes;
+  R.pack.map += (size_t)f0 * R.pack.frame_stride;
+  R.pack.plane_a = A; R.pack.nframes = nf;
+  R.step.plane_a = A; R.step.plane_b = B; R.step.removed = T; R.step.nframes = nf;
+  R.step.total_items = nf * R.step.npanels * R.step.ntiles;
+  R.unpack.plane_a = A; R.unpack.removed = T; R.unpack.nframes = nf;
+  R.unpack.out += (size_t)f0 * R.unpack.out_frame_stride;
+  if (R.unpack.status) R.unpack.status += 2 * (size_t)f0;
+  return R;
 }
 
 }  // namespace hc

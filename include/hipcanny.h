@@ -660,6 +660,67 @@ int hc_distance_transform_device(hc_ctx *ctx, const void *d_map, size_t pitch, s
                                  void *d_dist, size_t dist_pitch, size_t dist_frame_stride,
                                  void *d_nearest /* may be NULL */, size_t nearest_pitch, size_t nearest_frame_stride);
 
+/* Thinning of binary maps on the device: the Zhang-Suen and the Guo-Hall skeleton, what callers take from
+ * cv::ximgproc::thinning(.., THINNING_ZHANGSUEN / THINNING_GUOHALL) -- the inverse step of hc_morphology_device: a closed edge map
+ * has contours three to seven pixels wide, and the point lists, Hough transforms and distances that follow want them one pixel
+ * wide again (k_thin_pack, k_thin_step, k_thin_unpack: cudacam_amd/csrc/thin.hip, on bit planes, one bit per pixel).  The
+ * semantics are stated here and restated in tests/thin_ref.py (numpy, and a naive per-pixel loop); like the rest of Mode O they
+ * are not pinned against a build of OpenCV.  With W, H the context's frame size:
+ * Map.  d_map is what hc_connected_components_device reads: one-channel u8 maps of W x H in a pitched view, whatever `channels`
+ *   the context has; any alignment of base, pitch and frame stride; pitch >= W; no byte outside [row, row + W) of a row is read.
+ *   A pixel is foreground iff its byte is non-zero.  Frames are independent.  The map is never written.
+ * Neighbours.  For pixel P1 at (y, x) the eight neighbours are numbered clockwise from north: P2 (y-1, x), P3 (y-1, x+1),
+ *   P4 (y, x+1), P5 (y+1, x+1), P6 (y+1, x), P7 (y+1, x-1), P8 (y, x-1), P9 (y-1, x-1); each is 1 for foreground and 0 otherwise,
+ *   and a position outside the frame is background.  Every pixel of the frame, its outermost rows and columns included, is a
+ *   candidate: the textbook rule.  (opencv_contrib's implementation, as far as it is remembered here and not checked, leaves the
+ *   outermost rows and columns as they are; a caller who compares with it should look there first.)
+ * Sub-iteration s (0 or 1), method = HC_THIN_ZHANGSUEN.  B = P2 + .. + P9; A = the number of positions i in the cyclic sequence
+ *   P2, P3, .., P9, P2 with P_i = 0 and P_(i+1) = 1.  A foreground pixel is removed iff 2 <= B <= 6, A == 1 and
+ *   s = 0: P2 P4 P6 == 0 and P4 P6 P8 == 0;   s = 1: P2 P4 P8 == 0 and P2 P6 P8 == 0.
+ * Sub-iteration s, method = HC_THIN_GUOHALL.  C = (!P2 & (P3 | P4)) + (!P4 & (P5 | P6)) + (!P6 & (P7 | P8)) + (!P8 & (P9 | P2));
+ *   N1 = (P9 | P2) + (P3 | P4) + (P5 | P6) + (P7 | P8); N2 = (P2 | P3) + (P4 | P5) + (P6 | P7) + (P8 | P9); N = min(N1, N2);
+ *   m = (P6 | P7 | !P9) & P8 for s = 0 and (P2 | P3 | !P5) & P4 for s = 1.  A foreground pixel is removed iff C == 1,
+ *   2 <= N <= 3 and m == 0.
+ * Parallel rule.  All decisions of a sub-iteration are taken on the map as it was when the sub-iteration began; the removed
+ *   pixels are cleared together.  (Zhang-Suen therefore erases an isolated 2 x 2 block; Guo-Hall leaves one pixel of it.)
+ * Iterations.  Iteration k = 1, 2, .. is sub-iteration 0 followed by sub-iteration 1, and r_k the number of pixels it removes.
+ *   An iteration depends on nothing but the map it starts from, so r_k = 0 means the map is a fixed point.  Let K be the smallest
+ *   k <= max_iterations with r_k = 0, if there is one.  The output is the map after min(K - 1, max_iterations) iterations, written
+ *   as 0 / 255.  A call with max_iterations too small returns exactly that intermediate map, and a second call on its output goes
+ *   on from there and ends at the same fixed point.
+ * Output view.  Exactly the bytes [row, row + W) of each row of each frame are written; base, pitch and frame stride may have any
+ *   alignment (4-byte aligned views get dword stores); out_pitch >= W.  The byte ranges of the two views, from a view's first to
+ *   its last byte, must not overlap (there is no in-place operation); ranges that merely touch are fine.
+ * Status.  When d_status is not null (4-byte aligned) it receives uint32 [nframes][2]: d_status[f][0] = the number of iterations
+ *   of frame f that removed a pixel (K - 1, or max_iterations), d_status[f][1] = 1 iff K exists, that is, the output is known to be
+ *   the fixed point.  Nothing else is written.
+ * Asynchronous on the context stream (hc_set_stream honoured); chained behind hc_morphology_device and ahead of
+ *   hc_edge_points_device or hc_connected_components_device it needs no synchronisation.  Contexts of either mode.  It is not a
+ *   run, exactly as hc_morphology_device is none (hc_last_run_info, the stage timers, the hysteresis schedule / history and the
+ *   pipeline slots stay as they were), and like that entry it completes first a pipelined run still in flight whose output
+ *   overlaps either view.
+ * Scratch.  Owned by the context, allocated on first use, grown when a call needs more, freed by hc_destroy: per frame of a pass
+ *   two bit planes (H rows of ceil(W / 32) dwords each) and a table of max_iterations + 1 removal words, under the bound of
+ *   hc_hough_lines_device's scratch (256 MiB).  A batch that does not fit runs in passes of as many whole frames as do, and a
+ *   single frame above the bound is HC_E_ARG.  Successive calls share it and are ordered by the stream they are queued on, across
+ *   a change of the stream too.
+ * Cost.  Every one of the 2 * max_iterations sub-iteration launches of a pass is queued whatever the content; the waves of a frame
+ *   that has reached its fixed point exit on their first load, and the removal counts are integer sums, so the result is a function
+ *   of the map alone.  max_iterations is therefore a cost, and 16 suits closed Canny maps: the largest count the restatement
+ *   needed on 3 x 3-dilated curves is 7 (Guo-Hall), and the closed 1080p Canny maps of the eight synthetic scenes that
+ *   tools/thin_bench.py measures -- no more than those eight -- needed at most 10 (Zhang-Suen).  Thick blobs take more, about
+ *   half their thickness, and the continuation above serves them.
+ *   Measurements: DESIGN.md 3.7l, profiles/thinning/README.md (tools/thin_bench.py).
+ * HC_E_ARG: ctx, d_map or d_out null; method outside the enum; max_iterations outside 1..1024; d_status not 4-byte aligned;
+ * pitch < W on either side; H * pitch >= 2^32 on either side; nframes outside 1..(max_batch, 3 * max_batch with
+ * HC_OPT_PER_CHANNEL); nframes > 1 with a frame stride below H * pitch; a view that wraps the address space; overlapping views;
+ * one frame's scratch above the bound.  Every refusal lies above the first allocation or launch, and a refused call writes
+ * nothing. */
+enum { HC_THIN_ZHANGSUEN = 0, HC_THIN_GUOHALL = 1 };
+int hc_thinning_device(hc_ctx *ctx, const void *d_map, size_t pitch, size_t frame_stride, void *d_out, size_t out_pitch,
+                       size_t out_frame_stride, int nframes, int method, int max_iterations,
+                       void *d_status /* uint32 [nframes][2]; may be NULL */);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
