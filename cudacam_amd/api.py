@@ -76,6 +76,9 @@ DT_NONE = 2147483647
 # methods of hc_thinning_device (the header's HC_THIN_*) and the names Context.thinning takes for them
 THIN_ZHANGSUEN, THIN_GUOHALL = 0, 1
 THIN_METHODS = {"zhangsuen": THIN_ZHANGSUEN, "guohall": THIN_GUOHALL}
+# methods of hc_corner_response_device (the header's HC_CORNER_*) and the names Context.corner_response takes for them
+CORNER_MIN_EIGEN, CORNER_HARRIS = 0, 1
+CORNER_METHODS = {"min_eigen": CORNER_MIN_EIGEN, "harris": CORNER_HARRIS}
 # words of hc_last_hysteresis_schedule, in the order of the header's HC_SCHED_* indices
 SCHEDULE_FIELDS = ("launches", "lists", "loop", "hist_grid", "longest", "overflows", "tiles", "tile_rows", "waves", "panels", "frames")
 
@@ -90,7 +93,7 @@ ABI_SYMBOLS = [
     "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
     "hc_hough_segments_device", "hc_hough_walk_tables", "hc_hough_circles_device", "hc_hough_circle_geometry",
     "hc_connected_components_device", "hc_morphology_device", "hc_structuring_element", "hc_distance_transform_device",
-    "hc_thinning_device",
+    "hc_thinning_device", "hc_corner_response_device", "hc_good_features_device",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -165,6 +168,8 @@ def load_library(legacy=False):
     L.hc_structuring_element.argtypes = [i, i, C.POINTER(C.c_int8)]
     L.hc_distance_transform_device.argtypes = [vp, vp, sz, sz, i, i, i, vp, sz, sz, vp, sz, sz]
     L.hc_thinning_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, vp]
+    L.hc_corner_response_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, i, i, i, d]
+    L.hc_good_features_device.argtypes = [vp, vp, sz, sz, i, d, d, sz, vp, vp, vp, sz]
     L.hc_hough_circle_geometry.argtypes = [i, i, d, d, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
@@ -1178,6 +1183,114 @@ class Context:
             return skel.cpu().numpy(), status.cpu().numpy().view(np.uint32)
         maps, st = self._again_if_continued(skeleton)
         return maps, st[:, 0].copy(), st[:, 1].copy()
+
+    def corner_response_device(self, d_dx, d_dy, pitch, fs, d_response, out_pitch, out_fs, nframes, block_size=3, method=CORNER_MIN_EIGEN, k=0.04):
+        """cv::cornerMinEigenVal / cv::cornerHarris on given one-channel int16 derivative planes on device memory
+        (hc_corner_response_device, either mode): block_size 3, 5 or 7 with a replicated border, exact integer window sums, no
+        normalisation; float32 planes of W x H out.  Pitches and frame strides in bytes (input even, output multiples of 4); the
+        views must not overlap.  Asynchronous on the context stream; not a run."""
+        _ck(self.lib.hc_corner_response_device(self.handle, C.c_void_p(d_dx), C.c_void_p(d_dy), pitch, fs, C.c_void_p(d_response), out_pitch, out_fs,
+                                               int(nframes), int(block_size), int(method), float(k)))
+
+    def good_features_device(self, d_response, pitch, fs, nframes, quality_level, min_distance, candidate_capacity, d_corner_counts, d_corners,
+                             d_quality, corner_capacity):
+        """cv::goodFeaturesToTrack on float32 response planes of W x H on device memory (hc_good_features_device, either mode; the
+        form of cv::cuda::CornersDetector): d_corner_counts uint32 [nframes] (always the full counts), d_corners float32
+        [nframes][corner_capacity][2] = (x, y) by descending response, d_quality (or None) float32 [nframes][corner_capacity]
+        their responses; corner_capacity 0 (d_corners None): counts only.  Only the strongest candidate_capacity (1 .. 4096) local
+        maxima go on to the smallest-distance rule.  Asynchronous on the context stream; not a run."""
+        _ck(self.lib.hc_good_features_device(self.handle, C.c_void_p(d_response), pitch, fs, int(nframes), float(quality_level), float(min_distance),
+                                             int(candidate_capacity), C.c_void_p(d_corner_counts), C.c_void_p(d_corners or None), C.c_void_p(d_quality or None),
+                                             int(corner_capacity)))
+
+    @staticmethod
+    def _corner_method(method):
+        if isinstance(method, str):
+            if method.lower() not in CORNER_METHODS:
+                raise HipCannyError(f"corner_response: method must be one of {sorted(CORNER_METHODS)}, not {method!r}")
+            return CORNER_METHODS[method.lower()]
+        return int(method)
+
+    def _feature_buffers(self, n, max_corners, candidate_capacity, dev):
+        """(capacity, counts, corners, qualities): the output tensors of one good_features_device call"""
+        import torch
+        cap = int(candidate_capacity) if max_corners is None else int(max_corners)
+        return (cap, torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n, max(cap, 1), 2), dtype=torch.float32, device=dev),
+                torch.empty((n, max(cap, 1)), dtype=torch.float32, device=dev))
+
+    def _queue_response(self, gx, gy, resp, n, block_size, method, k):
+        """Queues the corner measure of tight int16 planes [n, H, W] into the tight float32 tensor resp; no host wait."""
+        self.corner_response_device(gx.data_ptr(), gy.data_ptr(), 2 * self.w, 2 * self.w * self.h, resp.data_ptr(), 4 * self.w, 4 * self.w * self.h, n,
+                                    block_size, method, k)
+
+    def _queue_features(self, resp, n, quality_level, min_distance, candidate_capacity, bufs):
+        """Queues the selection on a tight float32 tensor [n, H, W] into the tensors of _feature_buffers; no host wait."""
+        cap, counts, corners, quality = bufs
+        self.good_features_device(resp.data_ptr(), 4 * self.w, 4 * self.w * self.h, n, quality_level, min_distance, candidate_capacity, counts.data_ptr(),
+                                  corners.data_ptr() if cap else None, quality.data_ptr() if cap else None, cap)
+
+    def _features_from(self, n, bufs):
+        """Waits for the context stream; ([float32 (count_f, 2) = (x, y)], [float32 (count_f,) responses]) of the tensors."""
+        cap, counts, corners, quality = bufs
+        self.sync()
+        cnt = counts.cpu().numpy().view(np.uint32)
+        xy, q = corners.cpu().numpy(), quality.cpu().numpy()
+        keep = [min(int(cnt[f]), cap) for f in range(n)]
+        return [xy[f, :keep[f]].copy() for f in range(n)], [q[f, :keep[f]].copy() for f in range(n)]
+
+    def corner_response(self, dx, dy, block_size=3, method="min_eigen", k=0.04):
+        """Host or torch int16 planes dx, dy [n, H, W] (or one plane each) in, the float32 corner measure [n, H, W] out as a torch
+        tensor on the device (hc_corner_response_device): method "min_eigen" or "harris" (k: the Harris constant)."""
+        import torch
+        n = 1 if (dx.ndim if isinstance(dx, torch.Tensor) else np.asarray(dx).ndim) == 2 else len(dx)
+        gx, gy = self._planes_on_device(dx, n, "corner_response: dx"), self._planes_on_device(dy, n, "corner_response: dy")
+        resp = torch.empty((n, self.h, self.w), dtype=torch.float32, device=gx.device)
+        self._wait_for_torch()
+        self._queue_response(gx, gy, resp, n, block_size, self._corner_method(method), k)
+        self.sync()
+        return resp
+
+    def good_features(self, response, quality_level, min_distance, max_corners=None, candidate_capacity=4096):
+        """Host or torch float32 response planes [n, H, W] (or one plane) in; per frame the corners float32 (count, 2) = (x, y) by
+        descending response and their responses float32 (count,) out, as hc_good_features_device states them: at most
+        max_corners a frame (None: all that are kept)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(response, torch.Tensor):
+            d = response
+        else:
+            d = torch.from_numpy(np.ascontiguousarray(response))
+        if d.dtype != torch.float32:
+            raise HipCannyError(f"good_features: the response must be float32, not {d.dtype}")
+        d = (d if d.ndim == 3 else d[None]).to(dev).contiguous()
+        if d.ndim != 3 or tuple(d.shape[1:]) != (self.h, self.w):
+            raise HipCannyError(f"good_features: planes {tuple(d.shape)} do not match the context's {(self.h, self.w)}")
+        n = d.shape[0]
+        bufs = self._feature_buffers(n, max_corners, candidate_capacity, dev)
+        self._wait_for_torch()
+        self._queue_features(d, n, quality_level, min_distance, candidate_capacity, bufs)
+        return self._features_from(n, bufs)
+
+    def features(self, frames, ksize=3, block_size=3, method="min_eigen", k=0.04, quality_level=0.01, min_distance=10, max_corners=1000, blur=None,
+                 candidate_capacity=4096):
+        """cv::goodFeaturesToTrack of u8 frames (1-channel contexts): cv::GaussianBlur (blur = (ksize, sigma), optional), the
+        derivatives of aperture ksize (derivatives_device), the corner measure and the selection chained on the device with no
+        host copy and no synchronisation in between.  Returns (corners, responses) per frame as good_features gives them."""
+        import torch
+        if self.c != 1:
+            raise ValueError("features: a 1-channel context is required (the derivative planes of 3-channel frames are interleaved)")
+        raw, n, row, fs = self._device_view(frames, "features")
+        m = self._corner_method(method)
+        # every tensor first, then one wait for torch's stream (_blurred waits once more, before anything of the chain is queued)
+        gx, gy = torch.empty_like(raw, dtype=torch.int16), torch.empty_like(raw, dtype=torch.int16)
+        resp = torch.empty((n, self.h, self.w), dtype=torch.float32, device=raw.device)
+        bufs = self._feature_buffers(n, max_corners, candidate_capacity, raw.device)
+        self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)   # (raw stays referenced until the call has synchronised)
+        self.derivatives_device(src.data_ptr(), row, fs, gx.data_ptr(), gy.data_ptr(), 2 * row, 2 * fs, n, ksize)
+        self._queue_response(gx, gy, resp, n, block_size, m, k)
+        self._queue_features(resp, n, quality_level, min_distance, candidate_capacity, bufs)
+        return self._features_from(n, bufs)
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -42,6 +42,10 @@ hipError_t launch_distance_transform(const DistParams &p, hipStream_t s);  // di
 hipError_t launch_thin_pack(const ThinPackParams &p, hipStream_t s);
 hipError_t launch_thin_step(const ThinStepParams &p, int sub, int iteration, hipStream_t s);
 hipError_t launch_thin_unpack(const ThinUnpackParams &p, hipStream_t s);
+// corners.hip (the product library only): k_corner_response; one pass of the kernels of hc_good_features_device (p.hist and p.state
+// must be zero when it starts)
+hipError_t launch_corner_response(const CornerParams &p, hipStream_t s);
+hipError_t launch_good_features(const FeatParams &p, hipStream_t s);
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

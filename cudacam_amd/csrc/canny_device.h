@@ -145,6 +145,34 @@ static __device__ __forceinline__ u32 peak_rank(const uint2 *pk, u32 np, uint2 m
   return rank;
 }
 
+// The loop of k_circle_sift and k_feat_sift, for ONE wave (a workgroup of 64 threads that all call it): the nc ranked records
+// in[] = (weight, x, y, -) are gone through in order, and one is kept iff every record kept before it lies at squared distance
+// >= min_d2; the kept records -> out[] in that order, their number is returned (wave-uniform).  kept_xy: LDS, nc entries at least;
+// the lanes compare the candidate with 64 kept records per trip.  Sequential by definition.
+static __device__ __forceinline__ u32 sift_min_distance(const int4 *in, u32 nc, long long min_d2, int2 *kept_xy, int4 *out)
+{
+  const int lane = threadIdx.x;
+  u32 nk = 0;  // wave-uniform: it changes by ballots only
+  for (u32 c = 0; c < nc; ++c) {
+    const int4 cand = in[c];  // one address for the whole wave
+    bool too_close = false;
+    for (u32 j = lane; j < nk; j += 64) {
+      const int2 k = kept_xy[j];
+      const long long ddx = (long long)cand.y - k.x, ddy = (long long)cand.z - k.y;
+      too_close = too_close || ddx * ddx + ddy * ddy < min_d2;
+    }
+    if (__ballot(too_close) == 0) {
+      if (lane == 0) {
+        kept_xy[nk] = make_int2(cand.y, cand.z);
+        out[nk] = cand;
+      }
+      ++nk;
+      __syncthreads();  // (one wave: the kept list as the next candidate's lanes read it)
+    }
+  }
+  return nk;
+}
+
 // Mode O, per-frame thresholds (FrontParams::frame_thr != null): the pair of the work item's frame as the kernel compares
 // it (the normalisation itself is frame_threshold_pair, canny_params.h, which the host can call too).  `frame` is wave-uniform:
 // one scalar load of the pair's 8 bytes and a few scalar instructions per work item, the results in SGPRs.

@@ -265,6 +265,70 @@ HC_HOST_DEVICE inline u32 thin_removed(const ThinRow &N, const ThinRow &C, const
   }
 }
 
+// k_corner_response (corners.hip): the Harris / smallest-eigenvalue measure of one-channel int16 derivative planes
+// (hc_corner_response_device, where the arithmetic is stated).  The lane layout of k_deriv16: a wave owns a strip of
+// CORNER_STRIP_W columns, lane l the 4 pixels at strip * CORNER_STRIP_W - 4 + 4 l, lanes 0 and 63 are halo (4 >= block_size / 2
+// columns); a work item is (frame, strip, CORNER_CHUNK_ROWS output rows) with a warm-up of block_size - 1 rows.
+constexpr int CORNER_MIN_EIGEN = 0, CORNER_HARRIS = 1;  // HC_CORNER_* (host_plan.h asserts the match)
+constexpr int CORNER_STRIP_W = 248;
+constexpr int CORNER_LANE_PX = 4;
+constexpr int CORNER_CHUNK_ROWS = 64;
+inline bool corner_block_ok(int b) { return b == 3 || b == 5 || b == 7; }
+inline int corner_strips(int W) { return (W + CORNER_STRIP_W - 1) / CORNER_STRIP_W; }
+inline int corner_chunks(int H) { return (H + CORNER_CHUNK_ROWS - 1) / CORNER_CHUNK_ROWS; }
+struct CornerParams {
+  const uint8_t *dx, *dy;  // int16 planes of W x H, one channel; one pitch and one frame stride (bytes, even)
+  size_t pitch, frame_stride;
+  uint8_t *out;            // float32 planes of W x H; exactly [row, row + 4 W) of a row is written
+  size_t out_pitch, out_frame_stride;
+  int W, H, nframes;
+  int block_size, method;  // 3 / 5 / 7; CORNER_MIN_EIGEN / CORNER_HARRIS
+  float k;                 // (float)harris_k; 0 with CORNER_MIN_EIGEN
+  int in_align;            // 8 / 4 / 2: what both bases, the pitch and the frame stride are multiples of
+  int out_align;           // 16 / 8 / 4 likewise
+  int nstrips, nchunks, total_items;  // total_items = nframes * nstrips * nchunks
+};
+
+// The kernels of hc_good_features_device (corners.hip).  A key is the bit pattern of a response v > 0, else 0 (feat_key): keys
+// order as the values do, so every comparison is an integer one.  The cut at candidate_capacity is an exact radix select on the
+// key, FEAT_PASSES passes of FEAT_BINS bins at most, from the top digit down (feat_digit).
+// k_feat_plane: a workgroup of 4 waves takes FEAT_GROUP_ROWS rows of a frame, wave w the rows r0 + w, r0 + w + 4, ..; in a row a
+// trip covers FEAT_TRIP_PX centre columns with the lanes 1 .. 62, lanes 0 and 63 hold the neighbour columns.
+constexpr int FEAT_MAX_CANDIDATES = 4096;  // candidate_capacity at most: the kept list of the sift sits in LDS, as k_circle_sift's
+constexpr int FEAT_PASSES = 3;
+constexpr int FEAT_BINS = 2048;
+constexpr int FEAT_GROUP_ROWS = 32;
+constexpr int FEAT_TRIP_PX = 62;
+constexpr int FEAT_STATE_WORDS = 8;
+// the words of a frame's state: the largest key of the frame; the cut key T (built digit by digit); how many candidates are
+// still to admit among those that agree with T so far (after the last pass: the ties admitted); 1: the frame has no more
+// candidates than the capacity, all are admitted; candidates with key > T; candidates admitted; corners kept
+enum { FEAT_MAXKEY = 0, FEAT_T = 1, FEAT_NEED = 2, FEAT_ALL = 3, FEAT_NGT = 4, FEAT_NCAND = 5, FEAT_NKEPT = 6 };
+HC_HOST_DEVICE inline u32 feat_key(u32 bits) { return ((int32_t)bits > 0 && bits <= 0x7F800000u) ? bits : 0u; }
+HC_HOST_DEVICE inline int feat_shift(int pass) { return pass == 0 ? 21 : pass == 1 ? 10 : 0; }  // digits of 11, 11 and 10 bits
+HC_HOST_DEVICE inline u32 feat_digit(u32 key, int pass) { return pass == 0 ? key >> 21 : pass == 1 ? (key >> 10) & 0x7FFu : key & 0x3FFu; }
+// the bits of a key above the digit of `pass`: what the earlier passes fixed
+HC_HOST_DEVICE inline u32 feat_prefix(u32 key, int pass) { return pass == 0 ? 0u : pass == 1 ? key >> 21 : key >> 10; }
+inline int feat_groups(int H) { return (H + FEAT_GROUP_ROWS - 1) / FEAT_GROUP_ROWS; }
+struct FeatParams {
+  const uint8_t *plane;    // float32 planes of W x H, 4-byte aligned
+  size_t pitch, frame_stride;
+  int W, H, nframes, ngroups;
+  float quality;           // (float)quality_level
+  long long min_d2;
+  int candidate_capacity;  // 1 .. FEAT_MAX_CANDIDATES
+  size_t corner_capacity;
+  u32 *counts;             // [nframes]
+  float *corners;          // [nframes][corner_capacity][2], or null with corner_capacity 0
+  float *quality_out;      // [nframes][corner_capacity], or null
+  // scratch, per frame of the pass
+  int32_t *ranked, *kept;  // [candidate_capacity] int4 (key, x, y, 0): in the order of the cut / after the sift
+  u32 *cand;               // [candidate_capacity] (key, index)
+  u32 *hist;               // [FEAT_BINS]
+  u32 *state;              // [FEAT_STATE_WORDS]
+  u32 *rows;               // [H][2]: candidates with key > T / == T of the row, then their exclusive prefix sums
+};
+
 // k_hist256 (stats.hip): 256-bin histograms of u8 frames, all channels pooled.  A work item is (frame, chunk of rows); a wave
 // counts its rows into a wave-private LDS histogram and adds the non-zero bins to hist[frame] with global atomics.
 constexpr int HIST_MAX_CHUNK_ROWS = 64, HIST_MIN_CHUNK_ROWS = 8;

@@ -342,4 +342,40 @@ int hc_thinning_device(hc_ctx *c, const void *d_map, size_t pitch, size_t fs, vo
   return HC_OK;
 }
 
+// One launch of k_corner_response on the context stream (corners.hip).  Not a run, exactly as hc_derivatives_device is none, whose
+// planes it reads: no run writes an int16 or a float32 plane, so nothing is completed first.  No scratch.
+int hc_corner_response_device(hc_ctx *c, const void *d_dx, const void *d_dy, size_t pitch, size_t fs, void *d_response, size_t out_pitch, size_t out_fs, int n,
+                              int block_size, int method, double harris_k)
+{
+  if (!c) return fail(HC_E_ARG, "hc_corner_response_device: null argument");
+  const CornerPlan P = plan_corner_response(c->W, c->H, c->max_batch * (c->per_channel ? 3 : 1), View{ (uintptr_t)d_dx, pitch, fs }, (uintptr_t)d_dy,
+                                            View{ (uintptr_t)d_response, out_pitch, out_fs }, n, block_size, method, harris_k);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_corner_response_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  // every refusal lies above
+  HIPCK(launch_corner_response(P.cp, c->stream));
+  return HC_OK;
+}
+
+// Per pass the zeroing of the histograms and state words and the kernels of launch_good_features on the context stream
+// (corners.hip).  Not a run, as hc_hough_circles_device; no run writes a float32 plane, so nothing is completed first.  Successive
+// calls share the scratch and are ordered by the stream they are queued on (include/hipcanny.h).
+int hc_good_features_device(hc_ctx *c, const void *d_response, size_t pitch, size_t fs, int n, double quality_level, double min_distance, size_t candidate_capacity,
+                            void *d_corner_counts, void *d_corners, void *d_quality, size_t corner_capacity)
+{
+  if (!c) return fail(HC_E_ARG, "hc_good_features_device: null argument");
+  const FeatPlan P = plan_good_features(c->W, c->H, c->max_batch * (c->per_channel ? 3 : 1), View{ (uintptr_t)d_response, pitch, fs }, n, quality_level, min_distance,
+                                        candidate_capacity, (uintptr_t)d_corner_counts, (uintptr_t)d_corners, (uintptr_t)d_quality, corner_capacity, c->hough_bound);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_good_features_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  // every refusal lies above.  A larger scratch: what is queued on the context stream may still read the old one
+  if (int rc = ensure_scratch(c, c->feat, P.scratch_bytes)) return rc;
+  for (int k = 0; k < P.passes; ++k) {
+    const FeatPass fp = feat_pass(P, k, (uintptr_t)c->feat.p);
+    HIPCK(hipMemsetAsync((void *)fp.zero, 0, fp.zero_bytes, c->stream));
+    HIPCK(launch_good_features(fp.fp, c->stream));
+  }
+  return HC_OK;
+}
+
 }  // extern "C"

@@ -228,6 +228,9 @@ struct hc_ctx {
   // hc_thinning_device: the two bit planes and the removal table of every frame of one pass (thin_pass, host_plan.h), bounded by
   // hough_bound as well
   hc::DeviceScratch thin;
+  // hc_good_features_device: the candidate, ranked and kept lists, the histogram, the state words and the per-row counts of every
+  // frame of one pass (feat_pass, host_plan.h), bounded by hough_bound as well
+  hc::DeviceScratch feat;
 };
 
 namespace hc {

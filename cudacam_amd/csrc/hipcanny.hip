@@ -615,7 +615,7 @@ void hc_destroy(hc_ctx *c)
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   for (void *q : { (void *)c->d_in, (void *)c->d_mono, (void *)c->d_out, (void *)c->d_blur, (void *)c->d_nms, (void *)c->d_sx, (void *)c->d_sy, (void *)c->d_bplane, (void *)c->d_dump }) (void)hipFree(q);
-  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab, &c->seg_items, &c->seg_tab, &c->circles, &c->ccl_items, &c->morph_mid, &c->thin }) (void)hipFree(q->p);
+  for (DeviceScratch *q : { &c->hist256, &c->edge_items, &c->hough, &c->hough_tab, &c->seg_items, &c->seg_tab, &c->circles, &c->ccl_items, &c->morph_mid, &c->thin, &c->feat }) (void)hipFree(q->p);
   for (Slot &q : c->slot) free_slot(q);
   free_debug_buffers(c);
   for (auto &e : c->prof.evpool) if (e) (void)hipEventDestroy(e);

@@ -2,7 +2,7 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology, plan_distance_transform, plan_thinning; the taps rule of
+// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology, plan_distance_transform, plan_thinning, plan_corner_response, plan_good_features; the taps rule of
 // hc_gaussian_taps_q8, the table rules of hc_hough_tables and hc_hough_walk_tables and the geometry of hc_hough_circle_geometry).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
@@ -1516,6 +1516,126 @@ inline ThinPass thin_pass(const ThinPlan &P, int k, uintptr_t scratch)
   R.unpack.plane_a = A; R.unpack.removed = T; R.unpack.nframes = nf;
   R.unpack.out += (size_t)f0 * R.unpack.out_frame_stride;
   if (R.unpack.status) R.unpack.status += 2 * (size_t)f0;
+  return R;
+}
+
+// ---- hc_corner_response_device --------------------------------------------------------------------
+static_assert(CORNER_MIN_EIGEN == HC_CORNER_MIN_EIGEN && CORNER_HARRIS == HC_CORNER_HARRIS, "canny_params.h names the header's methods");
+// Everything the entry refuses and decides, but for the context pointer: one launch of k_corner_response, no scratch, no passes.
+// A refused plan holds nothing but its text.
+struct CornerPlan { const char *error = nullptr; CornerParams cp{}; };
+inline CornerPlan plan_corner_response(int W, int H, int max_frames, const View &dx, uintptr_t dy, const View &out, int n, int block_size, int method, double harris_k)
+{
+  CornerPlan P;
+  auto refuse = [](const char *text) { CornerPlan R; R.error = text; return R; };
+  if (!dx.p || !dy || !out.p) return refuse("null argument");
+  if (!corner_block_ok(block_size)) return refuse("block_size must be 3, 5 or 7");
+  if (method != CORNER_MIN_EIGEN && method != CORNER_HARRIS) return refuse("method must be HC_CORNER_MIN_EIGEN or HC_CORNER_HARRIS");
+  if (method == CORNER_HARRIS && !std::isfinite(harris_k)) return refuse("harris_k must be finite");
+  if (W < 1 || H < 1) return refuse("width and height must be positive");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  const size_t row16 = 2 * (size_t)W, row32 = 4 * (size_t)W;
+  const View dyv{ dy, dx.pitch, dx.fs };
+  if (const ViewFault f = check_view(dx, row16, H, n, 2, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  if (const ViewFault f = check_view(dyv, row16, H, n, 2, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  if (const ViewFault f = check_view(out, row32, H, n, 4, true)) return refuse(f == VIEW_ALIGN ? "d_response, out_pitch and out_frame_stride must be multiples of 4" : VIEW_FAULT_TEXT[f]);
+  uintptr_t ex = 0, ey = 0, eo = 0;
+  if (!view_end(dx, row16, H, n, &ex) || !view_end(dyv, row16, H, n, &ey) || !view_end(out, row32, H, n, &eo)) return refuse("a view wraps the address space");
+  if ((dx.p < eo && out.p < ex) || (dy < eo && out.p < ey)) return refuse("a derivative plane and the response view overlap");
+  CornerParams &c = P.cp;
+  c.dx = (const uint8_t *)dx.p; c.dy = (const uint8_t *)dy; c.pitch = dx.pitch; c.frame_stride = dx.fs;
+  c.out = (uint8_t *)out.p; c.out_pitch = out.pitch; c.out_frame_stride = out.fs;
+  c.W = W; c.H = H; c.nframes = n; c.block_size = block_size; c.method = method;
+  c.k = method == CORNER_HARRIS ? (float)harris_k : 0.0f;
+  const uintptr_t ia = dx.p | dy | dx.pitch | dx.fs, oa = out.p | out.pitch | out.fs;
+  c.in_align = (ia & 7u) == 0 ? 8 : (ia & 3u) == 0 ? 4 : 2;
+  c.out_align = (oa & 15u) == 0 ? 16 : (oa & 7u) == 0 ? 8 : 4;
+  c.nstrips = corner_strips(W); c.nchunks = corner_chunks(H);
+  const long long items = (long long)n * c.nstrips * c.nchunks;
+  if (items > 0x7FFFFFF0ll) return refuse("too many work items (nframes x strips x row chunks)");
+  c.total_items = (int)items;
+  return P;
+}
+
+// ---- hc_good_features_device ----------------------------------------------------------------------
+// The smallest int64 whose double is >= min_distance^2, capped at 2^62 as hough_circle_geometry caps its own (no two pixels lie
+// 2^62 apart: a larger bound is that one).  min_distance finite and >= 0.
+inline long long feat_min_d2(double min_distance)
+{
+  const double v = min_distance * min_distance;
+  return v >= 4611686018427387904.0 ? (1ll << 62) : (long long)std::ceil(v);
+}
+// Everything the entry refuses and decides, but for the context pointer.  A call is, per pass, the zeroing of the histograms and
+// state words and one launch_good_features.  The context's scratch holds, per frame of a pass, the ranked and kept lists (16 bytes
+// a candidate each), the candidate list (8 bytes), the histogram, the state words and two words a row: O(candidate_capacity + rows
+// + bins), no plane.  It falls under the context's scratch bound: a batch is cut into passes of as many whole frames as fit.  fp
+// describes the first pass with null scratch pointers; feat_pass gives pass k.  A refused plan holds nothing but its text.
+struct FeatPlan {
+  const char *error = nullptr;
+  FeatParams fp{};
+  int frames = 0, frames_per_pass = 0, passes = 0;
+  size_t frame_list_bytes = 0, frame_cand_bytes = 0, frame_hist_bytes = 0, frame_state_bytes = 0, frame_rows_bytes = 0, frame_bytes = 0, scratch_bytes = 0;
+};
+inline FeatPlan plan_good_features(int W, int H, int max_frames, const View &plane, int n, double quality_level, double min_distance, size_t candidate_capacity,
+                                   uintptr_t counts, uintptr_t corners, uintptr_t quality, size_t corner_capacity, size_t scratch_bound)
+{
+  FeatPlan P;
+  auto refuse = [](const char *text) { FeatPlan R; R.error = text; return R; };
+  if (!plane.p || !counts) return refuse("null argument");
+  if (corner_capacity && !corners) return refuse("d_corners is null with corner_capacity > 0");
+  if (counts & 3u) return refuse("d_corner_counts must be 4-byte aligned");
+  if (corners & 7u) return refuse("d_corners must be 8-byte aligned");
+  if (quality & 3u) return refuse("d_quality must be 4-byte aligned");
+  if (!std::isfinite(quality_level) || !(quality_level > 0) || quality_level > 1) return refuse("quality_level must lie in (0, 1]");
+  if (!std::isfinite(min_distance) || min_distance < 0) return refuse("min_distance must be finite and not negative");
+  if (candidate_capacity < 1 || candidate_capacity > (size_t)FEAT_MAX_CANDIDATES) return refuse("candidate_capacity must lie in 1 .. 4096");
+  if (W < 1 || H < 1) return refuse("width and height must be positive");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  if (const ViewFault f = check_view(plane, 4 * (size_t)W, H, n, 4, true)) return refuse(f == VIEW_ALIGN ? "d_response, pitch and frame_stride must be multiples of 4" : VIEW_FAULT_TEXT[f]);
+  uintptr_t end = 0;
+  if (!view_end(plane, 4 * (size_t)W, H, n, &end)) return refuse("a view wraps the address space");
+  if (corner_capacity > SIZE_MAX / 8 / (size_t)n) return refuse("corner_capacity * 8 * nframes overflows size_t");
+  P.frame_list_bytes = candidate_capacity * 16; P.frame_cand_bytes = candidate_capacity * 8;
+  P.frame_hist_bytes = (size_t)FEAT_BINS * 4; P.frame_state_bytes = (size_t)FEAT_STATE_WORDS * 4; P.frame_rows_bytes = (size_t)H * 8;
+  P.frame_bytes = 2 * P.frame_list_bytes + P.frame_cand_bytes + P.frame_hist_bytes + P.frame_state_bytes + P.frame_rows_bytes;
+  if (scratch_bound < P.frame_bytes) return refuse("one frame's lists and tables exceed the context's scratch bound");
+  P.frames = n;
+  P.frames_per_pass = (int)std::min<size_t>(std::min<size_t>((size_t)n, scratch_bound / P.frame_bytes), HOUGH_MAX_PASS_FRAMES);
+  P.passes = (n + P.frames_per_pass - 1) / P.frames_per_pass;
+  P.scratch_bytes = (size_t)P.frames_per_pass * P.frame_bytes;
+  FeatParams &f = P.fp;
+  f.plane = (const uint8_t *)plane.p; f.pitch = plane.pitch; f.frame_stride = plane.fs;
+  f.W = W; f.H = H; f.nframes = P.frames_per_pass; f.ngroups = feat_groups(H);
+  f.quality = (float)quality_level; f.min_d2 = feat_min_d2(min_distance);
+  f.candidate_capacity = (int)candidate_capacity; f.corner_capacity = corner_capacity;
+  f.counts = (u32 *)counts; f.corners = (float *)corners; f.quality_out = (float *)quality;
+  return P;
+}
+
+// Pass k of a plan that was not refused (0 <= k < passes), on `scratch` (scratch_bytes, 16-byte aligned): the sections lie in the
+// order ranked | kept | candidates | histograms | state words | rows, the widest alignment first; [zero, zero + zero_bytes) is
+// what the pass zeroes first: the histograms and the state words of its frames (the two sections are neighbours)
+struct FeatPass { FeatParams fp; uintptr_t zero; size_t zero_bytes; };
+inline FeatPass feat_pass(const FeatPlan &P, int k, uintptr_t scratch)
+{
+  FeatPass R{ P.fp, 0, 0 };
+  FeatParams &f = R.fp;
+  const int f0 = k * P.frames_per_pass;
+  const size_t fpp = (size_t)P.frames_per_pass;
+  f.nframes = std::min(P.frames_per_pass, P.frames - f0);
+  f.plane += (size_t)f0 * f.frame_stride;
+  f.counts += f0;
+  if (f.corners) f.corners += (size_t)f0 * f.corner_capacity * 2;
+  if (f.quality_out) f.quality_out += (size_t)f0 * f.corner_capacity;
+  uintptr_t q = scratch;
+  f.ranked = (int32_t *)q; q += fpp * P.frame_list_bytes;
+  f.kept = (int32_t *)q;   q += fpp * P.frame_list_bytes;
+  f.cand = (u32 *)q;       q += fpp * P.frame_cand_bytes;
+  f.hist = (u32 *)q;       q += fpp * P.frame_hist_bytes;
+  f.state = (u32 *)q;      q += fpp * P.frame_state_bytes;
+  f.rows = (u32 *)q;
+  R.zero = (uintptr_t)f.hist;
+  R.zero_bytes = fpp * P.frame_hist_bytes + (size_t)f.nframes * P.frame_state_bytes;
   return R;
 }
 

@@ -12,7 +12,7 @@
 //   k_circle_rank   the comparison loop of k_hough_rank (peak_rank, canny_device.h): a lane per peak; ranks below centre_capacity
 //                   write (votes, cx, cy) into the ranked list.
 //   k_circle_sift   one wave per frame goes through the ranked centres in order; the kept list sits in LDS (8 bytes a centre) and
-//                   the lanes compare the candidate with 64 kept centres per trip.  Sequential by definition.
+//                   the lanes compare the candidate with 64 kept centres per trip (sift_min_distance, canny_device.h).
 //   k_circle_radii  a workgroup per (frame, kept-centre slot): the histogram of the distances of the frame's points from the
 //                   centre, in LDS with LDS atomics whose result nobody reads, then the radius rule by the workgroup's first wave,
 //                   64 radii per trip.  <false>: the centre's circle count -> items.  <true>: the histogram again, and the circles
@@ -89,24 +89,7 @@ __global__ __launch_bounds__(64) void k_circle_sift(const CircleParams p)
   const u32 nc = min(p.npeaks[frame], (u32)p.centre_capacity);
   const int4 *in = reinterpret_cast<const int4 *>(p.ranked) + (size_t)frame * p.centre_capacity;
   int4 *out = reinterpret_cast<int4 *>(p.kept) + (size_t)frame * p.centre_capacity;
-  u32 nk = 0;  // wave-uniform: it changes by ballots only
-  for (u32 c = 0; c < nc; ++c) {
-    const int4 cand = in[c];  // one address for the whole wave
-    bool too_close = false;
-    for (u32 j = lane; j < nk; j += 64) {
-      const int2 k = kept_xy[j];
-      const long long ddx = (long long)cand.y - k.x, ddy = (long long)cand.z - k.y;
-      too_close = too_close || ddx * ddx + ddy * ddy < p.min_d2;
-    }
-    if (__ballot(too_close) == 0) {
-      if (lane == 0) {
-        kept_xy[nk] = make_int2(cand.y, cand.z);
-        out[nk] = cand;
-      }
-      ++nk;
-      __syncthreads();  // (one wave: the kept list as the next candidate's lanes read it)
-    }
-  }
+  const u32 nk = sift_min_distance(in, nc, p.min_d2, kept_xy, out);  // (canny_device.h: shared with k_feat_sift)
   if (lane == 0) p.nkept[frame] = nk;
 }
 

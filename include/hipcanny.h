@@ -721,6 +721,83 @@ int hc_thinning_device(hc_ctx *ctx, const void *d_map, size_t pitch, size_t fram
                        size_t out_frame_stride, int nframes, int method, int max_iterations,
                        void *d_status /* uint32 [nframes][2]; may be NULL */);
 
+/* Corners on the device, the other half of a feature front end: the Harris / smallest-eigenvalue measure of given derivatives
+ * (cv::cornerHarris / cv::cornerMinEigenVal, cv::cuda::createHarrisCorner / createMinEigenValCorner) and the strong, well-separated
+ * local maxima of a response plane (cv::goodFeaturesToTrack, cv::cuda::createGoodFeaturesToTrackDetector), chained like the edge
+ * points and the Hough entries (cudacam_amd/csrc/corners.hip).  The semantics are stated here and restated in tests/corner_ref.py
+ * (numpy); like the rest of Mode O they are the library's own statement, not pinned against a build of OpenCV, and every deviation
+ * from OpenCV is named: border, units, interior rule, capacity.  W, H: the context's frame size.
+ *
+ * hc_corner_response_device.
+ * Input.  d_dx, d_dy: ONE-channel int16 planes of W x H with a common pitch and frame stride (bytes), exactly what
+ *   hc_derivatives_device writes on a 1-channel context, at any ksize; any int16 value is legal, -32768 included.  Nothing of the
+ *   input is written.
+ * Window.  block_size B is 3, 5 or 7, centred; window positions are clamped to the frame (replicate), as the derivative entry
+ *   clamps.  DEVIATION (border): OpenCV's box filter reflects (BORDER_REFLECT_101 by default), so the results differ from OpenCV's
+ *   in the outermost B / 2 rows and columns -- on top of what the derivatives' own border does.
+ * Sums.  Over the B x B window a = sum dx^2, b = sum dx dy, c = sum dy^2, as EXACT integers (they do not fit 32 bits: 49 * 2^30 at
+ *   most); the order of summation cannot matter.
+ * Response.  fa = (float)a, fb = (float)b, fc = (float)c, each one conversion of the exact integer, round to nearest even.  Every
+ *   step below is one rounded float32 operation, the root correctly rounded:
+ *   HC_CORNER_MIN_EIGEN: h = 0.5f fa, g = 0.5f fc, d = h - g; r = (h + g) - sqrtf(d d + fb fb).
+ *   HC_CORNER_HARRIS:    k = (float)harris_k, t = fa + fc;    r = (fa fc - fb fb) - (k t) t.
+ *   DEVIATION (units): there is no normalisation; values are in derivative^2 (min-eigen) or derivative^4 (Harris) units.
+ *   OpenCV scales the derivatives of aperture ksize by s = 1 / (255 * 2^(ksize-1) * B) first, so its values are s^2 (min-eigen) or
+ *   s^4 (Harris) times these; quality_level below is relative, so the corner selection does not depend on the factor.
+ * Memory.  No byte outside [row, row + 2 W) of an input row is read, none outside [row, row + 4 W) of an output row is written;
+ *   both sides may be ROIs of larger planes.  Alignment: d_dx, d_dy, pitch, frame_stride even; d_response, out_pitch,
+ *   out_frame_stride multiples of 4; wider alignment (8 on the input, 8 / 16 on the output) gets wider accesses.  Offsets are
+ *   32-bit: H * pitch and H * out_pitch must be below 2^32.
+ * Asynchronous on the context stream (hc_set_stream honoured); behind hc_derivatives_device and ahead of hc_good_features_device
+ *   it needs no synchronisation.  Contexts of either mode and any `channels`: the planes have one channel.  It is not a run,
+ *   exactly as hc_derivatives_device is none.  No scratch.
+ * HC_E_ARG: ctx, d_dx, d_dy or d_response null; misalignment; pitch < 2 W, out_pitch < 4 W; H * pitch or H * out_pitch >= 2^32;
+ * nframes outside 1..(max_batch, 3 * max_batch with HC_OPT_PER_CHANNEL), the bound of hc_hough_circles_device; nframes > 1 with a
+ * frame stride below H * pitch; a view that wraps the address space; block_size not 3, 5, 7; method outside the enum; harris_k not
+ * finite with HC_CORNER_HARRIS (it is ignored with HC_CORNER_MIN_EIGEN); the byte range of the response view overlapping that of
+ * either derivative plane.  Every refusal lies above the launch, and a refused call writes nothing. */
+enum { HC_CORNER_MIN_EIGEN = 0, HC_CORNER_HARRIS = 1 };
+int hc_corner_response_device(hc_ctx *ctx, const void *d_dx, const void *d_dy, size_t pitch, size_t frame_stride /* int16, ONE channel */,
+                              void *d_response, size_t out_pitch, size_t out_frame_stride /* float32, W x H */,
+                              int nframes, int block_size, int method, double harris_k);
+
+/* hc_good_features_device: cv::goodFeaturesToTrack on a float32 response plane of W x H -- the form of cv::cuda::CornersDetector, a
+ * function of the plane alone; the plane may be the caller's own, and nothing of it is written.  Frames are independent.
+ * Keys.  key(v) = the bits of v as uint32 if v > 0.0f, else 0: NaN, -0 and negatives give 0, denormals keep their bits, +inf
+ *   orders above every finite value.  All comparisons below are on keys, so they are integer comparisons.
+ * Threshold.  M is the value with the largest key among ALL W * H pixels of the frame; q = (float)quality_level; t = M q, one
+ *   rounded product.  A pixel passes iff key(v) > key(t).  M with key 0 gives no corners (and so does M = +inf).
+ * Candidates.  A passing pixel with 1 <= x <= W - 2 and 1 <= y <= H - 2 whose key is >= the keys of all eight neighbours:
+ *   OpenCV's val == dilate(val), on the interior.  DEVIATION (interior rule): the outermost rows and columns count for M and as
+ *   neighbours but are never corners; frames with W < 3 or H < 3 have none.  A plateau makes every one of its pixels a candidate.
+ * Order and cut.  Key descending, ties by ascending index y W + x.  Only the first candidate_capacity (1 .. 4096) candidates in that
+ *   order go on.  DEVIATION (capacity): cv::goodFeaturesToTrack sifts all of them; this is the analogue of the centre cut of
+ *   hc_hough_circles_device, and the one way the kept set can differ from OpenCV's rule on the same plane.
+ * Smallest distance.  min_d2 = ceil(min_distance * min_distance), the product as a double -- the smallest int64 whose double is >=
+ *   it --, capped at 2^62 as in hc_hough_circle_geometry; min_distance 0 gives 0.  The candidates are gone through in that order,
+ *   and one is kept iff every candidate kept before it lies at squared distance >= min_d2 (int64 arithmetic).
+ * Output.  d_corner_counts[f] is the full number kept, always.  The slot of frame f (corner_capacity corners) receives its first
+ *   min(count, corner_capacity) corners as ((float)x, (float)y): the memory of a CV_32FC2 / std::vector<cv::Point2f>.  With
+ *   d_quality, slot f of it (corner_capacity floats) receives their response values bit for bit.  corner_capacity 0 gives the
+ *   counts only.  Nothing else is written.
+ * Asynchronous on the context stream (hc_set_stream honoured); not a run, as hc_hough_circles_device is none.
+ * Scratch.  Owned by the context, allocated on first use, grown when a call needs more, freed by hc_destroy: per frame of a pass
+ *   40 bytes a candidate of capacity, a histogram of 2048 words, 8 state words and 2 words a row -- no plane --, under the bound of
+ *   hc_hough_lines_device's scratch (256 MiB).  A batch that does not fit runs in passes of as many whole frames as do.  Successive
+ *   calls share it and are ordered by the stream they are queued on, across a change of the stream too.
+ * Cost.  Six walks over the plane (the maximum, three histogram passes of an exact radix select of the cut key -- digits of 11, 11
+ *   and 10 bits --, a count and an emit in raster order), whatever the number of candidates; only the rank and the sift are
+ *   quadratic, in candidate_capacity.  All sums are integer sums: the result is a function of the plane alone.
+ * HC_E_ARG: ctx, d_response or d_corner_counts null, d_corners null with corner_capacity > 0; d_response, pitch or frame_stride not
+ * multiples of 4, d_corner_counts or d_quality not 4-byte, d_corners not 8-byte aligned; pitch < 4 W; H * pitch >= 2^32; nframes > 1
+ * with a frame stride below H * pitch; a view that wraps the address space; quality_level not finite or outside (0, 1];
+ * min_distance not finite or negative; candidate_capacity outside 1..4096; nframes outside the bound above; corner_capacity * 8 *
+ * nframes overflowing size_t; one frame's scratch above the bound.  Every refusal lies above the first allocation or launch. */
+int hc_good_features_device(hc_ctx *ctx, const void *d_response, size_t pitch, size_t frame_stride /* float32, W x H */, int nframes,
+                            double quality_level, double min_distance, size_t candidate_capacity,
+                            void *d_corner_counts /* uint32 [nframes] */, void *d_corners /* float32 [nframes][corner_capacity][2] = (x, y) */,
+                            void *d_quality /* float32 [nframes][corner_capacity], may be NULL */, size_t corner_capacity);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
