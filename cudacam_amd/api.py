@@ -93,7 +93,7 @@ ABI_SYMBOLS = [
     "hc_edge_points_device", "hc_gaussian_blur_device", "hc_hough_lines_device", "hc_hough_tables",
     "hc_hough_segments_device", "hc_hough_walk_tables", "hc_hough_circles_device", "hc_hough_circle_geometry",
     "hc_connected_components_device", "hc_morphology_device", "hc_structuring_element", "hc_distance_transform_device",
-    "hc_thinning_device", "hc_corner_response_device", "hc_good_features_device",
+    "hc_thinning_device", "hc_corner_response_device", "hc_good_features_device", "hc_pyr_down_device", "hc_lk_flow_device",
 ]
 # ... and the one whose name ends in a digit, which the name pattern of tests/test_abi_cpu.py does not read from the header
 ABI_SYMBOLS_HOST = ["hc_gaussian_taps_q8"]
@@ -170,6 +170,8 @@ def load_library(legacy=False):
     L.hc_thinning_device.argtypes = [vp, vp, sz, sz, vp, sz, sz, i, i, i, vp]
     L.hc_corner_response_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, i, i, i, d]
     L.hc_good_features_device.argtypes = [vp, vp, sz, sz, i, d, d, sz, vp, vp, vp, sz]
+    L.hc_pyr_down_device.argtypes = [vp, vp, sz, sz, i, i, vp, sz, sz, i]
+    L.hc_lk_flow_device.argtypes = [vp, vp, vp, sz, sz, i, i, i, i, vp, vp, vp, sz, i, i, d, d, i, vp, vp]
     L.hc_hough_circle_geometry.argtypes = [i, i, d, d, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_longlong)]
     L.hc_download.argtypes = [vp, vp, sz, sz, i]
     L.hc_download_begin.argtypes = [vp, vp, sz, sz, i]
@@ -1291,6 +1293,142 @@ class Context:
         self._queue_response(gx, gy, resp, n, block_size, m, k)
         self._queue_features(resp, n, quality_level, min_distance, candidate_capacity, bufs)
         return self._features_from(n, bufs)
+
+    def pyr_down_device(self, d_src, pitch, fs, src_width, src_height, d_dst, dst_pitch, dst_fs, nframes):
+        """cv::pyrDown of one-channel u8 planes of src_width x src_height on device memory (hc_pyr_down_device, either mode): planes of
+        ((src_width + 1) // 2) x ((src_height + 1) // 2) out.  Pitches and frame strides in bytes, any alignment; the views must not
+        overlap.  Asynchronous on the context stream; not a run."""
+        _ck(self.lib.hc_pyr_down_device(self.handle, C.c_void_p(d_src), pitch, fs, int(src_width), int(src_height), C.c_void_p(d_dst), dst_pitch, dst_fs,
+                                        int(nframes)))
+
+    def lk_flow_device(self, d_prev, d_next, pitch, fs, width, height, level, nframes, d_counts, d_prev_pts, d_next_pts, capacity, win, max_iterations,
+                       epsilon, min_eig_threshold, use_initial, d_status, d_err):
+        """One pyramid level of cv::calcOpticalFlowPyrLK on device memory (hc_lk_flow_device, either mode): u8 levels of width x
+        height, points in level-0 units, d_next_pts in / out; d_status and d_err (or None) are written at level 0 only.
+        Asynchronous on the context stream; not a run."""
+        _ck(self.lib.hc_lk_flow_device(self.handle, C.c_void_p(d_prev), C.c_void_p(d_next), pitch, fs, int(width), int(height), int(level), int(nframes),
+                                       C.c_void_p(d_counts), C.c_void_p(d_prev_pts), C.c_void_p(d_next_pts), int(capacity), int(win), int(max_iterations),
+                                       float(epsilon), float(min_eig_threshold), int(use_initial), C.c_void_p(d_status), C.c_void_p(d_err or None)))
+
+    def _u8_planes(self, frames, who, width=None, height=None):
+        """Host or torch u8 planes [n, h, w] (or one plane) as a contiguous tensor on the context's device; (h, w) is (height, width)
+        where given, else the planes' own, and no larger than the context's frame."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(frames, torch.Tensor):
+            d = frames.to(device=dev, dtype=torch.uint8)
+        else:
+            d = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8)).to(dev)
+        d = (d[None] if d.ndim == 2 else d).contiguous()
+        if d.ndim != 3 or (width is not None and d.shape[2] != int(width)) or (height is not None and d.shape[1] != int(height)):
+            raise HipCannyError(f"{who}: planes {tuple(d.shape)} do not match (n, {height}, {width})")
+        if d.shape[1] > self.h or d.shape[2] > self.w:
+            raise HipCannyError(f"{who}: planes {tuple(d.shape)} exceed the context's {(self.h, self.w)}")
+        return d
+
+    def _queue_pyr_down(self, src):
+        """Queues cv::pyrDown of a tight u8 tensor [n, h, w] into a new tight tensor and returns it; no host wait (the caller has
+        waited for torch's stream after its own allocations; this one's memory is not written by torch)."""
+        import torch
+        n, h, w = src.shape
+        dst = torch.empty((n, (h + 1) // 2, (w + 1) // 2), dtype=torch.uint8, device=src.device)
+        self._wait_for_torch()
+        self.pyr_down_device(src.data_ptr(), w, w * h, w, h, dst.data_ptr(), dst.shape[2], dst.shape[2] * dst.shape[1], n)
+        return dst
+
+    def pyr_down(self, frames, width=None, height=None):
+        """Host or torch u8 planes [n, h, w] (or one plane) in, cv::pyrDown of them [n, (h + 1) // 2, (w + 1) // 2] out as a torch
+        tensor on the device (hc_pyr_down_device).  width, height: what the planes must measure (None: their own size)."""
+        src = self._u8_planes(frames, "pyr_down", width, height)
+        self._wait_for_torch()
+        dst = self._queue_pyr_down(src)
+        self.sync()
+        return dst
+
+    def lk_level(self, prev, nxt, level, counts, prev_pts, next_pts, win=21, max_iterations=30, epsilon=0.01, min_eig_threshold=1e-4, use_initial=False,
+                 status=None, err=None):
+        """One level call on torch tensors of the context's device, queued on the context stream with no host wait: prev, nxt tight u8
+        [n, h, w]; counts int32 / uint32 [n]; prev_pts, next_pts float32 [n, capacity, 2] (next_pts in / out); status u8
+        [n, capacity]; err float32 [n, capacity] or None.  A thin wrapper of hc_lk_flow_device."""
+        n, h, w = prev.shape
+        if tuple(nxt.shape) != (n, h, w) or not (prev.is_contiguous() and nxt.is_contiguous() and prev_pts.is_contiguous() and next_pts.is_contiguous()):
+            raise HipCannyError("lk_level: prev and next must be contiguous tensors of one shape, the points contiguous")
+        self.lk_flow_device(prev.data_ptr(), nxt.data_ptr(), w, w * h, w, h, level, n, counts.data_ptr(), prev_pts.data_ptr(), next_pts.data_ptr(),
+                            prev_pts.shape[1], win, max_iterations, epsilon, min_eig_threshold, use_initial, status.data_ptr() if status is not None else None,
+                            err.data_ptr() if err is not None else None)
+
+    def _queue_flow(self, a, b, pts, counts, nxt, status, err, win, levels, max_iterations, epsilon, min_eig_threshold, use_initial):
+        """Queues both pyramids and the level calls, from the coarsest level down; returns the pyramids (they must outlive the
+        calls).  The pyramid stops at the last level whose sides are still at least 3."""
+        pa, pb = [a], [b]
+        for _ in range(int(levels)):
+            h, w = pa[-1].shape[1:]
+            if (h + 1) // 2 < 3 or (w + 1) // 2 < 3:
+                break
+            pa.append(self._queue_pyr_down(pa[-1]))
+            pb.append(self._queue_pyr_down(pb[-1]))
+        top = len(pa) - 1
+        for lv in range(top, -1, -1):
+            self.lk_level(pa[lv], pb[lv], lv, counts, pts, nxt, win, max_iterations, epsilon, min_eig_threshold, use_initial or lv < top, status, err)
+        return pa, pb
+
+    def optical_flow(self, prev, next, points, counts, win=21, levels=3, max_iterations=30, epsilon=0.01, min_eig_threshold=1e-4, initial=None):
+        """cv::calcOpticalFlowPyrLK of u8 frames [n, H, W] (or one frame) of the context's size: points float32 [n, capacity, 2] =
+        (x, y) and counts [n] as hc_good_features_device writes them (host or torch); initial: a guess of the same shape.  Both
+        pyramids and the levels + 1 level calls are chained on the context stream.  Returns torch tensors on the device:
+        (next_pts [n, capacity, 2], status u8 [n, capacity], err float32 [n, capacity]); slots at or beyond a frame's count hold the
+        points (or the guess) they were given, status 0 and err 0."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        a, b = self._u8_planes(prev, "optical_flow: prev", self.w, self.h), self._u8_planes(next, "optical_flow: next", self.w, self.h)
+        n = a.shape[0]
+        as_dev = lambda v, dt: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).to(device=dev, dtype=dt).contiguous()
+        pts = as_dev(points, torch.float32)
+        pts = pts[None] if pts.ndim == 2 else pts
+        cnt = as_dev(np.asarray(counts).astype(np.int64) if not isinstance(counts, torch.Tensor) else counts, torch.int32).reshape(-1)
+        if b.shape[0] != n or pts.ndim != 3 or pts.shape[0] != n or pts.shape[2] != 2 or cnt.shape[0] != n:
+            raise HipCannyError(f"optical_flow: {n} prev frames, {b.shape[0]} next frames, points {tuple(pts.shape)}, {cnt.shape[0]} counts")
+        nxt = (pts if initial is None else as_dev(initial, torch.float32).reshape(pts.shape)).clone()
+        status = torch.zeros(pts.shape[:2], dtype=torch.uint8, device=dev)
+        err = torch.zeros(pts.shape[:2], dtype=torch.float32, device=dev)
+        self._wait_for_torch()
+        keep = self._queue_flow(a, b, pts, cnt, nxt, status, err, win, levels, max_iterations, epsilon, min_eig_threshold, initial is not None)
+        self.sync()
+        del keep
+        return nxt, status, err
+
+    def track(self, prev, next, ksize=3, block_size=3, method="min_eigen", k=0.04, quality_level=0.01, min_distance=10, max_corners=1000, blur=None,
+              candidate_capacity=4096, win=21, levels=3, max_iterations=30, epsilon=0.01, min_eig_threshold=1e-4):
+        """Detect and follow (1-channel contexts): the chain of `features` on prev -- blur, derivatives, corner measure, selection --
+        and then the flow of those corners into next, all on the context stream with no host copy in between.  Returns torch tensors
+        on the device: (counts int32 [n] = min(kept, max_corners), points [n, max_corners, 2], next_pts likewise, status u8
+        [n, max_corners], err float32 [n, max_corners]); slots at or beyond a frame's count hold zeros."""
+        import torch
+        if self.c != 1:
+            raise ValueError("track: a 1-channel context is required")
+        raw, n, row, fs = self._device_view(prev, "track: prev")
+        nx = self._u8_planes(next, "track: next", self.w, self.h)
+        if nx.shape[0] != n:
+            raise HipCannyError(f"track: {n} prev frames, {nx.shape[0]} next frames")
+        m = self._corner_method(method)
+        gx, gy = torch.empty_like(raw, dtype=torch.int16), torch.empty_like(raw, dtype=torch.int16)
+        resp = torch.empty((n, self.h, self.w), dtype=torch.float32, device=raw.device)
+        cap = int(max_corners)
+        counts = torch.zeros((n,), dtype=torch.int32, device=raw.device)
+        pts = torch.zeros((n, cap, 2), dtype=torch.float32, device=raw.device)
+        nxt = torch.zeros_like(pts)
+        status = torch.zeros((n, cap), dtype=torch.uint8, device=raw.device)
+        err = torch.zeros((n, cap), dtype=torch.float32, device=raw.device)
+        self._wait_for_torch()
+        src = self._blurred(raw, n, row, fs, blur)
+        self.derivatives_device(src.data_ptr(), row, fs, gx.data_ptr(), gy.data_ptr(), 2 * row, 2 * fs, n, ksize)
+        self._queue_response(gx, gy, resp, n, block_size, m, k)
+        self.good_features_device(resp.data_ptr(), 4 * self.w, 4 * self.w * self.h, n, quality_level, min_distance, candidate_capacity, counts.data_ptr(),
+                                  pts.data_ptr(), None, cap)
+        keep = self._queue_flow(raw.reshape(n, self.h, self.w), nx, pts, counts, nxt, status, err, win, levels, max_iterations, epsilon, min_eig_threshold, False)
+        self.sync()
+        del keep
+        return torch.clamp(counts, max=cap), pts, nxt, status, err
 
     def hysteresis_device(self, d_thr, in_pitch, in_fs, d_out, out_pitch, out_fs, nframes):
         _ck(self.lib.hc_hysteresis_device(self.handle, C.c_void_p(d_thr), in_pitch, in_fs, C.c_void_p(d_out), out_pitch,

@@ -46,6 +46,9 @@ hipError_t launch_thin_unpack(const ThinUnpackParams &p, hipStream_t s);
 // must be zero when it starts)
 hipError_t launch_corner_response(const CornerParams &p, hipStream_t s);
 hipError_t launch_good_features(const FeatParams &p, hipStream_t s);
+// flow.hip (the product library only): k_pyr_down8; k_lk_flow, one pyramid level of the tracker
+hipError_t launch_pyr_down(const PyrParams &p, hipStream_t s);
+hipError_t launch_lk_flow(const FlowParams &p, hipStream_t s);
 #ifdef HC_LEGACY_FRONT  // legacy_front.hip: the round-1 front kernels of Mode R, built into libhipcanny_legacy.so only (parity tests)
 hipError_t launch_front(const FrontParams &p, hipStream_t s);
 hipError_t launch_blur(const FrontParams &p, hipStream_t s);

@@ -329,6 +329,54 @@ struct FeatParams {
   u32 *rows;               // [H][2]: candidates with key > T / == T of the row, then their exclusive prefix sums
 };
 
+// k_pyr_down8 (flow.hip): cv::pyrDown of one-channel u8 planes (hc_pyr_down_device, where the arithmetic is stated).  The lane
+// layout of k_gauss8 on the SOURCE plane: a wave owns a strip of PYR_STRIP_W source columns, lane l the 4 source pixels at
+// strip * PYR_STRIP_W - 4 + 4 l, which are the 2 destination pixels at half that column; lanes 0 and 63 are halo.  A work item is
+// (frame, strip, PYR_CHUNK_ROWS destination rows) with a warm-up of 3 source rows.
+constexpr int PYR_STRIP_W = 248;     // source columns per wave: 124 destination columns
+static_assert(PYR_STRIP_W == STRIP_W && PYR_STRIP_W % 4 == 0, "k_pyr_down8 uses the lane layout of k_gauss8; a lane's source group starts at an even destination column");
+constexpr int PYR_CHUNK_ROWS = 32;   // destination rows per work item
+constexpr int PYR_MIN_SIDE = 3;      // one reflection suffices
+inline int pyr_half(int n) { return (n + 1) / 2; }
+inline int pyr_strips(int W) { return (W + PYR_STRIP_W - 1) / PYR_STRIP_W; }
+inline int pyr_chunks(int dH) { return (dH + PYR_CHUNK_ROWS - 1) / PYR_CHUNK_ROWS; }
+struct PyrParams {
+  const uint8_t *in;       // u8 planes of W x H; any alignment (in_aligned: base, pitch and frame stride are multiples of 4)
+  size_t in_pitch, in_frame_stride;
+  uint8_t *out;            // u8 planes of dW x dH; any alignment (out_aligned: base, pitch and frame stride are even)
+  size_t out_pitch, out_frame_stride;
+  int W, H, dW, dH, nframes;
+  int in_aligned, out_aligned;
+  int nstrips, nchunks, total_items;  // total_items = nframes * nstrips * nchunks
+};
+
+// k_lk_flow (flow.hip): one pyramid level of cv::calcOpticalFlowPyrLK (hc_lk_flow_device, where the arithmetic is stated).  One
+// wave per (frame, point slot), 4 waves a workgroup; window pixel t = lane + 64 r (r < rounds) is (t % win, t / win).
+constexpr int FLOW_MIN_WIN = 5, FLOW_MAX_WIN = 31, FLOW_MAX_ITERATIONS = 64, FLOW_MAX_LEVEL = 15;
+constexpr int FLOW_WAVES = 4;  // waves (points) per workgroup
+inline bool flow_win_ok(int win) { return win >= FLOW_MIN_WIN && win <= FLOW_MAX_WIN && (win & 1); }
+// rounds of 64 window pixels, and the class the kernel is compiled for: the smallest of 1, 2, 4, 7, 10, 16 that holds them
+inline int flow_rounds(int win) { return (win * win + 63) / 64; }
+inline int flow_round_class(int win)
+{
+  const int r = flow_rounds(win);
+  return r <= 1 ? 1 : r <= 2 ? 2 : r <= 4 ? 4 : r <= 7 ? 7 : r <= 10 ? 10 : 16;
+}
+struct FlowParams {
+  const uint8_t *prev, *next;  // u8 planes of W x H with a common pitch and frame stride; any alignment
+  size_t pitch, frame_stride;
+  int W, H, level, nframes;
+  const u32 *counts;           // [nframes]
+  const float *prev_pts;       // [nframes][capacity][2], level-0 units
+  float *next_pts;             // likewise, in / out
+  size_t capacity;
+  int win, max_iterations, use_initial;
+  float eps2, min_eig;         // (float)(epsilon * epsilon), (float)min_eig_threshold
+  uint8_t *status;             // [nframes][capacity]; written at level 0 only
+  float *err;                  // [nframes][capacity] or null; level 0 only
+  u32 groups;                  // workgroups per frame: ceil(capacity / FLOW_WAVES)
+};
+
 // k_hist256 (stats.hip): 256-bin histograms of u8 frames, all channels pooled.  A work item is (frame, chunk of rows); a wave
 // counts its rows into a wave-private LDS histogram and adds the non-zero bins to hist[frame] with global atomics.
 constexpr int HIST_MAX_CHUNK_ROWS = 64, HIST_MIN_CHUNK_ROWS = 8;

@@ -378,4 +378,41 @@ int hc_good_features_device(hc_ctx *c, const void *d_response, size_t pitch, siz
   return HC_OK;
 }
 
+// One launch of k_pyr_down8 on the context stream (flow.hip).  Not a run, as hc_morphology_device, and like it it completes first a
+// pipelined run in flight whose output overlaps either view: u8 planes may be run outputs.  No scratch.
+int hc_pyr_down_device(hc_ctx *c, const void *d_src, size_t pitch, size_t fs, int src_width, int src_height, void *d_dst, size_t dst_pitch, size_t dst_fs, int n)
+{
+  if (!c) return fail(HC_E_ARG, "hc_pyr_down_device: null argument");
+  const View src{ (uintptr_t)d_src, pitch, fs }, dst{ (uintptr_t)d_dst, dst_pitch, dst_fs };
+  const PyrPlan P = plan_pyr_down(c->W, c->H, c->max_batch * (c->per_channel ? 3 : 1), src, src_width, src_height, dst, n);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_pyr_down_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  // (finish_writers_of takes the context's height for the views' byte ranges: a level is no taller)
+  if (int rc = finish_writers_of(c, src, (size_t)src_width, n)) return rc;
+  if (int rc = finish_writers_of(c, dst, (size_t)P.pp.dW, n)) return rc;
+  // every refusal lies above
+  HIPCK(launch_pyr_down(P.pp, c->stream));
+  return HC_OK;
+}
+
+// One launch of k_lk_flow on the context stream (flow.hip): one pyramid level of the tracker.  Not a run; like hc_pyr_down_device it
+// completes first a pipelined run in flight whose output overlaps either image.  No scratch.
+int hc_lk_flow_device(hc_ctx *c, const void *d_prev, const void *d_next, size_t pitch, size_t fs, int width, int height, int level, int n, const void *d_counts,
+                      const void *d_prev_pts, void *d_next_pts, size_t capacity, int win, int max_iterations, double epsilon, double min_eig_threshold, int use_initial,
+                      void *d_status, void *d_err)
+{
+  if (!c) return fail(HC_E_ARG, "hc_lk_flow_device: null argument");
+  const View prev{ (uintptr_t)d_prev, pitch, fs }, next{ (uintptr_t)d_next, pitch, fs };
+  const FlowPlan P = plan_lk_flow(c->W, c->H, c->max_batch * (c->per_channel ? 3 : 1), prev, (uintptr_t)d_next, width, height, level, n, (uintptr_t)d_counts,
+                                  (uintptr_t)d_prev_pts, (uintptr_t)d_next_pts, capacity, win, max_iterations, epsilon, min_eig_threshold, use_initial, (uintptr_t)d_status,
+                                  (uintptr_t)d_err);
+  if (P.error) return fail(HC_E_ARG, std::string("hc_lk_flow_device: ") + P.error);
+  HIPCK(hipSetDevice(c->device));
+  if (int rc = finish_writers_of(c, prev, (size_t)width, n)) return rc;
+  if (int rc = finish_writers_of(c, next, (size_t)width, n)) return rc;
+  // every refusal lies above
+  HIPCK(launch_lk_flow(P.fp, c->stream));
+  return HC_OK;
+}
+
 }  // extern "C"

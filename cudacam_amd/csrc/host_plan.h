@@ -2,7 +2,7 @@
 // how its work is cut (plan_front: stage_views, choose_form, one cut_* function per kernel family), the hysteresis launch schedule (plan_hyst) and what it learns from finished runs
 // (HystHistory), the slot count of pipelined runs (pipeline_slots, ChainWatch); what every device entry point refuses of a
 // caller's pitched view (check_view) and the kernel parameters of the entries that are not runs (plan_derivatives,
-// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology, plan_distance_transform, plan_thinning, plan_corner_response, plan_good_features; the taps rule of
+// plan_histogram, plan_edge_points, plan_gaussian_blur, plan_hough_lines, plan_hough_segments, plan_hough_circles, plan_connected_components, plan_morphology, plan_distance_transform, plan_thinning, plan_corner_response, plan_good_features, plan_pyr_down, plan_lk_flow; the taps rule of
 // hc_gaussian_taps_q8, the table rules of hc_hough_tables and hc_hough_walk_tables and the geometry of hc_hough_circle_geometry).  No HIP, no hc_ctx: hipcanny.hip fills
 // the inputs, patches the device pointers in and launches; tests/cpp/plan_driver.cpp checks the plans without a GPU.
 #pragma once
@@ -1637,6 +1637,81 @@ inline FeatPass feat_pass(const FeatPlan &P, int k, uintptr_t scratch)
   R.zero = (uintptr_t)f.hist;
   R.zero_bytes = fpp * P.frame_hist_bytes + (size_t)f.nframes * P.frame_state_bytes;
   return R;
+}
+
+// ---- hc_pyr_down_device ---------------------------------------------------------------------------
+// Everything the entry refuses and decides, but for the context pointer: one launch of k_pyr_down8, no scratch, no passes.  The
+// planes are sw x sh, a level of the context's W x H frame: 3 <= sw <= W, 3 <= sh <= H.  A refused plan holds nothing but its text.
+struct PyrPlan { const char *error = nullptr; PyrParams pp{}; };
+inline PyrPlan plan_pyr_down(int W, int H, int max_frames, const View &src, int sw, int sh, const View &dst, int n)
+{
+  PyrPlan P;
+  auto refuse = [](const char *text) { PyrPlan R; R.error = text; return R; };
+  if (!src.p || !dst.p) return refuse("null argument");
+  if (sw < PYR_MIN_SIDE || sh < PYR_MIN_SIDE) return refuse("src_width and src_height must be 3 at least");
+  if (sw > W || sh > H) return refuse("src_width and src_height must not exceed the context's frame");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  const int dw = pyr_half(sw), dh = pyr_half(sh);
+  if (const ViewFault f = check_view(src, (size_t)sw, sh, n, 1, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  if (const ViewFault f = check_view(dst, (size_t)dw, dh, n, 1, true)) return refuse(f == VIEW_PITCH ? "dst_pitch smaller than a destination row" : f == VIEW_STRIDE ? "dst_frame_stride below the destination height * dst_pitch" : VIEW_FAULT_TEXT[f]);
+  uintptr_t es = 0, ed = 0;
+  if (!view_end(src, (size_t)sw, sh, n, &es) || !view_end(dst, (size_t)dw, dh, n, &ed)) return refuse("a view wraps the address space");
+  if (src.p < ed && dst.p < es) return refuse("the source and destination views overlap");
+  PyrParams &q = P.pp;
+  q.in = (const uint8_t *)src.p; q.in_pitch = src.pitch; q.in_frame_stride = src.fs;
+  q.out = (uint8_t *)dst.p; q.out_pitch = dst.pitch; q.out_frame_stride = dst.fs;
+  q.W = sw; q.H = sh; q.dW = dw; q.dH = dh; q.nframes = n;
+  q.in_aligned = aligned4(src.p, src.pitch, src.fs); q.out_aligned = ((dst.p | dst.pitch | dst.fs) & 1u) == 0;
+  q.nstrips = pyr_strips(sw); q.nchunks = pyr_chunks(dh);
+  const long long items = (long long)n * q.nstrips * q.nchunks;
+  if (items > 0x7FFFFFF0ll) return refuse("too many work items (nframes x strips x row chunks)");
+  q.total_items = (int)items;
+  return P;
+}
+
+// ---- hc_lk_flow_device ----------------------------------------------------------------------------
+// Everything the entry refuses and decides, but for the context pointer: one launch of k_lk_flow, a wave per point slot, no scratch.
+// The planes are w x h, a level of the context's frame: 1 <= w <= W, 1 <= h <= H.  A refused plan holds nothing but its text.
+struct FlowPlan { const char *error = nullptr; FlowParams fp{}; };
+inline FlowPlan plan_lk_flow(int W, int H, int max_frames, const View &prev, uintptr_t next, int w, int h, int level, int n, uintptr_t counts, uintptr_t prev_pts,
+                             uintptr_t next_pts, size_t capacity, int win, int max_iterations, double epsilon, double min_eig_threshold, int use_initial,
+                             uintptr_t status, uintptr_t err)
+{
+  FlowPlan P;
+  auto refuse = [](const char *text) { FlowPlan R; R.error = text; return R; };
+  if (!prev.p || !next || !counts || !prev_pts || !next_pts || !status) return refuse("null argument");
+  if ((counts | prev_pts | next_pts | err) & 3u) return refuse("d_counts, d_prev_pts, d_next_pts and d_err must be 4-byte aligned");
+  if (level < 0 || level > FLOW_MAX_LEVEL) return refuse("level must lie in 0 .. 15");
+  if (!flow_win_ok(win)) return refuse("win must be odd and lie in 5 .. 31");
+  if (max_iterations < 1 || max_iterations > FLOW_MAX_ITERATIONS) return refuse("max_iterations must lie in 1 .. 64");
+  if (!std::isfinite(epsilon) || epsilon < 0) return refuse("epsilon must be finite and not negative");
+  if (!std::isfinite(min_eig_threshold) || min_eig_threshold < 0) return refuse("min_eig_threshold must be finite and not negative");
+  if (w < 1 || h < 1) return refuse("width and height must be positive");
+  if (w > W || h > H) return refuse("width and height must not exceed the context's frame");
+  if (n < 1 || n > max_frames) return refuse("nframes out of range");
+  if (capacity < 1) return refuse("capacity must be positive");
+  if (capacity > SIZE_MAX / 8 / (size_t)n) return refuse("capacity * 8 * nframes overflows size_t");
+  if (capacity > ((size_t)1 << 30)) return refuse("capacity above 2^30 (a wave per point slot)");
+  const View nextv{ next, prev.pitch, prev.fs };
+  if (const ViewFault f = check_view(prev, (size_t)w, h, n, 1, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  if (const ViewFault f = check_view(nextv, (size_t)w, h, n, 1, true)) return refuse(VIEW_FAULT_TEXT[f]);
+  uintptr_t ep = 0, en = 0;
+  if (!view_end(prev, (size_t)w, h, n, &ep) || !view_end(nextv, (size_t)w, h, n, &en)) return refuse("a view wraps the address space");
+  const size_t pts_bytes = capacity * 8 * (size_t)n;
+  if (next_pts > UINTPTR_MAX - pts_bytes || prev_pts > UINTPTR_MAX - pts_bytes || counts > UINTPTR_MAX - 4 * (size_t)n) return refuse("a view wraps the address space");
+  const uintptr_t o0 = next_pts, o1 = next_pts + pts_bytes;
+  if (prev_pts < o1 && o0 < prev_pts + pts_bytes) return refuse("d_next_pts overlaps d_prev_pts");
+  if (counts < o1 && o0 < counts + 4 * (size_t)n) return refuse("d_next_pts overlaps d_counts");
+  if ((prev.p < o1 && o0 < ep) || (next < o1 && o0 < en)) return refuse("d_next_pts overlaps an image");
+  FlowParams &f = P.fp;
+  f.prev = (const uint8_t *)prev.p; f.next = (const uint8_t *)next; f.pitch = prev.pitch; f.frame_stride = prev.fs;
+  f.W = w; f.H = h; f.level = level; f.nframes = n;
+  f.counts = (const u32 *)counts; f.prev_pts = (const float *)prev_pts; f.next_pts = (float *)next_pts; f.capacity = capacity;
+  f.win = win; f.max_iterations = max_iterations; f.use_initial = use_initial ? 1 : 0;
+  f.eps2 = (float)(epsilon * epsilon); f.min_eig = (float)min_eig_threshold;
+  f.status = (uint8_t *)status; f.err = (float *)err;
+  f.groups = (u32)((capacity + FLOW_WAVES - 1) / FLOW_WAVES);
+  return P;
 }
 
 }  // namespace hc

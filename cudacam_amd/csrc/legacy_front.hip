@@ -1000,7 +1000,9 @@ using namespace hc;
 
 extern "C" {
 // the test library (round-1 front kernels) is built without stats.hip, edge_points.hip, blur.hip, hough.hip, hough_segments.hip and
-// hough_circles.hip, nor ccl.hip, morph.hip, dist.hip, thin.hip and corners.hip
+// hough_circles.hip, nor ccl.hip, morph.hip, dist.hip, thin.hip, corners.hip and flow.hip
+int hc_pyr_down_device(hc_ctx *, const void *, size_t, size_t, int, int, void *, size_t, size_t, int) { return fail(HC_E_ARG, "hc_pyr_down_device: not part of the test library"); }
+int hc_lk_flow_device(hc_ctx *, const void *, const void *, size_t, size_t, int, int, int, int, const void *, const void *, void *, size_t, int, int, double, double, int, void *, void *) { return fail(HC_E_ARG, "hc_lk_flow_device: not part of the test library"); }
 int hc_corner_response_device(hc_ctx *, const void *, const void *, size_t, size_t, void *, size_t, size_t, int, int, int, double) { return fail(HC_E_ARG, "hc_corner_response_device: not part of the test library"); }
 int hc_good_features_device(hc_ctx *, const void *, size_t, size_t, int, double, double, size_t, void *, void *, void *, size_t) { return fail(HC_E_ARG, "hc_good_features_device: not part of the test library"); }
 int hc_thinning_device(hc_ctx *, const void *, size_t, size_t, void *, size_t, size_t, int, int, int, void *) { return fail(HC_E_ARG, "hc_thinning_device: not part of the test library"); }

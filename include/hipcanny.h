@@ -798,6 +798,72 @@ int hc_good_features_device(hc_ctx *ctx, const void *d_response, size_t pitch, s
                             void *d_corner_counts /* uint32 [nframes] */, void *d_corners /* float32 [nframes][corner_capacity][2] = (x, y) */,
                             void *d_quality /* float32 [nframes][corner_capacity], may be NULL */, size_t corner_capacity);
 
+/* Sparse optical flow on the device: cv::pyrDown and one pyramid level of cv::calcOpticalFlowPyrLK, which follows the corner lists of
+ * hc_good_features_device into the next frame (cudacam_amd/csrc/flow.hip).  The semantics are stated here and restated in
+ * tests/flow_ref.py (numpy); like the rest of Mode O they are the library's own statement, not pinned against a build of OpenCV, and
+ * every deviation from OpenCV is named.  Both entries take the size of the planes they work on PER CALL, because pyramid levels are
+ * smaller than the context's W x H frame: 1 <= width <= W, 1 <= height <= H, plus the minimum each entry states.  The caller owns
+ * every pyramid plane; neither entry has scratch.  Both are asynchronous on the context stream (hc_set_stream honoured) and are not
+ * runs, as hc_corner_response_device is none; a pipelined run in flight whose output overlaps one of their u8 views is completed first,
+ * as hc_morphology_device does.
+ *
+ * hc_pyr_down_device: cv::pyrDown(src, dst) for one-channel u8 planes of src_width x src_height.
+ * Arithmetic.  dw = (src_width + 1) / 2, dh = (src_height + 1) / 2;
+ *   dst(x, y) = (sum_{j=-2..2} sum_{i=-2..2} t[i] t[j] src(r(2x+i, src_width), r(2y+j, src_height)) + 128) >> 8, t = {1, 4, 6, 4, 1},
+ *   r = BORDER_REFLECT_101 (-1 -> 1, -2 -> 2, n -> n-2, n+1 -> n-3).  All integer; the sum fits 16 bits.
+ * Memory.  Any alignment on both sides, and both may be ROIs: no byte outside [row, row + src_width) of a source row is read, none
+ *   outside [row, row + dw) of a destination row is written.  Offsets are 32-bit: height * pitch below 2^32 on both sides.
+ * HC_E_ARG: ctx, d_src or d_dst null; src_width or src_height below 3 (one reflection suffices) or above the context's; pitch <
+ * src_width, dst_pitch < dw; nframes outside the bound of hc_corner_response_device; nframes > 1 with frame_stride < src_height *
+ * pitch or dst_frame_stride < dh * dst_pitch; offsets of 2^32 and more; a view that wraps the address space; overlapping byte ranges
+ * of the two views.  Every refusal lies above the launch, and a refused call writes nothing. */
+int hc_pyr_down_device(hc_ctx *ctx, const void *d_src, size_t pitch, size_t frame_stride, int src_width, int src_height,
+                       void *d_dst, size_t dst_pitch, size_t dst_frame_stride, int nframes);
+
+/* hc_lk_flow_device: ONE pyramid level of cv::calcOpticalFlowPyrLK on u8 planes of width x height (level `level` of both frames, with
+ * one pitch and frame stride).  A full track is levels + 1 calls from the coarsest level down to level 0 on one stream with no
+ * synchronisation between them: the first with use_initial as the caller has a guess or not, the others with use_initial 1.
+ * d_counts and d_prev_pts are exactly what hc_good_features_device writes; min(counts[f], capacity) points of frame f are processed,
+ * slots beyond that are not touched.  Points are (x, y) in LEVEL-0 units on both sides.
+ * Every float step is one rounded float32 operation, none contracted; the root and the divisions are correctly rounded.
+ *   s = 2^-level, S = 2^level (exact scalings); hw = (win - 1) * 0.5f.
+ *   P(img, x, y) = img[clamp(y, 0, height-1)][clamp(x, 0, width-1)].
+ *   Scharr on prev: Dx(x, y) = 3 (P(x+1,y-1) - P(x-1,y-1)) + 10 (P(x+1,y) - P(x-1,y)) + 3 (P(x+1,y+1) - P(x-1,y+1)), Dy its transpose:
+ *   integers, |.| <= 4080.
+ * 1. Weights at a position q = (qx, qy): ix = floorf(qx), a = qx - ix, iy, b likewise; t0 = 1 - a, t1 = 1 - b;
+ *    w00 = (int)rintf((t0 t1) 16384), w01 = (int)rintf((a t1) 16384), w10 = (int)rintf((t0 b) 16384), w11 = 16384 - w00 - w01 - w10
+ *    (rintf rounds half to even).  interp(F, i, j) = w00 F(ix+i, iy+j) + w01 F(ix+i+1, iy+j) + w10 F(ix+i, iy+j+1) + w11 F(ix+i+1, iy+j+1),
+ *    an exact integer.
+ * 2. q is OUT iff ix < -win or ix >= width or iy < -win or iy >= height, tested on ix, iy as floats before any conversion: NaN and
+ *    values beyond int32 are out.
+ * 3. Template.  u = prev_pts * s - hw.  u out: the point is LOST.  Otherwise, for 0 <= i, j < win, with arithmetic shifts:
+ *    I(i, j) = (interp(P_prev) + 256) >> 9, gx(i, j) = (interp(Dx) + 8192) >> 14, gy likewise.
+ * 4. Matrix.  A11 = sum gx^2, A12 = sum gx gy, A22 = sum gy^2 as exact int64; f11 = (float)A11 * 2^-20, f12, f22 likewise;
+ *    D = f11 f22 - f12 f12; d = f11 - f22; m = (f22 + f11) - sqrtf(d d + 4 (f12 f12)); min_eig = m / (float)(2 win win).
+ *    The point is lost iff min_eig < (float)min_eig_threshold or D < 1.1920929e-7f.  Dinv = 1.0f / D.
+ * 5. Start.  v = (use_initial ? next_pts : prev_pts) * s - hw.
+ * 6. For k = 0 .. max_iterations - 1: v out: the point is lost.  With the weights at v: diff(i, j) = ((interp(P_next) + 256) >> 9) -
+ *    I(i, j); b1 = sum diff gx, b2 = sum diff gy as exact int64; g1 = (float)b1 * 2^-20, g2 likewise;
+ *    ex = (f12 g2 - f22 g1) Dinv, ey = (f12 g1 - f11 g2) Dinv; v += e.  Stop if ex ex + ey ey <= (float)(epsilon * epsilon), the
+ *    product taken as a double.  If k > 0 and |ex + px| < 0.01f and |ey + py| < 0.01f (p: the e of the iteration before):
+ *    v -= e * 0.5f and stop.
+ * 7. Not lost: next_pts = (v + hw) * S.  Lost: next_pts = (use_initial ? next_pts : prev_pts), bit for bit.
+ * 8. Only with level == 0 are d_status and d_err written: status = 1 iff the point is not lost and the final v is not out, else 0.
+ *    With d_err: status 1: diff recomputed at the final v, err = (float)(sum |diff|) / (float)(32 win win); status 0: err = 0.
+ * DEVIATIONS from OpenCV: pixel fetches are clamped to the level (OpenCV pads its pyramid and takes derivatives of the padded
+ * planes); the window sums are exact integers (OpenCV adds floats, in an order that depends on its vector width); a lost point stays
+ * lost only for the level's call: the next level starts again from the unchanged position.
+ * HC_E_ARG: the view rules of hc_pyr_down_device for both images (width, height >= 1); level outside 0..15; win even or outside
+ * 5..31; max_iterations outside 1..64; epsilon or min_eig_threshold not finite or negative; capacity 0 or above 2^30 (a wave per
+ * slot), or capacity * 8 * nframes overflowing size_t; a null pointer but d_err; d_counts, d_prev_pts, d_next_pts or d_err not 4-byte
+ * aligned; d_next_pts overlapping d_prev_pts, d_counts or either image.  Every refusal lies above the launch. */
+int hc_lk_flow_device(hc_ctx *ctx, const void *d_prev, const void *d_next, size_t pitch, size_t frame_stride /* u8 levels, common geometry */,
+                      int width, int height, int level, int nframes,
+                      const void *d_counts /* uint32 [nframes] */, const void *d_prev_pts /* float32 [nframes][capacity][2], level-0 units */,
+                      void *d_next_pts /* float32, same shape, level-0 units, in/out */, size_t capacity,
+                      int win /* odd, 5..31 */, int max_iterations /* 1..64 */, double epsilon, double min_eig_threshold, int use_initial,
+                      void *d_status /* uint8 [nframes][capacity] */, void *d_err /* float32 [nframes][capacity], may be NULL */);
+
 /* The hysteresis stage alone (kernels `hysteresis` + `removeCandidates`, src/cvp/cannyEdgeD.cu:295-395,
  * loop of cannyEdgeH.cu:297-338) on device tri-state maps (0 / 128 / 255) -> 0 / 255. */
 int hc_hysteresis_device(hc_ctx *ctx, const void *d_thresh, size_t in_pitch, size_t in_frame_stride, void *d_out, size_t out_pitch,
