@@ -72,13 +72,16 @@ def _interp(fn, ix, iy, wts, ii, jj):
 
 
 def lk_point(prev, nxt, level, prev_pt, next_pt, win, max_iterations, epsilon, min_eig_threshold, use_initial):
-    """One point of one level: (next_pt float32[2], status or None, err or None, info).  Points are level-0 units."""
+    """One point of one level: (next_pt float32[2], status or None, err or None, info).  Points are level-0 units.  info says how the
+    point went: the iterations run, whether the half-step stop fired, min_eig, why it was lost ("lost": None, or "start" -- the
+    window around prev_pt is out of the frame --, "eigen", "left" -- an iteration's position is out --, "end" -- the final one is,
+    at level 0), and the exact integer window sums where they were made (A11, A12, A22; B1, B2 of every iteration; err_sum)."""
     h, w = prev.shape
     s, S = F(2.0 ** -level), F(2.0 ** level)
     hw = F(F(win - 1) * F(0.5))
     prev_pt = np.asarray(prev_pt, dtype=F)
     start = np.asarray(next_pt if use_initial else prev_pt, dtype=F).copy()
-    info = {"half_step": False, "iterations": 0}
+    info = {"half_step": False, "iterations": 0, "lost": None, "B1": [], "B2": []}
     jj, ii = np.mgrid[0:win, 0:win]
 
     def finish(lost, v):
@@ -89,29 +92,36 @@ def lk_point(prev, nxt, level, prev_pt, next_pt, win, max_iterations, epsilon, m
         if level != 0:
             return out, None, None, info
         ok = (not lost) and not _out(v, win, w, h)
+        if not lost and not ok:
+            info["lost"] = "end"
         err = F(0)
         if ok:
             ix, iy, wts = _weights(v)
             d = ((_interp(lambda x, y: _pix(nxt, x, y), ix, iy, wts, ii, jj) + 256) >> 9) - I
-            err = F(F(int(np.abs(d).sum())) / F(32 * win * win))
+            info["err_sum"] = int(np.abs(d).sum())
+            err = F(F(info["err_sum"]) / F(32 * win * win))
         return out, int(ok), err, info
 
     with np.errstate(all="ignore"):
         u = (F(F(prev_pt[0] * s) - hw), F(F(prev_pt[1] * s) - hw))
         if _out(u, win, w, h):
+            info["lost"] = "start"
             return finish(True, None)
         ix, iy, wts = _weights(u)
         I = (_interp(lambda x, y: _pix(prev, x, y), ix, iy, wts, ii, jj) + 256) >> 9
         gx = (_interp(lambda x, y: _scharr(prev, x, y)[0], ix, iy, wts, ii, jj) + 8192) >> 14
         gy = (_interp(lambda x, y: _scharr(prev, x, y)[1], ix, iy, wts, ii, jj) + 8192) >> 14
         sc = F(2.0 ** -20)
-        f11, f12, f22 = F(F(int((gx * gx).sum())) * sc), F(F(int((gx * gy).sum())) * sc), F(F(int((gy * gy).sum())) * sc)
+        A11, A12, A22 = int((gx * gx).sum()), int((gx * gy).sum()), int((gy * gy).sum())
+        info.update(A11=A11, A12=A12, A22=A22)
+        f11, f12, f22 = F(F(A11) * sc), F(F(A12) * sc), F(F(A22) * sc)
         D = F(F(f11 * f22) - F(f12 * f12))
         d = F(f11 - f22)
         m = F(F(f22 + f11) - np.sqrt(F(F(d * d) + F(F(4) * F(f12 * f12)))))
         min_eig = F(m / F(2 * win * win))
         info["min_eig"] = min_eig
         if min_eig < F(min_eig_threshold) or D < FLT_EPS:
+            info["lost"] = "eigen"
             return finish(True, None)
         Dinv = F(F(1) / D)
         v = [F(F(start[0] * s) - hw), F(F(start[1] * s) - hw)]
@@ -119,11 +129,15 @@ def lk_point(prev, nxt, level, prev_pt, next_pt, win, max_iterations, epsilon, m
         px = py = F(0)
         for k in range(max_iterations):
             if _out(v, win, w, h):
+                info["lost"] = "left"
                 return finish(True, None)
             info["iterations"] = k + 1
             ix, iy, wts = _weights(v)
             diff = ((_interp(lambda x, y: _pix(nxt, x, y), ix, iy, wts, ii, jj) + 256) >> 9) - I
-            g1, g2 = F(F(int((diff * gx).sum())) * sc), F(F(int((diff * gy).sum())) * sc)
+            B1, B2 = int((diff * gx).sum()), int((diff * gy).sum())
+            info["B1"].append(B1)
+            info["B2"].append(B2)
+            g1, g2 = F(F(B1) * sc), F(F(B2) * sc)
             ex = F(F(F(f12 * g2) - F(f22 * g1)) * Dinv)
             ey = F(F(F(f12 * g1) - F(f11 * g2)) * Dinv)
             v = [F(v[0] + ex), F(v[1] + ey)]
