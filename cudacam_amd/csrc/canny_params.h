@@ -628,6 +628,16 @@ static_assert(is_hyst_shape(16, 8) && is_hyst_shape(32, 2), "the looping shapes 
 // launch and leaves itself the reason that reopens its rows in the next one.  The budget keeps a launch short (4096 rounds are
 // 27 ms of an 8-wave workgroup, 57 ms of a 16-wave one) for whoever waits for it: the other workgroups at k_hyst_loop's barrier, the next run's chain.
 constexpr int HYST_ROUND_CAP = 4096;
+// Patching a provisional map (hyst_tile's write-back): a changed row with at least this many changed 16-px groups is written
+// whole, straight from its row register, instead of group by group through the LDS queue.  The queue suits the two or three
+// groups a row of a camera-like frame changes; a row of dense content (iid noise: 87 of 120 groups at the median) costs it
+// several LDS round trips and expansion passes of scattered stores.  The choice is per row and wave-uniform.
+// (measured over 16 .. 64: DESIGN.md 3.3, profiles/r16_dense_rows)
+#ifndef HC_HYST_ROW_FULL
+#define HC_HYST_ROW_FULL 32  // (-D: the sweep's builds)
+#endif
+constexpr int HYST_ROW_FULL = HC_HYST_ROW_FULL;
+static_assert(HYST_ROW_FULL >= 1 && HYST_ROW_FULL <= 128, "a panel row has 128 groups");
 // 8 waves x 32 rows (256-row tiles) when the hysteresis has the chip to itself: fewer tile boundaries, fewer
 // launches.  4 waves x 32 rows (one wave per SIMD) when it runs beside the next run's front kernels (pipelined mode):
 // a 4-wave workgroup finds a place as soon as one wave slot per SIMD frees up, an 8-wave one has to wait for two --

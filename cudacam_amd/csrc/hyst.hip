@@ -177,6 +177,53 @@ static __device__ __forceinline__ RowBits<NW> row_dilate(const RowBits<NW> &p)
   return d;
 }
 
+// Whole rows of a wave's tile to the 0/255 map, straight from the row registers: the rows in `rows` (bit r = row r of the tile,
+// wave-uniform; `srow` = the wave's strong rows, this lane's dword of each; out0 = row 0 of the tile in the frame's map), the
+// columns of the panel that starts at dword pcol, below W.  Two passes of 64 groups of 16 pixels, a group per lane and store.
+// Exactly the bytes [32 pcol, min(W, 32 (pcol + ROWW))) of each row are written.
+template <int ROWW, class RowVec>
+static __device__ __forceinline__ void expand_rows(const RowVec &srow, u64 rows, uint8_t *out0, size_t pitch, int pcol, int W, bool a16, int lane)
+{
+  for (u64 m = rows; m != 0; m &= m - 1) {
+    const int r = __builtin_ctzll(m);
+    const u32 rowv = srow[r];
+    uint8_t *orow = out0 + (size_t)r * pitch;
+    for (int pass = 0; pass * 1024 < ROWW * 32 && pcol * 32 + pass * 1024 < W; ++pass) {
+      // this lane writes px [32*pcol + 1024*pass + 16*lane, +16): half-word 64*pass + lane of the panel row
+      const u32 x = __shfl(rowv, 32 * pass + (lane >> 1));  // before any lane drops out: the permute only sees active lanes
+      const u32 b = (x >> (16 * (lane & 1))) & 0xFFFFu;
+      const int c0 = pcol * 32 + pass * 1024 + lane * 16;
+      if (c0 + 15 >= W) continue;  // whole 16-pixel groups here; the ragged last group of a row below
+      u32 v[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = nibble_to_bytes((b >> (4 * k)) & 0xFu);
+      uint8_t *dst = orow + c0;
+      if (a16) {
+        // (the pointer goes through an empty asm: seeing two branches that store the same bytes, the optimizer otherwise
+        //  merges them into the four dword stores -- twice the store instructions)
+        uint8_t *d16 = dst;
+        asm volatile("" : "+v"(d16));
+        *reinterpret_cast<uint4 *>(d16) = make_uint4(v[0], v[1], v[2], v[3]);
+      } else
+#pragma unroll
+        for (int k = 0; k < 4; ++k) reinterpret_cast<u32 *>(dst)[k] = v[k];
+    }
+  }
+  // Widths that are not a multiple of 16: the last W % 16 pixels of every row, a byte per lane, in a loop of their own
+  // (inside the loop above, the byte-wise tail -- unrolled 16 times under 16 exec masks -- cost the kernel an SGPR
+  // spill, i.e. an 81st VGPR, and as a plain loop it made the compiler split the hot loop: 0.94 instead of 0.76 ms
+  // for launch 0 of 1024 frames in plain mode)
+  const int ragged = W & 15, cl = W - ragged;  // first column of the ragged group
+  if (ragged != 0 && cl >= pcol * 32 && cl < (pcol + ROWW) * 32) {
+    const int hw = (cl - pcol * 32) >> 4;  // its half-word in the panel row: dword hw / 2 is held by lane hw / 2
+    for (u64 m = rows; m != 0; m &= m - 1) {
+      const int r = __builtin_ctzll(m);
+      const u32 x = __shfl(srow[r], hw >> 1);
+      const u32 b = (x >> (16 * (hw & 1))) & 0xFFFFu;
+      if (lane < ragged) (out0 + (size_t)r * pitch + cl)[lane] = ((b >> lane) & 1u) ? (uint8_t)255 : (uint8_t)0;
+    }
+  }
+}
 
 // Workgroup tile = WAVES waves x TR rows.  Every wave keeps its TR rows of both planes in REGISTERS
 // (lane l holds dwords l*NW.. of each row; rows are picked with a wave-uniform index, which the
@@ -463,13 +510,17 @@ static __device__ __forceinline__ void hyst_tile(const HystParams &p, int gtile,
   // only the 16-pixel groups whose bits changed are rewritten: the old dword of a row is read back (one row ahead)
   // and compared with the new one.  A changed row typically has two or three such groups out of 120, so they are not
   // expanded row by row (a few active lanes per instruction) but collected in a wave-private LDS queue -- one dword
-  // per group: its 16 bits, row and position -- and expanded 64 at a time, a group per lane.
+  // per group: its 16 bits, row and position -- and expanded 64 at a time, a group per lane.  Dense content is the exception
+  // (iid noise: a changed row has 87 changed groups at the median, profiles/r16_dense_rows/groups_per_row.txt): a row with
+  // HYST_ROW_FULL changed groups or more (canny_params.h) skips the queue and is written whole, as launch 0 of a run without a
+  // provisional map writes every row (expand_rows).
   {
     const bool patch = p.out && (LATE || p.prov);
     const bool a16 = (((uintptr_t)p.out | p.out_pitch | p.out_frame_stride) & 15u) == 0;
     uint8_t *obase = p.out ? p.out + (size_t)frame * p.out_frame_stride : nullptr;
     u32 *Sw = S + (size_t)(b0 + w0) * RD;  // the wave's first row (uniform); this lane's dword is at pcol + lane
     const u32 s_lane = (u32)(pcol + lane);
+    uint8_t *out0 = obase + (size_t)(b0 + w0) * p.out_pitch;  // the wave's first row in the map (only used with p.out)
     // 16 pixels whose bits are `b`, starting at column c0 of row `row` of this frame
     auto put16 = [&](u32 b, int row, int c0) {
       if (c0 >= p.W) return;
@@ -501,44 +552,14 @@ static __device__ __forceinline__ void hyst_tile(const HystParams &p, int gtile,
       xhead = (xhead + nent) & (XQ_CAP - 1);
       xcount -= nent;
     };
+    u64 whole = 0;  // rows that go to the map whole, after the groups of the others: all of them, or the changed rows with HYST_ROW_FULL changed groups or more
     if (p.out && !patch) {
       // first launch on planes the output does not show yet: every row of the tile, whole rows, two passes of 64 groups
-      for (int r = 0; r < n; ++r) {
-        const u32 rowv = sr[0][r];
-        if ((changed >> r) & 1ull) (Sw + (size_t)r * RD)[s_lane] = rowv;
-        uint8_t *orow = obase + (size_t)(b0 + w0 + r) * p.out_pitch;
-        for (int pass = 0; pass * 1024 < ROWW * 32 && pcol * 32 + pass * 1024 < p.W; ++pass) {
-          // this lane writes px [32*pcol + 1024*pass + 16*lane, +16): half-word 64*pass + lane of the panel row
-          const u32 x = __shfl(rowv, 32 * pass + (lane >> 1));  // before any lane drops out: the permute only sees active lanes
-          const u32 b = (x >> (16 * (lane & 1))) & 0xFFFFu;
-          const int c0 = pcol * 32 + pass * 1024 + lane * 16;
-          if (c0 + 15 >= p.W) continue;  // whole 16-pixel groups here; the ragged last group of a row below
-          u32 v[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) v[k] = nibble_to_bytes((b >> (4 * k)) & 0xFu);
-          uint8_t *dst = orow + c0;
-          if (a16) {
-            uint8_t *d16 = dst;
-            asm volatile("" : "+v"(d16));  // (keeps the 16-byte store: see put16)
-            *reinterpret_cast<uint4 *>(d16) = make_uint4(v[0], v[1], v[2], v[3]);
-          } else
-#pragma unroll
-            for (int k = 0; k < 4; ++k) reinterpret_cast<u32 *>(dst)[k] = v[k];
-        }
+      for (u64 m = changed; m != 0; m &= m - 1) {
+        const int r = __builtin_ctzll(m);
+        (Sw + (size_t)r * RD)[s_lane] = sr[0][r];
       }
-      // Widths that are not a multiple of 16: the last W % 16 pixels of every row, a byte per lane, in a loop of their own
-      // (inside the loop above, the byte-wise tail -- unrolled 16 times under 16 exec masks -- cost the kernel an SGPR
-      // spill, i.e. an 81st VGPR, and as a plain loop it made the compiler split the hot loop: 0.94 instead of 0.76 ms
-      // for launch 0 of 1024 frames in plain mode)
-      const int ragged = p.W & 15, cl = p.W - ragged;  // first column of the ragged group
-      if (ragged != 0 && cl >= pcol * 32 && cl < (pcol + ROWW) * 32) {
-        const int hw = (cl - pcol * 32) >> 4;  // its half-word in the panel row: dword hw / 2 is held by lane hw / 2
-        for (int r = 0; r < n; ++r) {
-          const u32 x = __shfl(sr[0][r], hw >> 1);
-          const u32 b = (x >> (16 * (hw & 1))) & 0xFFFFu;
-          if (lane < ragged) (obase + (size_t)(b0 + w0 + r) * p.out_pitch + cl)[lane] = ((b >> lane) & 1u) ? (uint8_t)255 : (uint8_t)0;
-        }
-      }
+      whole = all_rows;
     } else {
       u64 m = changed;
       typedef u32 Old16 __attribute__((ext_vector_type(16)));
@@ -577,12 +598,24 @@ static __device__ __forceinline__ void hyst_tile(const HystParams &p, int gtile,
           u32 nlo, nhi;
           asm("s_bcnt1_i32_b64 %0, %1" : "=s"(nlo) : "s"(mlo) : "scc");
           asm("s_bcnt1_i32_b64 %0, %1" : "=s"(nhi) : "s"(mhi) : "scc");
+          if (nlo + nhi >= (u32)HYST_ROW_FULL) {  // (wave-uniform) most of the row changed: the whole row below, nothing queued
+            whole |= 1ull << r;
+            continue;
+          }
           const u32 base = (u32)(xhead + xcount), tag = (u32)r << 16;
           if (clo) xq[(base + mbcnt64(mlo)) & (XQ_CAP - 1)] = (rowv & 0xFFFFu) | tag | ((u32)(2 * lane) << 22);
           if (chi) xq[(base + nlo + mbcnt64(mhi)) & (XQ_CAP - 1)] = (rowv >> 16) | tag | ((u32)(2 * lane + 1) << 22);
           xcount += (int)(nlo + nhi);
         }
       }
+    }
+    // (patching, a group that did not change gets the bytes it holds: the map shows the plane, and the row belongs to this wave alone)
+    if (whole != 0) {
+      // (the lane index through an empty asm: what expand_rows derives from it -- half-word, column, byte offsets -- is
+      //  otherwise computed ahead of the tile loop and held in registers through it: 82 VGPRs in two instances)
+      int xlane = lane;
+      asm volatile("" : "+v"(xlane));
+      expand_rows<ROWW>(sr[0], whole, out0, p.out_pitch, pcol, p.W, a16, xlane);
     }
   }
   const bool first_changed = n > 0 && w0 == 0 && (changed & 1ull);
